@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- render FPS of the MI355X rasterizer path on BASELINE.json's configs.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20            # the headline figure alone
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     # + every other leg (training, other configs, CPU, ...)
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR
     python bench.py --gpus N ...            # no RANK in the environment: re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -15,7 +17,16 @@ a full replica of the scene: the path shards by view and a forward render has no
 data-path collective (weak scaling); the training step -- which does exchange gradients -- is reported per N under
 "multi_gpu".
 
-Rank 0 prints ONE JSON line (driver contract):
+A plain run (no --full) measures the headline figure and nothing else: it loads the scene, sizes the renderer, brings
+the clocks to their steady state, runs W warm-up steps and then EXACTLY K timed steps in one block (barrier + synchronize
+on both sides, max over ranks); value = frames/s and ms_per_step = milliseconds per step of that block.  Its line holds
+metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data and config.
+`--full` runs everything else listed below as well (the `--legs` selection, --no-extra, --no-cpu-baseline and --quick apply
+to it alone).  `--dump-outputs DIR` writes what the last timed step of the headline returned to its caller --
+image.npy, the [H, W, 3] float32 frame of rank 0's view -- after the timing; the inputs are seeded, so runs with the same
+arguments render the same frames.
+
+Rank 0 prints ONE JSON line (driver contract), in a --full run with:
   value / ms_per_step  the K timed steps of the headline workload, one frame in flight.  The K-step block (barrier +
                        synchronize on both sides, max over ranks) is repeated R times ("repeats": R >= 15 and >= 0.3 s
                        of GPU work, so that an external sampler can see the run); value / ms_per_step are the MEDIAN
@@ -51,8 +62,8 @@ Rank 0 prints ONE JSON line (driver contract):
                        bandwidth, and exposed_ms = the step with its exchange minus the same step without it in the same
                        process; the two-slice pipeline's figure; with peers also one and four slices;
   cpu_baseline         the C oracle (CPU port of the reference path, OpenMP over every host core) on the same scene.
-`--legs` selects what runs (default: everything that fits the rank count); profiles/ holds rocprofv3 traces of
-`--legs headline`.
+With --full, `--legs` selects what runs (default: everything that fits the rank count); profiles/ holds rocprofv3
+traces of `--full --legs headline` (recorded as `--legs headline`, before --full existed).
 """
 import argparse
 import json
@@ -73,10 +84,29 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))  # train_timing.py, compat_fps.p
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 ALL_LEGS = ("headline", "cfg1", "cfg2", "train", "fit", "cfg4", "trained", "soak", "pipelined", "compat", "multi_gpu", "cpu")
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most this much
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, arrays):
+    """`arrays` (name -> tensor) as path/<name>.npy: float64 stays float64, other floats become float32, integers and
+    booleans float64 (exact).  An array beyond what is left of DUMP_BYTES is replaced by a fixed, seeded sample of its
+    elements (flattened)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+        if a.nbytes > left:
+            keep = np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def stage_table(n, V, M, W, H, C, stage_ms):
@@ -106,7 +136,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg5", help="headline workload: cfg1..cfg5 of gs_scene.CONFIGS")
-    ap.add_argument("--legs", default="all", help="comma list of " + ",".join(ALL_LEGS) + " (default: all)")
+    ap.add_argument("--legs", default="all", help="with --full: comma list of " + ",".join(ALL_LEGS) + " (default: all)")
     ap.add_argument("--no-extra", action="store_true", help="= --legs headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-collective", action="store_true",
@@ -114,7 +144,17 @@ def main():
     ap.add_argument("--quick", action="store_true",
                     help="test hook (tests/test_gpu_train.py runs this file's multi_gpu leg under two ranks): three blocks "
                          "per timing instead of 15, the multi_gpu leg on the headline scene only -- not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline figure: its latency, moving-camera, unculled and "
+                         "roofline figures, and the legs of --legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed headline step returned (rank 0's image) to DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        moved = [flag for flag, given in (("--legs", args.legs != "all"), ("--no-extra", args.no_extra),
+                                          ("--no-cpu-baseline", args.no_cpu_baseline), ("--quick", args.quick)) if given]
+        if moved:
+            ap.error(f"{', '.join(moved)}: select what a --full run measures (add --full)")
     # test hooks: GS_BENCH_BACKEND=gloo + GS_BENCH_SHARE_GPU=1 run N ranks on ONE device (RCCL refuses two ranks on a
     # device; gloo stages device tensors through the host) so that the N > 1 code path of this file -- rank-symmetric
     # legs, barriers, max over ranks, the multi_gpu leg -- is executed on the one-GPU boxes the builder has
@@ -265,7 +305,11 @@ def main():
         n, W, H, use_sh = CONFIGS[cfg]
         r, st = sized_renderer(params, cam, training=False)
         log(f"[rank {rank}] {cfg}: N={n} V={st.visible} M={st.pairs} {W}x{H} sh={use_sh}")
-        frame = lambda: r.forward(*params, cam)  # noqa: E731
+        last = [None]  # what the latest frame returned to its caller: (image, None)
+
+        def frame():
+            last[0] = r.forward(*params, cam)
+
         settle(frame)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -274,6 +318,7 @@ def main():
         host_us = (time.perf_counter() - t0) / 50 * 1e6  # host cost of issuing one frame, GPU free-running
         torch.cuda.synchronize()
         dt, blocks = time_frames(frame, steps, warmup)
+        outputs = last[0]  # ... of the last timed frame (--dump-outputs)
         lat = latency_fps(frame)
         st_run = r.stats()  # the steady-state frame: pairs EMITTED (after the occlusion cull), did it fall back
         st_run_culled = bool(r._frame.flags & 256)
@@ -310,7 +355,7 @@ def main():
             for _ in range(3):
                 r.forward(*params, cam)
         res = {"fps": world * steps / dt, "ms": dt / steps * 1e3, "host_us": host_us, "stats": st, "latency": lat,
-               "scene": scene, "cam": cam, "params": params, "renderer": r, "repeats": len(blocks),
+               "scene": scene, "cam": cam, "params": params, "renderer": r, "repeats": len(blocks), "outputs": outputs,
                "occlusion_cull": {"active": st_run_culled, "pairs_emitted": st_run.pairs,
                                   "pairs_of_the_frame": st.pairs, "fell_back": st_run.cull_fallback,
                                   "fps_without_the_cull": fps_no_cull, "stage_ms_without_the_cull": stages_no_cull},
@@ -390,20 +435,54 @@ def main():
         return (f"{cfg}: {n} Gaussians, {W}x{H}, {'SH deg2 (27 coeff)' if use_sh else 'no SH'}, forward render, "
                 f"one frame in flight, one view per GPU -- {what}")
 
+    n, W, H, use_sh = CONFIGS[args.config]
+
+    def headline_line(fps, ms, st):
+        """The fields of the result line that a plain and a --full run share."""
+        return {
+            "metric": "render_fps", "value": round(fps, 2), "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": workload_name(args.config, st), "n_gaussians": n, "visible": st.visible,
+                       "tile_pairs": st.pairs, "width": W, "height": H,
+                       "parallelism": f"view-sharded x{world} (no data-path collective)", "frames_in_flight": 1}}
+
+    def emit(out):
+        if rank == 0:
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if use_dist:
+            dist.destroy_process_group()
+
+    # ---------------------------------------------------------------- plain run: the headline figure alone
+    if not args.full:
+        _, cam, params = load(args.config)
+        r, st = sized_renderer(params, cam, training=False)
+        log(f"[rank {rank}] {args.config}: N={n} V={st.visible} M={st.pairs} {W}x{H} sh={use_sh}")
+        last = [None]  # what the latest frame returned to its caller: (image, None)
+
+        def frame():
+            last[0] = r.forward(*params, cam)
+
+        settle(frame)
+        for _ in range(args.warmup):
+            frame()
+        dt = time_block(frame, args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"image": last[0][0]})
+        emit(headline_line(world * args.steps / dt, dt / args.steps * 1e3, st))
+        return
+
     # ---------------------------------------------------------------- headline: render FPS, one frame in flight
     head = render_leg(args.config, args.steps, args.warmup)
-    n, W, H, use_sh = CONFIGS[args.config]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": head["outputs"][0]})
+    del head["outputs"]
     st = head["stats"]
     out = {
-        "metric": "render_fps", "value": round(head["fps"], 2), "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(head["ms"], 4),
+        **headline_line(head["fps"], head["ms"], st),
         "repeats": head["repeats"], "ms_per_step_min": round(head["ms_min"], 4),
         "ms_per_step_max": round(head["ms_max"], 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": workload_name(args.config, st), "n_gaussians": n, "visible": st.visible,
-                   "tile_pairs": st.pairs, "width": W, "height": H,
-                   "parallelism": f"view-sharded x{world} (no data-path collective)", "frames_in_flight": 1},
         "host_us_per_frame": round(head["host_us"], 1),
         # temporal occlusion cull (include/gs_abi.h, GS_FRAME_OCCLUSION_CULL): the steady-state frame emits / sorts only the
         # pairs in front of the depth at which the previous frame's tiles stopped; the image is bit-identical
@@ -1030,10 +1109,7 @@ def main():
 
         guarded("cpu", _leg_cpu)
 
-    if rank == 0:
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    if use_dist:
-        dist.destroy_process_group()
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -299,6 +299,68 @@ def train_cli():
     print("train_cli ok", len(out))
 
 
+def reference_call_sites():
+    """Every call of the reference's host files into `gaussian` / `renderer` (function, number of positional arguments,
+    keyword names, line) and the attributes splatter.py's _tocpp methods store on the C++ objects, read from its SOURCE
+    with the ast module -> reference_call_sites.json (tests/test_reference_call_sites.py binds them to this package)."""
+    import ast
+    import json
+
+    ref_root = os.path.dirname(os.path.dirname(build_ref.REF_SRC))
+
+    def module_calls(path, module_names, imported_from):
+        tree = ast.parse(open(path).read(), filename=path)
+        direct = set()
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and node.module in imported_from:
+                direct.update(a.asname or a.name for a in node.names)
+        out = []
+        for node in ast.walk(tree):
+            if not isinstance(node, ast.Call):
+                continue
+            fn = node.func
+            name = mod = None
+            if isinstance(fn, ast.Attribute) and isinstance(fn.value, ast.Name) and fn.value.id in module_names:
+                mod, name = fn.value.id, fn.attr
+            elif isinstance(fn, ast.Name) and fn.id in direct:
+                mod, name = next(iter(imported_from)), fn.id
+            if name is None or any(isinstance(a, ast.Starred) for a in node.args) or any(k.arg is None for k in node.keywords):
+                continue
+            out.append((mod, name, len(node.args), [k.arg for k in node.keywords], node.lineno))
+        return out
+
+    calls = []
+    for fname in ("renderer.py", "splatter.py", "train.py", "visergui.py"):
+        path = os.path.join(ref_root, fname)
+        if os.path.exists(path):
+            calls += [[fname, line, mod, name, npos, kws]
+                      for mod, name, npos, kws, line in module_calls(path, {"gaussian", "renderer"}, {"renderer"})]
+    stored = set()
+    for node in ast.walk(ast.parse(open(os.path.join(ref_root, "splatter.py")).read())):
+        if isinstance(node, ast.Assign):
+            for t in node.targets:
+                if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id in ("_cobj", "_tile"):
+                    stored.add((t.value.id, t.attr))
+    with open(os.path.join(HERE, "reference_call_sites.json"), "w") as f:
+        json.dump({"calls": calls, "stored_attributes": sorted(list(x) for x in stored)}, f, indent=1)
+    print("reference_call_sites ok", len(calls), len(stored))
+
+
+def ref_live():
+    """The reference kernels' outputs on the inputs of tests/test_ref_live.py -> ref_live.npz: the module's tests run
+    once with the live library, recording what they receive from it."""
+    import test_ref_live
+
+    test_ref_live.RECORD = {}
+    for seed in (31, 32):
+        test_ref_live.test_oracle_vs_reference_kernels_fresh_seed(seed)
+    test_ref_live.test_reference_backward_defect_between_chunks_is_real()
+    for use_sh in (False, True):
+        test_ref_live.test_sigmoid_flag_forward_and_backward_vs_reference_kernels(use_sh)
+    np.savez_compressed(os.path.join(HERE, "ref_live.npz"), **test_ref_live.RECORD)
+    print("ref_live ok", len(test_ref_live.RECORD))
+
+
 if __name__ == "__main__":
     assert os.path.isdir("/root/reference"), "needs the reference checkout"
     oracle.build()
@@ -313,3 +375,5 @@ if __name__ == "__main__":
     densify()
     colmap()
     train_cli()
+    reference_call_sites()
+    ref_live()

@@ -623,7 +623,7 @@ def test_bench_multi_gpu_leg_runs_under_two_ranks(gpu, tmp_path):
     env = dict(os.environ, GS_BENCH_BACKEND="gloo", GS_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--config", "cfg1", "--legs", "headline,multi_gpu", "--quick"]
+           "--config", "cfg1", "--full", "--legs", "headline,multi_gpu", "--quick"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

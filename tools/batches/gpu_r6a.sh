@@ -12,5 +12,5 @@ for CFG in trained_rgb trained_sh; do for LL in off on; do
   cp $(find "$OUT/st_${CFG}_$LL" -name '*kernel_stats.csv' | head -1) "$OUT/kernel_stats_${CFG}_$LL.csv"; rm -rf "$OUT/st_${CFG}_$LL"
 done; done
 cd "$R"
-timeout 900 python bench.py --legs headline,cfg2,trained --steps 20 --warmup 5 > "$OUT/bench_headline_trained.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
+timeout 900 python bench.py --full --legs headline,cfg2,trained --steps 20 --warmup 5 > "$OUT/bench_headline_trained.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
 cat "$OUT/steps.txt"; grep -h "CALIB" "$OUT/new_tests.txt" | head -80; tail -5 "$OUT/new_tests.txt"; tail -3 "$OUT/gpu_tier.txt"

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$R/gpurun_out/r6ag; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 1200 python -m pytest tests/test_gpu_frame.py tests/test_gpu_kernels.py tests/test_gpu_golden.py -q -m gpu -k "sh or SH or cfg4 or deg" > "$OUT/tests.txt" 2>&1; grep -n "passed\|failed\|FAILED" "$OUT/tests.txt"
-python bench.py --legs headline,cfg4,trained 2>"$OUT/b.err" > "$OUT/bench.json"
+python bench.py --full --legs headline,cfg4,trained 2>"$OUT/b.err" > "$OUT/bench.json"
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r6ag/bench.json").read().strip().splitlines()[-1]); e=d["extra"]

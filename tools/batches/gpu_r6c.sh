@@ -6,8 +6,8 @@ OUT=$R/gpurun_out/r6c; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 900 python -m pytest tests/test_gpu_frame.py -q -m gpu -s -k "occlusion or sort_window or long_list or pile or 2p4M_forward" > "$OUT/cull_tests.txt" 2>&1; echo "cull tests rc=$?" | tee -a "$OUT/steps.txt"
 timeout 1500 python -m pytest tests/test_grad_calibration.py tests/test_gpu_kernels.py -q -m gpu -s > "$OUT/new_tests.txt" 2>&1; echo "parity tests rc=$?" | tee -a "$OUT/steps.txt"
-timeout 900 python bench.py --legs headline,cfg2,cfg1 --steps 20 --warmup 5 > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
-GS_NO_CULL=1 timeout 900 python bench.py --legs headline --steps 20 --warmup 5 > "$OUT/bench_headline_nocull.json" 2> "$OUT/bench_nocull.err"; echo "bench nocull rc=$?" | tee -a "$OUT/steps.txt"
+timeout 900 python bench.py --full --legs headline,cfg2,cfg1 --steps 20 --warmup 5 > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
+GS_NO_CULL=1 timeout 900 python bench.py --full --legs headline --steps 20 --warmup 5 > "$OUT/bench_headline_nocull.json" 2> "$OUT/bench_nocull.err"; echo "bench nocull rc=$?" | tee -a "$OUT/steps.txt"
 timeout 1800 python -m pytest tests -q -m gpu > "$OUT/gpu_tier.txt" 2>&1; echo "gpu tier rc=$?" | tee -a "$OUT/steps.txt"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/st_cfg5" -o s -- python "$R/tools/prof_target.py" cfg5 --frames 100 > "$OUT/target_cfg5.json" 2> "$OUT/st_cfg5.err"

@@ -5,8 +5,8 @@ OUT=$R/gpurun_out/r6d; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 900 python -m pytest tests/test_gpu_frame.py -q -m gpu -s -k "occlusion or 2p4M_forward" > "$OUT/cull_tests.txt" 2>&1; echo "cull tests rc=$?" | tee -a "$OUT/steps.txt"
 timeout 1500 python -m pytest tests/test_gpu_kernels.py -q -m gpu -s -k "full_size" > "$OUT/api_tests.txt" 2>&1; echo "api tests rc=$?" | tee -a "$OUT/steps.txt"
-timeout 900 python bench.py --legs headline,cfg2,cfg1 --steps 20 --warmup 5 > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
-GS_NO_CULL=1 timeout 900 python bench.py --legs headline,cfg2,cfg1 --steps 20 --warmup 5 > "$OUT/bench_headline_nocull.json" 2> "$OUT/bench_nocull.err"; echo "bench nocull rc=$?" | tee -a "$OUT/steps.txt"
+timeout 900 python bench.py --full --legs headline,cfg2,cfg1 --steps 20 --warmup 5 > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
+GS_NO_CULL=1 timeout 900 python bench.py --full --legs headline,cfg2,cfg1 --steps 20 --warmup 5 > "$OUT/bench_headline_nocull.json" 2> "$OUT/bench_nocull.err"; echo "bench nocull rc=$?" | tee -a "$OUT/steps.txt"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/st_cfg5" -o s -- python "$R/tools/prof_target.py" cfg5 --frames 100 > "$OUT/target_cfg5.json" 2> "$OUT/st_cfg5.err"
 F=$(find "$OUT/st_cfg5" -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp "$F" "$OUT/kernel_stats_cfg5_culled.csv"; rm -rf "$OUT/st_cfg5"

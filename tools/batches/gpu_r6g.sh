@@ -7,7 +7,7 @@ cd "$R"
 timeout 900 python -m pytest tests/test_gpu_frame.py -q -m gpu -s -k "occlusion or sort_window or long_list or pile or graph" > "$OUT/cull_tests.txt" 2>&1; echo "cull tests rc=$?" | tee -a "$OUT/steps.txt"
 timeout 900 python tools/soak_end_state.py 2 2000 > "$OUT/soak_end_sh2.json" 2> "$OUT/soak_end_sh2.err"; echo "soak end sh2 rc=$?" | tee -a "$OUT/steps.txt"
 timeout 900 python tools/soak_end_state.py 0 3000 > "$OUT/soak_end_rgb.json" 2> "$OUT/soak_end_rgb.err"; echo "soak end rgb rc=$?" | tee -a "$OUT/steps.txt"
-timeout 900 python bench.py --legs headline,cfg2,cfg1 > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
+timeout 900 python bench.py --full --legs headline,cfg2,cfg1 > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
 cat "$OUT/steps.txt"; tail -4 "$OUT/cull_tests.txt"; grep "occlusion cull over" "$OUT/cull_tests.txt"; cat "$OUT/soak_end_sh2.json" "$OUT/soak_end_rgb.json"
 python - <<'PY'
 import json

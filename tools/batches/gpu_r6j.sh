@@ -5,8 +5,8 @@ OUT=$R/gpurun_out/r6j; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 900 python -m pytest tests/test_gpu_train.py -q -m gpu -k "fused_backward_adam" > "$OUT/fused_tests.txt" 2>&1; echo "fused tests rc=$?" | tee -a "$OUT/steps.txt"
 timeout 900 python -m pytest tests/test_gpu_frame.py -q -m gpu -k "occlusion" > "$OUT/cull_tests.txt" 2>&1; echo "cull tests rc=$?" | tee -a "$OUT/steps.txt"
-timeout 1200 python bench.py --legs headline,trained,soak > "$OUT/bench_fused.json" 2> "$OUT/bench_fused.err"; echo "bench fused rc=$?" | tee -a "$OUT/steps.txt"
-GS_TRAIN_FUSE_ADAM=0 timeout 1200 python bench.py --legs headline,trained,soak > "$OUT/bench_unfused.json" 2> "$OUT/bench_unfused.err"; echo "bench unfused rc=$?" | tee -a "$OUT/steps.txt"
+timeout 1200 python bench.py --full --legs headline,trained,soak > "$OUT/bench_fused.json" 2> "$OUT/bench_fused.err"; echo "bench fused rc=$?" | tee -a "$OUT/steps.txt"
+GS_TRAIN_FUSE_ADAM=0 timeout 1200 python bench.py --full --legs headline,trained,soak > "$OUT/bench_unfused.json" 2> "$OUT/bench_unfused.err"; echo "bench unfused rc=$?" | tee -a "$OUT/steps.txt"
 cat "$OUT/steps.txt"; tail -5 "$OUT/fused_tests.txt"; tail -3 "$OUT/cull_tests.txt"
 python - <<'PY'
 import json

@@ -5,8 +5,8 @@ OUT=$R/gpurun_out/r6k; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 900 python -m pytest tests/test_gpu_train.py -q -m gpu -k "fused_backward_adam" > "$OUT/fused_tests.txt" 2>&1; echo "fused tests rc=$?" | tee -a "$OUT/steps.txt"
 for i in 1 2; do
-timeout 1200 python bench.py --legs headline,soak > "$OUT/bench_fused$i.json" 2> "$OUT/bench_fused.err"; echo "bench fused rc=$?" | tee -a "$OUT/steps.txt"
-GS_TRAIN_FUSE_ADAM=0 timeout 1200 python bench.py --legs headline,soak > "$OUT/bench_unfused$i.json" 2> "$OUT/bench_unfused.err"; echo "bench unfused rc=$?" | tee -a "$OUT/steps.txt"
+timeout 1200 python bench.py --full --legs headline,soak > "$OUT/bench_fused$i.json" 2> "$OUT/bench_fused.err"; echo "bench fused rc=$?" | tee -a "$OUT/steps.txt"
+GS_TRAIN_FUSE_ADAM=0 timeout 1200 python bench.py --full --legs headline,soak > "$OUT/bench_unfused$i.json" 2> "$OUT/bench_unfused.err"; echo "bench unfused rc=$?" | tee -a "$OUT/steps.txt"
 done
 tail -5 "$OUT/fused_tests.txt"
 python - <<'PY'

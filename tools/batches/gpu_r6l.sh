@@ -4,8 +4,8 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$R/gpurun_out/r6l; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 900 python -m pytest tests/test_gpu_frame.py -q -m gpu -x -k "occlusion or 2p4M_forward" > "$OUT/cull_tests.txt" 2>&1; echo "cull tests rc=$?" | tee -a "$OUT/steps.txt"
-timeout 900 python bench.py --legs headline > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
-GS_NO_CULL=1 timeout 900 python bench.py --legs headline > "$OUT/bench_headline_nocull.json" 2> "$OUT/bench_nocull.err"; echo "bench nocull rc=$?" | tee -a "$OUT/steps.txt"
+timeout 900 python bench.py --full --legs headline > "$OUT/bench_headline.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
+GS_NO_CULL=1 timeout 900 python bench.py --full --legs headline > "$OUT/bench_headline_nocull.json" 2> "$OUT/bench_nocull.err"; echo "bench nocull rc=$?" | tee -a "$OUT/steps.txt"
 tail -15 "$OUT/cull_tests.txt"
 python - <<'PY'
 import json

@@ -8,7 +8,7 @@ timeout 1800 python -m pytest tests -q -m gpu > "$OUT/gpu_tier.txt" 2>&1; echo "
 ps aux | grep -c python > "$OUT/ps_after_tests.txt"; ps aux | grep python | head -20 >> "$OUT/ps_after_tests.txt"
 rocm-smi --showuse --showmemuse 2>/dev/null | head -20 >> "$OUT/ps_after_tests.txt"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1; echo "smoke rc=$?" | tee -a "$OUT/steps.txt"
-GS_LOG_FLAGS=1 timeout 1500 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
+GS_LOG_FLAGS=1 timeout 1500 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench.err"; echo "bench rc=$?" | tee -a "$OUT/steps.txt"
 cat "$OUT/steps.txt"; grep -n "FAILED\|passed\|failed" "$OUT/gpu_tier.txt" | tail -4; tail -1 "$OUT/smoke.txt"
 python - <<'PY'
 import json

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/r6z; rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$R"
 timeout 900 python -m pytest tests/test_gpu_frame.py tests/test_gpu_train.py -q -m gpu -k "long or pile or segment or beyond_the_sort_window" > "$OUT/tests.txt" 2>&1; echo "tests rc=$?"; tail -15 "$OUT/tests.txt"
 for tp in 0 1; do
-  GS_SEG_TWO_PASS=$tp timeout 900 python bench.py --legs headline,trained > "$OUT/bench_tp$tp.json" 2> "$OUT/err$tp.txt"
+  GS_SEG_TWO_PASS=$tp timeout 900 python bench.py --full --legs headline,trained > "$OUT/bench_tp$tp.json" 2> "$OUT/err$tp.txt"
   python - "$OUT/bench_tp$tp.json" $tp <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

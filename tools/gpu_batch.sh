@@ -18,8 +18,8 @@ for STEP in "$@"; do
     prof_cfg4) timeout 600 tools/profile_round.sh $TAG/prof_cfg4 cfg4 fwdbwd > "$OUT/prof_cfg4.log" 2>&1 ;;
     prof_cfg5t) timeout 600 tools/profile_round.sh $TAG/prof_cfg5t cfg5 fwdbwd > "$OUT/prof_cfg5t.log" 2>&1 ;;
     prof_cfg2) timeout 600 tools/profile_round.sh $TAG/prof_cfg2 cfg2 fwd > "$OUT/prof_cfg2.log" 2>&1 ;;
-    bench)     timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
-    benchprof) (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/benchprof" -o s -- python "$R/bench.py" --legs headline --no-cpu-baseline > "$OUT/benchprof.json" 2> "$OUT/benchprof.err"; cp $(find "$OUT/benchprof" -name '*kernel_stats.csv' | head -1) "$OUT/benchprof_kernel_stats.csv") ;;
+    bench)     timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    benchprof) (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/benchprof" -o s -- python "$R/bench.py" --full --legs headline --no-cpu-baseline > "$OUT/benchprof.json" 2> "$OUT/benchprof.err"; cp $(find "$OUT/benchprof" -name '*kernel_stats.csv' | head -1) "$OUT/benchprof_kernel_stats.csv") ;;
     diag)      (cd /tmp && export TMPDIR=/tmp && for V in $(ls "$R/build/variants"); do GS_AMD_LIB="$R/build/variants/$V/libgs_amd.so" timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/diag_$V" -o s -- python "$R/tools/prof_target.py" cfg5 --frames 60 > "$OUT/diag_$V.json" 2> "$OUT/diag_$V.err"; cp $(find "$OUT/diag_$V" -name '*kernel_stats.csv' | head -1) "$OUT/diag_${V}_kernel_stats.csv"; done) ;;
     ubench)    timeout 120 tools/ubench/sort_ops > "$OUT/ubench_sort_ops.txt" 2>&1 ;;
     smoke)     timeout 300 python __graft_entry__.py --smoke > "$OUT/smoke.log" 2>&1 ;;

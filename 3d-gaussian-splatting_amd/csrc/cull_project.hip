@@ -1050,6 +1050,70 @@ __global__ void __launch_bounds__(1024) sh_big_rows_kernel(const uint4 *__restri
     }
 }
 
+// GS_FRAME_AUX training frames: dL/dd_i of the depth map (d_i = |p_c|, res_pos[:, 2] of global_culling) is the sum of the
+// depth floats (gs_row_aux_depth) of the Gaussian's existing rows -- the same rows, in the same ascending order, the
+// projection backward reads: the tiles' stop keys decide, and an SH Gaussian beyond GS_PB_SH_BIG rows has its total in its
+// first row (sh_big_rows_kernel adds the depth float up with the rest) --, and it enters grad_pos as gradout_pos[:, 2] of
+// global_culling_backward (gaussian.cu:1400-1406): R^T (g_d p_c / |p_c|), added to what frame_project_backward_kernel wrote.
+// A kernel of its own, behind the geometry part, so that the projection backward of frames without the flag stays as it is.
+template <int CDIM>
+__global__ void __launch_bounds__(256) frame_aux_depth_backward_kernel(const float *__restrict__ pos, int64_t n, int64_t g_first,
+                                                                       ProjectParams P, const float4 *__restrict__ rec_geom,
+                                                                       const float *__restrict__ rows,
+                                                                       const unsigned long long *__restrict__ stop_keys, GsDistCull D,
+                                                                       const uint32_t *__restrict__ pair_offsets,
+                                                                       const uint4 *__restrict__ rects, uint64_t max_pairs,
+                                                                       float *__restrict__ grad_pos) {
+    constexpr int RWF = gs_row_floats(CDIM), SLOT = gs_row_aux_depth(CDIM);
+    const int64_t pid = g_first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pid >= n) return;
+    const uint4 rc = rects[pid];
+    if (rc.z == 0) return;  // culled by the frustum test: zero gradient (written by the projection backward)
+    const uint64_t off = pair_offsets[pid], cnt = rc.w;
+    float gd = 0.f;
+    if (CDIM != 3 && cnt > (uint64_t)GS_PB_SH_BIG) {
+        if (off < max_pairs) gd = rows[off * RWF + SLOT];
+    } else {
+        const uint32_t *stop_depth = reinterpret_cast<const uint32_t *>(stop_keys), *stop_id = stop_depth + P.ntx * P.nty;
+        const uint32_t y0 = rc.x & 0xffff, x0 = rc.y & 0xffff, x1 = rc.y >> 16;
+        float cx = 0.f, cy = 0.f;
+        if (P.cull_method == 0) {
+            const float4 g = rec_geom[pid * GS_REC_STRIDE];
+            cx = g.x;
+            cy = g.y;
+        }
+        uint32_t ix = x0, iy = y0;
+        for (uint64_t k = 0; k < cnt && off + k < max_pairs; ++k) {
+            const uint32_t t = iy * P.ntx + ix, sd = stop_depth[t];
+            bool ex = rc.z < sd || (rc.z == sd && (uint32_t)pid <= stop_id[t]);
+            if (P.cull_method == 0 && !gs_dist_listed(cx, cy, ix, iy, D)) ex = false;
+            if (ex) gd += rows[(off + k) * RWF + SLOT];
+            if (++ix == x1) {
+                ix = x0;
+                ++iy;
+            }
+        }
+    }
+    float p[3], pc[3], gp[3];
+    load3(pos, pid, p);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        pc[r] = P.cam.rot[r * 3 + 0] * p[0] + P.cam.rot[r * 3 + 1] * p[1] + P.cam.rot[r * 3 + 2] * p[2] + P.cam.tran[r];
+    const float ir_ = gs_rsq(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);
+    float gc[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) gc[r] = gd * pc[r] * ir_;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float a = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a += P.cam.rot[k * 3 + c] * gc[k];
+        gp[c] = a;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) grad_pos[pid * 3 + c] += gp[c];
+}
+
 #ifndef GS_PB_DIRECT
 #define GS_PB_DIRECT 2  // A/B switch (tools/ab_variants.py): how the rgb rows are fetched, see below
 #endif
@@ -2008,6 +2072,28 @@ int gs_stage_sh_big_rows(const gs_frame *f, const gs_frame_ws &ws, hipStream_t s
     else
         GS_LAUNCH_BIG_ROWS(27);
 #undef GS_LAUNCH_BIG_ROWS
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+int gs_stage_aux_depth_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, int64_t g_begin, int64_t g_end,
+                                hipStream_t stream) {
+    if (g_end <= g_begin) return 0;
+    ProjectParams P = make_params(f);
+    gs_frame_geom G = gs_frame_geometry(f);
+    GsDistCull D = {(float)(G.padW / 2), (float)(G.padH / 2), f->focal_x, f->focal_y, f->thresh};
+    const unsigned grid = (unsigned)gs_div_up(g_end - g_begin, 256);
+#define GS_LAUNCH_AUX_DEPTH(CD)                                                                                          \
+    hipLaunchKernelGGL(frame_aux_depth_backward_kernel<CD>, dim3(grid), dim3(256), 0, stream, f->pos, g_end, g_begin, P,  \
+                       ws.rec_geom, ws.rows, (const unsigned long long *)ws.stop_keys, D, ws.pair_offsets, ws.rects,      \
+                       (uint64_t)f->max_pairs, grad_pos)
+    if (f->color_dim == 48)
+        GS_LAUNCH_AUX_DEPTH(48);
+    else if (f->color_dim == 27)
+        GS_LAUNCH_AUX_DEPTH(27);
+    else
+        GS_LAUNCH_AUX_DEPTH(3);
+#undef GS_LAUNCH_AUX_DEPTH
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -65,17 +65,34 @@ static int validate(const gs_frame *f) {
     }
     GS_CHECK_ARG((f->flags & ~(GS_FRAME_EMIT_SORTED_KEYS | GS_FRAME_SLICE_SORT | GS_FRAME_TABLE_BIN |
                                GS_FRAME_SERIAL_LONG_LISTS | GS_FRAME_LONG_LISTS | GS_FRAME_STRIP_BIN |
-                               GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR)) == 0,
+                               GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR |
+                               GS_FRAME_AUX)) == 0,
                  "unknown flag bits");
     GS_CHECK_ARG(f->sort_mode >= 0 && f->sort_mode <= 2,
                  "sort_mode must be 0 (full LSD radix), 1 (tile-bit radix + per-tile LDS sort) or 2 (LDS counting sort "
                  "by tile + per-tile LDS sort)");
+    if (f->flags & GS_FRAME_AUX) {  // the trailing fields exist only for callers that set the flag
+        GS_CHECK_ARG(f->aux_workspace != nullptr && ((uintptr_t)f->aux_workspace & 255) == 0,
+                     "GS_FRAME_AUX: aux_workspace null or not 256-byte aligned");
+        const size_t aux_need = gs_frame_aux_workspace_bytes(f->max_pairs, f->width, f->height, f->training);
+        if (f->aux_workspace_bytes < aux_need) {
+            gs_set_error("gs_frame: GS_FRAME_AUX: aux workspace too small (%zu < %zu bytes)", f->aux_workspace_bytes, aux_need);
+            return GS_E_INVALID;
+        }
+        GS_CHECK_ARG(!f->training || f->aux_padded != nullptr, "GS_FRAME_AUX: training needs aux_padded");
+        GS_CHECK_ARG(((uintptr_t)f->aux_padded & 7) == 0, "GS_FRAME_AUX: aux_padded must be 8-byte aligned");
+    }
     const size_t need = gs_frame_workspace_bytes(f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
     if (f->workspace_bytes < need) {
         gs_set_error("gs_frame: workspace too small (%zu < %zu bytes)", f->workspace_bytes, need);
         return GS_E_CAPACITY;
     }
     return 0;
+}
+
+extern "C" size_t gs_frame_aux_workspace_bytes(int64_t max_pairs, int32_t width, int32_t height, int32_t training) {
+    if (max_pairs < 0 || width <= 0 || height <= 0 || width > 65535 * 16 || height > 65535 * 16) return 0;
+    return gs_frame_aux_carve(nullptr, max_pairs, width, height, training).total_bytes;
 }
 
 extern "C" size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int32_t height,
@@ -400,6 +417,10 @@ static int frame_backward_impl(const gs_frame *f, const float *grad_image, float
         (rc = gs_stage_project_backward(f, ws, grad_pos, grad_quat, grad_scale, grad_opa, grad_rgb,
                                         part == GS_BWD_GEOMETRY ? 1 : part == GS_BWD_COLOR ? 2 : 0, g_begin, g_end, s)))
         return rc;
+    // GS_FRAME_AUX: the depth gradients of the rows, summed per Gaussian, enter grad_pos (dL/d|p_c| through the projection)
+    if ((f->flags & GS_FRAME_AUX) && part != GS_BWD_RASTER && part != GS_BWD_COLOR &&
+        (rc = gs_stage_aux_depth_backward(f, ws, grad_pos, g_begin, g_end, s)))
+        return rc;
     tm.mark();
     return tm.finish(stage_ms, 3);
 }
@@ -414,6 +435,10 @@ extern "C" int gs_frame_backward_adam(const gs_frame *f, const float *grad_image
                                       gs_stream_t stream) {
     int rc = validate(f);
     if (rc) return rc;
+    if (f->flags & GS_FRAME_AUX) {
+        gs_set_error("gs_frame_backward_adam: GS_FRAME_AUX frames are not supported (use gs_frame_backward + an optimizer step)");
+        return GS_E_UNSUPPORTED;
+    }
     GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam needs a training forward (image_padded kept)");
     GS_CHECK_ARG(grad_image && adam, "null pointer");
     if ((rc = gs_validate_adam_fused(f, adam))) return rc;  // before anything is enqueued

@@ -227,6 +227,10 @@ static constexpr int gs_row_geo(int color_dim, int m) { return color_dim == 27 ?
 static constexpr int gs_row_col(int color_dim, int c) {
     return color_dim == 27 ? 16 * (c / 9) + c % 9 : color_dim == 48 ? 16 + c : 7 + c;
 }
+// GS_FRAME_AUX frames: dL/d(depth d_i) of the pair = sum over the tile's pixels of dL/dD w_i, in a float that is padding
+// otherwise (rgb: float 10; degree 2: the last float of header piece 1; degree 3: float 7 of the header line).  Readers that
+// do not know it skip it as padding; the big-row summation (gs_stage_sh_big_rows) adds it up with the rest of the row.
+static constexpr int gs_row_aux_depth(int color_dim) { return color_dim == 3 ? 10 : color_dim == 27 ? 31 : 7; }
 // inverse: float f of a row -> its index in the compact order (dx, dy, da, db, dc, dd, dopa, colour 0 .. color_dim - 1), or -1
 // for a padding float
 static constexpr int gs_row_compact(int color_dim, int f) {
@@ -453,6 +457,30 @@ static inline gs_frame_ws gs_frame_carve(void *base, int64_t N, int64_t max_pair
     return ws;
 }
 
+// GS_FRAME_AUX frames: the caller's second workspace (gs_frame.aux_workspace).  The main workspace keeps its layout.
+//   header : 256 bytes, reserved (keeps the size positive for inference frames and the checkpoints line-aligned)
+//   ckpt   : training: [max_buckets][256] float2 (D, A) at bucket starts, in the slots of the colour checkpoints
+struct gs_frame_aux_ws {
+    float2 *ckpt;
+    size_t total_bytes;
+};
+static inline gs_frame_aux_ws gs_frame_aux_carve(void *base, int64_t max_pairs, int W, int H, int training) {
+    gs_frame_aux_ws a;
+    const gs_frame_geom G = gs_frame_geometry_i(W, H);
+    size_t off = 256;
+    a.ckpt = nullptr;
+    if (training) {
+        a.ckpt = base ? (float2 *)((char *)base + off) : nullptr;
+        off += gs_align_up(sizeof(float2) * 256 * (size_t)gs_max_buckets(max_pairs, G.n_tiles), 256);
+    }
+    a.total_bytes = off;
+    return a;
+}
+static inline gs_frame_aux_ws gs_frame_aux(const gs_frame *f) {
+    return gs_frame_aux_carve((f->flags & GS_FRAME_AUX) ? f->aux_workspace : nullptr, f->max_pairs, f->width, f->height,
+                              f->training);
+}
+
 // stage entry points (defined across the .hip files)
 // the cut table a culled frame trims its lists by: the tiles' own cuts, or (GS_FRAME_CULL_DILATE) their neighbourhood maxima
 static inline const uint32_t *gs_frame_cut_table(const gs_frame *f, const gs_frame_ws &ws) {
@@ -482,5 +510,7 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
                             bool second_pass = false);
 int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids, hipStream_t stream);
 int gs_stage_sh_big_rows(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
+int gs_stage_aux_depth_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, int64_t g_begin, int64_t g_end,
+                                hipStream_t stream);
 int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids,
                              const float *grad_image, hipStream_t stream, bool prepared);

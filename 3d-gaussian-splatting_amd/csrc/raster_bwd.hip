@@ -800,17 +800,31 @@ struct PixShCfg {
 #ifndef GS_BWD_PAIR_SKIP
 #define GS_BWD_PAIR_SKIP 1
 #endif
-template <int CDIM, bool FRAME, bool EXACT = false>
-__global__ void __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu(CDIM == 48 ? GS_BWD_SH48_WPE : CDIM == 3 ? 5 : GS_BWD_SH_WPE)))  // rgb: five (LDS: 7.9 KiB per wave)
-raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
+// Inputs of the depth / alpha terms (GS_FRAME_AUX training frames; raster_aux_backward_kernel): the forward's final (D, A)
+// sums and its per-bucket (D, A) checkpoints, dL/d(depth) and dL/d(alpha) of the cropped maps (NULL = zero).
+struct AuxBwdIn {
+    const float2 *padded;
+    const float2 *ckpt;
+    const float *grad_depth, *grad_alpha;
+};
+
+// The body of the pixel-parallel backward.  AUX = true: the maps are two more "colour channels" d_i and 1 -- dL/dalpha_i gains
+// g_D (d_i T - (D_final - D_<=i) / (1 - alpha)) + g_A (T - (A_final - A_<=i) / (1 - alpha)) through the same gc / rho recursion,
+// and one more row sum, sum_pixels g_D w_i = dL/dd_i, goes into the pair's row (gs_row_aux_depth).  AUX = false compiles to
+// the plain kernel unchanged.
+template <int CDIM, bool FRAME, bool EXACT, bool AUX>
+__device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O,
+                                                              const AuxBwdIn &X) {
     static_assert(!(EXACT && FRAME), "the exact-exp flavour belongs to the reference API (gs_draw_backward, fast = 0)");
-    constexpr int NB = PixShCfg<CDIM>::NB, NROW = PixShCfg<CDIM>::NROW;
+    static_assert(!AUX || (FRAME && !EXACT), "depth / alpha maps belong to the frame path");
+    constexpr int NB = PixShCfg<CDIM>::NB, NROW0 = PixShCfg<CDIM>::NROW;
+    constexpr int NROW = NROW0 + (AUX ? 1 : 0);  // AUX: row NROW0 = sum g_D w (the depth gradient)
     constexpr bool PRE = GS_SH_PRESCALE && CDIM == 27;  // SH basis pre-scaled by -log2(e): raster_common.h
     typedef float f2 __attribute__((ext_vector_type(2)));
     enum { FX, FY, FA, FB, FC, FOPA, FC0, FC1, FC2, NFLD };  // FC0..2: the Gaussian's colour (CDIM == 3 only)
     __shared__ float s_g[NFLD][64];
     __shared__ uint32_t s_id[64];          // FRAME: Gaussian id; else index of the pair in the sorted arrays
+    __shared__ float s_dep[AUX ? 64 : 1];  // AUX: d_i = rec_geom.z
     // [row][lane] partial sums of the current Gaussian, 16 rows at a time (rows padded to 65).  rgb colours have only 10
     // rows: 2.6 instead of 4.2 KiB, 7.6 KiB of LDS per wave in all -- five resident waves per SIMD instead of four
     // (same-box A/B, round 3: 0.377 -> 0.359 ms at cfg2, 0.547 -> 0.515 ms at 2.4 M Gaussians)
@@ -821,7 +835,7 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
     // (four lanes x 16 bytes).  Round 3 stored floats 6..9 of a row from the Gaussian loop and the geometry part after
     // it: two or three partial 32-byte sectors per 48-byte row plus a flag byte = 134 bytes of HBM writes per row.
     constexpr bool STAGED = FRAME && CDIM == 3;
-    constexpr int TOTW = STAGED ? 10 : 8;
+    constexpr int TOTW = STAGED ? (AUX ? 11 : 10) : 8;
     __shared__ float s_tot[64][TOTW];
     __shared__ uint32_t s_slot[64];        // FRAME: emission slot of Gaussian i's gradient row (GS_NO_SLOT: no row)
     constexpr uint32_t GS_NO_SLOT = 0xffffffffu;
@@ -851,9 +865,22 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
     float4 c[4];
     float f[4][3], gr[4][3];
     bool inside[4];
+    float2 xfin[4], xck[4];  // AUX: final (D, A) and (D, A) at the bucket's start
+    float xgd[4], xga[4];    // AUX: dL/dD, dL/dA
+    (void)xfin; (void)xck; (void)xgd; (void)xga;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         c[k] = ck[64 * k + lane];
+        if constexpr (AUX) {
+            const uint32_t id_y = id_y0 + 4 * k;
+            xfin[k] = X.padded[(size_t)id_y * G.padW + id_x];
+            xck[k] = base == 0 ? make_float2(0.f, 0.f) : X.ckpt[raster_ckpt_slot(start, tile, base / GS_BUCKET) * 256 + 64 * k + lane];
+            const int ox = (int)id_x - G.crop_left, oy = (int)id_y - G.crop_top;
+            const bool in = ox >= 0 && ox < G.width && oy >= 0 && oy < G.height;
+            const size_t pi = (size_t)(in ? oy : 0) * G.width + (in ? ox : 0);
+            xgd[k] = (in && X.grad_depth) ? X.grad_depth[pi] : 0.f;
+            xga[k] = (in && X.grad_alpha) ? X.grad_alpha[pi] : 0.f;
+        }
         const uint32_t id_y = id_y0 + 4 * k;
         const float *cf = I.c_final + ((size_t)id_y * G.padW + id_x) * 3;
         const int ox = FRAME ? (int)id_x - G.crop_left : (int)id_x, oy = FRAME ? (int)id_y - G.crop_top : (int)id_y;
@@ -892,6 +919,7 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             s_g[FC2][lane] = r2;
         }
         s_id[lane] = FRAME ? gid : jl;
+        if constexpr (AUX) s_dep[lane] = S.geom[(size_t)gid * GS_REC_STRIDE].z;
         uint32_t myslot = GS_NO_SLOT;
         if (valid && FRAME) {
             const uint4 rc = O.rects[gid];
@@ -905,6 +933,7 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
     }
     // pixel pairs: h = 0: rows y0, y0 + 4 (k = 0, 1); h = 1: rows y0 + 8, y0 + 12 (k = 2, 3)
     f2 py2[2], T[2], rho[2], g0[2], g1[2], g2[2], SHB[2][NB];
+    f2 gD[AUX ? 2 : 1], gA[AUX ? 2 : 1];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if constexpr (CDIM > 3) {
@@ -929,6 +958,12 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             const float4 ci = base == 0 ? make_float4(1.f, 0.f, 0.f, 0.f) : c[k];
             Tk[e] = ci.x;
             rk[e] = gr[k][0] * (f[k][0] - ci.y) + gr[k][1] * (f[k][1] - ci.z) + gr[k][2] * (f[k][2] - ci.w);
+            if constexpr (AUX)  // the maps' suffixes behind the bucket's start
+                rk[e] += xgd[k] * (xfin[k].x - xck[k].x) + xga[k] * (xfin[k].y - xck[k].y);
+        }
+        if constexpr (AUX) {
+            gD[h] = f2{xgd[2 * h], xgd[2 * h + 1]};
+            gA[h] = f2{xga[2 * h], xga[2 * h + 1]};
         }
         T[h] = f2{Tk[0], Tk[1]};
         rho[h] = f2{rk[0], rk[1]};
@@ -971,7 +1006,9 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
         const uint32_t id_i = id_next;
         const float dx = px - gx;
         const float bdx = uB * dx, adx2 = uA * dx * dx;
-        f2 S1 = {0.f, 0.f}, Sy = S1, Syy = S1, Sq = S1, Sopa = S1;
+        f2 S1 = {0.f, 0.f}, Sy = S1, Syy = S1, Sq = S1, Sopa = S1, Sd = S1;
+        const float dep_i = AUX ? s_dep[i] : 0.f;
+        (void)dep_i;
         f2 D[2][3];
         // A pixel pair (= a half of the tile: rows 8 h .. 8 h + 7) whose 128 pixels are all finished adds exact zeros to
         // every sum below and its transmittance no longer changes: it is left out (wave-uniform branch, re-evaluated
@@ -1025,7 +1062,11 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             const f2 araw = Gv * splat(opa);
             const f2 alpha = {l0 ? araw.x : 0.f, l1 ? araw.y : 0.f};
             const f2 w = alpha * T[h];
-            const f2 gc = pk_fma(g2[h], c2, pk_fma(g1[h], c1, g0[h] * c0));
+            f2 gc = pk_fma(g2[h], c2, pk_fma(g1[h], c1, g0[h] * c0));
+            if constexpr (AUX) {
+                gc += pk_fma(gD[h], splat(dep_i), gA[h]);  // the two maps as colour channels d_i and 1
+                Sd = pk_fma(gD[h], w, Sd);
+            }
             rho[h] = pk_fma(-w, gc, rho[h]);
             f2 d_alpha = pk_fma(T[h], gc, -(rho[h] * rc));
             d_alpha = f2{l0 ? d_alpha.x : 0.f, l1 ? d_alpha.y : 0.f};
@@ -1062,6 +1103,7 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             if (m == 4) return Syy.x + Syy.y;      // Syy
             if (m == 5) return Sq.x + Sq.y;        // Sq
             if (m == 6) return Sopa.x + Sopa.y;
+            if (AUX && m == NROW0) return Sd.x + Sd.y;
             const int ch = (m - 7) / NB, k = (m - 7) % NB;
             if constexpr (CDIM > 3) {
 #if GS_BWD_SH_SCALAR_ROWS
@@ -1108,7 +1150,10 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             } else if (FRAME) {
                 const uint32_t sl = s_slot[i];  // sum dL/dalpha G (opacity), then the coefficient sums (row layout: gs_frame_layout.h)
                 if (sl != GS_NO_SLOT)
-                    O.rows[(size_t)sl * gs_row_floats(CDIM) + (lane == 6 ? gs_row_geo(CDIM, 6) : gs_row_col(CDIM, lane - 7))] = t;
+                    O.rows[(size_t)sl * gs_row_floats(CDIM) +
+                           (lane == 6                  ? gs_row_geo(CDIM, 6)
+                            : (AUX && lane == NROW0) ? gs_row_aux_depth(CDIM)
+                                                     : gs_row_col(CDIM, lane - 7))] = t;
             } else {
                 const size_t j = id_i;
                 if (lane == 6)
@@ -1146,6 +1191,7 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                     for (int e = 0; e < 7; ++e) used = used || m == gs_row_geo(CDIM, e);
 #pragma unroll
                     for (int e = 0; e < CDIM; ++e) used = used || m == gs_row_col(CDIM, e);
+                    if (AUX) used = used || m == gs_row_aux_depth(CDIM);
                     if (!used) row[m] = 0.f;
                 }
             }
@@ -1170,12 +1216,39 @@ raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (qd == 0) v = make_float4(t[0], t[1], t[2], t[3]);
             else if (qd == 1) v = make_float4(t[4], t[5], t[6], t[7]);
-            else if (qd == 2) v = make_float4(t[8], t[9], 0.f, 0.f);
+            else if (qd == 2) v = make_float4(t[8], t[9], AUX ? t[TOTW - 1] : 0.f, 0.f);  // (AUX: float 10 = the depth sum)
             reinterpret_cast<float4 *>(O.rows + (size_t)sl * gs_row_floats(3))[qd] = v;
         }
     }
     lds_order();  // (the next bucket of this wave reuses the LDS arrays)
     }
+}
+
+template <int CDIM, bool FRAME, bool EXACT = false>
+__global__ void __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu(CDIM == 48 ? GS_BWD_SH48_WPE : CDIM == 3 ? 5 : GS_BWD_SH_WPE)))  // rgb: five (LDS: 7.9 KiB per wave)
+raster_backward_pixel_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
+    raster_backward_pixel_sh_body<CDIM, FRAME, EXACT, false>(S, G, I, O, AuxBwdIn{});
+}
+
+// GS_FRAME_AUX training frames, every colour model (the rgb row-layout kernel and the SH kernel on the matrix pipe carry no
+// depth / alpha terms).  rgb: four waves per SIMD (the depth row and field add ~0.8 KiB of LDS per wave).
+// SH: one step fewer than the plain kernel (degree 2: three, degree 3: two waves per SIMD) -- at the plain kernel's budget the
+// allocator spilled inside the per-Gaussian loop (tests/test_aux_host.py).
+#ifndef GS_BWD_AUX_RGB_WPE
+#define GS_BWD_AUX_RGB_WPE 4
+#endif
+#ifndef GS_BWD_AUX_SH27_WPE
+#define GS_BWD_AUX_SH27_WPE 3
+#endif
+#ifndef GS_BWD_AUX_SH48_WPE
+#define GS_BWD_AUX_SH48_WPE 2
+#endif
+template <int CDIM>
+__global__ void __launch_bounds__(64)
+__attribute__((amdgpu_waves_per_eu(CDIM == 48 ? GS_BWD_AUX_SH48_WPE : CDIM == 3 ? GS_BWD_AUX_RGB_WPE : GS_BWD_AUX_SH27_WPE)))
+raster_aux_backward_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O, AuxBwdIn X) {
+    raster_backward_pixel_sh_body<CDIM, true, false, true>(S, G, I, O, X);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2510,13 +2583,15 @@ int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const ui
                        FG.n_tiles, ws.tile_ranges, sorted_ids, ws.rects, (unsigned long long *)ws.stop_keys);
     // the bucket work list is what the one-wave-per-bucket kernels read; the SH backward on the matrix pipe walks a
     // tile's buckets itself (one workgroup per tile) and needs none
+    // (GS_FRAME_AUX frames of every colour model take the one-wave-per-bucket pixel kernel: they need the list)
     const bool per_tile = ((f->color_dim == 48 && GS_BWD_SH_MFMA >= 1) || (f->color_dim == 27 && GS_BWD_SH_MFMA >= 2)) &&
-                          (GS_MFMA_ITEMS || !gs_frame_long_lists(f, FG.n_tiles));  // (no items + flagged frame: the buckets
+                          (GS_MFMA_ITEMS || !gs_frame_long_lists(f, FG.n_tiles)) && !(f->flags & GS_FRAME_AUX);  // (no items + flagged frame: the buckets
                                                                                     // beyond a tile's first 32: hand-over)
     if (!per_tile)
         gs_launch_bucket_list(ws.tile_nproc, FG.n_tiles, ws.bucket_offsets, ws.counters + GS_CNT_BUCKETS, ws.bucket_info,
                               ws.tile_ranges, 1, stream);
-    const bool mfma_frame = (f->color_dim == 48 && GS_BWD_SH_MFMA >= 1) || (f->color_dim == 27 && GS_BWD_SH_MFMA >= 2);
+    const bool mfma_frame = ((f->color_dim == 48 && GS_BWD_SH_MFMA >= 1) || (f->color_dim == 27 && GS_BWD_SH_MFMA >= 2)) &&
+                            !(f->flags & GS_FRAME_AUX);
     if (mfma_frame && GS_MFMA_ITEMS) {  // the matrix-pipe kernel's work items, heavy tiles first where the frame has an order
         const uint32_t cap = 0u;  // (work items spread a long list over the device: no hand-over, see gs_stage_raster_backward)
         hipLaunchKernelGGL(mfma_items_kernel, dim3(1), dim3(1024), 0, stream, ws.tile_nproc, FG.n_tiles,
@@ -2571,7 +2646,20 @@ int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uin
     if (!GS_MFMA_ITEMS && f->color_dim != 3 && gs_frame_long_lists(f, FG.n_tiles))
         I.bucket_cap = I.bucket_first = GS_BWD_SH_HANDOVER;
     BwdOut O = {ws.rows, ws.bwd_exec_rows, ws.pair_offsets, ws.rects, (uint64_t)f->max_pairs, nullptr, nullptr, nullptr, nullptr};
-    if (f->color_dim == 48)
+    if (f->flags & GS_FRAME_AUX) {
+        // every bucket of the work list (gs_stage_backward_prepare builds it for aux frames of every colour model) on the
+        // one-wave-per-bucket pixel kernel, grid as in launch_bwd
+        I.bucket_cap = I.bucket_first = 0;
+        const AuxBwdIn X = {(const float2 *)f->aux_padded, gs_frame_aux(f).ckpt, f->grad_depth, f->grad_alpha};
+        const int64_t mb = ws.max_buckets;
+        const unsigned fgrid = (unsigned)(mb > 0 ? (mb < GS_BWD_GRID_CAP ? mb : GS_BWD_GRID_CAP) : 1);
+        if (f->color_dim == 48)
+            hipLaunchKernelGGL(raster_aux_backward_kernel<48>, dim3(fgrid), dim3(64), 0, stream, S, G, I, O, X);
+        else if (f->color_dim == 27)
+            hipLaunchKernelGGL(raster_aux_backward_kernel<27>, dim3(fgrid), dim3(64), 0, stream, S, G, I, O, X);
+        else
+            hipLaunchKernelGGL(raster_aux_backward_kernel<3>, dim3(fgrid), dim3(64), 0, stream, S, G, I, O, X);
+    } else if (f->color_dim == 48)
         launch_bwd<48, true>(S, G, I, O, ws.max_buckets, stream);
     else if (f->color_dim == 27)
         launch_bwd<27, true>(S, G, I, O, ws.max_buckets, stream);

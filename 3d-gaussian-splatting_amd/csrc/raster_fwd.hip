@@ -104,24 +104,35 @@ __device__ __forceinline__ f2 live_mask(f2 t, f2 scale, f2 bias) {
 #ifndef GS_FWD_SH48_WPE
 #define GS_FWD_SH48_WPE 2
 #endif
-template <int CDIM, bool FRAME, bool CKPT, bool SIG, bool WN, bool EXACT = false>
-__global__ void __launch_bounds__(FWD_THREADS)
-__attribute__((amdgpu_waves_per_eu(CDIM == 48 ? GS_FWD_SH48_WPE : CDIM == 27 ? GS_FWD_SH27_WPE
-                                               : (SIG || WN || EXACT) ? 1 : GS_FWD_RGB_WPE)))  // (the rare flags would spill at 128)
-raster_forward_kernel(RasterSrc S, RasterGeom G,
-                                                                    const int32_t *__restrict__ ranges,
-                                                                    float *__restrict__ out_padded,
-                                                                    float *__restrict__ out_image,
-                                                                    float4 *__restrict__ ckpt,
-                                                                    uint32_t *__restrict__ tile_nproc,
-                                                                    uint32_t n_tiles,
-                                                                    float4 *__restrict__ cont_state,
-                                                                    uint32_t *__restrict__ cont_flag,
-                                                                    const uint32_t *__restrict__ tile_order,
-                                                                    uint32_t *__restrict__ tile_cost,
-                                                                    const uint32_t *cut_in, uint32_t *cut_out,
-                                                                    unsigned long long *__restrict__ ranpast,
-                                                                    const unsigned long long *__restrict__ gate) {
+// Outputs of the depth / alpha maps (GS_FRAME_AUX): the aux entry point below passes them, the plain kernel an empty set.
+struct AuxFwdOut {
+    float2 *padded;  // [padH, padW] (D, A) raw sums
+    float *depth;    // [H, W] cropped, may be NULL
+    float *alpha;    // [H, W] cropped, may be NULL
+    float2 *ckpt;    // training: [max_buckets][256] (D, A) at bucket starts (the slots of the colour checkpoints)
+};
+
+// The body of the compositing kernel.  AUX = true (raster_aux_forward_kernel): two more accumulators per pixel -- D = sum w d
+// with d = rec_geom.z staged in LDS as one more field, and A = sum w accumulated exactly like a colour channel of value
+// 1.0 -- with their checkpoints and maps; everything else (stop, cut table, order, statistics) as in the plain kernel.
+// AUX = false compiles to the plain kernel unchanged.
+template <int CDIM, bool FRAME, bool CKPT, bool SIG, bool WN, bool EXACT, bool AUX>
+__device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
+                                                    const int32_t *__restrict__ ranges,
+                                                    float *__restrict__ out_padded,
+                                                    float *__restrict__ out_image,
+                                                    float4 *__restrict__ ckpt,
+                                                    uint32_t *__restrict__ tile_nproc,
+                                                    uint32_t n_tiles,
+                                                    float4 *__restrict__ cont_state,
+                                                    uint32_t *__restrict__ cont_flag,
+                                                    const uint32_t *__restrict__ tile_order,
+                                                    uint32_t *__restrict__ tile_cost,
+                                                    const uint32_t *cut_in, uint32_t *cut_out,
+                                                    unsigned long long *__restrict__ ranpast,
+                                                    const unsigned long long *__restrict__ gate,
+                                                    const AuxFwdOut &X) {
+    static_assert(!AUX || (FRAME && !SIG && !WN && !EXACT), "depth / alpha maps belong to the frame path");
     static_assert(!(EXACT && FRAME), "the exact-exp flavour belongs to the reference API (gs_draw, fast = 0)");
     // frame path, temporal occlusion cull (gs_frame_layout.h): `cut_out` [T] receives, per tile, the depth behind which this
     // launch composited nothing (all its pixels had stopped) or GS_NO_CUT; `cut_in` (the same table, set when this frame's
@@ -143,6 +154,7 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
 #endif
     constexpr uint32_t LIVE_EVERY = CDIM == 3 ? GS_FWD_LIVE_EVERY : 4;
     __shared__ SM sm;
+    __shared__ float s_dep[AUX ? SM::NBUF : 1][AUX ? CH : 1] __attribute__((aligned(16)));  // AUX: d of the chunk's Gaussians
     const int lane = threadIdx.x;
 
     auto range_of = [&](uint32_t t, uint32_t &s0, uint32_t &cnt) {
@@ -171,6 +183,7 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
     GaussianRec g;
     float r0 = 0, r1 = 0, r2 = 0;
     float4 cq = make_float4(0.f, 0.f, 0.f, 0.f);
+    float dz = 0.f;  // AUX: the Gaussian's depth |p_c| (rec_geom.z, the sort key)
     uint32_t gid = 0, gj = 0;
     bool have = false;
     auto fetch = [&](uint32_t s0, uint32_t cnt, uint32_t base) {
@@ -179,6 +192,7 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
             gj = s0 + base + lane;
             gid = raster_load<FRAME>(S, gj, g);
             if (FRAME) cq = S.conic4[(size_t)gid * GS_REC_STRIDE];
+            if constexpr (AUX) dz = S.geom[(size_t)gid * GS_REC_STRIDE].z;
             if (CDIM == 3) raster_load_rgb<FRAME>(S, gj, gid, r0, r1, r2);
         }
     };
@@ -218,6 +232,11 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
         T[h] = f2{1.0f, 1.0f};
         cr[h] = cg[h] = cb[h] = accw[h] = f2{0.f, 0.f};
     }
+    f2 cd[AUX ? NPP : 1], ca[AUX ? NPP : 1];  // AUX: sum w d, sum w
+    if constexpr (AUX) {
+#pragma unroll
+        for (int h = 0; h < NPP; ++h) cd[h] = ca[h] = f2{0.f, 0.f};
+    }
     f2 live_scale = splat(GS_LIVE_SCALE), live_bias = splat(-GS_T_STOP * GS_LIVE_SCALE);
     // opaque to the compiler: otherwise it keeps the two constants in SGPRs and copies them into VGPR pairs for the
     // inline v_pk_fma inside the hot loop (two v_mov_b64 per four Gaussians)
@@ -230,6 +249,14 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
         for (int h = 0; h < NPP; ++h) {
             c[128 * h + lane] = make_float4(T[h].x, cr[h].x, cg[h].x, cb[h].x);
             c[128 * h + 64 + lane] = make_float4(T[h].y, cr[h].y, cg[h].y, cb[h].y);
+        }
+        if constexpr (AUX) {
+            float2 *a = X.ckpt + raster_ckpt_slot(start, tile, idx_in_tile / GS_BUCKET) * 256;
+#pragma unroll
+            for (int h = 0; h < NPP; ++h) {
+                a[128 * h + lane] = make_float2(cd[h].x, ca[h].x);
+                a[128 * h + 64 + lane] = make_float2(cd[h].y, ca[h].y);
+            }
         }
     };
     auto any_live = [&]() {
@@ -301,6 +328,7 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
             // frame path: the opacity (a sigmoid, > 0) rides in the exponent, alpha = 2^-(q + nlop); the
             // reference API may be handed any opacity (zero, negative), so it keeps the multiplication
             sm.f[buf][SM::NLOP][lane] = FRAME ? -__log2f(opa) : opa;
+            if constexpr (AUX) s_dep[buf][lane] = dz;
             if constexpr (CDIM == 3) {
                 // a NaN colour must reach the LIVE pixels only (the reference never evaluates the Gaussian for a
                 // finished one); 0 x NaN in the colour FMAs would poison every pixel, so the NaN is moved into the
@@ -322,6 +350,7 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
 #pragma unroll
             for (int q = 0; q < SM::NFIELD; ++q)  // (exact flavour: denominator 1, so that the null Gaussian's alpha is 0 x exp(0))
                 sm.f[buf][q][lane] = (FRAME && q == SM::NLOP) ? 1e30f : (EXACT && q == SM::DH) ? 1.0f : 0.f;
+            if constexpr (AUX) s_dep[buf][lane] = 0.f;
             if constexpr (CDIM > 3) {
 #pragma unroll
                 for (int q = 0; q < CDIM; ++q) sm.sh[buf][lane][q] = 0.f;
@@ -375,7 +404,12 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
                 DH4 = ld4(SM::DH);
                 DL4 = ld4(SM::DL);
             }
-            Vg R4 = {}, G4 = {}, L4 = {};
+            Vg R4 = {}, G4 = {}, L4 = {}, D4 = {};
+            if constexpr (AUX) {
+                static_assert(GROUP == 4, "AUX: the depths are read four at a time");
+                const float4 t = *(const float4 *)__builtin_assume_aligned(&s_dep[buf][i + i4], 16);
+                D4.v[0] = t.x; D4.v[1] = t.y; D4.v[2] = t.z; D4.v[3] = t.w;
+            }
             if constexpr (CDIM == 3) {
                 R4 = ld4(SM::R);
                 G4 = ld4(SM::G);
@@ -444,6 +478,14 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
                         cb[h] = pk_fma(w, c2, cb[h]);
                     }
                     if (WN) accw[h] += w;
+                    if constexpr (AUX) {  // alpha: a colour channel of value 1.0 (fma(1, w, a) == a + w)
+                        cd[h] = pk_fma(splat(D4.v[u]), w, cd[h]);
+                        // w opaque here: otherwise a + alpha x T is contracted into one fma, which rounds differently
+                        // from the colour channels' fma(c, w, C) of the ROUNDED w
+                        f2 wr = w;
+                        asm("" : "+v"(wr));
+                        ca[h] += wr;
+                    }
                     const f2 t = T[h] - w;  // T * (1 - alpha)
                     T[h] = t * live_mask(t, live_scale, live_bias);
                 }
@@ -491,6 +533,15 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
             if (!WN || aw < 0.01f) aw = 1.0f;  // gaussian.cu:964-969
             const float o0 = (e ? cr[h].y : cr[h].x) / aw, o1 = (e ? cg[h].y : cg[h].x) / aw,
                         o2 = (e ? cb[h].y : cb[h].x) / aw;
+            if constexpr (AUX) {
+                const float dv = e ? cd[h].y : cd[h].x, av = e ? ca[h].y : ca[h].x;
+                if (X.padded) X.padded[(size_t)id_y * G.padW + id_x] = make_float2(dv, av);
+                const int ox = (int)id_x - G.crop_left, oy = (int)id_y - G.crop_top;
+                if (ox >= 0 && ox < G.width && oy >= 0 && oy < G.height) {  // cropped like the image, not clamped
+                    if (X.depth) X.depth[(size_t)oy * G.width + ox] = dv;
+                    if (X.alpha) X.alpha[(size_t)oy * G.width + ox] = av;
+                }
+            }
             if (out_padded) {
                 float *o = out_padded + ((size_t)id_y * G.padW + id_x) * 3;
                 o[0] = o0;
@@ -509,6 +560,44 @@ raster_forward_kernel(RasterSrc S, RasterGeom G,
             }
         }
     }  // tile loop
+}
+
+template <int CDIM, bool FRAME, bool CKPT, bool SIG, bool WN, bool EXACT = false>
+__global__ void __launch_bounds__(FWD_THREADS)
+__attribute__((amdgpu_waves_per_eu(CDIM == 48 ? GS_FWD_SH48_WPE : CDIM == 27 ? GS_FWD_SH27_WPE
+                                               : (SIG || WN || EXACT) ? 1 : GS_FWD_RGB_WPE)))  // (the rare flags would spill at 128)
+raster_forward_kernel(RasterSrc S, RasterGeom G, const int32_t *__restrict__ ranges, float *__restrict__ out_padded,
+                      float *__restrict__ out_image, float4 *__restrict__ ckpt, uint32_t *__restrict__ tile_nproc,
+                      uint32_t n_tiles, float4 *__restrict__ cont_state, uint32_t *__restrict__ cont_flag,
+                      const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost, const uint32_t *cut_in,
+                      uint32_t *cut_out, unsigned long long *__restrict__ ranpast,
+                      const unsigned long long *__restrict__ gate) {
+    raster_forward_body<CDIM, FRAME, CKPT, SIG, WN, EXACT, false>(S, G, ranges, out_padded, out_image, ckpt, tile_nproc,
+                                                                  n_tiles, cont_state, cont_flag, tile_order, tile_cost,
+                                                                  cut_in, cut_out, ranpast, gate, AuxFwdOut{});
+}
+
+// GS_FRAME_AUX frames (frame path only): the compositing with the depth and alpha maps.  No segmented compositing of long
+// lists (the frame walks every list with one wave, as GS_FRAME_SERIAL_LONG_LISTS frames do).  Register budget: the four
+// accumulators and the staged depth do not fit the rgb kernel's 128 VGPRs -- three waves per SIMD (budgets:
+// tests/test_aux_host.py).
+#ifndef GS_FWD_AUX_RGB_WPE
+#define GS_FWD_AUX_RGB_WPE 3
+#endif
+#ifndef GS_FWD_AUX_SH27_WPE
+#define GS_FWD_AUX_SH27_WPE GS_FWD_SH27_WPE
+#endif
+template <int CDIM, bool CKPT>
+__global__ void __launch_bounds__(FWD_THREADS)
+__attribute__((amdgpu_waves_per_eu(CDIM == 48 ? GS_FWD_SH48_WPE : CDIM == 27 ? GS_FWD_AUX_SH27_WPE : GS_FWD_AUX_RGB_WPE)))
+raster_aux_forward_kernel(RasterSrc S, RasterGeom G, const int32_t *__restrict__ ranges, float *__restrict__ out_padded,
+                          float *__restrict__ out_image, float4 *__restrict__ ckpt, uint32_t *__restrict__ tile_nproc,
+                          uint32_t n_tiles, const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost,
+                          const uint32_t *cut_in, uint32_t *cut_out, unsigned long long *__restrict__ ranpast,
+                          const unsigned long long *__restrict__ gate, AuxFwdOut X) {
+    raster_forward_body<CDIM, true, CKPT, false, false, false, true>(S, G, ranges, out_padded, out_image, ckpt, tile_nproc,
+                                                                     n_tiles, nullptr, nullptr, tile_order, tile_cost,
+                                                                     cut_in, cut_out, ranpast, gate, X);
 }
 
 // =================================================================================================================
@@ -966,8 +1055,10 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
         G.vdy[i] = f->vec_dy[i];
     }
     // dense frames: tiles still alive after GS_LONG_MIN Gaussians hand the rest of their list to the segment kernels
+    // (GS_FRAME_AUX frames walk every list with one wave: the segment kernels carry no depth / alpha)
+    const bool aux = (f->flags & GS_FRAME_AUX) != 0;
     const bool dense = gs_frame_long_lists(f, FG.n_tiles) && ws.cont_state != nullptr &&
-                       !(f->flags & GS_FRAME_SERIAL_LONG_LISTS);
+                       !(f->flags & GS_FRAME_SERIAL_LONG_LISTS) && !aux;
     float4 *cs = dense ? ws.cont_state : nullptr;
     uint32_t *cf = dense ? ws.cont_flag : nullptr;
     // longest-first dispatch: the order is written by the strip variant's project + count launch and the cost is recorded
@@ -991,7 +1082,31 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
             launch_fwd<CD, true, false, false>(S, G, ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, 0,   \
                                                stream, cs, cf, order, cost, cut_in, ws.cut, ranpast, gate);            \
     } while (0)
-    if (f->color_dim == 48)
+    if (aux) {
+        if (!fwd_plan().order) order = nullptr;
+        const uint32_t T = (uint32_t)FG.n_tiles;
+        const uint32_t grid = gate ? (T < 1024u ? T : 1024u) : fwd_grid(T);
+        const gs_frame_aux_ws aw = gs_frame_aux(f);
+        AuxFwdOut X = {(float2 *)f->aux_padded, f->depth, f->alpha, aw.ckpt};
+#define GS_LAUNCH_AUX_FWD(CD)                                                                                           \
+    do {                                                                                                                \
+        if (f->training)                                                                                                \
+            hipLaunchKernelGGL((raster_aux_forward_kernel<CD, true>), dim3(grid), dim3(FWD_THREADS), 0, stream, S, G,    \
+                               ws.tile_ranges, f->image_padded, f->image, ws.ckpt, ws.tile_nproc, T, order, cost,       \
+                               nullptr, nullptr, ranpast, nullptr, X);                                                  \
+        else                                                                                                            \
+            hipLaunchKernelGGL((raster_aux_forward_kernel<CD, false>), dim3(grid), dim3(FWD_THREADS), 0, stream, S, G,   \
+                               ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, T, order, cost, cut_in,     \
+                               ws.cut, ranpast, gate, X);                                                               \
+    } while (0)
+        if (f->color_dim == 48)
+            GS_LAUNCH_AUX_FWD(48);
+        else if (f->color_dim == 27)
+            GS_LAUNCH_AUX_FWD(27);
+        else
+            GS_LAUNCH_AUX_FWD(3);
+#undef GS_LAUNCH_AUX_FWD
+    } else if (f->color_dim == 48)
         GS_LAUNCH_FRAME_FWD(48);
     else if (f->color_dim == 27)
         GS_LAUNCH_FRAME_FWD(27);

@@ -117,6 +117,8 @@ class FrameRenderer:
         # + per-tile LDS sort (all three give the same list)
         self.sort_mode = int(sort_mode)
         self._ws: Optional[torch.Tensor] = None
+        self._aux_ws: Optional[torch.Tensor] = None  # GS_FRAME_AUX frames: the library's second workspace (grown with the first)
+        self._aux_keep = None  # (depth, alpha, aux_padded) of the last forward, kept for its backward
         self._stats_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
         self._frame: Optional[_lib.GsFrame] = None
         self._frame_serial = 0  # counts forwards: autograd checks that backward() belongs to the latest one
@@ -130,7 +132,7 @@ class FrameRenderer:
         self.overflowed_frames = 0  # frames that were rendered empty / truncated and could not be redone (see forward)
 
     # ------------------------------------------------------------------ frame descriptor
-    def _describe(self, pos, quat, scale, opa, rgb, camera, training) -> _lib.GsFrame:
+    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrame:
         # A viewer or a benchmark renders the same tensors from the same camera object again and again: the descriptor
         # of the previous call is reused as long as nothing it was built from has changed (tensor identities and
         # storage, camera object, renderer settings) -- the validation below, ~40 ctypes stores and a library call cost
@@ -153,6 +155,7 @@ class FrameRenderer:
                self.emit_sorted_keys, self.slice_sort, self.table_bin, self.force_strips, self.serial_long_lists,
                self.long_lists, self._long_lists_seen, self._long_sort_seen, self.bwd_rows, self._bwd_rows_seen,
                self.occlusion_cull, self._cut_key, getattr(self, "_cut_ck", None), self._frame_serial >= self._cull_off_until,
+               bool(aux), self._aux_ws.data_ptr() if (aux and self._aux_ws is not None) else 0,
                self._ws.data_ptr() if self._ws is not None else 0)
         cached = getattr(self, "_desc_cache", None)
         if cached is not None and cached[0] == key:
@@ -160,15 +163,15 @@ class FrameRenderer:
             C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFrame))
             self._grid = cached[3]
             return f
-        f = self._describe_uncached(pos, quat, scale, opa, rgb, camera, training)
-        # (the key is taken again: building the descriptor may have (re)allocated the workspace)
-        key = key[:-1] + (self._ws.data_ptr(),)
+        f = self._describe_uncached(pos, quat, scale, opa, rgb, camera, training, aux)
+        # (the key is taken again: building the descriptor may have (re)allocated the workspaces)
+        key = key[:-2] + (self._aux_ws.data_ptr() if aux else 0, self._ws.data_ptr())
         keep = _lib.GsFrame()
         C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFrame))
         self._desc_cache = (key, keep, None, self._grid)
         return f
 
-    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training) -> _lib.GsFrame:
+    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrame:
         n = int(pos.shape[0])
         color_dim = int(rgb.shape[1]) if rgb.dim() == 2 else 1
         if color_dim not in (3, 27, 48):  # rgb logits, SH degree 2 (the reference's), SH degree 3 (extension)
@@ -247,6 +250,15 @@ class FrameRenderer:
         base = self._ws.data_ptr()
         f.workspace = (base + 255) // 256 * 256
         f.workspace_bytes = self._ws.numel() - (f.workspace - base)
+        if aux:  # GS_FRAME_AUX: the (depth, alpha) checkpoints live in a second workspace, sized and grown with the first
+            aux_need = _lib.gs_frame_aux_workspace_bytes(self.max_pairs, grid.width, grid.height, int(training))
+            if self._aux_ws is None or self._aux_ws.numel() < aux_need + 256:
+                self._release_workspace()  # (a backward of an earlier frame may still be queued against the old one)
+                self._aux_ws = torch.empty(int(aux_need) + 256, dtype=torch.uint8, device=self.device)
+            abase = self._aux_ws.data_ptr()
+            f.aux_workspace = (abase + 255) // 256 * 256
+            f.aux_workspace_bytes = self._aux_ws.numel() - (f.aux_workspace - abase)
+            f.flags |= _lib.GS_FRAME_AUX
         if getattr(self, "_cull_scene_key", None) != (pos.data_ptr(), n):
             # other tensors / another Gaussian count: what the cull was judged against no longer applies
             self._cull_scene_key, self._cull_full_pairs, self._cull_settled = (pos.data_ptr(), n), None, False
@@ -287,8 +299,11 @@ class FrameRenderer:
             pass
 
     # ------------------------------------------------------------------ low-level API
-    def forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None):
-        """Raw parameters -> (image [H,W,3] clamped+cropped, padded raw image or None).
+    def forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None, aux: bool = False):
+        """Raw parameters -> (image [H,W,3] clamped+cropped, padded raw image or None); with ``aux`` (GS_FRAME_AUX,
+        include/gs_abi.h) -> (image, padded, depth [H,W], alpha [H,W]): depth = sum w_i d_i with d_i the distance from the
+        camera centre, alpha = sum w_i, over the Gaussians the colour composites, cropped and not clamped.  A training aux
+        frame's ``backward`` takes grad_depth / grad_alpha as well.
 
         Capacity (``max_pairs``) and ``auto_grow``: ``True`` reads the frame's counters after every frame (one host
         synchronisation) and redoes an overflowed frame in a larger workspace.  ``"async"`` does that for the FIRST
@@ -300,7 +315,10 @@ class FrameRenderer:
         to the fused Adam so that such a step is skipped on the device.  ``False`` never checks."""
         training = self.training if training is None else training
         with torch.cuda.device(self.device):
-            return self._forward(pos, quat, scale, opa, rgb, camera, training)
+            image, padded = self._forward(pos, quat, scale, opa, rgb, camera, training, aux)
+        if aux:
+            return image, padded, self._aux_keep[0], self._aux_keep[1]
+        return image, padded
 
     # auto_grow="async": how many frames the host may issue beyond the frame whose counters are still on their way.  A
     # Python loop issues a training step in ~0.1 ms and the device takes ~1 ms for it: unbounded, the host runs hundreds of
@@ -479,20 +497,21 @@ class FrameRenderer:
         self._poll_async_counters()
         return getattr(self, "_last_overflow_serial", -1) == self._frame_serial
 
-    def _forward(self, pos, quat, scale, opa, rgb, camera, training):
+    def _forward(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False):
         self._begun = None  # any frame opened by forward_begin lived in the workspace this frame is about to overwrite
         stream = self._stream().cuda_stream
         sync_check = self.auto_grow is True or (self.auto_grow == "async" and (not training or not self._checked_once))
         if self.auto_grow == "async":
             self._poll_async_counters()
         while True:
-            f = self._describe(pos, quat, scale, opa, rgb, camera, training)
+            f = self._describe(pos, quat, scale, opa, rgb, camera, training, aux)
             g = self._grid
             image = torch.empty(g.height, g.width, 3, device=self.device, dtype=torch.float32)
             padded = torch.empty(g.padded_height, g.padded_width, 3, device=self.device,
                                  dtype=torch.float32) if training else None
             f.image = image.data_ptr()
             f.image_padded = padded.data_ptr() if padded is not None else None
+            self._aux_keep = self._aux_outputs(f, training) if aux else None
             _lib.check(_lib.gs_frame_forward(C.byref(f), stream), "gs_frame_forward")
             self._frame = f
             self._frame_serial += 1
@@ -519,6 +538,18 @@ class FrameRenderer:
                 self._async_serial = self._frame_serial
             break
         return image, padded
+
+    def _aux_outputs(self, f, training):
+        """(depth, alpha, aux_padded) of a GS_FRAME_AUX frame, wired into the descriptor ``f``."""
+        g = self._grid
+        depth = torch.empty(g.height, g.width, device=self.device, dtype=torch.float32)
+        alpha = torch.empty(g.height, g.width, device=self.device, dtype=torch.float32)
+        aux_padded = torch.empty(g.padded_height, g.padded_width, 2, device=self.device,
+                                 dtype=torch.float32) if training else None
+        f.depth, f.alpha = depth.data_ptr(), alpha.data_ptr()
+        f.aux_padded = aux_padded.data_ptr() if aux_padded is not None else None
+        f.grad_depth = f.grad_alpha = None
+        return depth, alpha, aux_padded
 
     # ------------------------------------------------------------------ a frame in two phases (view-parallel trainer)
     def forward_begin(self, pos, quat, scale, opa, rgb, camera, slice_begin: int, slice_end: int,
@@ -645,9 +676,11 @@ class FrameRenderer:
                                                    self._stream().cuda_stream), "gs_frame_backward_adam")
         self._bwd_serial = self._frame_serial
 
-    def backward(self, grad_image, out=None, part: int = 0):
+    def backward(self, grad_image, out=None, part: int = 0, grad_depth=None, grad_alpha=None):
         """dL/d(image) -> (grad_pos, grad_quat, grad_scale, grad_opa, grad_rgb).  ``out`` may
         supply the five destination tensors (e.g. views of one flat all-reduce bucket).
+        After ``forward(..., aux=True)``: ``grad_depth`` / ``grad_alpha`` [H,W] are dL/d(depth), dL/d(alpha) (None = zero);
+        ``grad_image`` may then be None (zero) as well.
 
         ``part`` (view-parallel gradient exchange, gs_dp.py): 0 = everything; ``_lib.GS_BWD_RASTER`` = only the
         raster backward (per-pair rows), then ``GS_BWD_GEOMETRY`` (pos / quat / scale) and ``GS_BWD_COLOR`` (opa /
@@ -659,6 +692,22 @@ class FrameRenderer:
         pos, quat, scale, opa, rgb = self._keep[:5]
         if out is None:
             out = tuple(torch.empty_like(t) for t in (pos, quat, scale, opa, rgb))
+        aux = bool(f.flags & _lib.GS_FRAME_AUX)
+        if not aux and (grad_depth is not None or grad_alpha is not None):
+            raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
+        if aux and part in (0, _lib.GS_BWD_RASTER):
+            maps = []
+            for name, t in (("grad_depth", grad_depth), ("grad_alpha", grad_alpha)):
+                if t is not None:
+                    t = t.contiguous()
+                    if t.dtype != torch.float32 or tuple(t.shape) != (f.height, f.width):
+                        raise RuntimeError(f"{name} must be float32 [H,W]")
+                maps.append(t)
+            grad_depth, grad_alpha = maps
+            f.grad_depth = grad_depth.data_ptr() if grad_depth is not None else None
+            f.grad_alpha = grad_alpha.data_ptr() if grad_alpha is not None else None
+            if grad_image is None:
+                grad_image = torch.zeros(f.height, f.width, 3, device=self.device, dtype=torch.float32)
         if part in (0, _lib.GS_BWD_RASTER):
             grad_image = grad_image.contiguous()
             if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
@@ -678,18 +727,19 @@ class FrameRenderer:
             self._bwd_serial = self._frame_serial  # this frame's bucket counter is final once the stream gets here
         return out
 
-    def profile_forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None):
+    def profile_forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None, aux: bool = False):
         """One forward frame with every stage bracketed by hipEvents (synchronises).  Returns
         {stage: ms}; the raster stage is exactly one kernel launch."""
         training = self.training if training is None else training
         self._begun = None
-        f = self._describe(pos, quat, scale, opa, rgb, camera, training)
+        f = self._describe(pos, quat, scale, opa, rgb, camera, training, aux)
         g = self._grid
         image = torch.empty(g.height, g.width, 3, device=self.device, dtype=torch.float32)
         padded = torch.empty(g.padded_height, g.padded_width, 3, device=self.device,
                              dtype=torch.float32) if training else None
         f.image = image.data_ptr()
         f.image_padded = padded.data_ptr() if padded is not None else None
+        self._aux_keep = self._aux_outputs(f, training) if aux else None
         ms = (C.c_float * 6)()
         with torch.cuda.device(self.device):
             _lib.check(_lib.gs_frame_forward_profile(C.byref(f), ms, self._stream().cuda_stream),
@@ -878,6 +928,14 @@ class FrameRenderer:
             return _FrameFunction.apply(pos, quat, scale, opa, rgb, self, camera)
         return self.forward(pos, quat, scale, opa, rgb, camera, training=False)[0]
 
+    def render_aux(self, pos, quat, scale, opa, rgb, camera):
+        """Differentiable frame with its depth and alpha maps: -> (image [H,W,3], depth [H,W], alpha [H,W]) (GS_FRAME_AUX;
+        see ``forward``).  The expected depth is ``depth / alpha`` -- left to torch, so that autograd handles it."""
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (pos, quat, scale, opa, rgb)):
+            return _FrameAuxFunction.apply(pos, quat, scale, opa, rgb, self, camera)
+        image, _, depth, alpha = self.forward(pos, quat, scale, opa, rgb, camera, training=False, aux=True)
+        return image, depth, alpha
+
 
 class _FrameFunction(torch.autograd.Function):
     @staticmethod
@@ -894,4 +952,22 @@ class _FrameFunction(torch.autograd.Function):
         if r._frame_serial != ctx.frame_serial:
             raise RuntimeError("FrameRenderer workspace was reused by another forward before backward()")
         g = r.backward(grad_image)
+        return (*g, None, None)
+
+
+class _FrameAuxFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, quat, scale, opa, rgb, renderer, camera):
+        image, _, depth, alpha = renderer.forward(pos.detach(), quat.detach(), scale.detach(), opa.detach(), rgb.detach(),
+                                                  camera, training=True, aux=True)
+        ctx.renderer = renderer
+        ctx.frame_serial = renderer._frame_serial
+        return image, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_image, grad_depth, grad_alpha):
+        r = ctx.renderer
+        if r._frame_serial != ctx.frame_serial:
+            raise RuntimeError("FrameRenderer workspace was reused by another forward before backward()")
+        g = r.backward(grad_image, grad_depth=grad_depth, grad_alpha=grad_alpha)
         return (*g, None, None)

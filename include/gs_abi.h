@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8 (round 6): gs_frame_is_occlusion_culled; an occlusion-culled frame's first pass projects only the Gaussians that are not
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_AUX with the trailing
+ *   gs_frame fields depth / alpha / aux_padded / aux_workspace / aux_workspace_bytes / grad_depth / grad_alpha (read only
+ *   when the flag is set) and gs_frame_aux_workspace_bytes.
+ * 8 (round 6): gs_frame_is_occlusion_culled; an occlusion-culled frame's first pass projects only the Gaussians that are not
  * behind every cut they can reach and writes rectangle records for those only (workspace layout: + the survivor list).
  *   GS_FRAME_CULL_DILATE.
  * 7 (round 6): GS_FRAME_LONG_SORT, GS_FRAME_OCCLUSION_CULL + gs_frame_cull_fallback_async; gs_frame_stats_serial (the frame the
@@ -52,7 +55,8 @@ extern "C" {
 #define GS_ABI_VERSION 8
 
 #define GS_E_INVALID (-1)   /* bad argument (null pointer, negative size, bad enum)   */
-#define GS_E_UNSUPPORTED (-2) /* valid in the reference but not implemented here (none at present) */
+#define GS_E_UNSUPPORTED (-2) /* a valid request this entry point does not implement (gs_frame_backward_adam of a
+                                 GS_FRAME_AUX frame) */
 #define GS_E_CAPACITY (-3)  /* workspace too small for this frame                     */
 
 typedef void *gs_stream_t;
@@ -242,6 +246,24 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        kernel is correct for any frame; the results differ in the last bits (another
                                        summation order).  Ignored by SH frames. */
 
+#define GS_FRAME_AUX 2048             /* the frame also renders two per-pixel maps over exactly the Gaussians the colour composites
+                                       (up to the same 1e-4 stop), cropped like the image and NOT clamped:
+                                         alpha[H,W] = sum_i w_i            (accumulated like a colour channel of value 1.0;
+                                                                            = 1 - the final transmittance)
+                                         depth[H,W] = sum_i w_i d_i        d_i = |p_c|, the distance from the camera centre
+                                                                            (rec_geom.z, the key the lists are sorted by --
+                                                                            not camera z)
+                                       with w_i = alpha_i T_i.  The expected depth is depth / alpha (left to the caller).
+                                       Every colour model, training and inference frames; the trailing fields of gs_frame
+                                       below carry the buffers.  Training frames: gs_frame_backward / _part / _slice take
+                                       grad_depth / grad_alpha as well (gs_frame_backward_adam refuses the frame:
+                                       GS_E_UNSUPPORTED).  Such frames walk every tile list with one wave (no segmented
+                                       compositing of long lists, as with GS_FRAME_SERIAL_LONG_LISTS: the same result,
+                                       slower on very long lists only), and their backward composites on the
+                                       one-wave-per-bucket pixel kernel for every colour model (not the row-layout rgb
+                                       kernel, not the matrix pipe).  Frames without the flag run exactly the kernels
+                                       they ran before it existed. */
+
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
  * splatter.py does (Tiles, RayInfo, frustum guard band); rot/tran are passed by value. */
 typedef struct gs_frame {
@@ -300,11 +322,23 @@ typedef struct gs_frame {
     struct gs_frame_async *async; /* NULL, or a handle from gs_frame_async_create: training forwards then run the
                                  backward's preparation underneath the caller's loss (see gs_frame_forward) */
     int32_t flags;            /* GS_FRAME_* bits */
+    /* GS_FRAME_AUX (read only when the flag is set; a client built against a header without these fields never sets it) */
+    float *depth, *alpha;     /* [height,width] cropped maps (either may be NULL)                                      */
+    float *aux_padded;        /* [padH,padW,2] raw (depth, alpha) sums; required when training (the backward reads it)  */
+    void *aux_workspace;      /* caller-allocated, 256-byte aligned: gs_frame_aux_workspace_bytes(max_pairs, width,
+                                 height, training) bytes, kept with `workspace` from the forward to its backward          */
+    size_t aux_workspace_bytes;
+    const float *grad_depth, *grad_alpha; /* backward inputs dL/d(depth), dL/d(alpha) [height,width]; NULL = zero           */
 } gs_frame;
 
 /* Bytes of workspace needed for N Gaussians, `max_pairs` pairs, a width x height image. */
 size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int32_t height,
                                 int32_t color_dim, int32_t training);
+
+/* Bytes of aux workspace a GS_FRAME_AUX frame needs (host-only, no device call): the per-bucket (depth, alpha) checkpoints
+ * of training frames (8 B x 256 pixels x the bucket capacity of `max_pairs` pairs) and a small header.  0 on bad arguments.
+ * The main workspace (gs_frame_workspace_bytes) and its layout are the same with or without the flag. */
+size_t gs_frame_aux_workspace_bytes(int64_t max_pairs, int32_t width, int32_t height, int32_t training);
 
 /* Forward frame.  Launches everything on `stream`, never synchronises, and keeps no state of its own.
  * With f->training AND f->async the zero-fill of the per-pair gradient rows and the backward's bucket list are

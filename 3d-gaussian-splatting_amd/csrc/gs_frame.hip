@@ -66,7 +66,7 @@ static int validate(const gs_frame *f) {
     GS_CHECK_ARG((f->flags & ~(GS_FRAME_EMIT_SORTED_KEYS | GS_FRAME_SLICE_SORT | GS_FRAME_TABLE_BIN |
                                GS_FRAME_SERIAL_LONG_LISTS | GS_FRAME_LONG_LISTS | GS_FRAME_STRIP_BIN |
                                GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR |
-                               GS_FRAME_AUX)) == 0,
+                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD)) == 0,
                  "unknown flag bits");
     GS_CHECK_ARG(f->sort_mode >= 0 && f->sort_mode <= 2,
                  "sort_mode must be 0 (full LSD radix), 1 (tile-bit radix + per-tile LDS sort) or 2 (LDS counting sort "
@@ -82,6 +82,19 @@ static int validate(const gs_frame *f) {
         GS_CHECK_ARG(!f->training || f->aux_padded != nullptr, "GS_FRAME_AUX: training needs aux_padded");
         GS_CHECK_ARG(((uintptr_t)f->aux_padded & 7) == 0, "GS_FRAME_AUX: aux_padded must be 8-byte aligned");
     }
+    if (f->flags & GS_FRAME_POSE_GRAD) {  // (trailing fields, as above)
+        GS_CHECK_ARG(f->grad_rot != nullptr && f->grad_tran != nullptr, "GS_FRAME_POSE_GRAD: grad_rot / grad_tran null");
+        GS_CHECK_ARG(((uintptr_t)f->grad_rot & 3) == 0 && ((uintptr_t)f->grad_tran & 3) == 0,
+                     "GS_FRAME_POSE_GRAD: grad_rot / grad_tran must be 4-byte aligned");
+        GS_CHECK_ARG(f->pose_workspace != nullptr && ((uintptr_t)f->pose_workspace & 255) == 0,
+                     "GS_FRAME_POSE_GRAD: pose_workspace null or not 256-byte aligned");
+        const size_t pose_need = gs_frame_pose_workspace_bytes(f->N);
+        if (f->pose_workspace_bytes < pose_need) {
+            gs_set_error("gs_frame: GS_FRAME_POSE_GRAD: pose workspace too small (%zu < %zu bytes)", f->pose_workspace_bytes,
+                         pose_need);
+            return GS_E_INVALID;
+        }
+    }
     const size_t need = gs_frame_workspace_bytes(f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
     if (f->workspace_bytes < need) {
         gs_set_error("gs_frame: workspace too small (%zu < %zu bytes)", f->workspace_bytes, need);
@@ -93,6 +106,11 @@ static int validate(const gs_frame *f) {
 extern "C" size_t gs_frame_aux_workspace_bytes(int64_t max_pairs, int32_t width, int32_t height, int32_t training) {
     if (max_pairs < 0 || width <= 0 || height <= 0 || width > 65535 * 16 || height > 65535 * 16) return 0;
     return gs_frame_aux_carve(nullptr, max_pairs, width, height, training).total_bytes;
+}
+
+extern "C" size_t gs_frame_pose_workspace_bytes(int64_t N) {
+    if (N < 0) return 0;
+    return gs_frame_pose_carve(nullptr, N).total_bytes;
 }
 
 extern "C" size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int32_t height,
@@ -400,7 +418,26 @@ static int frame_backward_impl(const gs_frame *f, const float *grad_image, float
     GS_CHECK_ARG(part == GS_BWD_RASTER || part == GS_BWD_COLOR || (grad_pos && grad_quat && grad_scale), "null pointer");
     GS_CHECK_ARG(part == GS_BWD_RASTER || part == GS_BWD_GEOMETRY || (grad_opa && grad_rgb), "null pointer");
     GS_CHECK_ARG(((uintptr_t)grad_quat & 15) == 0, "grad_quat must be 16-byte aligned");
-    if (f->N == 0) return 0;
+    const bool pose = (f->flags & GS_FRAME_POSE_GRAD) != 0;
+    if (pose) {  // (everything refused before anything is enqueued)
+        if (f->color_dim != 3) {
+            gs_set_error("gs_frame_backward: GS_FRAME_POSE_GRAD needs rgb colours (color_dim 3): with SH colours the image "
+                         "also depends on the pose through the pixels' ray directions");
+            return GS_E_UNSUPPORTED;
+        }
+        if (part == -1 || g_begin != 0 || g_end != f->N) {
+            gs_set_error("gs_frame_backward_slice: GS_FRAME_POSE_GRAD frames are not supported");
+            return GS_E_UNSUPPORTED;
+        }
+    }
+    const bool pose_out = pose && (part == 0 || part == GS_BWD_GEOMETRY);  // the parts that write grad_rot / grad_tran
+    if (f->N == 0) {
+        if (pose_out) {  // no partial sums: zeros, written all the same
+            GS_HIP(hipMemsetAsync(f->grad_rot, 0, 9 * sizeof(float), s));
+            GS_HIP(hipMemsetAsync(f->grad_tran, 0, 3 * sizeof(float), s));
+        }
+        return 0;
+    }
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
     uint64_t *skeys, *okeys;
     uint32_t *sids;
@@ -413,6 +450,17 @@ static int frame_backward_impl(const gs_frame *f, const float *grad_image, float
         if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
     }
     tm.mark();
+    if (pose_out) {
+        // GS_FRAME_POSE_GRAD: the pose variants of the geometry kernels leave one row of partial sums per workgroup, the
+        // finalize kernel adds them up behind the last of them
+        if ((rc = gs_stage_project_backward_pose(f, ws, grad_pos, grad_quat, grad_scale, grad_opa, grad_rgb,
+                                                 part == GS_BWD_GEOMETRY ? 1 : 0, s)))
+            return rc;
+        if ((f->flags & GS_FRAME_AUX) && (rc = gs_stage_aux_depth_pose_backward(f, ws, grad_pos, s))) return rc;
+        if ((rc = gs_stage_pose_finalize(f, ws, s))) return rc;
+        tm.mark();
+        return tm.finish(stage_ms, 3);
+    }
     if (part != GS_BWD_RASTER &&
         (rc = gs_stage_project_backward(f, ws, grad_pos, grad_quat, grad_scale, grad_opa, grad_rgb,
                                         part == GS_BWD_GEOMETRY ? 1 : part == GS_BWD_COLOR ? 2 : 0, g_begin, g_end, s)))
@@ -437,6 +485,11 @@ extern "C" int gs_frame_backward_adam(const gs_frame *f, const float *grad_image
     if (rc) return rc;
     if (f->flags & GS_FRAME_AUX) {
         gs_set_error("gs_frame_backward_adam: GS_FRAME_AUX frames are not supported (use gs_frame_backward + an optimizer step)");
+        return GS_E_UNSUPPORTED;
+    }
+    if (f->flags & GS_FRAME_POSE_GRAD) {
+        gs_set_error("gs_frame_backward_adam: GS_FRAME_POSE_GRAD frames are not supported (use gs_frame_backward + an "
+                     "optimizer step)");
         return GS_E_UNSUPPORTED;
     }
     GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam needs a training forward (image_padded kept)");
@@ -470,6 +523,15 @@ extern "C" int gs_frame_backward_slice(const gs_frame *f, float *grad_pos, float
                                        gs_stream_t stream) {
     GS_CHECK_ARG(part == GS_BWD_GEOMETRY || part == GS_BWD_COLOR || part == (GS_BWD_GEOMETRY | GS_BWD_COLOR),
                  "part must be GS_BWD_GEOMETRY, GS_BWD_COLOR or both");
+    // GS_FRAME_POSE_GRAD: the pose gradient is a sum over ALL Gaussians, and a frame in slices has no call at which the last
+    // partial sum is in
+    int rc = validate(f);
+    if (rc) return rc;
+    if (f->flags & GS_FRAME_POSE_GRAD) {
+        gs_set_error("gs_frame_backward_slice: GS_FRAME_POSE_GRAD frames are not supported (use gs_frame_backward or "
+                     "gs_frame_backward_part)");
+        return GS_E_UNSUPPORTED;
+    }
     if (part == (GS_BWD_GEOMETRY | GS_BWD_COLOR)) {  // everything of the range in one kernel: the rows are read once
         GS_CHECK_ARG(grad_pos && grad_quat && grad_scale && grad_opa && grad_rgb, "null pointer");
         return frame_backward_impl(f, nullptr, grad_pos, grad_quat, grad_scale, grad_opa, grad_rgb, -1,

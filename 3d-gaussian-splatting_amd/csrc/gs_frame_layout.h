@@ -481,6 +481,26 @@ static inline gs_frame_aux_ws gs_frame_aux(const gs_frame *f) {
                               f->training);
 }
 
+// GS_FRAME_POSE_GRAD frames: the caller's third workspace (gs_frame.pose_workspace), the per-workgroup partial sums of the
+// pose gradient (12 floats: dL/drot row-major, dL/dtran), summed by pose_grad_finalize_kernel in row order.
+//   header : 256 bytes, reserved (keeps the size positive for N = 0)
+//   proj   : [ceil(N / 256)][12] float, one row per workgroup of the rgb projection backward (256 threads)
+//   aux    : [ceil(N / 256)][12] float, one row per workgroup of the aux depth backward (GS_FRAME_AUX frames), right
+//            behind proj: the finalize kernel reads proj and aux as one run of rows
+struct gs_frame_pose_ws {
+    float *proj, *aux;
+    int64_t rows;  // rows of each part
+    size_t total_bytes;
+};
+static inline gs_frame_pose_ws gs_frame_pose_carve(void *base, int64_t N) {
+    gs_frame_pose_ws p;
+    p.rows = gs_div_up(N > 0 ? N : 0, 256);
+    p.proj = base ? (float *)((char *)base + 256) : nullptr;
+    p.aux = p.proj ? p.proj + p.rows * 12 : nullptr;
+    p.total_bytes = 256 + gs_align_up(sizeof(float) * 12 * 2 * (size_t)p.rows, 256);
+    return p;
+}
+
 // stage entry points (defined across the .hip files)
 // the cut table a culled frame trims its lists by: the tiles' own cuts, or (GS_FRAME_CULL_DILATE) their neighbourhood maxima
 static inline const uint32_t *gs_frame_cut_table(const gs_frame *f, const gs_frame_ws &ws) {
@@ -512,5 +532,11 @@ int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const ui
 int gs_stage_sh_big_rows(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
 int gs_stage_aux_depth_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, int64_t g_begin, int64_t g_end,
                                 hipStream_t stream);
+// GS_FRAME_POSE_GRAD (rgb colours, all Gaussians): the projection backward's pose variant (part 0 or 1), the aux depth
+// backward's, and the reduction of the partial rows into f->grad_rot / f->grad_tran
+int gs_stage_project_backward_pose(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, float *grad_quat,
+                                   float *grad_scale, float *grad_opa, float *grad_rgb, int part, hipStream_t stream);
+int gs_stage_aux_depth_pose_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, hipStream_t stream);
+int gs_stage_pose_finalize(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
 int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids,
                              const float *grad_image, hipStream_t stream, bool prepared);

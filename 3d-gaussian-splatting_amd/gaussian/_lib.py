@@ -44,6 +44,8 @@ class GsFrame(C.Structure):
         # GS_FRAME_AUX (read by the library only when the flag is set)
         ("depth", vp), ("alpha", vp), ("aux_padded", vp), ("aux_workspace", vp), ("aux_workspace_bytes", sz),
         ("grad_depth", vp), ("grad_alpha", vp),
+        # GS_FRAME_POSE_GRAD (read by the library only when the flag is set)
+        ("grad_rot", vp), ("grad_tran", vp), ("pose_workspace", vp), ("pose_workspace_bytes", sz),
     ]
 
 
@@ -59,6 +61,7 @@ GS_FRAME_OCCLUSION_CULL = 256
 GS_FRAME_CULL_DILATE = 512
 GS_FRAME_CULL_DILATE_NEAR = 1024
 GS_FRAME_AUX = 2048
+GS_FRAME_POSE_GRAD = 4096
 
 
 def _sig(name, restype, *argtypes):
@@ -89,6 +92,7 @@ gs_sort_pairs = _sig("gs_sort_pairs", ci, vp, vp, vp, vp, vp, i64, ci, vp, sz, C
 gs_sort_pairs_bits = _sig("gs_sort_pairs_bits", ci, vp, vp, vp, vp, vp, i64, ci, ci, vp, sz, C.POINTER(ci), vp)
 gs_frame_workspace_bytes = _sig("gs_frame_workspace_bytes", sz, i64, i64, i32, i32, i32, i32)
 gs_frame_aux_workspace_bytes = _sig("gs_frame_aux_workspace_bytes", sz, i64, i32, i32, i32)
+gs_frame_pose_workspace_bytes = _sig("gs_frame_pose_workspace_bytes", sz, i64)
 gs_frame_forward = _sig("gs_frame_forward", ci, C.POINTER(GsFrame), vp)
 gs_frame_backward = _sig("gs_frame_backward", ci, C.POINTER(GsFrame), vp, vp, vp, vp, vp, vp, vp)
 gs_frame_backward_part = _sig("gs_frame_backward_part", ci, C.POINTER(GsFrame), vp, vp, vp, vp, vp, vp, i32, vp)
@@ -161,7 +165,7 @@ EXPORTS = [
     "gs_jacobian", "gs_global_culling", "gs_global_culling_backward", "gs_calc_tile_list",
     "gs_gather_gaussians", "gs_draw", "gs_draw_backward_workspace_bytes", "gs_draw_backward",
     "gs_sort_pairs_tmp_bytes", "gs_sort_pairs", "gs_sort_pairs_bits", "gs_frame_workspace_bytes",
-    "gs_frame_aux_workspace_bytes", "gs_frame_forward",
+    "gs_frame_aux_workspace_bytes", "gs_frame_pose_workspace_bytes", "gs_frame_forward",
     "gs_frame_stats_async", "gs_frame_longest_list_async", "gs_frame_stats_tagged_async", "gs_frame_cull_fallback_async", "gs_frame_is_occlusion_culled", "gs_frame_debug_views", "gs_frame_debug_rects", "gs_frame_binning_variant", "gs_frame_debug_tile_nproc", "gs_frame_debug_bwd_exec_rows", "gs_frame_backward", "gs_frame_backward_adam", "gs_frame_forward_profile",
     "gs_frame_backward_part", "gs_frame_async_create", "gs_frame_async_wait", "gs_frame_async_destroy",
     "gs_frame_backward_slice", "gs_frame_project_slices", "gs_frame_forward_project", "gs_frame_forward_rest",

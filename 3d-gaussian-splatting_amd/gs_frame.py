@@ -15,6 +15,7 @@ reductions) are not reproduced.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 import sys
@@ -119,6 +120,7 @@ class FrameRenderer:
         self._ws: Optional[torch.Tensor] = None
         self._aux_ws: Optional[torch.Tensor] = None  # GS_FRAME_AUX frames: the library's second workspace (grown with the first)
         self._aux_keep = None  # (depth, alpha, aux_padded) of the last forward, kept for its backward
+        self._pose_ws: Optional[torch.Tensor] = None  # GS_FRAME_POSE_GRAD backwards: the per-workgroup partial sums
         self._stats_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
         self._frame: Optional[_lib.GsFrame] = None
         self._frame_serial = 0  # counts forwards: autograd checks that backward() belongs to the latest one
@@ -676,11 +678,16 @@ class FrameRenderer:
                                                    self._stream().cuda_stream), "gs_frame_backward_adam")
         self._bwd_serial = self._frame_serial
 
-    def backward(self, grad_image, out=None, part: int = 0, grad_depth=None, grad_alpha=None):
+    def backward(self, grad_image, out=None, part: int = 0, grad_depth=None, grad_alpha=None, grad_pose=None):
         """dL/d(image) -> (grad_pos, grad_quat, grad_scale, grad_opa, grad_rgb).  ``out`` may
         supply the five destination tensors (e.g. views of one flat all-reduce bucket).
         After ``forward(..., aux=True)``: ``grad_depth`` / ``grad_alpha`` [H,W] are dL/d(depth), dL/d(alpha) (None = zero);
         ``grad_image`` may then be None (zero) as well.
+
+        ``grad_pose`` = (grad_rot [3,3], grad_tran [3]), contiguous float32 tensors on the renderer's device: also write
+        dL/d(camera.rot) and dL/d(camera.tran) of the frame's pose into them (GS_FRAME_POSE_GRAD, include/gs_abi.h;
+        overwritten, not accumulated; J of the projection held fixed, as for every per-Gaussian gradient).  rgb colours
+        only, ``part`` 0 or ``GS_BWD_GEOMETRY``.
 
         ``part`` (view-parallel gradient exchange, gs_dp.py): 0 = everything; ``_lib.GS_BWD_RASTER`` = only the
         raster backward (per-pair rows), then ``GS_BWD_GEOMETRY`` (pos / quat / scale) and ``GS_BWD_COLOR`` (opa /
@@ -715,6 +722,8 @@ class FrameRenderer:
         for t, ref in zip(out, (pos, quat, scale, opa, rgb)):
             if t.shape != ref.shape or t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("gradient destinations must match the parameters")
+        if grad_pose is not None:
+            f = self._pose_frame(f, grad_pose, part)
         with torch.cuda.device(self.device):
             if part == 0:
                 _lib.check(_lib.gs_frame_backward(C.byref(f), grad_image.data_ptr(), *(t.data_ptr() for t in out),
@@ -726,6 +735,30 @@ class FrameRenderer:
         if part in (0, _lib.GS_BWD_RASTER):
             self._bwd_serial = self._frame_serial  # this frame's bucket counter is final once the stream gets here
         return out
+
+    def _pose_frame(self, f, grad_pose, part):
+        """A copy of the descriptor ``f`` flagged GS_FRAME_POSE_GRAD, with the destinations ``grad_pose`` and the
+        renderer's pose workspace (grown as needed) wired in.  The renderer's own descriptor stays unflagged."""
+        if part not in (0, _lib.GS_BWD_GEOMETRY):
+            raise RuntimeError("grad_pose is written by backward(part=0) or backward(part=GS_BWD_GEOMETRY) only")
+        if int(f.color_dim) != 3:
+            raise RuntimeError("pose gradients need rgb colours: with SH colours the image also depends on the pose through "
+                               "each pixel's ray direction, which the backward does not differentiate")
+        grad_rot, grad_tran = grad_pose
+        for name, t, shape in (("grad_rot", grad_rot, (3, 3)), ("grad_tran", grad_tran, (3,))):
+            if (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device):
+                raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {list(shape)} on {self.device}")
+        need = _lib.gs_frame_pose_workspace_bytes(int(f.N))
+        if self._pose_ws is None or self._pose_ws.numel() < need + 256:
+            self._pose_ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
+        g = _lib.GsFrame()
+        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFrame))
+        base = self._pose_ws.data_ptr()
+        g.pose_workspace = (base + 255) // 256 * 256
+        g.pose_workspace_bytes = self._pose_ws.numel() - (g.pose_workspace - base)
+        g.grad_rot, g.grad_tran = grad_rot.data_ptr(), grad_tran.data_ptr()
+        g.flags |= _lib.GS_FRAME_POSE_GRAD
+        return g
 
     def profile_forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None, aux: bool = False):
         """One forward frame with every stage bracketed by hipEvents (synchronises).  Returns
@@ -922,28 +955,76 @@ class FrameRenderer:
         return out
 
     # ------------------------------------------------------------------ autograd entry point
-    def render(self, pos, quat, scale, opa, rgb, camera):
-        """Differentiable frame: the drop-in for ``Splatter.forward`` on explicit tensors."""
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (pos, quat, scale, opa, rgb)):
-            return _FrameFunction.apply(pos, quat, scale, opa, rgb, self, camera)
-        return self.forward(pos, quat, scale, opa, rgb, camera, training=False)[0]
+    @staticmethod
+    def _posed_camera(camera, pose, rgb):
+        """(camera with ``pose`` = (rot [3,3], tran [3]) in place of its own rot / tran, does the pose need a gradient?).
+        The descriptor takes the pose by value: device tensors are copied to the host here (a small copy that
+        synchronises with the current stream)."""
+        if pose is None:
+            return camera, False
+        rot, tran = pose
+        if tuple(rot.shape) != (3, 3) or tuple(tran.shape) != (3,):
+            raise RuntimeError("pose must be (rot [3,3], tran [3])")
+        grad = torch.is_grad_enabled() and (rot.requires_grad or tran.requires_grad)
+        if grad and (rgb.dim() != 2 or rgb.shape[1] != 3):
+            raise RuntimeError("pose gradients need rgb colours ([N,3]): with SH colours the image also depends on the pose "
+                               "through each pixel's ray direction, which the backward does not differentiate")
+        cam = copy.copy(camera)
+        cam.rot = rot.detach().to("cpu", torch.float32).numpy().astype(np.float32)
+        cam.tran = tran.detach().to("cpu", torch.float32).numpy().astype(np.float32)
+        return cam, grad
 
-    def render_aux(self, pos, quat, scale, opa, rgb, camera):
-        """Differentiable frame with its depth and alpha maps: -> (image [H,W,3], depth [H,W], alpha [H,W]) (GS_FRAME_AUX;
-        see ``forward``).  The expected depth is ``depth / alpha`` -- left to torch, so that autograd handles it."""
+    def render(self, pos, quat, scale, opa, rgb, camera, pose=None):
+        """Differentiable frame: the drop-in for ``Splatter.forward`` on explicit tensors.
+
+        ``pose`` = (rot [3,3], tran [3]) float32 tensors (CPU, or the device at the cost of one small synchronising copy):
+        the world-to-camera pose, in place of ``camera.rot`` / ``camera.tran`` (``camera`` still gives the image size, the
+        focal lengths and ``near``).  If either requires grad, the backward also returns dL/d(rot) and dL/d(tran)
+        (GS_FRAME_POSE_GRAD, rgb colours only), also when no Gaussian tensor requires grad."""
+        cam, pose_grad = self._posed_camera(camera, pose, rgb)
+        if pose_grad:
+            return _FrameFunction.apply(pos, quat, scale, opa, rgb, self, cam, pose[0], pose[1])
         if torch.is_grad_enabled() and any(t.requires_grad for t in (pos, quat, scale, opa, rgb)):
-            return _FrameAuxFunction.apply(pos, quat, scale, opa, rgb, self, camera)
-        image, _, depth, alpha = self.forward(pos, quat, scale, opa, rgb, camera, training=False, aux=True)
+            return _FrameFunction.apply(pos, quat, scale, opa, rgb, self, cam)
+        return self.forward(pos, quat, scale, opa, rgb, cam, training=False)[0]
+
+    def render_aux(self, pos, quat, scale, opa, rgb, camera, pose=None):
+        """Differentiable frame with its depth and alpha maps: -> (image [H,W,3], depth [H,W], alpha [H,W]) (GS_FRAME_AUX;
+        see ``forward``).  The expected depth is ``depth / alpha`` -- left to torch, so that autograd handles it.
+        ``pose``: as for ``render``."""
+        cam, pose_grad = self._posed_camera(camera, pose, rgb)
+        if pose_grad:
+            return _FrameAuxFunction.apply(pos, quat, scale, opa, rgb, self, cam, pose[0], pose[1])
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (pos, quat, scale, opa, rgb)):
+            return _FrameAuxFunction.apply(pos, quat, scale, opa, rgb, self, cam)
+        image, _, depth, alpha = self.forward(pos, quat, scale, opa, rgb, cam, training=False, aux=True)
         return image, depth, alpha
+
+
+def _pose_grad_buffers(renderer):
+    """(grad_rot, grad_tran) destinations on the renderer's device."""
+    return (torch.empty(3, 3, device=renderer.device, dtype=torch.float32),
+            torch.empty(3, device=renderer.device, dtype=torch.float32))
+
+
+def _pose_grads_out(ctx, gp):
+    """The pose gradients as autograd returns them: on the pose tensors' devices and dtypes, None where not needed."""
+    if gp is None:
+        return None, None
+    return tuple(g.to(device=d, dtype=t) if need else None
+                 for g, d, t, need in zip(gp, ctx.pose_devices, ctx.pose_dtypes, ctx.needs_input_grad[7:9]))
 
 
 class _FrameFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos, quat, scale, opa, rgb, renderer, camera):
+    def forward(ctx, pos, quat, scale, opa, rgb, renderer, camera, rot=None, tran=None):
         image, _ = renderer.forward(pos.detach(), quat.detach(), scale.detach(), opa.detach(), rgb.detach(), camera,
                                     training=True)
         ctx.renderer = renderer
         ctx.frame_serial = renderer._frame_serial
+        ctx.has_pose = rot is not None  # (camera carries the pose's values already)
+        if ctx.has_pose:
+            ctx.pose_devices, ctx.pose_dtypes = (rot.device, tran.device), (rot.dtype, tran.dtype)
         return image
 
     @staticmethod
@@ -951,17 +1032,23 @@ class _FrameFunction(torch.autograd.Function):
         r = ctx.renderer
         if r._frame_serial != ctx.frame_serial:
             raise RuntimeError("FrameRenderer workspace was reused by another forward before backward()")
-        g = r.backward(grad_image)
-        return (*g, None, None)
+        gp = _pose_grad_buffers(r) if ctx.has_pose else None
+        g = r.backward(grad_image, grad_pose=gp)
+        if not ctx.has_pose:
+            return (*g, None, None)
+        return (*g, None, None, *_pose_grads_out(ctx, gp))
 
 
 class _FrameAuxFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pos, quat, scale, opa, rgb, renderer, camera):
+    def forward(ctx, pos, quat, scale, opa, rgb, renderer, camera, rot=None, tran=None):
         image, _, depth, alpha = renderer.forward(pos.detach(), quat.detach(), scale.detach(), opa.detach(), rgb.detach(),
                                                   camera, training=True, aux=True)
         ctx.renderer = renderer
         ctx.frame_serial = renderer._frame_serial
+        ctx.has_pose = rot is not None
+        if ctx.has_pose:
+            ctx.pose_devices, ctx.pose_dtypes = (rot.device, tran.device), (rot.dtype, tran.dtype)
         return image, depth, alpha
 
     @staticmethod
@@ -969,5 +1056,8 @@ class _FrameAuxFunction(torch.autograd.Function):
         r = ctx.renderer
         if r._frame_serial != ctx.frame_serial:
             raise RuntimeError("FrameRenderer workspace was reused by another forward before backward()")
-        g = r.backward(grad_image, grad_depth=grad_depth, grad_alpha=grad_alpha)
-        return (*g, None, None)
+        gp = _pose_grad_buffers(r) if ctx.has_pose else None
+        g = r.backward(grad_image, grad_depth=grad_depth, grad_alpha=grad_alpha, grad_pose=gp)
+        if not ctx.has_pose:
+            return (*g, None, None)
+        return (*g, None, None, *_pose_grads_out(ctx, gp))

@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_AUX with the trailing
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_POSE_GRAD with the
+ *   trailing gs_frame fields grad_rot / grad_tran / pose_workspace / pose_workspace_bytes (behind the GS_FRAME_AUX fields,
+ *   read only when the flag is set) and gs_frame_pose_workspace_bytes.
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_AUX with the trailing
  *   gs_frame fields depth / alpha / aux_padded / aux_workspace / aux_workspace_bytes / grad_depth / grad_alpha (read only
  *   when the flag is set) and gs_frame_aux_workspace_bytes.
  * 8 (round 6): gs_frame_is_occlusion_culled; an occlusion-culled frame's first pass projects only the Gaussians that are not
@@ -56,7 +59,8 @@ extern "C" {
 
 #define GS_E_INVALID (-1)   /* bad argument (null pointer, negative size, bad enum)   */
 #define GS_E_UNSUPPORTED (-2) /* a valid request this entry point does not implement (gs_frame_backward_adam of a
-                                 GS_FRAME_AUX frame) */
+                                 GS_FRAME_AUX or GS_FRAME_POSE_GRAD frame; gs_frame_backward_slice of a
+                                 GS_FRAME_POSE_GRAD frame; any backward of a GS_FRAME_POSE_GRAD frame with SH colours) */
 #define GS_E_CAPACITY (-3)  /* workspace too small for this frame                     */
 
 typedef void *gs_stream_t;
@@ -264,6 +268,30 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        kernel, not the matrix pipe).  Frames without the flag run exactly the kernels
                                        they ran before it existed. */
 
+#define GS_FRAME_POSE_GRAD 4096       /* the backward also writes the gradient of the loss with respect to the camera pose:
+                                         grad_rot[3,3] = dL/d(rot) (row-major, the Euclidean gradient in the nine entries:
+                                                         not projected onto SO(3) -- parametrise the rotation upstream),
+                                         grad_tran[3]  = dL/d(tran),
+                                       with p_c = rot p + tran.  The projection Jacobian J of cov2d = J rot C rot^T J^T is
+                                       held fixed, as for every per-Gaussian gradient of this library (and the reference's
+                                       global_culling_backward): the pose gradient is exactly the one the per-Gaussian
+                                       gradients imply -- moving the camera is moving every Gaussian the other way --, so a
+                                       joint pose + scene fit stays consistent.  Per visible Gaussian, gc = dL/dp_c:
+                                         dL/dtran += gc,  dL/drot += gc p^T + J^T (G + G^T) J rot C,  G = dL/dcov2d;
+                                       with GS_FRAME_AUX the depth map's term (gc = g_d p_c / |p_c|) counts as well.
+                                       Culled Gaussians contribute nothing; a frame with N = 0 or one that overflowed its
+                                       workspace (rendered empty) gets zeros.  Both are written (overwritten, never
+                                       accumulated) by gs_frame_backward, gs_frame_backward_profile and
+                                       gs_frame_backward_part(GS_BWD_GEOMETRY); GS_BWD_RASTER / GS_BWD_COLOR leave them
+                                       alone, forwards ignore the flag apart from validating the fields.  The sum runs in a
+                                       fixed order without atomics: bitwise repeatable.
+                                       rgb colours only (color_dim 3): with SH colours the image also depends on the pose
+                                       through each pixel's ray direction, which is not differentiated -- every backward of
+                                       such a frame returns GS_E_UNSUPPORTED.  gs_frame_backward_slice returns
+                                       GS_E_UNSUPPORTED (a frame in slices has no point at which all partial sums are in)
+                                       and so does gs_frame_backward_adam.  All refusals come before anything is enqueued.
+                                       Frames without the flag run exactly the kernels they ran before it existed. */
+
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
  * splatter.py does (Tiles, RayInfo, frustum guard band); rot/tran are passed by value. */
 typedef struct gs_frame {
@@ -329,6 +357,12 @@ typedef struct gs_frame {
                                  height, training) bytes, kept with `workspace` from the forward to its backward          */
     size_t aux_workspace_bytes;
     const float *grad_depth, *grad_alpha; /* backward inputs dL/d(depth), dL/d(alpha) [height,width]; NULL = zero           */
+    /* GS_FRAME_POSE_GRAD (read only when the flag is set): device buffers, all required                                  */
+    float *grad_rot;          /* [3,3] row-major: dL/d(rot)                                                                */
+    float *grad_tran;         /* [3]: dL/d(tran)                                                                           */
+    void *pose_workspace;     /* caller-allocated, 256-byte aligned: gs_frame_pose_workspace_bytes(N) bytes (per-workgroup
+                                 partial sums; needed by the backward only, free between frames)                          */
+    size_t pose_workspace_bytes;
 } gs_frame;
 
 /* Bytes of workspace needed for N Gaussians, `max_pairs` pairs, a width x height image. */
@@ -339,6 +373,10 @@ size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int
  * of training frames (8 B x 256 pixels x the bucket capacity of `max_pairs` pairs) and a small header.  0 on bad arguments.
  * The main workspace (gs_frame_workspace_bytes) and its layout are the same with or without the flag. */
 size_t gs_frame_aux_workspace_bytes(int64_t max_pairs, int32_t width, int32_t height, int32_t training);
+
+/* Bytes of pose workspace a GS_FRAME_POSE_GRAD frame of N Gaussians needs (host-only, no device call): one row of 12 floats
+ * per 256 Gaussians for the projection backward and one for the aux depth backward, and a small header.  0 when N < 0. */
+size_t gs_frame_pose_workspace_bytes(int64_t N);
 
 /* Forward frame.  Launches everything on `stream`, never synchronises, and keeps no state of its own.
  * With f->training AND f->async the zero-fill of the per-pair gradient rows and the backward's bucket list are

@@ -1272,8 +1272,30 @@ __global__ void __launch_bounds__(BLOCK) frame_project_backward_kernel(
     float *__restrict__ grad_pos,
     float4 *__restrict__ grad_quat, float *__restrict__ grad_scale, float *__restrict__ grad_opa,
     float *__restrict__ grad_rgb, AdamFusedDev A = AdamFusedDev{}) {
-    constexpr bool POSE = false;
+    constexpr bool POSE = false, AUX = false;
     [[maybe_unused]] float *const pose_part = nullptr;
+#include "frame_project_backward_body.inc"
+}
+
+// GS_FRAME_AUX frames with the fused step (gs_frame_backward_adam_aux): the ADAM = 1 / 2 instantiations above with the depth
+// map's position term added to gp in front of the epilogue (AUX; aux_depth_term.inc: the row walk of
+// frame_aux_depth_backward_kernel).  A kernel of its own name, so that the kernels of frames without the flag keep theirs.
+template <int CDIM, int BLOCK, int ADAM>
+__global__ void __launch_bounds__(BLOCK) frame_project_backward_adam_aux_kernel(
+    const float *pos, const float4 *quat, const float *scale,
+    int64_t n, ProjectParams P, const float4 *__restrict__ rec_geom,
+    const float4 *__restrict__ rec_color, const float4 *__restrict__ rows,
+    const unsigned long long *__restrict__ stop_keys, const float *opa_raw,
+    const float *rgb_raw, GsDistCull D,
+    const uint32_t *__restrict__ pair_offsets, const uint4 *__restrict__ rects, uint64_t max_pairs, AdamFusedDev A) {
+    static_assert(ADAM != 0, "the fused step's variant");
+    constexpr int PART = 0;
+    constexpr bool POSE = false, AUX = true;
+    const int64_t g_first = 0;
+    [[maybe_unused]] float *const pose_part = nullptr;
+    // (no gradient is stored: the names the body's unfused tail mentions)
+    [[maybe_unused]] float *const grad_pos = nullptr, *const grad_scale = nullptr, *const grad_opa = nullptr, *const grad_rgb = nullptr;
+    [[maybe_unused]] float4 *const grad_quat = nullptr;
 #include "frame_project_backward_body.inc"
 }
 
@@ -1291,7 +1313,7 @@ __global__ void __launch_bounds__(256) frame_project_backward_pose_kernel(
     float4 *__restrict__ grad_quat, float *__restrict__ grad_scale, float *__restrict__ grad_opa,
     float *__restrict__ grad_rgb, float *__restrict__ pose_part) {
     constexpr int CDIM = 3, BLOCK = 256, ADAM = 0;
-    constexpr bool POSE = true;
+    constexpr bool POSE = true, AUX = false;
     const int64_t g_first = 0;
     [[maybe_unused]] const AdamFusedDev A{};
 #include "frame_project_backward_body.inc"
@@ -1643,7 +1665,8 @@ int gs_validate_adam_fused(const gs_frame *f, const gs_adam_fused *a) {
     return 0;
 }
 
-int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream) {
+int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream,
+                                   bool aux) {
     int vrc = gs_validate_adam_fused(f, a);
     if (vrc) return vrc;
     if (f->N <= 0) return 0;
@@ -1682,13 +1705,29 @@ int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, con
                        (const unsigned long long *)ws.stop_keys, f->opa, f->rgb, Dc, ws.pair_offsets, ws.rects,        \
                        (uint64_t)f->max_pairs, (int64_t)0, (float *)nullptr, (float4 *)nullptr, (float *)nullptr,      \
                        (float *)nullptr, (float *)nullptr, A)
-    if (f->color_dim == 48) {
+    // GS_FRAME_AUX (gs_frame_backward_adam_aux): the variant that adds the depth map's position term in front of the step
+#define GS_LAUNCH_PB_ADAM_AUX(CD, BLK, MODE)                                                                            \
+    hipLaunchKernelGGL((frame_project_backward_adam_aux_kernel<CD, BLK, MODE>), dim3((unsigned)gs_div_up(f->N, BLK)),   \
+                       dim3(BLK), 0, stream, f->pos,                                                                   \
+                       (const float4 *)f->quat, f->scale, f->N, P, ws.rec_geom, ws.rec_color, (const float4 *)ws.rows, \
+                       (const unsigned long long *)ws.stop_keys, f->opa, f->rgb, Dc, ws.pair_offsets, ws.rects,        \
+                       (uint64_t)f->max_pairs, A)
+    if (aux) {
+        if (f->color_dim == 48) {
+            if (nt) GS_LAUNCH_PB_ADAM_AUX(48, 128, 2); else GS_LAUNCH_PB_ADAM_AUX(48, 128, 1);
+        } else if (f->color_dim == 27) {
+            if (nt) GS_LAUNCH_PB_ADAM_AUX(27, 128, 2); else GS_LAUNCH_PB_ADAM_AUX(27, 128, 1);
+        } else {
+            if (nt) GS_LAUNCH_PB_ADAM_AUX(3, 256, 2); else GS_LAUNCH_PB_ADAM_AUX(3, 256, 1);
+        }
+    } else if (f->color_dim == 48) {
         if (nt) GS_LAUNCH_PB_ADAM(48, 128, 2); else GS_LAUNCH_PB_ADAM(48, 128, 1);
     } else if (f->color_dim == 27) {
         if (nt) GS_LAUNCH_PB_ADAM(27, 128, 2); else GS_LAUNCH_PB_ADAM(27, 128, 1);
     } else {
         if (nt) GS_LAUNCH_PB_ADAM(3, 256, 2); else GS_LAUNCH_PB_ADAM(3, 256, 1);
     }
+#undef GS_LAUNCH_PB_ADAM_AUX
 #undef GS_LAUNCH_PB_ADAM
     GS_CHECK_LAUNCH();
     return 0;

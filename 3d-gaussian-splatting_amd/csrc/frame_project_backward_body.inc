@@ -1,10 +1,11 @@
 // frame_project_backward_body.inc -- the body of frame_project_backward_kernel and of its GS_FRAME_POSE_GRAD variant
 // frame_project_backward_pose_kernel (cull_project.hip), expanded in place in both.  Expects in scope: the kernel's
-// parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE` and `pose_part`.  (Included rather than called: an
+// parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE`, `constexpr bool AUX` and `pose_part`.  (Included rather than called: an
 // inlined device function leaves the kernel without the flag with other register assignments than before it existed;
 // expanded in place, it compiles to the same code.)
     static_assert(ADAM == 0 || PART == 0, "the fused optimizer step: everything in one kernel");
     static_assert(!POSE || (CDIM == 3 && PART != 2 && ADAM == 0), "pose gradients: rgb colours, geometry part, no fused step");
+    static_assert(!AUX || (ADAM != 0 && !POSE), "the depth map's position term is added here only in front of the fused step");
     // rgb rows (round 4): only rows that EXIST are fetched.  71 % of the pairs of the 2.4 M scene lie behind their
     // tile's stop point and their rows are uninitialised memory; round 3 streamed all of them through LDS and looked at
     // the flags afterwards (PMC: 916 MB of traffic against 316 MB algorithmic).  Whether the row of pair (tile, g) was
@@ -560,6 +561,23 @@
             gcol[2] = d2.y * c2 * (1.0f - c2);
         } else {
             gopa = d1.z * g.w * (1.0f - g.w);
+        }
+    }
+    if constexpr (AUX) {
+        // GS_FRAME_AUX frames in front of the fused step (gs_frame_backward_adam_aux): what frame_aux_depth_backward_kernel adds
+        // to the stored grad_pos behind this kernel is added to gp here -- the same row walk (aux_depth_term.inc), and
+        // fl(gp) + gpa in that order (no contraction in this file): the step sees the bits gs_frame_backward leaves
+        if (vis) {
+            const float *const rows_f = reinterpret_cast<const float *>(rows);
+            float ga[3];
+            {
+                const float *const rows = rows_f;
+#include "aux_depth_term.inc"
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ga[c] = gpa[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gp[c] = gp[c] + ga[c];
         }
     }
     if constexpr (POSE) {

@@ -506,6 +506,59 @@ extern "C" int gs_frame_backward_adam(const gs_frame *f, const float *grad_image
     return gs_stage_project_backward_adam(f, ws, adam, s);
 }
 
+// An all-zero [bytes] device buffer for a NULL grad_image of gs_frame_backward_adam_aux: the raster backward reads dL/dimage
+// of every pixel, and its kernels are left as they are.  One buffer per device, owned by the library, allocated (and
+// cleared, once) at the first call that needs it and grown when a larger image arrives; only ever read afterwards.  Growing
+// frees the old buffer, which waits for the device: nothing that reads it is still in flight.
+static int zero_image(size_t bytes, const float **out) {
+    static std::mutex mu;
+    static struct { void *p; size_t bytes; } cache[64] = {};
+    int dev = 0;
+    GS_HIP(hipGetDevice(&dev));
+    GS_CHECK_ARG(dev >= 0 && dev < 64, "device index out of range");
+    std::lock_guard<std::mutex> lock(mu);
+    if (cache[dev].bytes < bytes) {
+        if (cache[dev].p) GS_HIP(hipFree(cache[dev].p));
+        cache[dev].p = nullptr;
+        cache[dev].bytes = 0;
+        void *q = nullptr;
+        GS_HIP(hipMalloc(&q, bytes));
+        GS_HIP(hipMemset(q, 0, bytes));
+        GS_HIP(hipDeviceSynchronize());
+        cache[dev].p = q;
+        cache[dev].bytes = bytes;
+    }
+    *out = (const float *)cache[dev].p;
+    return 0;
+}
+
+// gs_frame_backward_adam for GS_FRAME_AUX training frames: the raster backward takes f->grad_depth / f->grad_alpha with
+// grad_image, and the projection backward's fused step adds the depth map's position term before it steps.
+extern "C" int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
+                                          gs_stream_t stream) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG((f->flags & GS_FRAME_AUX) != 0, "the frame is not flagged GS_FRAME_AUX (gs_frame_backward_adam takes plain frames)");
+    if (f->flags & GS_FRAME_POSE_GRAD) {
+        gs_set_error("gs_frame_backward_adam_aux: GS_FRAME_POSE_GRAD frames are not supported (use gs_frame_backward + an "
+                     "optimizer step)");
+        return GS_E_UNSUPPORTED;
+    }
+    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam_aux needs a training forward (image_padded kept)");
+    GS_CHECK_ARG(adam, "null pointer");
+    if ((rc = gs_validate_adam_fused(f, adam))) return rc;  // before anything is enqueued
+    if (f->N == 0) return 0;
+    if (!grad_image && (rc = zero_image(sizeof(float) * 3 * (size_t)f->width * (size_t)f->height, &grad_image))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
+    uint64_t *skeys, *okeys;
+    uint32_t *sids;
+    sorted_buffers(f, ws, &skeys, &sids, &okeys);
+    const bool prepared = join_prepared(f, s);
+    if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
+    return gs_stage_project_backward_adam(f, ws, adam, s, true);
+}
+
 extern "C" int gs_frame_backward_part(const gs_frame *f, const float *grad_image, float *grad_pos, float *grad_quat,
                                       float *grad_scale, float *grad_opa, float *grad_rgb, int32_t part,
                                       gs_stream_t stream) {

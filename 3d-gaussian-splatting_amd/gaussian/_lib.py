@@ -124,6 +124,7 @@ class GsAdamFused(C.Structure):
 
 
 gs_frame_backward_adam = _sig("gs_frame_backward_adam", ci, C.POINTER(GsFrame), vp, C.POINTER(GsAdamFused), vp)
+gs_frame_backward_adam_aux = _sig("gs_frame_backward_adam_aux", ci, C.POINTER(GsFrame), vp, C.POINTER(GsAdamFused), vp)
 gs_frame_debug_tile_nproc = _sig("gs_frame_debug_tile_nproc", ci, C.POINTER(GsFrame), C.POINTER(vp))
 gs_frame_debug_bwd_exec_rows = _sig("gs_frame_debug_bwd_exec_rows", ci, C.POINTER(GsFrame), C.POINTER(vp), C.POINTER(C.c_int32))
 
@@ -143,6 +144,8 @@ gs_frame_async_wait = _sig("gs_frame_async_wait", ci, vp, vp)
 gs_frame_async_destroy = _sig("gs_frame_async_destroy", ci, vp)
 gs_loss_workspace_bytes = _sig("gs_loss_workspace_bytes", sz, i32, i32)
 gs_loss_l1_ssim = _sig("gs_loss_l1_ssim", ci, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp)
+gs_loss_depth_workspace_bytes = _sig("gs_loss_depth_workspace_bytes", sz, i32, i32)
+gs_loss_depth = _sig("gs_loss_depth", ci, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp)
 
 
 
@@ -171,6 +174,7 @@ EXPORTS = [
     "gs_frame_backward_slice", "gs_frame_project_slices", "gs_frame_forward_project", "gs_frame_forward_rest",
     "gs_adam_step_multi",
     "gs_frame_backward_profile", "gs_adam_step", "gs_adam_step_range", "gs_adam_step_sharded", "gs_frame_overflow_flag", "gs_grad_stat_update", "gs_loss_workspace_bytes", "gs_loss_l1_ssim",
+    "gs_loss_depth_workspace_bytes", "gs_loss_depth", "gs_frame_backward_adam_aux",
     "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
 ]
 

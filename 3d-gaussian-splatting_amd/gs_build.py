@@ -33,12 +33,13 @@ SOURCES = {
     "adam.hip": ["-ffp-contract=off"],  # same roundings as torch's unfused elementwise kernels
     "loss.hip": ["-fno-slp-vectorize"],  # as above: the packer costs ~50 v_mov per row step of the fused kernel
     "densify.hip": ["-ffp-contract=off"],
+    "depth_loss.hip": ["-ffp-contract=off"],  # r = D - A z as written: one rounding per operation
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
 HEADERS = ["gs_common.h", "gs_frame_layout.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
-           "frame_project_backward_body.inc", "aux_depth_backward_body.inc", os.path.join("..", "..", "include", "gs_abi.h")]
+           "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", os.path.join("..", "..", "include", "gs_abi.h")]
 
 
 def _stale(target: str, deps) -> bool:

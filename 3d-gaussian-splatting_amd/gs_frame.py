@@ -661,18 +661,50 @@ class FrameRenderer:
                                                     int(g_end), self._stream().cuda_stream), "gs_frame_backward_slice")
         return out
 
-    def backward_adam(self, grad_image, adam):
+    def _aux_grad_maps(self, f, grad_depth, grad_alpha):
+        """dL/d(depth), dL/d(alpha) of an aux frame, checked ([H,W] float32, None = zero) and wired into the descriptor."""
+        maps = []
+        for name, t in (("grad_depth", grad_depth), ("grad_alpha", grad_alpha)):
+            if t is not None:
+                t = t.contiguous()
+                if t.dtype != torch.float32 or tuple(t.shape) != (f.height, f.width):
+                    raise RuntimeError(f"{name} must be float32 [H,W]")
+            maps.append(t)
+        grad_depth, grad_alpha = maps
+        f.grad_depth = grad_depth.data_ptr() if grad_depth is not None else None
+        f.grad_alpha = grad_alpha.data_ptr() if grad_alpha is not None else None
+        return grad_depth, grad_alpha
+
+    def backward_adam(self, grad_image, adam, grad_depth=None, grad_alpha=None):
         """``backward`` with the optimizer step fused into its last kernel (gs_frame_backward_adam, include/
         gs_abi.h): the frame's own parameter tensors are updated in place, no gradient is written.  ``adam``: a filled
-        ``gaussian._lib.GsAdamFused`` (gs_train.FusedAdam.fused_descriptor)."""
+        ``gaussian._lib.GsAdamFused`` (gs_train.FusedAdam.fused_descriptor).
+        After ``forward(..., aux=True)`` the step goes through gs_frame_backward_adam_aux: ``grad_depth`` / ``grad_alpha``
+        [H,W] are dL/d(depth), dL/d(alpha) (None = zero), and ``grad_image`` may be None (zero) as well -- bit for bit
+        what ``backward(grad_image, grad_depth=..., grad_alpha=...)`` + the optimizer's step give."""
         f = self._frame
         if f is None or not f.training:
             raise RuntimeError("backward_adam() needs a preceding forward(training=True)")
+        aux = bool(f.flags & _lib.GS_FRAME_AUX)
+        if not aux and (grad_depth is not None or grad_alpha is not None):
+            raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
         # the step is applied to whatever the frame's pointers address: they must be the caller's LIVE parameter tensors
         # (ADVICE round 5: a forward handed converted / non-contiguous tensors would step a temporary copy silently)
         for ptr, t in zip((f.pos, f.quat, f.scale, f.opa, f.rgb), self._keep[:5]):
             if int(ptr or 0) != t.data_ptr():
                 raise RuntimeError("backward_adam(): the frame was rendered from tensors that are no longer alive")
+        if aux:
+            grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
+            if grad_image is not None:
+                grad_image = grad_image.contiguous()
+                if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
+                    raise RuntimeError("grad_image must be float32 [H,W,3]")
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.gs_frame_backward_adam_aux(C.byref(f), grad_image.data_ptr() if grad_image is not None
+                                                           else None, C.byref(adam), self._stream().cuda_stream),
+                           "gs_frame_backward_adam_aux")
+            self._bwd_serial = self._frame_serial
+            return
         with torch.cuda.device(self.device):
             _lib.check(_lib.gs_frame_backward_adam(C.byref(f), grad_image.contiguous().data_ptr(), C.byref(adam),
                                                    self._stream().cuda_stream), "gs_frame_backward_adam")
@@ -703,16 +735,7 @@ class FrameRenderer:
         if not aux and (grad_depth is not None or grad_alpha is not None):
             raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
         if aux and part in (0, _lib.GS_BWD_RASTER):
-            maps = []
-            for name, t in (("grad_depth", grad_depth), ("grad_alpha", grad_alpha)):
-                if t is not None:
-                    t = t.contiguous()
-                    if t.dtype != torch.float32 or tuple(t.shape) != (f.height, f.width):
-                        raise RuntimeError(f"{name} must be float32 [H,W]")
-                maps.append(t)
-            grad_depth, grad_alpha = maps
-            f.grad_depth = grad_depth.data_ptr() if grad_depth is not None else None
-            f.grad_alpha = grad_alpha.data_ptr() if grad_alpha is not None else None
+            grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
             if grad_image is None:
                 grad_image = torch.zeros(f.height, f.width, 3, device=self.device, dtype=torch.float32)
         if part in (0, _lib.GS_BWD_RASTER):

@@ -23,11 +23,13 @@ import math
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from gaussian import _lib
 from gs_dp import ORDER, FlatGaussianParams, ViewParallelGradStat
 from gs_frame import FrameRenderer
+from gs_geometry import RayBasis, TileGrid
 
 GROUPS = ("opa", "rgb", "pos", "scale", "quat")  # the reference's param-group order (train.py:59-65)
 
@@ -63,6 +65,12 @@ class TrainOptions:
     use_clone: int = 0
     use_split: int = 1
     clone_dt: float = 0.01
+    # depth supervision (Trainer(..., depths=...)): + depth_weight * mean over the view's measured pixels of |r|, with
+    # r = D - A z ("residual": no division, defined everywhere) or D / A - z ("expected": where A >= depth_alpha_min);
+    # D, A the frame's depth / alpha maps, z the measured range (gs_loss_depth, include/gs_abi.h).  0: rgb only.
+    depth_weight: float = 0.0
+    depth_mode: str = "residual"  # "residual" | "expected"
+    depth_alpha_min: float = 0.5
 
 
 def lr_lambdas(opt: TrainOptions) -> List[Callable[[int], float]]:
@@ -237,6 +245,56 @@ class ImageLoss:
         return self.grad
 
 
+class DepthLoss:
+    """``scale * sum |r|`` over the measured pixels of a range map and its gradients w.r.t. the depth / alpha maps of an aux
+    frame (gs_loss_depth, include/gs_abi.h): ``mode`` "residual" (r = D - A z) or "expected" (r = D / A - z where
+    A >= ``alpha_min``).  Owns the workspace and the two gradient maps; ``values`` = (loss, pixels that counted)."""
+
+    MODES = {"residual": 0, "expected": 1}
+
+    def __init__(self, height: int, width: int, mode: str = "residual", alpha_min: float = 0.5, device="cuda"):
+        if mode not in self.MODES:
+            raise ValueError(f"depth mode must be 'residual' or 'expected', got {mode!r}")
+        self.H, self.W, self.mode, self.alpha_min = int(height), int(width), self.MODES[mode], float(alpha_min)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DepthLoss needs a HIP device; there is no CPU fallback")
+        nbytes = _lib.gs_loss_depth_workspace_bytes(self.H, self.W)
+        self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        self.grad_depth = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
+        self.grad_alpha = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
+        self.values = torch.zeros(2, dtype=torch.float32, device=self.device)  # stays on the device
+
+    def __call__(self, depth: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, scale: float):
+        """``target``: [H,W] range from the camera centre (<= 0, inf, NaN: no measurement); ``scale``: weight / number of
+        measured pixels.  Returns (grad_depth, grad_alpha)."""
+        for name, t in (("depth", depth), ("alpha", alpha), ("target", target)):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (self.H, self.W):
+                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [{self.H},{self.W}]")
+        _lib.check(_lib.gs_loss_depth(depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), self.H, self.W, self.mode,
+                                      self.alpha_min, float(scale), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
+                                      self.values.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                      torch.cuda.current_stream().cuda_stream), "gs_loss_depth")
+        return self.grad_depth, self.grad_alpha
+
+
+def z_to_range(z: torch.Tensor, camera) -> torch.Tensor:
+    """Sensor z-depth [H,W] (distance along the optical axis) -> range from the camera centre, what the aux depth map
+    measures (d_i = |p_c|): range = z |ray| / ray_z with the renderer's own per-pixel rays (gs_geometry.RayBasis: pixel
+    centres of the padded image, cropped like the image), so the conversion and the rendered map agree on where a pixel
+    looks.  Pixels without a measurement (<= 0, inf, NaN) stay what they are."""
+    grid = TileGrid(int(camera.width), int(camera.height), float(camera.focal_x), float(camera.focal_y))
+    rays = RayBasis.from_camera(camera.rot, camera.tran, grid.padded_height, grid.padded_width, grid.focal_x, grid.focal_y)
+    top, left = grid.crop_offsets()
+    px = (np.arange(grid.width, dtype=np.float64) + left)[None, :, None]
+    py = (np.arange(grid.height, dtype=np.float64) + top)[:, None, None]
+    d = (rays.lefttop.astype(np.float64) - rays.rays_o.astype(np.float64))[None, None, :] \
+        + px * rays.dx.astype(np.float64)[None, None, :] + py * rays.dy.astype(np.float64)[None, None, :]
+    axis = np.asarray(camera.rot, np.float64).reshape(3, 3)[2]  # the optical axis in world coordinates
+    factor = np.linalg.norm(d, axis=2) / (d @ axis)
+    return (z.to(torch.float64) * torch.from_numpy(factor).to(z.device)).to(torch.float32)
+
+
 class Trainer:
     """One view per step on this rank; gradients are averaged over ranks when torch.distributed is up.
 
@@ -248,8 +306,39 @@ class Trainer:
                  opt: Optional[TrainOptions] = None, world_size: int = 1, max_pairs: int = 1 << 20,
                  scale_activation: str = "abs", densify: bool = False, generator: Optional[torch.Generator] = None,
                  per_view_stat: Optional[bool] = None, exchange: str = "all_reduce", n_slices: Optional[int] = None,
-                 bwd_rows: Optional[bool] = None, fuse_adam: Optional[bool] = None):
+                 bwd_rows: Optional[bool] = None, fuse_adam: Optional[bool] = None,
+                 depths: Optional[Sequence[Optional[torch.Tensor]]] = None, depth_kind: str = "range"):
         self.opt = opt or TrainOptions()
+        # `depths`: a list parallel to `targets`, each entry a measured depth map [H,W] float32 or None (a view without one).
+        # `depth_kind`: "range" = distance from the camera centre, what the frame's depth map accumulates; "z" = sensor
+        # z-depth, converted once here with the renderer's own rays (z_to_range).  Pixels <= 0, inf or NaN carry no
+        # measurement.  With opt.depth_weight > 0 a view that has a map is rendered with its depth / alpha maps and
+        # trained on colour AND depth (train_step); every other step issues exactly the calls it issues without `depths`.
+        if depth_kind not in ("range", "z"):
+            raise ValueError(f"depth_kind must be 'range' or 'z', got {depth_kind!r}")
+        if self.opt.depth_mode not in DepthLoss.MODES:
+            raise ValueError(f"depth_mode must be 'residual' or 'expected', got {self.opt.depth_mode!r}")
+        self.depths, self._depth_inv_n = None, None
+        if depths is not None:
+            if len(depths) != len(targets):
+                raise ValueError("depths must be a list parallel to targets (None for a view without a depth map)")
+            self.depths, self._depth_inv_n = [], []
+            for cam_, d in zip(cameras, depths):
+                if d is None:
+                    self.depths.append(None)
+                    self._depth_inv_n.append(0.0)
+                    continue
+                if d.dtype != torch.float32 or tuple(d.shape) != (int(cam_.height), int(cam_.width)):
+                    raise ValueError("a depth map must be float32 [H,W] of its camera")
+                d = d.to(params[0].device)
+                if depth_kind == "z":
+                    d = z_to_range(d, cam_)
+                d = d.contiguous()
+                n_valid = int((torch.isfinite(d) & (d > 0)).sum())  # once, here: no count pass in the step
+                self.depths.append(d)
+                self._depth_inv_n.append(1.0 / n_valid if n_valid else 0.0)
+        self._depth_loss = {}
+        self.depth_loss = None  # the DepthLoss of the last depth-supervised step (.values: loss, pixels that counted)
         # `fuse_adam`: apply the Adam step inside the backward's last kernel (FrameRenderer.backward_adam: no gradient buffer is
         # written, bit-identical parameters) where the step allows it -- one rank, no regulariser that edits the
         # gradient, the densification statistic fused into the optimizer.  None: on (GS_TRAIN_FUSE_ADAM=0 turns it off for
@@ -328,6 +417,19 @@ class Trainer:
             self._loss[key] = ImageLoss(h, w, self.opt.ssim_weight, self.flat.flat_param.device)
         return self._loss[key]
 
+    def _depth_loss_for(self, h: int, w: int) -> DepthLoss:
+        key = (h, w)
+        if key not in self._depth_loss:
+            self._depth_loss[key] = DepthLoss(h, w, self.opt.depth_mode, self.opt.depth_alpha_min,
+                                              self.flat.flat_param.device)
+        return self._depth_loss[key]
+
+    def _depth_target(self, camera_id: Optional[int]):
+        """The range map this view is supervised with, or None (no maps, no weight, no map for the view)."""
+        if self.depths is None or camera_id is None or not self.opt.depth_weight > 0:
+            return None
+        return self.depths[camera_id]
+
     def _can_fuse_adam(self) -> bool:
         o, rgb = self.opt, self.flat.params[4]
         return (self.fuse_adam and not self.flat.collective_active() and not self.optimizer.sharded
@@ -356,7 +458,16 @@ class Trainer:
         cam, target = self.cameras[camera_id], self.targets[camera_id]
         flat, r = self.flat, self.renderer
         flat.finish_gather()  # reduce-scatter mode: parameter all-gathers of the previous step that nobody waited for yet
-        if r.begun_frame_matches(*flat.params, cam):
+        depth_target = self._depth_target(camera_id)
+        depth_map = alpha_map = None
+        if depth_target is not None:
+            # a depth-supervised view: the frame also renders its depth / alpha maps (never projected ahead: below)
+            r.forward_abandon()
+            if camera_id not in self._views_checked:
+                self._views_checked.add(camera_id)
+                r._checked_once = False
+            image, _, depth_map, alpha_map = r.forward(*flat.params, cam, aux=True)
+        elif r.begun_frame_matches(*flat.params, cam):
             image, _ = r.forward_finish()  # projected behind the previous step's optimizer
         else:
             r.forward_abandon()
@@ -379,6 +490,13 @@ class Trainer:
             self._overflow_warned = r.overflowed_frames
         loss = self._loss_for(image.shape[0], image.shape[1])
         grad_image = loss(image, target)
+        # depth supervision: + depth_weight / n_valid * sum |r| on the frame's maps; its two gradient maps travel with
+        # grad_image through whichever backward the step takes
+        aux_grads = {}
+        if depth_target is not None:
+            self.depth_loss = self._depth_loss_for(image.shape[0], image.shape[1])
+            gd, ga = self.depth_loss(depth_map, alpha_map, depth_target, o.depth_weight * self._depth_inv_n[camera_id])
+            aux_grads = {"grad_depth": gd, "grad_alpha": ga}
         if self.densify and accum_start:  # train.py:141-142 (before this step's gradient is accumulated)
             self.optimizer.clear_grad_stat()
             self.grad_counter = None
@@ -422,7 +540,7 @@ class Trainer:
             # Nothing of a slice is applied before its exchange has finished: no stale gradients, the same numbers as
             # the blocking path bit for bit (tests/test_host_logic.py, tests/test_gpu_train.py).
             K = flat.n_slices
-            r.backward(grad_image, out=flat.grads, part=_lib.GS_BWD_RASTER)
+            r.backward(grad_image, out=flat.grads, part=_lib.GS_BWD_RASTER, **aux_grads)
             settle_backward_choice()
             if self.view_stat is not None and seen is not None:
                 self.view_stat.add_seen(seen)
@@ -446,9 +564,10 @@ class Trainer:
         elif self._can_fuse_adam():
             # one kernel less and no gradient round trip through memory: the per-Gaussian sums, the projection / activation
             # backward and the Adam update of the Gaussian's 14 parameters (+ the |pos.grad| statistic) in one launch
-            r.backward_adam(grad_image, self.optimizer.fused_descriptor())
+            # (a depth-supervised frame: gs_frame_backward_adam_aux, the same step with the depth map's position term)
+            r.backward_adam(grad_image, self.optimizer.fused_descriptor(), **aux_grads)
         else:
-            r.backward(grad_image, out=flat.grads)
+            r.backward(grad_image, out=flat.grads, **aux_grads)
             local_terms(0, flat.n)
             if self.view_stat is not None and seen is not None:
                 self.view_stat.add_seen(seen)
@@ -529,6 +648,8 @@ class Trainer:
         project stage read would no longer be the ones the frame is rendered with)."""
         o = self.opt
         if next_camera_id is None or next_camera_id not in self._views_checked:
+            return False
+        if self._depth_target(next_camera_id) is not None:  # rendered with its depth / alpha maps: one call, not in phases
             return False
         if self.densify and (rebinding or (i_iter % o.n_opa_reset == 0 and i_iter > 0)):
             return False

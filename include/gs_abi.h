@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_POSE_GRAD with the
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_depth +
+ *   gs_loss_depth_workspace_bytes (L1 depth supervision on the GS_FRAME_AUX maps) and gs_frame_backward_adam_aux (the fused
+ *   training step for GS_FRAME_AUX frames).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_POSE_GRAD with the
  *   trailing gs_frame fields grad_rot / grad_tran / pose_workspace / pose_workspace_bytes (behind the GS_FRAME_AUX fields,
  *   read only when the flag is set) and gs_frame_pose_workspace_bytes.
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_AUX with the trailing
@@ -59,7 +62,8 @@ extern "C" {
 
 #define GS_E_INVALID (-1)   /* bad argument (null pointer, negative size, bad enum)   */
 #define GS_E_UNSUPPORTED (-2) /* a valid request this entry point does not implement (gs_frame_backward_adam of a
-                                 GS_FRAME_AUX or GS_FRAME_POSE_GRAD frame; gs_frame_backward_slice of a
+                                 GS_FRAME_AUX frame -- gs_frame_backward_adam_aux takes those -- or of a
+                                 GS_FRAME_POSE_GRAD frame; gs_frame_backward_slice of a
                                  GS_FRAME_POSE_GRAD frame; any backward of a GS_FRAME_POSE_GRAD frame with SH colours) */
 #define GS_E_CAPACITY (-3)  /* workspace too small for this frame                     */
 
@@ -260,7 +264,8 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        with w_i = alpha_i T_i.  The expected depth is depth / alpha (left to the caller).
                                        Every colour model, training and inference frames; the trailing fields of gs_frame
                                        below carry the buffers.  Training frames: gs_frame_backward / _part / _slice take
-                                       grad_depth / grad_alpha as well (gs_frame_backward_adam refuses the frame:
+                                       grad_depth / grad_alpha as well, and so does the fused training step
+                                       gs_frame_backward_adam_aux (gs_frame_backward_adam itself refuses the frame:
                                        GS_E_UNSUPPORTED).  Such frames walk every tile list with one wave (no segmented
                                        compositing of long lists, as with GS_FRAME_SERIAL_LONG_LISTS: the same result,
                                        slower on very long lists only), and their backward composites on the
@@ -605,6 +610,18 @@ typedef struct gs_adam_fused {
 } gs_adam_fused;
 int gs_frame_backward_adam(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam, gs_stream_t stream);
 
+/* The same step for GS_FRAME_AUX training frames (RGB-D training: colour and depth supervision in one step).  The raster
+ * backward takes f->grad_depth / f->grad_alpha (NULL = zero) next to grad_image, which may be NULL here (zero: a depth-only
+ * step; the library then reads a zero image of its own, allocated once per device at the first such call), and the
+ * projection backward adds the depth map's position term rot^T (g_d p_c / |p_c|) -- g_d = the sum of the Gaussian's depth
+ * floats over the same rows in the same ascending order as frame_aux_depth_backward_kernel takes them -- to dL/dpos before it
+ * steps.  Every updated parameter, both moments and the grad_stat fold are bit for bit what gs_frame_backward of the
+ * flagged frame + gs_adam_step give; culled Gaussians take their zero-gradient step, skip_if_nonzero skips the step of an
+ * overflowed frame.  GS_E_INVALID for a frame without GS_FRAME_AUX (gs_frame_backward_adam is its entry point), a frame
+ * that is not a training frame, a NULL or invalid `adam`; GS_E_UNSUPPORTED with GS_FRAME_POSE_GRAD.  Everything is checked
+ * before anything is enqueued.  rgb and SH colours (color_dim 3 / 27 / 48). */
+int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam, gs_stream_t stream);
+
 /* Device address of the frame's overflow counter (inside the caller's workspace; 64-bit, 0 = the last forward of this
  * frame description fitted its pair capacity, else the pair count it would have needed).  No launch, no copy. */
 int gs_frame_overflow_flag(const gs_frame *f, const void **device_counter);
@@ -625,6 +642,21 @@ size_t gs_loss_workspace_bytes(int32_t H, int32_t W);
 int gs_loss_l1_ssim(const float *pred, const float *target, int32_t H, int32_t W, float ssim_weight,
                     float *grad, float *loss_out, void *workspace, size_t workspace_bytes,
                     gs_stream_t stream);
+
+/* Depth supervision on the maps of a GS_FRAME_AUX frame: depth D = sum_i w_i d_i and alpha A = sum_i w_i, [H,W] fp32, against
+ * a measured RANGE `target` [H,W] (distance from the camera centre, as d_i = |p_c| is; z-depth is converted by the caller:
+ * range = z |ray| / ray_z).  A target pixel that is <= 0, infinite or NaN carries no measurement and does not count.
+ *   mode 0: r = D - A target  (= sum_i w_i (d_i - target): no division, defined everywhere)
+ *   mode 1: r = D / A - target  (the expected depth), counted only where A >= alpha_min (> 0)
+ *   loss = scale * sum_counted |r|,  grad_depth = scale sign(r) dr/dD,  grad_alpha = scale sign(r) dr/dA,
+ * both gradients exactly zero where the pixel does not count.  Put weight / (number of valid target pixels) into `scale`:
+ * no count pass, no host synchronisation.  loss_out (device, may be NULL) receives (loss, number of pixels that counted --
+ * exact up to 2^24).  The five maps must be 16-byte aligned.  One streaming pass and a one-workgroup reduction in double,
+ * fixed order, no atomics: bitwise repeatable.  The two gradient maps are what gs_frame.grad_depth / grad_alpha take. */
+size_t gs_loss_depth_workspace_bytes(int32_t H, int32_t W);
+int gs_loss_depth(const float *depth, const float *alpha, const float *target, int32_t H, int32_t W, int32_t mode,
+                  float alpha_min, float scale, float *grad_depth, float *grad_alpha, float *loss_out, void *workspace,
+                  size_t workspace_bytes, gs_stream_t stream);
 
 /* ---- densification: Gaussian3ds.adaptive_control (splatter.py:122-228) ----
  * Two calls because the number of split Gaussians decides how many standard-normal draws the split

@@ -105,11 +105,7 @@ class OracleFrame:
         magnitudes of the (linear) projection / activation backward.  ``grad_close`` states tolerances in it."""
         sc, cam, grid, rays = self.scene, self.cam, self.grid, self.rays
         n = sc.n
-        top, left = grid.crop_offsets()
-        gpad = np.zeros_like(self.padded)
-        inside = ((self.padded >= 0) & (self.padded <= 1)).astype(np.float32)
-        gpad[top:top + grid.height, left:left + grid.width] = grad_image
-        gpad *= inside
+        gpad = self._padded_grad_image(grad_image)
         out = oracle.draw_backward(self.s_pos, self.s_rgb, self.s_opa, self.s_cov, self.accum, self.padded,
                                    gpad, grid.focal_x, grid.focal_y, use_sh=sc.use_sh, fast=True,
                                    rays_o=rays.rays_o, lefttop=rays.lefttop, vdx=rays.dx, vdy=rays.dy,
@@ -124,28 +120,43 @@ class OracleFrame:
         s_pos_i, s_cov, s_opa, s_col = (_sum_by_id(self.ids, a, n) for a in (cs[0], cs[3], cs[2], cs[1]))
         return grads, self._chain_scale(s_pos_i, s_cov, s_opa, s_col)
 
+    def _padded_grad_image(self, grad_image):
+        """dL/d(image) laid into the padded frame, zero where the clamp to [0, 1] passes no gradient."""
+        grid = self.grid
+        top, left = grid.crop_offsets()
+        gpad = np.zeros_like(self.padded)
+        inside = ((self.padded >= 0) & (self.padded <= 1)).astype(np.float32)
+        gpad[top:top + grid.height, left:left + grid.width] = grad_image
+        gpad *= inside
+        return gpad
+
+    def _rows_f64(self, grad_image):
+        """The (tile, Gaussian) rows (gp, gr, go, gc) of the image's backward in double (oracle.draw_backward_f64)."""
+        sc, grid, rays = self.scene, self.grid, self.rays
+        return oracle.draw_backward_f64(self.s_pos, self.s_rgb, self.s_opa, self.s_cov, self.accum,
+                                        self._padded_grad_image(grad_image), grid.focal_x, grid.focal_y, use_sh=sc.use_sh,
+                                        rays_o=rays.rays_o, lefttop=rays.lefttop, vdx=rays.dx, vdy=rays.dy)
+
     def backward_f64(self, grad_image):
         """The same chain as ``backward`` evaluated in DOUBLE on the fp32 inputs: K8 by oracle.draw_backward_f64
         (its own final colour, exp, sums -- only the stop decisions are the fp32 chain's), the index backward as a
         double sum, the projection backward as torch.autograd (float64) on oracle/torch_ref.project -- A.4 with the
         Jacobian detached, i.e. gaussian.cu:1371-1576 derived independently --, the activations in double.
         The yardstick of tests/test_grad_calibration.py.  -> ((gp, gr, go, gc) rows, {name: parameter gradient})."""
+        rows = self._rows_f64(grad_image)
+        gp, gr, go, gc = rows
+        d_pos_i, d_cov, d_opa, d_col = (_sum_by_id(self.ids, a, self.scene.n) for a in (gp, gc, go, gr))
+        return rows, self._chain_f64(d_pos_i, d_cov, d_opa, d_col)
+
+    def _chain_f64(self, d_pos_i, d_cov, d_opa, d_col):
+        """Per-Gaussian dL/d(pos_i, cov2d, activated opacity, activated colour) -> dL/d(raw parameter) in double: the
+        projection backward as torch.autograd (float64) on oracle/torch_ref.project, the activations in double."""
         import torch
 
         from oracle import torch_ref
 
-        sc, cam, grid, rays = self.scene, self.cam, self.grid, self.rays
+        sc, cam = self.scene, self.cam
         n = sc.n
-        top, left = grid.crop_offsets()
-        gpad = np.zeros_like(self.padded)
-        inside = ((self.padded >= 0) & (self.padded <= 1)).astype(np.float32)
-        gpad[top:top + grid.height, left:left + grid.width] = grad_image
-        gpad *= inside
-        rows = oracle.draw_backward_f64(self.s_pos, self.s_rgb, self.s_opa, self.s_cov, self.accum, gpad,
-                                        grid.focal_x, grid.focal_y, use_sh=sc.use_sh, rays_o=rays.rays_o,
-                                        lefttop=rays.lefttop, vdx=rays.dx, vdy=rays.dy)
-        gp, gr, go, gc = rows
-        d_pos_i, d_cov, d_opa, d_col = (_sum_by_id(self.ids, a, n) for a in (gp, gc, go, gr))
         vis = np.nonzero(self.mask)[0]
         f64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))  # noqa: E731
         q = sc.quat.astype(np.float64)
@@ -168,7 +179,74 @@ class OracleFrame:
         else:
             c = 1.0 / (1.0 + np.exp(-sc.rgb.astype(np.float64)))
             g_c = d_col * c * (1 - c)
-        return rows, {"pos": g_pos, "quat": g_q, "scale": g_s, "opa": g_o, "rgb": g_c}
+        return {"pos": g_pos, "quat": g_q, "scale": g_s, "opa": g_o, "rgb": g_c}
+
+    # ---- the depth / alpha maps of an aux frame (GS_FRAME_AUX): the oracle with the two maps posed as colours.
+    # oracle.draw with the sorted colours (d_i, 1, 0), d_i = s_pos[:, 2] = |p_c| (the sort key), gives the padded (D, A);
+    # oracle.draw_backward with those colours and the gradient (g_D, g_A, 0) gives their rows, whose per-Gaussian colour-0
+    # sum is dL/dd_i and enters d_pos_i[:, 2] of the same projection chain as the image's gradient.
+    def aux_maps(self):
+        """Padded [padH, padW, 3]: (D, A, 0)."""
+        g = self.grid
+        return oracle.draw(self.s_pos, aux_colours(self), self.s_opa, self.s_cov, self.accum, g.padded_height,
+                           g.padded_width, g.focal_x, g.focal_y, use_sh=False, fast=True)
+
+    def _padded_grad_maps(self, gd, ga):
+        """(g_D, g_A, 0) laid into the padded frame; no clamp mask: the maps are not clamped.  None = no such term."""
+        g = self.grid
+        top, left = g.crop_offsets()
+        gpad = np.zeros((g.padded_height, g.padded_width, 3), np.float32)
+        if gd is not None:
+            gpad[top:top + g.height, left:left + g.width, 0] = gd
+        if ga is not None:
+            gpad[top:top + g.height, left:left + g.width, 1] = ga
+        return gpad
+
+    def aux_backward(self, gimg, gd, ga, with_scale=True):
+        """The oracle's gradient of <gimg, image> + <gd, depth> + <ga, alpha> and (``with_scale``) its conditioning scale:
+        the image chain (``backward``) plus the chain of the maps' rows -- colour-0 row sum added to d_pos_i[:, 2], the
+        colour gradient of the aux part zero.  ``gimg`` / ``gd`` / ``ga`` = None: no such term.
+        Keeps the aux pass's (tile, Gaussian) rows in ``aux_pair_grads`` (gp, gr, go, gc)."""
+        g, sc = self.grid, self.scene
+        n = sc.n
+        cols = aux_colours(self)
+        (gp, gr, go, gc), cs = oracle.draw_backward(self.s_pos, cols, self.s_opa, self.s_cov, self.accum, self.aux_maps(),
+                                                    self._padded_grad_maps(gd, ga), g.focal_x, g.focal_y, use_sh=False,
+                                                    fast=True, with_scale=True)
+        self.aux_pair_grads = (gp, gr, go, gc)
+        d_pos_i, d_cov, d_opa = (_sum_by_id(self.ids, a, n) for a in (gp, gc, go))
+        d_pos_i[:, 2] += _sum_by_id(self.ids, gr[:, 0], n)
+        s_pos_i, s_cov, s_opa = (_sum_by_id(self.ids, a, n) for a in (cs[0], cs[3], cs[2]))
+        s_pos_i[:, 2] += _sum_by_id(self.ids, cs[1][:, 0], n)
+        zc = np.zeros((n, sc.rgb.shape[1]))
+        ref = self._chain(d_pos_i, d_cov, d_opa, zc)
+        ref["rgb"][:] = 0.0
+        scale = self._chain_scale(s_pos_i, s_cov, s_opa, zc)
+        if gimg is not None:
+            ref_i, scale_i = self.backward(gimg, with_scale=True)
+            ref = {k: ref_i[k] + ref[k] for k in ref_i}
+            scale = {k: scale_i[k] + scale[k] for k in scale_i}
+        return (ref, scale) if with_scale else ref
+
+    def aux_rows_f64(self, gd, ga):
+        """The maps' (tile, Gaussian) rows (gp, gr, go, gc) in double; gr[:, 0] is the row's share of dL/dd_i."""
+        g = self.grid
+        return oracle.draw_backward_f64(self.s_pos, aux_colours(self), self.s_opa, self.s_cov, self.accum,
+                                        self._padded_grad_maps(gd, ga), g.focal_x, g.focal_y, use_sh=False)
+
+    def aux_backward_f64(self, gimg, gd, ga):
+        """``aux_backward`` in double: the image's and the maps' rows of oracle.draw_backward_f64, summed per Gaussian,
+        through ONE fp64 projection / activation chain (``_chain_f64``, what ``backward_f64`` uses).  -> {name: gradient}"""
+        n = self.scene.n
+        gp, gr, go, gc = self.aux_rows_f64(gd, ga)
+        d_pos_i, d_cov, d_opa = (_sum_by_id(self.ids, a, n) for a in (gp, gc, go))
+        d_pos_i[:, 2] += _sum_by_id(self.ids, gr[:, 0], n)
+        d_col = np.zeros((n, self.scene.rgb.shape[1]))
+        if gimg is not None:
+            ip, ir, io, ic = self._rows_f64(gimg)
+            d_pos_i, d_cov, d_opa = (a + _sum_by_id(self.ids, b, n) for a, b in ((d_pos_i, ip), (d_cov, ic), (d_opa, io)))
+            d_col = _sum_by_id(self.ids, ir, n)
+        return self._chain_f64(d_pos_i, d_cov, d_opa, d_col)
 
     def _chain(self, d_pos_i, d_cov, d_opa, d_col):
         sc, cam = self.scene, self.cam
@@ -212,6 +290,64 @@ class OracleFrame:
             c = self.col_act.astype(np.float64)
             S_c = s_col * c * (1 - c)
         return {"pos": S_pos, "quat": S_q, "scale": S_s, "opa": S_o, "rgb": S_c}
+
+
+def aux_colours(of):
+    """The sorted colours that pose the depth / alpha maps as an image: (d_i, 1, 0), d_i = |p_c| (the sort key)."""
+    d = of.s_pos[:, 2].astype(np.float32)
+    return np.ascontiguousarray(np.stack([d, np.ones_like(d), np.zeros_like(d)], 1), np.float32)
+
+
+def aux_case(n, W, H, seed=7, use_sh=False, sh_degree=2, yaw=2.0, **kw):
+    """The aux tests' scene: make_scene seen from a camera yawed by ``yaw`` degrees and pushed off the origin."""
+    from gs_scene import make_camera, make_scene
+
+    scene = make_scene(n, W, H, seed=seed, use_sh=use_sh, sh_degree=sh_degree, **kw)
+    cam = make_camera(W, H, yaw_deg=yaw)
+    cam.tran = np.array([0.03, -0.01, 0.2], np.float32)
+    return scene, cam
+
+
+def robust_aux_grads(of, rng, image=True):
+    """White-noise dL/dimage [H,W,3] (zeros if not ``image``), dL/ddepth, dL/dalpha [H,W] from ``rng`` (a seed or a numpy
+    Generator), all three zeroed on the pixels whose early-stop decision is not robust in fp32
+    (OracleFrame.robust_grad_image).  -> (gimg, gd, ga, number of pixels masked): the caller caps that number."""
+    g = of.grid
+    rng = np.random.default_rng(rng)
+    gimg = rng.normal(size=of.image.shape).astype(np.float32) if image else np.zeros(of.image.shape, np.float32)
+    gimg_r, n_masked = of.robust_grad_image(np.ones(of.image.shape, np.float32))
+    keep = gimg_r[:, :, 0]  # 1 where the pixel's stop decision is robust, 0 where it is ambiguous
+    gimg = gimg * keep[:, :, None]
+    gd = (rng.normal(size=(g.height, g.width)) * keep).astype(np.float32)
+    ga = (rng.normal(size=(g.height, g.width)) * keep).astype(np.float32)
+    return gimg, gd, ga, n_masked
+
+
+def saturated_share(of, aux_padded=None):
+    """Share of the image's pixels that stopped inside their list: oracle alpha > 0.9999 (transmittance below the 1e-4
+    stop threshold)."""
+    a = of.grid.crop((of.aux_maps() if aux_padded is None else aux_padded)[:, :, 1:2])[:, :, 0]
+    return float(np.mean(a > 0.9999))
+
+
+def depth_loss_f64(D, A, z, mode, alpha_min, scale):
+    """gs_loss_depth's formulas in float64 (the reference of tests/test_gpu_rgbd.py::test_depth_loss_matches_fp64):
+    scale x sum |r| over the measured pixels (z finite and > 0; "expected": and A >= alpha_min), r = D - A z ("residual")
+    or D / A - z ("expected").  -> (dL/dD, dL/dA, loss, pixels counted, r, the mask of the measured pixels)"""
+    D, A, z = (np.asarray(a, np.float64) for a in (D, A, z))
+    valid = np.isfinite(z) & (np.where(np.isfinite(z), z, 0.0) > 0)
+    if mode == "expected":
+        valid &= A >= alpha_min
+    zz = np.where(valid, z, 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if mode == "residual":
+            r, dD, dA = D - A * zz, np.ones_like(D), -zz
+        else:
+            r, dD, dA = D / A - zz, 1.0 / A, -D / (A * A)
+    r = np.where(valid, r, 0.0)
+    gd = np.where(valid, scale * np.sign(r) * dD, 0.0)
+    ga = np.where(valid, scale * np.sign(r) * dA, 0.0)
+    return gd, ga, scale * float(np.abs(r).sum()), int(valid.sum()), r, valid
 
 
 def _sum_by_id(ids, rows, n):

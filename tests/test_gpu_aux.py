@@ -10,34 +10,23 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
 from gaussian import _lib
 from gs_frame import FrameRenderer
 from gs_scene import make_camera, make_scene
-from gs_testutil import OracleFrame, _sum_by_id, assert_grads_close, to_torch
+from gs_testutil import (OracleFrame, assert_grads_close, aux_case, aux_colours, robust_aux_grads,  # noqa: F401
+                         to_torch)
 
 pytestmark = pytest.mark.gpu
 
 IMG_ATOL = 5e-5
 
 
-def case(n, W, H, seed=7, use_sh=False, sh_degree=2, yaw=2.0, **kw):
-    scene = make_scene(n, W, H, seed=seed, use_sh=use_sh, sh_degree=sh_degree, **kw)
-    cam = make_camera(W, H, yaw_deg=yaw)
-    cam.tran = np.array([0.03, -0.01, 0.2], np.float32)
-    return scene, cam
-
-
-def aux_colours(of):
-    d = of.s_pos[:, 2].astype(np.float32)
-    return np.ascontiguousarray(np.stack([d, np.ones_like(d), np.zeros_like(d)], 1), np.float32)
+case = aux_case  # (the scene of every aux test; tests/test_gpu_pose.py imports it from here)
 
 
 def oracle_aux(of):
     """Padded [padH, padW, 3]: (D, A, 0)."""
-    g = of.grid
-    return oracle.draw(of.s_pos, aux_colours(of), of.s_opa, of.s_cov, of.accum, g.padded_height, g.padded_width,
-                       g.focal_x, g.focal_y, use_sh=False, fast=True)
+    return of.aux_maps()
 
 
 def check_maps(of, depth, alpha, aux_padded=None):
@@ -78,19 +67,21 @@ def test_aux_forward_parity(gpu, use_sh, deg, training, sort_mode):
 @pytest.mark.parametrize("training", [False, True])
 def test_aux_forward_long_lists(gpu, training):
     """Lists beyond 2,048 pairs (the per-tile sort's LDS window) with the long-list flags on: the aux frame walks them with
-    one wave (no segments) and still matches the oracle; the image equals the plain frame's within the segment rounding."""
+    one wave (no segments) and matches the oracle to the image standard."""
     scene, cam = make_scene(120_000, 128, 96, seed=8, max_px_sigma=40.0), make_camera(128, 96)
     of = OracleFrame(scene, cam)
     assert np.diff(of.accum).max() > 2048
     params = to_torch(scene, gpu)
     r = FrameRenderer(gpu, max_pairs=len(of.ids) + 64, training=training, auto_grow=False, long_lists=True)
     image, padded, depth, alpha = r.forward(*params, cam, aux=True)
-    assert np.abs(image.cpu().numpy() - of.image).max() < 1e-3
+    # the aux frame composites without segments: the image standard holds (1e-3 until the errors were measured on an MI355X,
+    # inference and training frame alike: image 3.6e-7, alpha 6.0e-7, depth 2.1e-7 absolute at a depth scale of 13.9)
+    assert np.abs(image.cpu().numpy() - of.image).max() < IMG_ATOL
     ref = oracle_aux(of)
     g = of.grid
-    assert np.abs(alpha.cpu().numpy() - g.crop(ref[:, :, 1:2])[:, :, 0]).max() < 1e-3
+    assert np.abs(alpha.cpu().numpy() - g.crop(ref[:, :, 1:2])[:, :, 0]).max() < IMG_ATOL
     dscale = float(np.abs(of.s_pos[:, 2]).max())
-    assert np.abs(depth.cpu().numpy() - g.crop(ref[:, :, 0:1])[:, :, 0]).max() < 1e-3 * dscale
+    assert np.abs(depth.cpu().numpy() - g.crop(ref[:, :, 0:1])[:, :, 0]).max() < IMG_ATOL * dscale
 
 
 @pytest.mark.parametrize("training", [False, True])
@@ -176,40 +167,11 @@ def test_cull_moving_camera_gated_second_pass_keeps_maps_exact(gpu):
 
 def _aux_reference(of, gimg, gd, ga):
     """The oracle's gradient of <gimg, image> + <gd, depth> + <ga, alpha> and its conditioning scale."""
-    g, sc = of.grid, of.scene
-    n = sc.n
-    top, left = g.crop_offsets()
-    ref_i, scale_i = of.backward(gimg, with_scale=True)
-    cols = aux_colours(of)
-    out = oracle_aux(of)
-    gpad = np.zeros_like(out)
-    gpad[top:top + g.height, left:left + g.width, 0] = gd
-    gpad[top:top + g.height, left:left + g.width, 1] = ga
-    (gp, gr, go, gc), cs = oracle.draw_backward(of.s_pos, cols, of.s_opa, of.s_cov, of.accum, out, gpad, g.focal_x,
-                                                g.focal_y, use_sh=False, fast=True, with_scale=True)
-    d_pos_i, d_cov, d_opa = (_sum_by_id(of.ids, a, n) for a in (gp, gc, go))
-    d_pos_i[:, 2] += _sum_by_id(of.ids, gr[:, 0], n)
-    s_pos_i, s_cov, s_opa = (_sum_by_id(of.ids, a, n) for a in (cs[0], cs[3], cs[2]))
-    s_pos_i[:, 2] += _sum_by_id(of.ids, cs[1][:, 0], n)
-    zc = np.zeros((n, sc.rgb.shape[1]))
-    ref_a = of._chain(d_pos_i, d_cov, d_opa, zc)
-    ref_a["rgb"][:] = 0.0
-    scale_a = of._chain_scale(s_pos_i, s_cov, s_opa, zc)
-    ref = {k: ref_i[k] + ref_a[k] for k in ref_i}
-    scale = {k: scale_i[k] + scale_a[k] for k in scale_i}
-    return ref, scale
+    return of.aux_backward(gimg, gd, ga, with_scale=True)
 
 
 def _random_grads(of, seed, image=True):
-    g = of.grid
-    rng = np.random.default_rng(seed)
-    gimg = rng.normal(size=of.image.shape).astype(np.float32) if image else np.zeros(of.image.shape, np.float32)
-    gimg_r, _ = of.robust_grad_image(np.ones(of.image.shape, np.float32))
-    keep = gimg_r[:, :, 0]  # 1 where the pixel's stop decision is robust, 0 where it is ambiguous
-    gimg = gimg * keep[:, :, None]
-    gd = (rng.normal(size=(g.height, g.width)) * keep).astype(np.float32)
-    ga = (rng.normal(size=(g.height, g.width)) * keep).astype(np.float32)
-    return gimg, gd, ga
+    return robust_aux_grads(of, seed, image=image)[:3]
 
 
 @pytest.mark.parametrize("use_sh,deg", [(False, 2), (True, 2), (True, 3)])

@@ -11,7 +11,7 @@ from gaussian import _lib
 from gs_dp import FlatGaussianParams
 from gs_frame import FrameRenderer
 from gs_scene import make_camera, make_scene
-from gs_testutil import to_torch
+from gs_testutil import depth_loss_f64, to_torch
 from gs_train import DepthLoss, FusedAdam, TrainOptions, Trainer, base_lrs, z_to_range
 
 pytestmark = pytest.mark.gpu
@@ -49,22 +49,11 @@ def test_depth_loss_matches_fp64(gpu, H, W, mode):
     dl.grad_alpha.fill_(7.0)
     gd2, ga2 = dl(tD, tA, tz, scale)
     assert torch.equal(gd, gd2) and torch.equal(ga, ga2) and torch.equal(vals, dl.values)  # bitwise repeatable
-    # fp64 reference
+    # fp64 reference (gs_testutil.depth_loss_f64: the one statement of the loss the aux gradient tests use too)
+    ref_gd, ref_ga, ref_loss, ref_n, r, valid = (torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+                                                 for x in depth_loss_f64(D, A, z, mode, alpha_min, scale))
     D64, A64, z64 = (torch.from_numpy(x.astype(np.float64)) for x in (D, A, z))
-    valid = torch.isfinite(z64) & (z64 > 0)
-    if mode == "expected":
-        valid &= A64 >= alpha_min
     zz = torch.where(valid, z64, torch.ones_like(z64))
-    if mode == "residual":
-        r = D64 - A64 * zz
-        dD, dA = torch.ones_like(r), -zz
-    else:
-        r = D64 / A64 - zz
-        dD, dA = 1.0 / A64, -D64 / (A64 * A64)
-    r = torch.where(valid, r, torch.zeros_like(r))
-    ref_gd = torch.where(valid, scale * torch.sign(r) * dD, torch.zeros_like(r))
-    ref_ga = torch.where(valid, scale * torch.sign(r) * dA, torch.zeros_like(r))
-    ref_loss, ref_n = scale * float(r.abs().sum()), int(valid.sum())
     undecidable = valid & (r.abs() < 1e-6 * torch.maximum(D64.abs(), (A64 * zz).abs()))
     share = float(undecidable.sum()) / (H * W)
     got_gd, got_ga = gd.cpu().double(), ga.cpu().double()

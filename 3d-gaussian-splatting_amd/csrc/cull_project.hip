@@ -531,14 +531,9 @@ __device__ __forceinline__ RawGaussian load_raw(const float *__restrict__ pos, c
 // "the prologue's loads are in flight" with the back edge's clean state, and the waitcnt pass, conservative across the
 // merge, puts an `s_waitcnt vmcnt(1)` in front of the first use of the current round's quaternion -- right behind the
 // five loads of the NEXT round, which are thereby waited for as well: the prefetch hid nothing.
-#ifndef GS_PROJECT_PROLOGUE_WAIT
-#define GS_PROJECT_PROLOGUE_WAIT 1
-#endif
 __device__ __forceinline__ void settle(const RawGaussian &r) {
-#if GS_PROJECT_PROLOGUE_WAIT
     asm volatile("" ::"v"(r.p[0]), "v"(r.p[1]), "v"(r.p[2]), "v"(r.sraw[0]), "v"(r.sraw[1]), "v"(r.sraw[2]), "v"(r.qraw[0]),
                  "v"(r.qraw[1]), "v"(r.qraw[2]), "v"(r.qraw[3]), "v"(r.opa), "v"(r.rgb[0]), "v"(r.rgb[1]), "v"(r.rgb[2]));
-#endif
 }
 
 // S1 for one Gaussian: activations -> project -> tile rectangle -> 64-byte record (visible Gaussians only) + the
@@ -638,7 +633,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
     // `gate`: the second, unculled pass of a GS_FRAME_OCCLUSION_CULL frame -- nothing to do unless a tile ran past its cut
     if (gate && *gate == 0) return;
     if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
-        tile_order_workgroup(tile_cost, n_tiles, tile_order, SG.ntx, SG.nty);
+        tile_order_workgroup(tile_cost, n_tiles, tile_order);
         return;
     }
     // this launch covers the slices [slice0, slice0 + S): all of them, or one range of a frame whose project stage is
@@ -757,7 +752,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     __shared__ uint32_t s_acc[2], s_qn, s_ns;
     if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
         if (diag & 16) return;
-        tile_order_workgroup(tile_cost, n_tiles, tile_order, SG.ntx, SG.nty);
+        tile_order_workgroup(tile_cost, n_tiles, tile_order);
         return;
     }
     const uint32_t slice = strip_slice_of_block(blockIdx.x, S);
@@ -1232,9 +1227,6 @@ __global__ void __launch_bounds__(1024) pose_grad_finalize_kernel(const float4 *
     }
 }
 
-#ifndef GS_PB_DIRECT
-#define GS_PB_DIRECT 2  // A/B switch (tools/ab_variants.py): how the rgb rows are fetched, see below
-#endif
 #ifndef GS_PB_SH_PASSES
 #define GS_PB_SH_PASSES 2  // A/B switch: the SH row walk in this many passes over 64 / PASSES owners each (LDS per wave)
 #endif

@@ -13,21 +13,10 @@
     // raster_bwd.hip: stop_key_kernel): the tile's list ascends in (depth bits, Gaussian), so the row exists iff
     // key(g) <= stop key.  Every thread first turns its rectangle into a bit mask of existing rows (stop-key loads eight
     // at a time: a loop with one dependent load per row costs a memory round trip per row -- the first version of this
-    // kernel: 278 us against round 3's 175), then adds the rows up in ascending order, as before: bitwise unchanged.
-    //   GS_PB_DIRECT 2: the wave fetches the existing rows of its 64 Gaussians together, 16 rows per load instruction;
-    //   GS_PB_DIRECT 1: every thread fetches its own existing rows (one aligned 64-byte line each, ~1 per visible
-    //                   Gaussian at 2.4 M Gaussians), two rows in flight;
-    //   GS_PB_DIRECT 0: the workgroup's contiguous row range goes through LDS chunk by chunk, four lanes per existing
-    //                   row, and every thread adds its rows out of LDS.
-    constexpr int CHUNK_ROWS = 512;  // staged variant: 24 KiB of LDS, three float4s (the 10 floats in use) per row
-    __shared__ float4 s_rows[(CDIM == 3 && GS_PB_DIRECT == 0) ? CHUNK_ROWS * 3 : 1];
-    __shared__ uint8_t s_flag[(CDIM == 3 && GS_PB_DIRECT == 0) ? CHUNK_ROWS : 1];
+    // kernel: 278 us against round 3's 175), then the wave fetches the existing rows of its 64 Gaussians together, 16 rows
+    // per load instruction, and every owner adds its rows up in ascending order, as before: bitwise unchanged.
     const int64_t pid0 = (int64_t)blockIdx.x * blockDim.x + g_first, pid = pid0 + threadIdx.x;
-    const int64_t pid_last = (pid0 + blockDim.x < n ? pid0 + blockDim.x : n) - 1;
     const bool valid = pid < n;
-    (void)pid_last;
-    (void)s_rows;
-    (void)s_flag;
     // (y0 | y1 << 16, x0 | x1 << 16, depth bits, tiles touched); depth bits != 0 <=> visible (depth > near > 0).  The
     // record of a culled Gaussian is unspecified (frame_project_kernel does not write it): not read.
     const uint4 rc = valid ? rects[pid] : make_uint4(0, 0, 0, 0);
@@ -134,10 +123,6 @@
     if (CDIM == 3) {
         // ---- which of this Gaussian's (at most 256) rows exist: four 64-bit words, stop keys loaded eight at a time
         unsigned long long wmask[4] = {0ull, 0ull, 0ull, 0ull};
-#ifndef GS_PB_DIAG
-#define GS_PB_DIAG 0  // timing-only builds (tools/ab_variants.py): 1 = no mask, no rows; 2 = mask but no row loads
-#endif
-#if GS_PB_DIRECT == 2
         constexpr int WAVES = BLOCK / 64;
         __shared__ uint32_t s_list[WAVES][64];   // row (relative to `rows`) of entry e of the current batch
         __shared__ float4 s_win[WAVES][64 * 3];  // the 12 leading floats of the batch's rows
@@ -149,8 +134,7 @@
         // their rectangles in owner order, the wave fetches 256 stop keys in one round trip, every owner compares its own
         // -- 0.125 - 0.133 ms against 0.129 - 0.131 ms for the per-thread walk below at 2.4 M Gaussians, 0.044 against
         // 0.043 ms at cfg2: the LDS hand-overs cost what the shorter dependency chain saves.)
-#endif
-        if (GS_PB_DIAG != 1 && vis && !big && cnt) {
+        if (vis && !big && cnt) {
             uint32_t ix = my_x0, iy = my_y0;  // tile of row k, advanced row by row (no division)
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
@@ -185,7 +169,6 @@
                 wmask[w] = m;
             }
         }
-#if GS_PB_DIRECT == 2
         // ---- the WAVE fetches the existing rows of its 64 Gaussians together.  A thread fetching its own rows keeps the
         // wave in the loop for as long as its busiest lane has rows (a Gaussian in front of a dense region: 9+ rows, the
         // average: 1.06), with a memory round trip per pair of rows -- 74 of the kernel's 162 us in a timing-only build
@@ -244,79 +227,6 @@
                 }
             }
         }
-#elif GS_PB_DIRECT
-        // ---- every thread adds its existing rows in ascending order, two rows (six loads) in flight
-        const float4 *myrows = rows + off * RW4;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            unsigned long long m = wmask[w];
-            if (GS_PB_DIAG == 2) {  // keep the mask alive, fetch nothing
-                d0.x += (float)__popcll(m);
-                m = 0;
-            }
-            while (m) {
-                const uint32_t ka = (uint32_t)__ffsll((long long)m) - 1;
-                m &= m - 1;
-                const bool two = m != 0;
-                const uint32_t kb = two ? (uint32_t)__ffsll((long long)m) - 1 : ka;
-                if (two) m &= m - 1;
-                const float4 *ra = myrows + (size_t)(w * 64 + ka) * RW4, *rb = myrows + (size_t)(w * 64 + kb) * RW4;
-                const float4 a0 = ra[0], a1 = ra[1], a2 = ra[2], b0 = rb[0], b1 = rb[1], b2 = rb[2];
-                d0.x += a0.x; d0.y += a0.y; d0.z += a0.z; d0.w += a0.w;
-                d1.x += a1.x; d1.y += a1.y; d1.z += a1.z; d1.w += a1.w;
-                d2.x += a2.x; d2.y += a2.y;
-                if (two) {
-                    d0.x += b0.x; d0.y += b0.y; d0.z += b0.z; d0.w += b0.w;
-                    d1.x += b1.x; d1.y += b1.y; d1.z += b1.z; d1.w += b1.w;
-                    d2.x += b2.x; d2.y += b2.y;
-                }
-            }
-        }
-#else
-        auto mask_bit = [&](uint32_t k) -> bool {  // k < 256
-            const unsigned long long m = k < 64 ? wmask[0] : k < 128 ? wmask[1] : k < 192 ? wmask[2] : wmask[3];
-            return (m >> (k & 63u)) & 1ull;
-        };
-        uint64_t row_begin = pair_offsets[pid0];
-        uint64_t row_end = (uint64_t)pair_offsets[pid_last] + rects[pid_last].w;
-        if (row_end > max_pairs) row_end = max_pairs;
-        for (uint64_t base = row_begin; base < row_end; base += CHUNK_ROWS) {
-            const uint32_t nrows = row_end - base < CHUNK_ROWS ? (uint32_t)(row_end - base) : (uint32_t)CHUNK_ROWS;
-            const uint64_t lo = off > base ? off : base, hi = off + cnt < base + nrows ? off + cnt : base + nrows;
-            // 1. every thread marks which of ITS rows inside this chunk exist (a row belongs to exactly one Gaussian;
-            //    the rows of "big" Gaussians were summed above and are marked absent)
-            for (uint64_t k = lo; k < hi; ++k) s_flag[k - base] = !big && mask_bit((uint32_t)(k - off));
-            __syncthreads();
-            // 2. existing rows -> LDS, four lanes per 64-byte row (the fourth quarter is padding: not fetched); all
-            //    loads of the chunk are issued before the first one is stored
-            const float4 *src = rows + base * RW4;
-            constexpr int PER = CHUNK_ROWS * 4 / 256;
-            float4 v[PER];
-            bool take[PER];
-#pragma unroll
-            for (int u = 0; u < PER; ++u) {
-                const uint32_t i = threadIdx.x + 256u * u, r = i >> 2, q = i & 3;
-                take[u] = i < nrows * 4 && q < 3 && s_flag[r];
-                if (take[u]) v[u] = src[i];
-            }
-#pragma unroll
-            for (int u = 0; u < PER; ++u) {
-                const uint32_t i = threadIdx.x + 256u * u, r = i >> 2, q = i & 3;
-                if (take[u]) s_rows[r * 3 + q] = v[u];
-            }
-            __syncthreads();
-            // 3. every thread adds its existing rows in ascending order
-            for (uint64_t k = lo; k < hi; ++k) {
-                if (!s_flag[k - base]) continue;
-                const float4 *row = s_rows + (k - base) * 3;
-                const float4 r0 = row[0], r1 = row[1], r2 = row[2];
-                d0.x += r0.x; d0.y += r0.y; d0.z += r0.z; d0.w += r0.w;
-                d1.x += r1.x; d1.y += r1.y; d1.z += r1.z; d1.w += r1.w;
-                d2.x += r2.x; d2.y += r2.y;
-            }
-            __syncthreads();
-        }
-#endif
     } else {
         // SH rows are 144 (224) contiguous bytes.  A thread walking its own rows issues, per row, nine (fourteen) loads
         // whose 64 lanes touch 64 different rows: the texture-address unit serialises them lane by lane -- PMC, round 2:
@@ -390,14 +300,6 @@
             }
         }
         static_assert(GS_PB_SH_BIG <= 64, "one 64-bit row mask per Gaussian");
-#ifndef GS_PB_SH_DIAG
-#define GS_PB_SH_DIAG 0  // timing-only builds (tools/ab_variants.py): 2 = the existence mask is built but no row is walked
-#endif
-        if (GS_PB_SH_DIAG == 2) {
-            asm volatile("" ::"v"((uint32_t)written_all), "v"((uint32_t)(written_all >> 32)));  // (the mask stays alive)
-            written_all = 0;
-            maxrows = 0;
-        }
         for (int pass = 0; pass < GS_PB_SH_PASSES; ++pass) {
         const int own0 = pass * OWN;
         const bool mine_pass = lane >= own0 && lane < own0 + OWN;

@@ -73,9 +73,6 @@ __device__ __forceinline__ float block_sum(float v, float *s_red) {
 #ifndef GS_LOSS_FT
 #define GS_LOSS_FT 512
 #endif
-#ifndef GS_LOSS_RCP
-#define GS_LOSS_RCP 1  // the three quotients of the pointwise step through v_rcp_f32 (1 ulp) instead of IEEE divisions
-#endif
 constexpr int FT = GS_LOSS_FT;      // threads = columns of the H1 / V1 / P stages
 constexpr int FHALO = 3 * R;        // flat halo of one horizontal filter
 constexpr int FCW = FT - 2 * FHALO; // output columns of a workgroup
@@ -198,13 +195,9 @@ __global__ void __launch_bounds__(FT) loss_fused_kernel(const float *__restrict_
                 const float vx = fmaxf(vx_raw, 0.f), vy = fmaxf(vy_raw, 0.f);
                 const float A1 = 2.f * mu * nu + L.c1, A2 = 2.f * (exy - mu * nu) + L.c2;
                 const float B1 = mu * mu + nu * nu + L.c1, B2 = vx + vy + L.c2;
-#if GS_LOSS_RCP
+                // the three quotients through v_rcp_f32 (1 ulp) instead of IEEE divisions
                 const float i1 = gs_rcp(B1), i2 = gs_rcp(B2), inv = i1 * i2;
                 const float S = A1 * A2 * inv, S_B2 = S * i2, S_B1 = S * i1;
-#else
-                const float inv = 1.0f / (B1 * B2);
-                const float S = A1 * A2 * inv, S_B2 = S / B2, S_B1 = S / B1;
-#endif
                 // dS/dExx = -S/B2 (zero where the variance clamp is active); the same factor enters dS/dmu
                 const float dExx = vx_raw > 0.f ? -S_B2 : 0.f;
                 const float dmu = 2.f * nu * (A2 - A1) * inv - 2.f * mu * S_B1 - 2.f * mu * dExx;

@@ -1,4 +1,4 @@
-// raster_bwd.hip -- tile rasterizer backward: one wave per 64-Gaussian bucket, two kernels.
+// raster_bwd.hip -- tile rasterizer backward: the tiles' lists in buckets of 64 Gaussians.
 //
 // Replaces draw_backward_kernel (gaussian.cu:440-803).  The reference keeps one pixel per
 // thread and, for EVERY Gaussian, reduces 10 (no SH) or 34 (SH) gradient terms across the
@@ -7,20 +7,25 @@
 //
 // Here a tile's sorted list is cut into BUCKETS of 64 consecutive Gaussians.  Buckets are independent because
 // the forward pass (or its replay for the reference-API entry point) checkpointed every pixel's (T, C_run) at
-// each bucket boundary, so the grid is one wave per (tile, bucket): long tiles are spread over many CUs
-// instead of serialising one workgroup.  Two kernels do the work inside a bucket:
+// each bucket boundary, so long tiles are spread over many CUs instead of serialising one workgroup.  Which
+// kernel works on a bucket (each has its own header):
 //
-//   * no SH -- raster_backward_pixel_kernel: lanes own PIXELS (four each), the bucket's Gaussians are applied
-//     front to back, the ten per-Gaussian sums are reduced over the wave through LDS (see its header);
-//   * SH (and the reference API's `sigmoid` flag) -- raster_backward_kernel, a 64-lane SYSTOLIC pipeline:
-//     lane l keeps Gaussian l's parameters AND its gradient accumulators (10 + 27 / 48 SH sums) in registers,
+//   * raster_backward_pixel_sh_kernel, one wave per bucket: lanes own PIXELS (four each), the bucket's Gaussians
+//     are applied front to back, the per-Gaussian sums are reduced over the wave through LDS.  Every colour model
+//     of the reference API, rgb frames, and -- as raster_aux_backward_kernel -- every GS_FRAME_AUX frame;
+//   * raster_backward_rows_kernel, one wave per bucket: lanes own GAUSSIANS, a step is one pixel row of the tile.
+//     rgb frames flagged GS_FRAME_BWD_ROWS;
+//   * raster_backward_mfma_sh_kernel, a workgroup per work item of up to eight buckets of a tile: the row layout
+//     with the two SH contractions on the matrix pipe.  SH frames;
+//   * raster_backward_kernel, `sigmoid = True` of the reference API only (a rarely used flag), a 64-lane SYSTOLIC
+//     pipeline: lane l keeps Gaussian l's parameters AND its gradient accumulators (10 + 27 SH sums) in registers,
 //     the tile's 256 pixels stream through the lanes: at step t lane l handles pixel t - l.  A pixel's
 //     running state (transmittance T, rho = dL/dC . (C_final - C_run), dL/dC, pixel centre: 7 registers) moves
 //     from lane l to lane l+1 with one DPP `wave_shr:1` per register; lane 0 is fed from LDS.  No cross-lane
 //     reduction and no atomics inside the loop: after 256+63 steps every lane holds the complete sums over
 //     the tile's pixels for its Gaussian.
 //
-// Gradient identities used by both (A.8 of SURVEY.md):
+// Gradient identities used by all of them (A.8 of SURVEY.md):
 //   s = dL/dalpha * alpha,  u = -ln G
 //   dL/dx = ln2 (2A' Sx - B' Sy),            Sx = sum s dx, Sy = sum s dy
 //   dL/da = (-Syy + 2 d Su)/Pn, dL/db = (Sxy - 2 c Su)/Pn, dL/dc = (Sxy - 2 b Su)/Pn,
@@ -159,8 +164,8 @@ struct BwdIn {
     const uint4 *bucket_info;        // [n_buckets] (tile, first Gaussian, count, start of the tile's list)
     const int32_t *ranges;           // FRAME: [T][2]; REF: accum [T+1]
     const uint32_t *tile_order;      // FRAME, optional: the tiles in descending order of their cost (one workgroup per tile)
-    // Long lists (frames flagged GS_FRAME_LONG_LISTS): the per-tile SH kernel takes the first bucket_cap buckets of a tile
-    // (0: all of them), the one-wave-per-bucket kernel the buckets from bucket_first on (see launch_bwd)
+    // Hand-over of long lists: the per-tile SH kernel takes the first bucket_cap buckets of a tile (0: all of them), the
+    // one-wave-per-bucket kernel the buckets from bucket_first on.  Both are 0 since work items (see launch_bwd)
     uint32_t bucket_cap, bucket_first;
     uint32_t use_rows;  // rgb frames: GS_FRAME_BWD_ROWS -- the row-layout kernel instead of the pixel-parallel one (launch_bwd)
     // SH frames on the matrix pipe: the work items (tile, first bucket, buckets) of mfma_items_kernel and their count
@@ -195,11 +200,10 @@ __device__ __forceinline__ void load_pixel_inputs(const BwdIn &I, const RasterGe
     }
 }
 
-// waves per workgroup of the systolic kernel: the degree-3 SH basis records need 20 KiB of LDS per wave, and
-// single-wave workgroups pack the CU's 160 KiB best (the waves of a workgroup never synchronise anyway)
+// the systolic kernel (rgb and degree-2 SH colours: what the reference API has)
 template <int CDIM>
 struct BwdCfg {
-    static constexpr int WPB = CDIM == 48 ? 1 : 4;
+    static constexpr int WPB = 4;  // waves per workgroup, one bucket each (they never synchronise)
     // What is constant per pixel (dL/dC, pixel centre) either rides the DPP chain with the pixel's running state or
     // is read by every lane from an LDS table indexed by the pixel it currently holds.  A DPP move costs as much
     // SIMD time as three plain instructions (tools/ubench/pk_rate.hip), a per-lane LDS read costs no VALU slot but
@@ -208,20 +212,19 @@ struct BwdCfg {
     // the SH basis records already load the LDS pipe).
     static constexpr bool TABLE = CDIM == 3;
     static constexpr int NB = CDIM > 3 ? CDIM / 3 : 1;        // SH basis functions per channel
-    static constexpr int SHS = CDIM == 48 ? 20 : NB;          // LDS record stride (floats): 9 is conflict-free for
-                                                              // scalar reads, 16 + 4 keeps float4 reads aligned
+    static constexpr int SHS = NB;                            // LDS record stride (floats): 9 is conflict-free
 };
 
-// SIG (reference API only): the `sigmoid` flag of draw / draw_backward -- alpha is squashed,
+// The `sigmoid` flag of the reference API's draw / draw_backward -- alpha is squashed,
 // alpha = 2 / (1 + e^-a) - 1 with a = p0 G opa, p0 = (pi/2) rsqrt(det + 1e-7) (gaussian.cu:593-594, 918, 930).
 // p0 is folded into the lane's opacity; its own cov gradient (gaussian.cu:622-630) only needs sum(dL/da G), which
 // is the opacity accumulator, so the loop pays two extra transcendentals and three plain instructions.
 // EXACT (reference API, `fast = 0`, gaussian.cu:596-603): the Gaussian's value through a double-precision exp of the
 // float argument, as the reference's backward evaluates it; v_exp_f32 otherwise.
-template <int CDIM, bool FRAME, bool SIG = false, bool EXACT = false>
+template <int CDIM, bool EXACT>
 __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel(RasterSrc S, RasterGeom G, BwdIn I,
                                                                               BwdOut O) {
-    static_assert(!(FRAME && SIG), "the frame path has no alpha squashing (splatter.py:627 passes sigmoid=False)");
+    static_assert(CDIM == 3 || CDIM == 27, "the reference API has rgb and degree-2 SH colours");
     constexpr int WPB = BwdCfg<CDIM>::WPB, NB = BwdCfg<CDIM>::NB, SHS = BwdCfg<CDIM>::SHS;
     // Feed ring: the 256 pixel states of a bucket enter lane 0 in four segments of 64; while a
     // segment streams through the lanes, the next one is prefetched into registers and then
@@ -232,9 +235,9 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
     __shared__ float4 s_feed[WPB][2][NF][64];
     __shared__ float4 s_pix[TABLE ? WPB : 1][TABLE ? 256 : 1];  // TABLE: (dL/dC rgb, pixel centre x) of tile pixel p
     __shared__ float s_py[TABLE ? WPB : 1][16];                 // TABLE: pixel centre y of tile row p >> 4
-    // SH only: the 9 (16) basis values of a pixel never change while it travels, so they do not ride the DPP chain
+    // SH only: the 9 basis values of a pixel never change while it travels, so they do not ride the DPP chain
     // (9 moves = 28 ns of SIMD time per step, tools/ubench/pk_rate.hip); they are staged once per bucket and
-    // every lane reads the record of the pixel it currently holds (3-4 LDS reads, no VALU issue slots).
+    // every lane reads the record of the pixel it currently holds (LDS reads, no VALU issue slots).
     __shared__ float s_sh[CDIM > 3 ? WPB : 1][CDIM > 3 ? 256 * SHS : 4] __attribute__((aligned(16)));
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t n_tiles = (uint32_t)(G.ntx * G.nty);
@@ -244,7 +247,7 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
     const uint4 info = I.bucket_info[kb];
     const uint32_t tile = info.x, b = info.y / GS_BUCKET;  // bucket -> (tile, local bucket)
     const uint32_t tx = tile % (uint32_t)G.ntx, ty = tile / (uint32_t)G.ntx;
-    const uint32_t start = (uint32_t)(FRAME ? I.ranges[2 * tile] : I.ranges[tile]);
+    const uint32_t start = (uint32_t)I.ranges[tile];
     const uint32_t nproc = I.tile_nproc[tile];
     const uint32_t jloc = b * GS_BUCKET + lane;
     const bool gvalid = jloc < nproc;
@@ -263,7 +266,7 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
         const uint32_t id_y = ty * 16 + (p >> 4);
         pc = b == 0 ? make_float4(1.f, 0.f, 0.f, 0.f) : ck[p];  // bucket 0 starts from the empty pixel (not stored)
         float f[3], g[3];
-        load_pixel_inputs<FRAME>(I, G, id_x, id_y, f, g);
+        load_pixel_inputs<false>(I, G, id_x, id_y, f, g);
         pf0 = f[0];
         pf1 = f[1];
         pf2 = f[2];
@@ -314,11 +317,11 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
     float coef[CDIM > 3 ? CDIM : 1];
     uint32_t gid = 0;
     if (gvalid) {
-        gid = raster_load<FRAME>(S, j, g);
+        gid = raster_load<false>(S, j, g);
         if (CDIM == 3) {
-            raster_load_rgb<FRAME>(S, j, gid, col0, col1, col2);
+            raster_load_rgb<false>(S, j, gid, col0, col1, col2);
         } else {
-            const float *src = raster_sh_ptr<FRAME, CDIM>(S, j, gid);
+            const float *src = raster_sh_ptr<false, CDIM>(S, j, gid);
 #pragma unroll
             for (int q = 0; q < CDIM; ++q) coef[q] = src[q];
         }
@@ -329,11 +332,8 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
     float cA = 0, cB = 0, cC = 0;
     if (gvalid) raster_conic(g, cA, cB, cC);
     float opa = gvalid ? g.opa : 0.f;  // opacity 0 => alpha 0 => state passes through unchanged
-    float p0 = 1.0f;
-    if (SIG) {  // the same folding as the forward kernel (raster_fwd.hip)
-        p0 = 1.5707963268f * rsqrtf(raster_det(g.a, g.b, g.c, g.d) + 1e-7f);
-        opa *= p0;
-    }
+    const float p0 = 1.5707963268f * rsqrtf(raster_det(g.a, g.b, g.c, g.d) + 1e-7f);
+    opa *= p0;  // the same folding as the forward kernel (raster_fwd.hip)
     write_segment(0, 0);
 
     // gradient accumulators
@@ -376,19 +376,8 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
             float sh[NB];
             if (CDIM > 3) {
                 const float *rec = &s_sh[wave][p * SHS];
-                if (NB % 4 == 0) {
 #pragma unroll
-                    for (int q = 0; q < NB / 4; ++q) {
-                        const float4 v = reinterpret_cast<const float4 *>(__builtin_assume_aligned(rec, 16))[q];
-                        sh[4 * q] = v.x;
-                        sh[4 * q + 1] = v.y;
-                        sh[4 * q + 2] = v.z;
-                        sh[4 * q + 3] = v.w;
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < NB; ++q) sh[q] = rec[q];
-                }
+                for (int q = 0; q < NB; ++q) sh[q] = rec[q];
             }
 
             const float dx = px - g.x, dy = py - g.y;
@@ -396,7 +385,7 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
             const float Gv = EXACT ? (float)exp(-(double)(q * GS_LN2)) : gs_exp2(-q);
             const bool live = T > GS_T_STOP;
             const float araw = live ? Gv * opa : 0.f;  // before squashing
-            const float alpha = SIG ? gs_squash_alpha(araw) : araw;
+            const float alpha = gs_squash_alpha(araw);
             const float w = alpha * T;
             if (CDIM > 3) {
                 float v0 = 0.f, v1 = 0.f, v2 = 0.f;
@@ -416,7 +405,7 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
             const float one_m = 1.0f - alpha;
             float d_alpha = fmaf(T, gc, -(rho * gs_rcp(one_m + 1e-7f)));
             d_alpha = live ? d_alpha : 0.f;
-            if (SIG) d_alpha *= (alpha + 1.0f) - 0.5f * (alpha + 1.0f) * (alpha + 1.0f);  // d squash / da, :727
+            d_alpha *= (alpha + 1.0f) - 0.5f * (alpha + 1.0f) * (alpha + 1.0f);  // d squash / da, :727
             if (CDIM > 3) {
                 const float D0 = g0 * w * (col0 * (1.0f - col0)), D1 = g1 * w * (col1 * (1.0f - col1)),
                             D2 = g2 * w * (col2 * (1.0f - col2));
@@ -466,310 +455,33 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
     float gb = iPn * (Sxy - 2.0f * g.c * Su);
     float gc = iPn * (Sxy - 2.0f * g.b * Su);
     float gd = iPn * (-Sxx + 2.0f * g.a * Su);
-    if (SIG) {
-        // dp0/d{a,b,c,d} = k0 (-d, c, b, -a), k0 = p0^3 / (2 (pi/2)^2) (gaussian.cu:622-626), times
-        // sum_pixels dL/da G opa_raw (:740-744); Sopa so far is sum dL/da G
-        const float k = 0.5f * (p0 * p0 * p0) / (1.5707963268f * 1.5707963268f) * Sopa * g.opa;
-        ga -= k * g.d;
-        gb += k * g.c;
-        gc += k * g.b;
-        gd -= k * g.a;
-        Sopa *= p0;  // dL/dopa = sum dL/da (p0 G)
-    }
-    if (FRAME) {
-        const uint4 rc = O.rects[gid];
-        const uint32_t y0 = rc.x & 0xffff, x0 = rc.y & 0xffff, x1 = rc.y >> 16;
-        const uint64_t slot = (uint64_t)O.pair_offsets[gid] + (ty - y0) * (x1 - x0) + (tx - x0);
-        if (slot < O.max_pairs) {
-            // (the A/B fallback of the frame path -- GS_BWD_SH_PIXEL = 0 -- and no hot path: float by float through the row
-            // layout of gs_frame_layout.h, every float of the row written)
-            constexpr int RW = gs_row_floats(CDIM);
-            float *row = O.rows + slot * RW;
-#pragma unroll
-            for (int m = 0; m < RW; ++m) row[m] = 0.f;
-            const float geo[7] = {gx, gy, ga, gb, gc, gd, Sopa};
-#pragma unroll
-            for (int m = 0; m < 7; ++m) row[gs_row_geo(CDIM, m)] = geo[m];
-            if (CDIM == 3) {
-                row[gs_row_col(3, 0)] = Sc0;
-                row[gs_row_col(3, 1)] = Sc1;
-                row[gs_row_col(3, 2)] = Sc2;
-            } else {
-#pragma unroll
-                for (int k = 0; k < CDIM; ++k) row[gs_row_col(CDIM, k)] = Ssh[k];
-            }
-        }
+    // dp0/d{a,b,c,d} = k0 (-d, c, b, -a), k0 = p0^3 / (2 (pi/2)^2) (gaussian.cu:622-626), times
+    // sum_pixels dL/da G opa_raw (:740-744); Sopa so far is sum dL/da G
+    const float k0 = 0.5f * (p0 * p0 * p0) / (1.5707963268f * 1.5707963268f) * Sopa * g.opa;
+    ga -= k0 * g.d;
+    gb += k0 * g.c;
+    gc += k0 * g.b;
+    gd -= k0 * g.a;
+    Sopa *= p0;  // dL/dopa = sum dL/da (p0 G)
+    O.grad_pos[(size_t)j * 3 + 0] = gx;
+    O.grad_pos[(size_t)j * 3 + 1] = gy;
+    O.grad_opa[j] = Sopa;
+    reinterpret_cast<float4 *>(O.grad_cov)[j] = make_float4(ga, gb, gc, gd);
+    if (CDIM == 3) {
+        O.grad_rgb[(size_t)j * 3 + 0] = Sc0;
+        O.grad_rgb[(size_t)j * 3 + 1] = Sc1;
+        O.grad_rgb[(size_t)j * 3 + 2] = Sc2;
     } else {
-        O.grad_pos[(size_t)j * 3 + 0] = gx;
-        O.grad_pos[(size_t)j * 3 + 1] = gy;
-        O.grad_opa[j] = Sopa;
-        reinterpret_cast<float4 *>(O.grad_cov)[j] = make_float4(ga, gb, gc, gd);
-        if (CDIM == 3) {
-            O.grad_rgb[(size_t)j * 3 + 0] = Sc0;
-            O.grad_rgb[(size_t)j * 3 + 1] = Sc1;
-            O.grad_rgb[(size_t)j * 3 + 2] = Sc2;
-        } else {
 #pragma unroll
-            for (int k = 0; k < CDIM; ++k) O.grad_rgb[(size_t)j * CDIM + k] = Ssh[k];
-        }
+        for (int k = 0; k < CDIM; ++k) O.grad_rgb[(size_t)j * CDIM + k] = Ssh[k];
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// No SH: the pixel-parallel bucket kernel.  One wave per (tile, bucket of 64 Gaussians), lanes own PIXELS (four
-// each, the forward's layout), the bucket's Gaussians are applied one after the other from the bucket's checkpoint,
-// and the ten per-Gaussian sums are reduced over the wave through LDS, two Gaussians at a time: 20 rows of 64
-// partials, three lanes per row add a slice each (60 lanes busy), one lane per row adds the three slice sums, and
-// at the end lane i finishes the algebra of Gaussian i and stores its row.
-// Why not the systolic pipeline here: per (pixel, Gaussian) pair it issues 0.89 VALU instructions (every lane
-// carries one pair per step: its own q, exp, rcp, DPP moves, table addressing; PMC), this layout 0.59 (dx and the
-// Gaussian's constants are shared by the lane's four pixels, the reduction costs 20 of 146 instructions per
-// Gaussian) -- and both are VALU-issue bound.  Measured, same run: cfg2 0.450 -> 0.362 ms, 2.4 M Gaussians
-// 0.776 -> 0.611 ms.  It started as the handler of the ragged tails of the systolic kernel (a 5-Gaussian bucket
-// costs the systolic pipeline as much as a full one) and took over the whole no-SH backward.
-#ifndef GS_PP_TG
-#define GS_PP_TG 2
-#endif
-#ifndef GS_PP_WPB
-#define GS_PP_WPB 1
-#endif
-template <bool FRAME>
-__global__ void __launch_bounds__(64 * GS_PP_WPB) raster_backward_pixel_kernel(RasterSrc S, RasterGeom G, BwdIn I,
-                                                                                BwdOut O) {
-    constexpr int TG = GS_PP_TG;          // Gaussians per reduction group (LDS: TG x 10 rows of 64 partials)
-    constexpr int LPR = 60 / (10 * TG);   // lanes that share the sum of one row (two-level reduction)
-    constexpr int CH = (64 + LPR - 1) / LPR;
-    enum { FX, FY, FA, FB, FC, FOPA, FC0, FC1, FC2, NFLD };
-    constexpr int WPB = GS_PP_WPB;  // waves per workgroup, one bucket each (they never synchronise); 1 measured best
-    __shared__ float sw_g[WPB][NFLD][64];
-    __shared__ float sw_red[WPB][TG * 10][65];
-    __shared__ float sw_part[WPB][TG * 10][LPR + 1];
-    __shared__ float sw_tot[WPB][64][10];
-    const int wave = threadIdx.x >> 6;
-    float (*s_g)[64] = sw_g[wave];
-    float (*s_red)[65] = sw_red[wave];
-    float (*s_part)[LPR + 1] = sw_part[wave];
-    float (*s_tot)[10] = sw_tot[wave];
-    // LDS traffic of ONE wave is processed in program order, so the stages below only need the compiler
-    // not to move LDS accesses across them.  (A `fence acq_rel` would also drain the outstanding global
-    // loads and stores -- measured: 80 us of a 124 us kernel when the row stores sat inside the loop.)
-    auto lds_order = [] {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-    };
-    const int lane = threadIdx.x & 63;
-    // ---- work item: ONE load; everything below is issued before anything is waited for (the loads of the wave's
-    // short life -- bucket record, ids -> Gaussian records, checkpoints, pixel inputs -- used to be eight dependent
-    // round trips, ~9 us in front of ~11 us of arithmetic)
-    const uint32_t n_tiles = (uint32_t)(G.ntx * G.nty), kb = blockIdx.x * WPB + wave;
-    const uint4 info = I.bucket_info[kb];  // in bounds for every launched wave (the table is padded)
-    if (kb >= I.bucket_offsets[n_tiles]) return;
-    const uint32_t tile = info.x, base = info.y, r = info.z, start = info.w;
-    const uint32_t tx = tile % (uint32_t)G.ntx, ty = tile / (uint32_t)G.ntx;
-
-    // ---- this lane's Gaussian (lanes >= r re-read the bucket's last one and are zeroed below: no branch around
-    // the loads) and its four pixels (x, y0 + 4k)
-    GaussianRec g;
-    float c0, c1, c2;
-    const uint32_t jl = start + base + ((uint32_t)lane < r ? (uint32_t)lane : r - 1);
-    const uint32_t gid = raster_load<FRAME>(S, jl, g);
-    raster_load_rgb<FRAME>(S, jl, gid, c0, c1, c2);
-    const uint32_t id_x = tx * 16 + (lane & 15), id_y0 = ty * 16 + (lane >> 4);
-    const float px = raster_pixel_coord(id_x, G.padW, G.focal_x);
-    const float4 *ck = I.ckpt + raster_ckpt_slot(start, tile, base / GS_BUCKET) * 256;
-    float4 c[4];
-    float f[4][3], gr[4][3];
-    bool inside[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        c[k] = ck[64 * k + lane];  // tile pixel index = 16 (y - ty 16) + (x - tx 16); stale for the first bucket
-        // final colour and dL/dC of the pixel (see load_pixel_inputs): raw loads from clamped addresses here, the
-        // crop / clamp masks after ALL loads are in flight
-        const uint32_t id_y = id_y0 + 4 * k;
-        const float *cf = I.c_final + ((size_t)id_y * G.padW + id_x) * 3;
-        const int ox = FRAME ? (int)id_x - G.crop_left : (int)id_x, oy = FRAME ? (int)id_y - G.crop_top : (int)id_y;
-        inside[k] = !FRAME || (ox >= 0 && ox < G.width && oy >= 0 && oy < G.height);
-        const float *gp = I.grad + ((size_t)(inside[k] ? oy : 0) * (FRAME ? G.width : G.padW) + (inside[k] ? ox : 0)) * 3;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            f[k][e] = cf[e];
-            gr[k][e] = gp[e];
-        }
-    }
-    // the compiler would otherwise sink each gradient load behind its `inside` test and wait for it there: four
-    // dependent round trips instead of one
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        asm volatile("" ::"v"(gr[k][0]), "v"(gr[k][1]), "v"(gr[k][2]), "v"(f[k][0]), "v"(f[k][1]), "v"(f[k][2]),
-                     "v"(c[k].x), "v"(c[k].y), "v"(c[k].z), "v"(c[k].w));
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-            gr[k][e] = (inside[k] && (!FRAME || (f[k][e] >= 0.f && f[k][e] <= 1.f))) ? gr[k][e] : 0.f;
-    float cA = 0, cB = 0, cC = 0;
-    {
-        const bool valid = (uint32_t)lane < r;
-        raster_conic(g, cA, cB, cC);
-        // what the pixel loop reads goes to LDS; what only the final algebra of THIS lane's Gaussian needs
-        // (covariance, conic, id) stays in its registers
-        s_g[FX][lane] = g.x;
-        s_g[FY][lane] = g.y;
-        s_g[FA][lane] = cA;
-        s_g[FB][lane] = cB;
-        s_g[FC][lane] = cC;
-        s_g[FOPA][lane] = valid ? g.opa : 0.f;  // opacity 0 => alpha 0: padded entries contribute exact zeros
-        s_g[FC0][lane] = c0;
-        s_g[FC1][lane] = c1;
-        s_g[FC2][lane] = c2;
-    }
-    float py[4], T[4], rho[4], g0[4], g1[4], g2[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        py[k] = raster_pixel_coord(id_y0 + 4 * k, G.padH, G.focal_y);
-        // the tile's first bucket starts from the empty pixel (T, C) = (1, 0), which the forward does not store
-        const float4 ci = base == 0 ? make_float4(1.f, 0.f, 0.f, 0.f) : c[k];
-        g0[k] = gr[k][0];
-        g1[k] = gr[k][1];
-        g2[k] = gr[k][2];
-        T[k] = ci.x;
-        rho[k] = g0[k] * (f[k][0] - ci.y) + g1[k] * (f[k][1] - ci.z) + g2[k] * (f[k][2] - ci.w);
-    }
-    lds_order();
-
-    for (uint32_t i0 = 0; i0 < r; i0 += TG) {
-        // Step 1, everything that does not depend on the pixels' running state: the exponent, G = 2^-q and
-        // 1 / (1 - alpha + 1e-7) for the TG x 4 (Gaussian, pixel) pairs -- 2 TG x 4 independent transcendentals
-        // in flight (left inside the serial chain below they cost ~10 ns each instead of 3.4: ablation).  The
-        // reciprocal is taken for the live case; a finished pixel has d_alpha forced to zero whatever it is.
-        float dxs[TG], dys[TG][4], qs[TG][4], Gs[TG][4], rcs[TG][4], ops[TG], cc[TG][3];
-#pragma unroll
-        for (int u = 0; u < TG; ++u) {
-            const uint32_t i = i0 + u;  // < 64: padded entries have opacity 0 and contribute exact zeros
-            const float gx = s_g[FX][i], gy = s_g[FY][i], uA = s_g[FA][i], uB = s_g[FB][i], uC = s_g[FC][i];
-            ops[u] = s_g[FOPA][i];
-            cc[u][0] = s_g[FC0][i];
-            cc[u][1] = s_g[FC1][i];
-            cc[u][2] = s_g[FC2][i];
-            const float dx = px - gx;
-            const float bdx = uB * dx, adx2 = uA * dx * dx;
-            dxs[u] = dx;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float dy = py[k] - gy;
-                const float q = fmaf(fmaf(uC, dy, -bdx), dy, adx2);
-                const float Gv = gs_exp2(-q);
-                dys[u][k] = dy;
-                qs[u][k] = q;
-                Gs[u][k] = Gv;
-                // 1 / (1 - alpha + 1e-7) (gaussian.cu:722) as ONE fma + rcp: the constant is the fp32 neighbour of
-                // 1 + 1e-7 (1 + 2^-23), 2e-8 away -- below the rounding of the two-step form it replaces
-                rcs[u][k] = gs_rcp(fmaf(-Gv, ops[u], 1.00000011920928955f));
-            }
-        }
-        // Step 2, front to back through the group: the chain through T and rho is plain arithmetic only
-#pragma unroll
-        for (int u = 0; u < TG; ++u) {
-            const float dx = dxs[u], opa = ops[u], c0 = cc[u][0], c1 = cc[u][1], c2 = cc[u][2];
-            // dx is the same for the lane's four pixels: sum(s), sum(s dy) are accumulated and multiplied by dx / dx^2
-            // once per Gaussian (Sx, Sxx, Sxy need no per-pixel instruction)
-            float S1 = 0, Sy = 0, Syy = 0, Sq = 0, Sopa = 0, Sc0 = 0, Sc1 = 0, Sc2 = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float dy = dys[u][k], q = qs[u][k], Gv = Gs[u][k];
-                const bool live = T[k] > GS_T_STOP;
-                const float alpha = live ? Gv * opa : 0.f;
-                const float w = alpha * T[k];
-                const float gc = fmaf(g2[k], c2, fmaf(g1[k], c1, g0[k] * c0));
-                rho[k] = fmaf(-w, gc, rho[k]);
-                float d_alpha = fmaf(T[k], gc, -(rho[k] * rcs[u][k]));
-                d_alpha = live ? d_alpha : 0.f;
-                Sc0 = fmaf(g0[k], w, Sc0);
-                Sc1 = fmaf(g1[k], w, Sc1);
-                Sc2 = fmaf(g2[k], w, Sc2);
-                Sopa = fmaf(d_alpha, Gv, Sopa);
-                const float s = d_alpha * alpha;
-                const float sdy = s * dy;
-                S1 += s;
-                Sy += sdy;
-                Syy = fmaf(sdy, dy, Syy);
-                Sq = fmaf(s, q, Sq);
-                T[k] = T[k] - w;
-            }
-            const float Sx = S1 * dx, Sxx = Sx * dx, Sxy = Sy * dx;
-            float *red = &s_red[u * 10][lane];
-            red[0 * 65] = Sx;
-            red[1 * 65] = Sy;
-            red[2 * 65] = Sxx;
-            red[3 * 65] = Sxy;
-            red[4 * 65] = Syy;
-            red[5 * 65] = Sq;
-            red[6 * 65] = Sopa;
-            red[7 * 65] = Sc0;
-            red[8 * 65] = Sc1;
-            red[9 * 65] = Sc2;
-        }
-        lds_order();
-        // two-level sum of the TG x 10 rows: LPR lanes per row add a slice each (60 lanes busy), then one lane per
-        // row adds the LPR slice sums.  Row 10 u + m = value m of Gaussian i0 + u.
-        if (lane < TG * 10 * LPR) {
-            const int row = lane / LPR, part = lane % LPR;
-            float t0 = 0, t1 = 0;
-#pragma unroll
-            for (int l = 0; l < CH; l += 2) {
-                const int a = part * CH + l;
-                t0 += a < 64 ? s_red[row][a] : 0.f;
-                t1 += a + 1 < 64 ? s_red[row][a + 1] : 0.f;
-            }
-            s_part[row][part] = t0 + t1;
-        }
-        lds_order();
-        if (lane < TG * 10) {
-            float t = s_part[lane][0];
-#pragma unroll
-            for (int l = 1; l < LPR; ++l) t += s_part[lane][l];
-            s_tot[i0 + lane / 10][lane % 10] = t;
-        }
-        lds_order();
-    }
-    if ((uint32_t)lane < r) {  // one lane per Gaussian finishes the algebra and stores its row
-        const uint32_t i = lane;
-        const float *t = s_tot[lane];
-        const float Sx = t[0], Sy = t[1], Sxx = t[2], Sxy = t[3], Syy = t[4], Sq = t[5];
-        const float a = g.a, b = g.b, c = g.c, d = g.d;
-        const float iPn = 1.0f / (2.0f * raster_det(a, b, c, d) + 1e-14f);
-        const float Su = Sq * GS_LN2;
-        const float ogx = GS_LN2 * (2.0f * cA * Sx - cB * Sy), ogy = GS_LN2 * (2.0f * cC * Sy - cB * Sx);
-        const float ga = iPn * (-Syy + 2.0f * d * Su), gb = iPn * (Sxy - 2.0f * c * Su);
-        const float gcc = iPn * (Sxy - 2.0f * b * Su), gd = iPn * (-Sxx + 2.0f * a * Su);
-        if (FRAME) {
-            const uint4 rc = O.rects[gid];
-            const uint32_t y0 = rc.x & 0xffff, x0 = rc.y & 0xffff, x1 = rc.y >> 16;
-            const uint64_t slot = (uint64_t)O.pair_offsets[gid] + (ty - y0) * (x1 - x0) + (tx - x0);
-            if (slot < O.max_pairs) {
-                float4 *row = reinterpret_cast<float4 *>(O.rows + slot * gs_row_floats(3));
-                row[0] = make_float4(ogx, ogy, ga, gb);
-                row[1] = make_float4(gcc, gd, t[6], t[7]);
-                row[2] = make_float4(t[8], t[9], 0.f, 0.f);
-                row[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        } else {
-            const size_t j = (size_t)start + base + i;
-            O.grad_pos[j * 3 + 0] = ogx;
-            O.grad_pos[j * 3 + 1] = ogy;
-            O.grad_opa[j] = t[6];
-            reinterpret_cast<float4 *>(O.grad_cov)[j] = make_float4(ga, gb, gcc, gd);
-            O.grad_rgb[j * 3 + 0] = t[7];
-            O.grad_rgb[j * 3 + 1] = t[8];
-            O.grad_rgb[j * 3 + 2] = t[9];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// SH: the pixel-parallel bucket kernel with per-pixel colours.  Same layout as raster_backward_pixel_kernel -- one
-// wave per (tile, bucket of 64 Gaussians), lanes own four PIXELS (x, y0 + 4k) as two packed pairs, the bucket's
-// Gaussians are applied front to back from the bucket's checkpoint -- plus what SH adds per (pixel, Gaussian):
+// The pixel-parallel bucket kernel, rgb and SH colours.  One wave per (tile, bucket of 64 Gaussians), lanes own four
+// PIXELS (x, y0 + 4k: the forward's layout) as two packed pairs, the bucket's Gaussians are applied front to back from
+// the bucket's checkpoint, dx and the Gaussian's constants are shared by the lane's four pixels.  What SH adds per
+// (pixel, Gaussian):
 //   colour_c = sigmoid(sum_k sh_k(pixel) coef[c][k])   (27 / 48 FMAs forward, packed over the pixel pair)
 //   dL/dcoef[c][k] += dL/dC_c w colour_c (1 - colour_c) sh_k(pixel)   (27 / 48 sums over the tile's pixels)
 // The basis values of the lane's four pixels live in registers for the whole bucket (9 or 16 pairs x 2), the
@@ -791,14 +503,8 @@ struct PixShCfg {
 #ifndef GS_BWD_SH48_WPE
 #define GS_BWD_SH48_WPE 3
 #endif
-#ifndef GS_BWD_SH_SCALAR_ROWS
-#define GS_BWD_SH_SCALAR_ROWS 1  // A/B switch (tools/ab_variants.py): see row_value below
-#endif
 #ifndef GS_BWD_SH_WPE
-#define GS_BWD_SH_WPE 4  // waves per SIMD the register allocation aims at (A/B switch, tools/ab_variants.py)
-#endif
-#ifndef GS_BWD_PAIR_SKIP
-#define GS_BWD_PAIR_SKIP 1
+#define GS_BWD_SH_WPE 4  // waves per SIMD the register allocation aims at (tunable, tools/ab_variants.py)
 #endif
 // Inputs of the depth / alpha terms (GS_FRAME_AUX training frames; raster_aux_backward_kernel): the forward's final (D, A)
 // sums and its per-bucket (D, A) checkpoints, dL/d(depth) and dL/d(alpha) of the cropped maps (NULL = zero).
@@ -819,7 +525,7 @@ __device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, Raste
     static_assert(!AUX || (FRAME && !EXACT), "depth / alpha maps belong to the frame path");
     constexpr int NB = PixShCfg<CDIM>::NB, NROW0 = PixShCfg<CDIM>::NROW;
     constexpr int NROW = NROW0 + (AUX ? 1 : 0);  // AUX: row NROW0 = sum g_D w (the depth gradient)
-    constexpr bool PRE = GS_SH_PRESCALE && CDIM == 27;  // SH basis pre-scaled by -log2(e): raster_common.h
+    constexpr bool PRE = CDIM == 27;  // degree 2: SH basis pre-scaled by -log2(e): raster_common.h
     typedef float f2 __attribute__((ext_vector_type(2)));
     enum { FX, FY, FA, FB, FC, FOPA, FC0, FC1, FC2, NFLD };  // FC0..2: the Gaussian's colour (CDIM == 3 only)
     __shared__ float s_g[NFLD][64];
@@ -892,8 +598,10 @@ __device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, Raste
             gr[k][e] = gp[e];
         }
     }
+    // the compiler would otherwise sink each gradient load behind its `inside` test and wait for it there: four
+    // dependent round trips instead of one
 #pragma unroll
-    for (int k = 0; k < 4; ++k)  // keep every load in front of the first use (see raster_backward_pixel_kernel)
+    for (int k = 0; k < 4; ++k)
         asm volatile("" ::"v"(gr[k][0]), "v"(gr[k][1]), "v"(gr[k][2]), "v"(f[k][0]), "v"(f[k][1]), "v"(f[k][2]),
                      "v"(c[k].x), "v"(c[k].y), "v"(c[k].z), "v"(c[k].w));
 #pragma unroll
@@ -994,10 +702,7 @@ __device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, Raste
         return id;
     };
     uint32_t id_next = load_coef(0);
-#ifndef GS_BWD_PAIR_SKIP48
-#define GS_BWD_PAIR_SKIP48 0  // A/B switch: the finished-half-tile skip for degree 3 as well (round 3: 18 spills at 3 waves)
-#endif
-    constexpr bool PAIR_SKIP = GS_BWD_PAIR_SKIP && (CDIM == 27 || (GS_BWD_PAIR_SKIP48 && CDIM == 48));
+    constexpr bool PAIR_SKIP = CDIM == 27;  // the finished-half-tile skip: degree-2 SH only (below)
     bool pair_live[2] = {true, true};
     (void)pair_live;
     for (uint32_t i = 0; i < r; ++i) {
@@ -1055,7 +760,8 @@ __device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, Raste
                 c1 = splat(s_g[FC1][i]);
                 c2 = splat(s_g[FC2][i]);
             }
-            // 1 / (1 - alpha + 1e-7) as one fma + rcp (see raster_backward_pixel_kernel)
+            // 1 / (1 - alpha + 1e-7) (gaussian.cu:722) as ONE fma + rcp: the constant is the fp32 neighbour of
+            // 1 + 1e-7 (1 + 2^-23), 2e-8 away -- below the rounding of the two-step form it replaces
             const f2 den = pk_fma(-Gv, splat(opa), splat(1.00000011920928955f));
             const f2 rc = {gs_rcp(den.x), gs_rcp(den.y)};
             const bool l0 = T[h].x > GS_T_STOP, l1 = T[h].y > GS_T_STOP;
@@ -1106,16 +812,11 @@ __device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, Raste
             if (AUX && m == NROW0) return Sd.x + Sd.y;
             const int ch = (m - 7) / NB, k = (m - 7) % NB;
             if constexpr (CDIM > 3) {
-#if GS_BWD_SH_SCALAR_ROWS
                 // four products of the lane's four pixels as ONE chain of scalar FMAs: a packed multiply + packed FMA +
                 // the add of the two halves is three instructions but 5.2 ns of issue (packed fp32 has no rate
                 // advantage on this chip: tools/ubench/pk_rate.hip), the chain is four instructions and 4.2 ns
                 return fmaf(D[1][ch].y, SHB[1][k].y,
                             fmaf(D[1][ch].x, SHB[1][k].x, fmaf(D[0][ch].y, SHB[0][k].y, D[0][ch].x * SHB[0][k].x)));
-#else
-                const f2 p = pk_fma(D[1][ch], SHB[1][k], D[0][ch] * SHB[0][k]);
-                return p.x + p.y;
-#endif
             } else {
                 const f2 p = D[0][ch] + D[1][ch];
                 return p.x + p.y;
@@ -1274,98 +975,32 @@ raster_aux_backward_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O, AuxBwdI
 // rho recursions -- over the 16 Gaussians of a group they are a prefix product / prefix sum across the 16 lanes of a DPP
 // row (row_shr 1, 2, 4, 8) -- and the seven geometry / opacity sums, which accumulate over the pixel rows in registers
 // (dx of a lane's four pixel columns is constant over the rows) and are reduced 4 : 1 once per group.
-// A workgroup = one tile (or half of its buckets: GS_BWD_MFMA_SPLIT), W waves; wave w takes buckets w, w + W, ...: the SH table (pre-scaled by -log2 e as in the
-// kernels above), dL/dC and the final colours are staged once per tile; per wave only the pixels' (T, rho) live in LDS
+// A workgroup = one work item (up to GS_MFMA_ITEM_BUCKETS buckets of one tile), W waves; wave w takes buckets w, w + W, ...:
+// the SH table (pre-scaled by -log2 e as in the kernels above), dL/dC and the final colours are staged once per item; per
+// wave only the pixels' (T, rho) live in LDS
 // (read as broadcast float4, written back by the lanes of Gaussian 15 after every pixel row).
 // Transmittance: T_before(g') = T_in prod_{h < g'} max(1 - alpha_h, 0) with UNMASKED alphas; a pixel is live while that
 // is > 1e-4, exactly the reference's test (gaussian.cu:906) up to the rounding of a product tree against a chain; behind
 // the stop every contribution is masked to zero and the unmasked product only ever falls, so it never revives a pixel.
-#ifndef GS_BWD_SH_MFMA
-#define GS_BWD_SH_MFMA 2  // 0: never, 1: degree 3 (48 coefficients) only, 2: degree 2 as well (A/B switch, tools/ab_variants.py)
-#endif
-#ifndef GS_BWD_MFMA_WAVES
-#define GS_BWD_MFMA_WAVES 0  // waves per workgroup: 0 = by the size of the tile grid (below), 2 / 4 = fixed (A/B switch)
-#endif
-// Waves per workgroup, workgroups per tile.  A tile of the 376 k-Gaussian scene has two or three buckets, one of the 2.4 M
+// Waves per workgroup.  A tile of the 376 k-Gaussian scene has two or three buckets, one of the 2.4 M
 // scene four or five, a dense one dozens.  Four waves per tile left one or two of their register / LDS slots idle for the
 // workgroup's whole life on the short tiles (376 k Gaussians, degree 2: 1.12 ms against 1.00 ms for the pixel-parallel
 // kernel); TWO waves: 1.01 ms there, and no worse at 2.4 M Gaussians (1.44 = 1.44 ms at degree 2, 1.46 against 1.50 ms at
 // degree 3; the kernel's first version had lost 5 % with two).  Only a small tile grid with long lists wants the four (192
 // tiles, 900 pairs each: 0.120 against 0.187 ms): fewer workgroups than the device has slots.  Hence two waves from 1,024
-// tiles on, four below.  Measured and dropped (profiles/r04_zz_*): TWO workgroups of two waves per tile (GS_BWD_MFMA_SPLIT =
-// 2: workgroup h takes buckets 2 h + wave, + 4, ...; the second leaves at once on short tiles): 1.61 / 1.67 ms.
-#ifndef GS_BWD_MFMA_SPLIT
-#define GS_BWD_MFMA_SPLIT 1
-#endif
+// tiles on, four below.
+static inline int gs_bwd_mfma_waves(int n_tiles) { return n_tiles >= 1024 ? 2 : 4; }
 #ifndef GS_BWD_MFMA_WPE
 #define GS_BWD_MFMA_WPE 3
 #endif
 
-template <int CTRL>
-__device__ __forceinline__ float gs_dpp(float old, float src) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src),
-                                                                 CTRL, 0xf, 0xf, false));
-}
-// inclusive product / sum over the 16 lanes of a DPP row (lanes whose source falls outside the row keep the identity)
-__device__ __forceinline__ float gs_row_scan_mul(float v) {
-    v *= gs_dpp<0x111>(1.0f, v);
-    v *= gs_dpp<0x112>(1.0f, v);
-    v *= gs_dpp<0x114>(1.0f, v);
-    v *= gs_dpp<0x118>(1.0f, v);
-    return v;
-}
-__device__ __forceinline__ float gs_row_scan_add(float v) {
-    v += gs_dpp<0x111>(0.0f, v);
-    v += gs_dpp<0x112>(0.0f, v);
-    v += gs_dpp<0x114>(0.0f, v);
-    v += gs_dpp<0x118>(0.0f, v);
-    return v;
-}
-
-// The same scans for the lane's four pixels at once, every step ONE instruction per pixel (v_mul_f32_dpp v, v, v row_shr:n:
-// lanes whose source falls outside the row are disabled by the DPP bound check and keep v -- the identity for free;
-// through the builtin the compiler emits v_mov 1.0 + v_mov_dpp + v_mul for a product step).  The four chains are
-// interleaved so that the write of a register and its DPP read in the next step are three instructions apart (the
-// hardware wants two wait states there, and the compiler's hazard pass does not look into inline assembly: hence also
-// the s_nop in front of the first and behind the last instruction of the block).
-#ifndef GS_BWD_MFMA_ASM_SCAN
-#define GS_BWD_MFMA_ASM_SCAN 1
-#endif
-#define GS_SCAN4(OP)                                                                                                   \
-    asm volatile("s_nop 1\n\t" OP " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %1, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %2, %2, %2 row_shr:1 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %3, %3, %3 row_shr:1 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %1, %1, %1 row_shr:2 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %2, %2, %2 row_shr:2 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %3, %3, %3 row_shr:2 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %1, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %2, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %3, %3, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %1, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %2, %2, %2 row_shr:8 row_mask:0xf bank_mask:0xf\n\t" OP                                          \
-                    " %3, %3, %3 row_shr:8 row_mask:0xf bank_mask:0xf\n\ts_nop 1"                                        \
-                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]))
-__device__ __forceinline__ void gs_row_scan_mul4(float v[4]) {
-#if GS_BWD_MFMA_ASM_SCAN
-    GS_SCAN4("v_mul_f32_dpp");
-#else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = gs_row_scan_mul(v[i]);
-#endif
-}
-__device__ __forceinline__ void gs_row_scan_add4(float v[4]) {
-#if GS_BWD_MFMA_ASM_SCAN
-    GS_SCAN4("v_add_f32_dpp");
-#else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = gs_row_scan_add(v[i]);
-#endif
-}
-
+// The DPP row scans of the row-layout kernels, for the lane's four pixels at once and every step ONE instruction per pixel
+// (v_mul_f32_dpp v, v, v row_shr:n: lanes whose source falls outside the row are disabled by the DPP bound check and keep v --
+// the identity for free; through the builtin the compiler emits v_mov 1.0 + v_mov_dpp + v_mul for a product step).  The four
+// chains are interleaved so that the write of a register and its DPP read in the next step are three instructions apart (the
+// hardware wants two wait states there, and the compiler's hazard pass does not look into inline assembly: hence also the
+// s_nop in front of a block).
+//
 // Inclusive prefix sum over the 16 lanes of a DPP row for the lane's four pixels, OUT of place: the first step's
 // bound_ctrl:0 reads 0 where a lane has no source -- the sum's identity --, so `in` survives (round 5: the unscanned w gc
 // gives s = w gc - rho beta one instruction cheaper than dL/dalpha alpha).
@@ -1391,18 +1026,6 @@ __device__ __forceinline__ void gs_row_scan_add4_oop(float out[4], const float i
                  : "v"(in[0]), "v"(in[1]), "v"(in[2]), "v"(in[3]));
     // (no s_nop behind the block: the hazard is VALU write -> DPP READ; what follows reads the results with plain VALU
     // instructions, and the kernels that use this helper contain no compiler-generated DPP instruction)
-}
-// T in front of the lane's Gaussian = T_in x the inclusive product scan of the lane to the left (row_shr:1); the row's first
-// lane has no source: the DPP bound check disables it and it keeps T_in.  t: T_in on entry, the result on exit.
-__device__ __forceinline__ void gs_row_excl_mul4(float t[4], const float scanned[4]) {
-    asm volatile("s_nop 1\n\t"
-                 "v_mul_f32_dpp %0, %4, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %1, %5, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %2, %6, %2 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %3, %7, %3 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3])
-                 : "v"(scanned[0]), "v"(scanned[1]), "v"(scanned[2]), "v"(scanned[3]));
 }
 // Both at once (one asm block, no s_nop between the two: a register written by the scan's last step is read four
 // instructions later): p <- inclusive product scan of p; t <- t x (scanned p of the lane to the left), lane 0 keeps t.
@@ -1430,48 +1053,25 @@ __device__ __forceinline__ void gs_row_scan_mul4_excl(float p[4], float t[4]) {
                  "v_mul_f32_dpp %3, %7, %3 row_shr:1 row_mask:0xf bank_mask:0xf"
                  : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
 }
-// Round 5 instruction diet of the SH row loop (first used by raster_backward_rows_kernel below): the opacity in the
-// exponent's constant term (no G x opacity product), T in front of the Gaussian as one DPP multiply (the builtin costs
-// v_mov 1.0 + v_mov_dpp + v_mul), s = w gc - rho beta.  A/B switch (tools/ab_variants.py).
-#ifndef GS_BWD_MFMA_DIET
-#define GS_BWD_MFMA_DIET 1
-#endif
-
-#ifndef GS_BWD_MFMA_PF
-#define GS_BWD_MFMA_PF 1
-#endif
-#ifndef GS_BWD_MFMA_PK
-// 1: the per-pixel algebra of a row step between the two matrix products on PAIRS of the lane's four pixels (packed fp32, as
-// raster_backward_rows_kernel's GS_BWD_ROWS_PK); the scans, the transcendentals and the stop-point selects stay per pixel
-#define GS_BWD_MFMA_PK 1
-#endif
-static_assert(!GS_BWD_MFMA_PK || GS_BWD_MFMA_DIET, "the packed row step is the diet's");
-#ifndef GS_BWD_MFMA_ORDER
-#define GS_BWD_MFMA_ORDER 1
-#endif
-#ifndef GS_BWD_MFMA_ROW_SKIP
-#define GS_BWD_MFMA_ROW_SKIP 1
-#endif
-#ifndef GS_BWD_MFMA_TILES
-#define GS_BWD_MFMA_TILES 1  // tiles per workgroup (see the kernel's header: the waves of a workgroup share their buckets)
-#endif
-#ifndef GS_BWD_MFMA_CHUNK
-#define GS_BWD_MFMA_CHUNK GS_MFMA_ITEM_BUCKETS  // buckets per work item (gs_frame_layout.h; 0: one workgroup per tile, round 4)
-#endif
-static_assert(GS_BWD_MFMA_CHUNK == 0 || GS_BWD_MFMA_CHUNK >= GS_MFMA_ITEM_BUCKETS, "the item list is sized for GS_MFMA_ITEM_BUCKETS");
-constexpr bool GS_MFMA_ITEMS = GS_BWD_MFMA_CHUNK > 0 && GS_BWD_MFMA_TILES == 1 && GS_BWD_MFMA_SPLIT == 1;
 // workgroups of the matrix-pipe launch: one per work item up to 2 T (the kernel walks the items with the grid as the stride;
 // the executed-row counters have GS_BWD_EXEC_SLOTS x T = 8 T slots for grid x waves)
+static_assert(4 <= GS_BWD_EXEC_SLOTS, "executed-row counters");
 static inline unsigned gs_bwd_mfma_grid(int n_tiles, int64_t max_buckets) {
-    if (!GS_MFMA_ITEMS)
-        return (unsigned)(gs_div_up(n_tiles, GS_BWD_MFMA_TILES) * (GS_BWD_MFMA_TILES == 1 ? GS_BWD_MFMA_SPLIT : 1));
-    const int64_t cap_items = n_tiles + max_buckets / (GS_BWD_MFMA_CHUNK ? GS_BWD_MFMA_CHUNK : 1);
+    const int64_t cap_items = n_tiles + max_buckets / GS_MFMA_ITEM_BUCKETS;
     return (unsigned)(cap_items < 2ll * n_tiles ? cap_items : 2ll * n_tiles);
 }
-template <int CDIM, int W, int TPW>
+// The row step (round 5's instruction diet, first used by raster_backward_rows_kernel below): the opacity in the exponent's
+// constant term (no G x opacity product), T in front of the Gaussian as one DPP multiply, s = w gc - rho beta; the per-pixel
+// algebra between the two matrix products runs on PAIRS of the lane's four pixels (packed fp32); the scans, the
+// transcendentals and the stop-point selects stay per pixel.
+template <int CDIM, int W>
 __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(GS_BWD_MFMA_WPE)))
 raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
     static_assert(CDIM == 27 || CDIM == 48, "SH colours only");
+    // tiles per workgroup, and workgroups per tile.  Both were experiments (two tiles sharing one workgroup's waves; two
+    // workgroups per tile: 1.61 / 1.67 against 1.44 / 1.46 ms) and are 1 for good; the loops below still run over them
+    // because writing them out flat changed the register allocation of all four instantiations (tools/isa_diff.py)
+    constexpr int TPW = 1;
     constexpr int NB = CDIM / 3;          // basis functions per channel: 9 | 16
     constexpr int KQ = NB / 4;            // k blocks of four of the colour product on the matrix pipe: 2 | 4
     // degree 2 has nine basis functions: the ninth would cost a third, three-quarters empty MFMA per channel (14 ns each);
@@ -1493,16 +1093,16 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
         __builtin_amdgcn_wave_barrier();
     };
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // Work items (round 5): (tile, first bucket, buckets) with at most GS_BWD_MFMA_CHUNK buckets, in the forward's dispatch
+    // Work items (round 5): (tile, first bucket, buckets) with at most GS_MFMA_ITEM_BUCKETS buckets, in the forward's dispatch
     // order of the tiles (heavy tiles first), built by mfma_items_kernel underneath the caller's loss.  One workgroup per TILE
     // (round 4) walks a tile's buckets W at a time, so the kernel lasts as long as its longest tile: on the 2.4 M scene
     // (3.8 buckets per tile on average, 14 at most) that is harmless, in a densifying run it is not -- a few tiles with 30 - 100
     // buckets kept one workgroup busy for milliseconds while the device idled (kernel trace of tools/soak.py, SH degree 2:
     // 1.78 ms per call on average, 5.4 ms at worst, at 376 k - 556 k Gaussians; 1.27 ms at 2.4 M Gaussians, profiles/r05_j_*).
     // A workgroup takes items blockIdx.x, + gridDim.x, ... and rebuilds the tile's tables per item (a few microseconds
-    // against >= 56 us per bucket).  Without an item list (GS_BWD_MFMA_CHUNK = 0): one item per tile / tile part, as before.
+    // against >= 56 us per bucket).  Without an item list (I.mfma_items = NULL): one item per tile, as before.
     const uint32_t n_tiles = (uint32_t)(G.ntx * G.nty);
-    constexpr uint32_t SPLIT = TPW == 1 ? GS_BWD_MFMA_SPLIT : 1;
+    constexpr uint32_t SPLIT = 1;
     const uint32_t n_items = I.mfma_items ? *I.mfma_n_items : gridDim.x;
     uint32_t n_exec = 0;  // (wave-uniform) pixel-row steps this wave executed: what its MFMA flops are counted from
     constexpr float KS = -GS_LOG2E;  // the table holds sh'_k = -log2(e) sh_k (raster_common.h)
@@ -1656,24 +1256,20 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 const float dxi = raster_pixel_coord(tx * 16 + 4 * jq + i, G.padW, G.focal_x) - g.x;
                 bdx[i] = cB * dxi;
                 adx2[i] = cA * dxi * dxi;
-#if GS_BWD_MFMA_DIET
                 // q' = q - log2 sigma(opa): alpha = 2^-q'.  A padded entry: q' = 1e30 => alpha = 0 exactly, 0 x 1e30 = 0 in
                 // the sum of s q'; an opacity that underflowed to 0: 2^-(q + 200) is flushed to 0
                 adx2[i] = valid ? adx2[i] - lopa : 1e30f;
-#endif
             }
             const float gy = g.y;
             f4 acc[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-            float S1[4] = {0.f, 0.f, 0.f, 0.f}, Sy[4] = {0.f, 0.f, 0.f, 0.f}, Syy = 0.f, Sq = 0.f;
-#if GS_BWD_MFMA_PK
+            float S1[4] = {0.f, 0.f, 0.f, 0.f}, Sy[4] = {0.f, 0.f, 0.f, 0.f}, Syy = 0.f, Sq = 0.f;  // (S1, Sy, Sq: unpacked behind the loop)
             typedef float f2 __attribute__((ext_vector_type(2)));
             auto pfma = [](f2 x, f2 y, f2 z) { return __builtin_elementwise_fma(x, y, z); };
             f2 S1p[2] = {{0.f, 0.f}, {0.f, 0.f}}, Syp[2] = {{0.f, 0.f}, {0.f, 0.f}}, Sqp = {0.f, 0.f};
-#endif
             // The LDS operands of a pixel row -- the A operands of both products, the row's pixel states and dL/dC -- are
             // requested one row ahead, behind the row's arithmetic and in front of its twelve coefficient MFMAs (registers
             // are free there, and the ~100 cycles of LDS latency pass under the MFMAs; asked for where they are used,
-            // every row started and ended with an exposed wait).  GS_BWD_MFMA_PF = 0: loads where they are used.
+            // every row started and ended with an exposed wait).
             float a_n[KQ], tb_n[4];
             f4 Tin_n, Rin_n, G0_n, G1_n, G2_n, S8_n = {0.f, 0.f, 0.f, 0.f};
             auto row_loads = [&](int s) {
@@ -1689,10 +1285,9 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 G2_n = *reinterpret_cast<const f4 *>(gr2 + prow + 4 * jq);
                 if (TAIL) S8_n = *reinterpret_cast<const f4 *>(tab8 + prow + 4 * jq);
             };
-            if (GS_BWD_MFMA_PF) row_loads(0);
+            row_loads(0);
             for (int s = 0; s < 16; ++s) {  // pixel row s of the tile
                 const int prow = 16 * s;
-                if (!GS_BWD_MFMA_PF) row_loads(s);
                 float a[KQ], tb[4];
 #pragma unroll
                 for (int kk = 0; kk < KQ; ++kk) a[kk] = a_n[kk];
@@ -1703,9 +1298,8 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 // falls) adds exact zeros to every sum of every Gaussian of the group and its states need not move: the
                 // row is left out (wave-uniform).  The tile's list ends where its LAST pixel stops, so at 2.4 M Gaussians a
                 // good part of the rows of a tile's later groups are of this kind.
-                if (GS_BWD_MFMA_ROW_SKIP &&
-                    __ballot(Tin[0] > GS_T_STOP || Tin[1] > GS_T_STOP || Tin[2] > GS_T_STOP || Tin[3] > GS_T_STOP) == 0ull) {
-                    if (GS_BWD_MFMA_PF && s + 1 < 16) row_loads(s + 1);
+                if (__ballot(Tin[0] > GS_T_STOP || Tin[1] > GS_T_STOP || Tin[2] > GS_T_STOP || Tin[3] > GS_T_STOP) == 0ull) {
+                    if (s + 1 < 16) row_loads(s + 1);
                     continue;
                 }
                 ++n_exec;
@@ -1719,7 +1313,6 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 for (int kk = 0; kk < KQ; ++kk)
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) lg[ch] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kk], cob[ch][kk], lg[ch], 0, 0, 0);
-#if GS_BWD_MFMA_PK
                 const float dy = pyt[s] - gy;
                 const f2 dy2 = {dy, dy};
                 f4 Tout, Rout;
@@ -1734,9 +1327,12 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    pin[i] = fminf(fmaxf(1.0f - araw[i], 0.f), 1.0f);  // (the subtraction's clamp modifier; see below)
+                    // (0 <= 1 - alpha <= 1 holds anyway for sane records; written as a clamp to [0, 1] it is the clamp
+                    // modifier of the subtraction, one instruction -- and a NaN / > 1 alpha of a broken record stops the pixel)
+                    pin[i] = fminf(fmaxf(1.0f - araw[i], 0.f), 1.0f);
                     Tb[i] = Tin[i];
                 }
+                // transmittance in front of this Gaussian: T_in times the product over the group's earlier Gaussians
                 gs_row_scan_mul4_excl(pin, Tb);
                 float alpha[4], wg[4], wsum[4];
                 f2 w2[2], al2[2], cc2[3][2];
@@ -1768,6 +1364,7 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                     const f2 den = f2{1.00000011920928955f, 1.00000011920928955f} - f2{araw[2 * h], araw[2 * h + 1]};
                     // s = dL/dalpha alpha = w gc - rho beta, beta = alpha / (1 - alpha + 1e-7): masked with alpha, like w
                     const f2 sv = pfma(-rho, al2[h] * f2{gs_rcp(den.x), gs_rcp(den.y)}, f2{wg[2 * h], wg[2 * h + 1]});
+                    // (the opacity sum, sum of dL/dalpha G over the live pixels, is sum of s / opacity: at the group's end)
                     // D = dL/dC_ch w c (1 - c) [x -ln 2: D sh' = D' sh]
                     const f2 wk = w2[h] * f2{-GS_LN2, -GS_LN2};
                     const f2 g0 = h ? G0.zw : G0.xy, g1 = h ? G1.zw : G1.xy, g2 = h ? G2.zw : G2.xy;
@@ -1786,79 +1383,7 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 }
                 const f2 ss = svs[0] + svs[1];
                 Syy = fmaf((ss.x + ss.y) * dy, dy, Syy);
-#else
-                const float dy = pyt[s] - gy;
-                f4 Tout, Rout;
-                float dv[3][4];
-                float q[4], Gv[4], araw[4], pin[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    q[i] = fmaf(fmaf(cC, dy, -bdx[i]), dy, adx2[i]);
-                    Gv[i] = gs_exp2(-q[i]);
-                    araw[i] = GS_BWD_MFMA_DIET ? Gv[i] : Gv[i] * opa;  // (diet: q is q', 2^-q' is alpha itself)
-                    // (0 <= 1 - alpha <= 1 holds anyway for sane records; written as a clamp to [0, 1] it is the clamp
-                    // modifier of the subtraction, one instruction -- and a NaN / > 1 alpha of a broken record stops the pixel)
-                    pin[i] = fminf(fmaxf(1.0f - araw[i], 0.f), 1.0f);
-                }
-                // transmittance in front of this Gaussian: T_in times the product over the group's earlier Gaussians
-                float Tb[4], alpha[4], w[4], gc[4], wg[4], cc[3][4];
-                bool live[4];
-#if GS_BWD_MFMA_DIET
-#pragma unroll
-                for (int i = 0; i < 4; ++i) Tb[i] = Tin[i];
-                gs_row_scan_mul4_excl(pin, Tb);
-#else
-                gs_row_scan_mul4(pin);
-#endif
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (!GS_BWD_MFMA_DIET) Tb[i] = Tin[i] * gs_dpp<0x111>(1.0f, pin[i]);
-                    live[i] = Tb[i] > GS_T_STOP;
-                    alpha[i] = live[i] ? araw[i] : 0.f;
-                    w[i] = alpha[i] * Tb[i];
-                    // colours sigma(logit) = 1 / (1 + 2^(logit')) with the pre-scaled basis
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) cc[ch][i] = gs_rcp(1.0f + gs_exp2(lg[ch][i]));
-                    gc[i] = fmaf(G2[i], cc[2][i], fmaf(G1[i], cc[1][i], G0[i] * cc[0][i]));
-                    wg[i] = w[i] * gc[i];
-                    Tout[i] = Tin[i] * pin[i];  // (meaningful in the lanes of Gaussian 15: the whole group's product)
-                }
-                // rho behind this Gaussian: rho_in minus the inclusive prefix sum of w gc
-#if GS_BWD_MFMA_DIET
-                float wsum[4];
-                gs_row_scan_add4_oop(wsum, wg);
-#else
-                gs_row_scan_add4(wg);
-                const float *wsum = wg;
-#endif
-                float ssum = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float rho = Rin[i] - wsum[i];
-#if GS_BWD_MFMA_DIET
-                    // s = dL/dalpha alpha = w gc - rho beta, beta = alpha / (1 - alpha + 1e-7): masked with alpha, like w
-                    const float sv = fmaf(-rho, alpha[i] * gs_rcp(1.00000011920928955f - araw[i]), wg[i]);
-#else
-                    const float rc = gs_rcp(fmaf(-Gv[i], opa, 1.00000011920928955f));  // 1 / (1 - alpha + 1e-7)
-                    float d_alpha = fmaf(Tb[i], gc[i], -(rho * rc));
-                    d_alpha = live[i] ? d_alpha : 0.f;
-                    const float sv = d_alpha * alpha[i];
-#endif
-                    // D = dL/dC_ch w c (1 - c) [x -ln 2: D sh' = D' sh]
-                    const float wk = w[i] * -GS_LN2;
-                    dv[0][i] = (G0[i] * wk) * fmaf(-cc[0][i], cc[0][i], cc[0][i]);
-                    dv[1][i] = (G1[i] * wk) * fmaf(-cc[1][i], cc[1][i], cc[1][i]);
-                    dv[2][i] = (G2[i] * wk) * fmaf(-cc[2][i], cc[2][i], cc[2][i]);
-                    // (the opacity sum, sum of dL/dalpha G over the live pixels, is sum of s / opacity: at the group's end)
-                    S1[i] += sv;
-                    Sy[i] = fmaf(sv, dy, Sy[i]);
-                    ssum += sv;
-                    Sq = fmaf(sv, q[i], Sq);
-                    Rout[i] = rho;
-                }
-                Syy = fmaf(ssum * dy, dy, Syy);
-#endif
-                if (GS_BWD_MFMA_PF && s + 1 < 16) {
+                if (s + 1 < 16) {
                     row_loads(s + 1);
                     __builtin_amdgcn_sched_barrier(0);  // (the requests stay in front of the MFMAs below)
                 }
@@ -1873,11 +1398,9 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 }
             }
             asm volatile("" ::"v"(warm));  // (the warming load must not be dropped; its value is not used)
-#if GS_BWD_MFMA_PK
             S1[0] = S1p[0].x, S1[1] = S1p[0].y, S1[2] = S1p[1].x, S1[3] = S1p[1].y;
             Sy[0] = Syp[0].x, Sy[1] = Syp[0].y, Sy[2] = Syp[1].x, Sy[3] = Syp[1].y;
             Sq = Sqp.x + Sqp.y;
-#endif
             // ---- close the group: the lane's four pixel columns, then the four pixel quads of the Gaussian
             const uint32_t gid2 = (uint32_t)__shfl((int)id_lane, (int)(valid ? gi : r - 1), 64);
             const float4 ge2 = S.geom[(size_t)gid2 * GS_REC_STRIDE], cv2 = S.cov4[(size_t)gid2 * GS_REC_STRIDE];
@@ -1886,7 +1409,6 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             // opacity that underflowed to 0 composites nothing; its derivative sigma (1 - sigma) downstream is 0 as well.)
             float Sopa = ((S1[0] + S1[1]) + (S1[2] + S1[3])) * (ge2.w > 0.f ? gs_rcp(ge2.w) : 0.f);
             const float lopa2 = fmaxf(__log2f(ge2.w), -200.0f);
-            (void)lopa2;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float dxi = raster_pixel_coord(tx * 16 + 4 * jq + i, G.padW, G.focal_x) - ge2.x;
@@ -1922,8 +1444,8 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 float cA, cB, cC;
                 gs_conic(a, bb, cc, d, cA, cB, cC);
                 const float iPn = 1.0f / (2.0f * raster_det(a, bb, cc, d) + 1e-14f);
-                // (diet: the loop summed s q' with q' = q - log2 sigma(opa); Sopa x sigma(opa) is the sum of s)
-                const float Su = (GS_BWD_MFMA_DIET ? fmaf(lopa2, Sopa * ge2.w, Sq) : Sq) * GS_LN2;
+                // (the loop summed s q' with q' = q - log2 sigma(opa); Sopa x sigma(opa) is the sum of s)
+                const float Su = fmaf(lopa2, Sopa * ge2.w, Sq) * GS_LN2;
                 h0[0] = GS_LN2 * (2.0f * cA * Sx - cB * Syt);
                 h0[1] = GS_LN2 * (2.0f * cC * Syt - cB * Sx);
                 h0[2] = iPn * (-Syy + 2.0f * d * Su);
@@ -2012,8 +1534,8 @@ __global__ void __launch_bounds__(1024) mfma_items_kernel(const uint32_t *__rest
 // ---------------------------------------------------------------------------------------------
 // rgb colours, frame path (round 5): the ROW layout of the kernel above without its matrix products.
 //
-// One wave per (tile, bucket of 64 Gaussians) -- the grid of raster_backward_pixel_sh_kernel<3>, which this kernel replaces on
-// the frame path --, but inside the bucket lanes own GAUSSIANS, not pixels: lane l = (Gaussian l & 15 of the current group of
+// One wave per (tile, bucket of 64 Gaussians) -- the grid of raster_backward_pixel_sh_kernel<3>, which this kernel replaces in
+// frames flagged GS_FRAME_BWD_ROWS --, but inside the bucket lanes own GAUSSIANS, not pixels: lane l = (Gaussian l & 15 of the current group of
 // 16, pixel quad l >> 4), and a step is one pixel ROW of the tile: 16 Gaussians x 16 pixels, four (pixel, Gaussian) pairs per
 // lane.  What that buys for rgb colours, where there is no contraction to hand to the matrix pipe:
 //   * the ten per-Gaussian sums accumulate in the lane's registers over the 16 pixel rows (a lane's four pixel columns have
@@ -2029,30 +1551,14 @@ __global__ void __launch_bounds__(1024) mfma_items_kernel(const uint32_t *__rest
 // Gaussian is ONE v_mul_f32_dpp (row_shr:1 of the scanned products times T_in, lanes without a source keep T_in).
 // Rows leave as one aligned 64-byte line each, sixteen rows per store instruction; no flags (stop keys).  No atomics; the
 // sums run in a fixed order: bitwise repeatable.
-#ifndef GS_BWD_RGB_ROWS
-// 2: this kernel in frames flagged GS_FRAME_BWD_ROWS (include/gs_abi.h: the caller's statistic says most buckets belong to
-//    saturated tiles), raster_backward_pixel_sh_kernel<3> in the others; 1: this kernel always; 0: never (A/B switch).
+// This kernel in frames flagged GS_FRAME_BWD_ROWS (include/gs_abi.h: the caller's statistic says most buckets belong to
+// saturated tiles), raster_backward_pixel_sh_kernel<3> in the others.
 // Why not always: kernel traces on one box (profiles/r05_e_*) -- 2.4 M Gaussians, every tile saturates: 446 -> 408 us; 376 k
 // Gaussians, none does and no row is ever left out: 276 -> 305 us (the DPP scans cost more than the LDS reduction they
 // replace).  Why not per tile (built: two work lists, one kernel each): the second launch is serial behind the first on
 // the stream and costs the tail of its slowest lone wave (33 us at 376 k Gaussians for the ~100 tiles that do saturate).
-#define GS_BWD_RGB_ROWS 2
-#endif
-#ifndef GS_BWD_ROWS_PF
-// 1: LDS operands of a pixel row requested one row ahead.  Measured equal (same box, 2.4 M Gaussians: 0.497 / 0.514 ms
-// without against 0.508 / 0.498 ms with; profiles/r05_b_*): four resident waves per SIMD cover the LDS latency, and without
-// the second register set the kernel needs 105 VGPRs and no scratch (128 and three spilled registers with it; with the
-// packed row step, GS_BWD_ROWS_PK: 126 and no scratch)
-#define GS_BWD_ROWS_PF 0
-#endif
 #ifndef GS_BWD_ROWS_WPE
 #define GS_BWD_ROWS_WPE 4  // waves per SIMD the register allocation aims at
-#endif
-#ifndef GS_BWD_ROWS_PK
-// 1: the per-pixel algebra of a row step on PAIRS of the lane's four pixels (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two
-// fp32 results per issue slot; the kernel sits at the VALU issue limit).  The DPP scans, the exponentials / reciprocals and
-// the stop-point selects stay per pixel.  0: one instruction per pixel (the first version; A/B switch)
-#define GS_BWD_ROWS_PK 1
 #endif
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GS_BWD_ROWS_WPE)))
 raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
@@ -2079,7 +1585,7 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
     const uint32_t id_lane = S.ids[start + base + ((uint32_t)lane < r ? (uint32_t)lane : r - 1)];
 
     // ---- the tile's pixels at the bucket's boundary: pixel 64 k + lane = (x = lane & 15, y = (lane >> 4) + 4 k).  Every
-    // load is issued before anything is waited for (see raster_backward_pixel_kernel).
+    // load is issued before anything is waited for (see raster_backward_pixel_sh_body).
     {
         const uint32_t id_x = tx * 16 + ((uint32_t)lane & 15), id_y0 = ty * 16 + ((uint32_t)lane >> 4);
         const float4 *ck = I.ckpt + raster_ckpt_slot(start, tile, base / GS_BUCKET) * 256;
@@ -2153,10 +1659,9 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             // (a padded entry: q' = 1e30 => alpha = 0 exactly, and 0 x 1e30 = 0 in the sum of s q')
             adx2[i] = valid ? fmaf(cq.x * dxi, dxi, -lopa) : 1e30f;
         }
-        float S1[4] = {0.f, 0.f, 0.f, 0.f}, Sy[4] = {0.f, 0.f, 0.f, 0.f}, Syy = 0.f, Sq = 0.f;
-        float Sc0 = 0.f, Sc1 = 0.f, Sc2 = 0.f;
-        // The LDS operands of a pixel row are requested one row ahead (GS_BWD_ROWS_PF); the loop runs two rows per trip so
-        // that the two register sets take turns without moves.
+        float Syy = 0.f;
+        // The LDS operands of a pixel row are read where they are used: four resident waves per SIMD cover the LDS latency
+        // (a request one row ahead measured equal and costs a second register set).
         struct RowIn {
             f4 T, R, G0, G1, G2;
             float py;
@@ -2170,19 +1675,23 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             d.G2 = *reinterpret_cast<const f4 *>(s_gr[2] + prow);
             d.py = s_py[s];
         };
-#if GS_BWD_ROWS_PK
+        // The per-pixel algebra of a row step runs on PAIRS of the lane's four pixels (v_pk_fma_f32 / v_pk_mul_f32 /
+        // v_pk_add_f32: two fp32 results per issue slot; the kernel sits at the VALU issue limit).  The DPP scans, the
+        // exponentials / reciprocals and the stop-point selects stay per pixel.
         typedef float f2 __attribute__((ext_vector_type(2)));
         auto sp = [](float v) { return f2{v, v}; };
         auto pfma = [](f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); };
         f2 Scp[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}}, S1p[2] = {{0.f, 0.f}, {0.f, 0.f}}, Syp[2] = {{0.f, 0.f}, {0.f, 0.f}};
         f2 Sqp = {0.f, 0.f};
         const f2 nbdx2[2] = {{nbdx[0], nbdx[1]}, {nbdx[2], nbdx[3]}}, adx22[2] = {{adx2[0], adx2[1]}, {adx2[2], adx2[3]}};
-        auto row_step = [&](RowIn &cur, RowIn &nxt, int s) {  // pixel row s of the tile
-            if (!GS_BWD_ROWS_PF) row_loads(cur, s);
+        auto row_step = [&](int s) {  // pixel row s of the tile
+            RowIn cur;
+            row_loads(cur, s);
+            // a pixel row whose 16 pixels have all stopped adds exact zeros to every sum of every Gaussian of the group and
+            // its states need not move: left out (wave-uniform; the transmittance only falls)
             const bool any_live = __ballot(cur.T[0] > GS_T_STOP || cur.T[1] > GS_T_STOP || cur.T[2] > GS_T_STOP ||
                                            cur.T[3] > GS_T_STOP) != 0ull;
-            if (GS_BWD_ROWS_PF && s + 1 < 16) row_loads(nxt, s + 1);
-            if (!any_live) return;  // (see the per-pixel version below)
+            if (!any_live) return;
             const float dy = cur.py - gy;
             const f2 dy2 = sp(dy);
             f2 q2[2];
@@ -2195,9 +1704,14 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                pin[i] = fminf(fmaxf(1.0f - araw[i], 0.f), 1.0f);  // (the subtraction's clamp modifier)
+                // (0 <= 1 - alpha <= 1 for sane records; as a clamp it is the subtraction's clamp modifier, and a NaN /
+                // > 1 alpha of a broken record stops the pixel)
+                pin[i] = fminf(fmaxf(1.0f - araw[i], 0.f), 1.0f);
                 Tb[i] = cur.T[i];
             }
+            // inclusive product over the group's Gaussians, in place; the transmittance in front of this Gaussian: T_in x the
+            // product over the group's EARLIER Gaussians -- one DPP multiply: lane g >= 1 takes the scanned product of lane
+            // g - 1, lane 0 has no source and keeps T_in
             gs_row_scan_mul4_excl(pin, Tb);
             float alpha[4], wg[4], ws[4];
             f2 w2[2], al2[2];
@@ -2212,6 +1726,7 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 wg[2 * h] = wgh.x;
                 wg[2 * h + 1] = wgh.y;
             }
+            // inclusive prefix sum of w gc over the group's Gaussians, OUT of place: the unscanned wg stays for s below
             gs_row_scan_add4_oop(ws, wg);
             f2 rho2[2], svs[2];
 #pragma unroll
@@ -2220,7 +1735,9 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 rho2[h] = R2 - f2{ws[2 * h], ws[2 * h + 1]};  // rho behind this Gaussian
                 const f2 den = sp(1.00000011920928955f) - f2{araw[2 * h], araw[2 * h + 1]};
                 const f2 beta = al2[h] * f2{gs_rcp(den.x), gs_rcp(den.y)};
-                const f2 sv = pfma(-rho2[h], beta, f2{wg[2 * h], wg[2 * h + 1]});  // s = w gc - rho beta (see below)
+                // s = dL/dalpha alpha with dL/dalpha = T gc - rho / (1 - alpha + 1e-7) (gaussian.cu:716-722)
+                //   = w gc - rho beta,  beta = alpha / (1 - alpha + 1e-7): masked with alpha, like w
+                const f2 sv = pfma(-rho2[h], beta, f2{wg[2 * h], wg[2 * h + 1]});
                 const f2 g0 = h ? cur.G0.zw : cur.G0.xy, g1 = h ? cur.G1.zw : cur.G1.xy, g2 = h ? cur.G2.zw : cur.G2.xy;
                 Scp[0] = pfma(g0, w2[h], Scp[0]);
                 Scp[1] = pfma(g1, w2[h], Scp[1]);
@@ -2242,79 +1759,12 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
                 *reinterpret_cast<f4 *>(s_rho + 16 * s + 4 * jq) = Rout;
             }
         };
-#else
-        auto row_step = [&](RowIn &cur, RowIn &nxt, int s) {  // pixel row s of the tile
-            if (!GS_BWD_ROWS_PF) row_loads(cur, s);
-            // a pixel row whose 16 pixels have all stopped adds exact zeros to every sum of every Gaussian of the group and
-            // its states need not move: left out (wave-uniform; the transmittance only falls)
-            const bool any_live = __ballot(cur.T[0] > GS_T_STOP || cur.T[1] > GS_T_STOP || cur.T[2] > GS_T_STOP ||
-                                           cur.T[3] > GS_T_STOP) != 0ull;
-            if (GS_BWD_ROWS_PF && s + 1 < 16) row_loads(nxt, s + 1);
-            if (!any_live) return;
-            const float dy = cur.py - gy;
-            float q[4], araw[4], pin[4], Tb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                q[i] = fmaf(fmaf(cC, dy, nbdx[i]), dy, adx2[i]);  // q' = q - log2 sigma(opa); the forward's evaluation order
-                araw[i] = gs_exp2(-q[i]);
-                // (0 <= 1 - alpha <= 1 for sane records; as a clamp it is the subtraction's clamp modifier, and a NaN /
-                // > 1 alpha of a broken record stops the pixel)
-                pin[i] = fminf(fmaxf(1.0f - araw[i], 0.f), 1.0f);
-                Tb[i] = cur.T[i];
-            }
-            // inclusive product over the group's Gaussians, in place; the transmittance in front of this Gaussian: T_in x the
-            // product over the group's EARLIER Gaussians -- one DPP multiply: lane g >= 1 takes the scanned product of lane
-            // g - 1, lane 0 has no source and keeps T_in
-            gs_row_scan_mul4_excl(pin, Tb);
-            float alpha[4], w[4], wg[4], ws[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                alpha[i] = Tb[i] > GS_T_STOP ? araw[i] : 0.f;
-                w[i] = alpha[i] * Tb[i];
-                wg[i] = w[i] * fmaf(cur.G2[i], c2, fmaf(cur.G1[i], c1, cur.G0[i] * c0));  // w (dL/dC . colour)
-            }
-            // inclusive prefix sum of w gc over the group's Gaussians, OUT of place: the unscanned wg stays for s below
-            gs_row_scan_add4_oop(ws, wg);
-            float ssum = 0.f;
-            f4 Rout;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float rho = cur.R[i] - ws[i];  // rho behind this Gaussian
-                // s = dL/dalpha alpha with dL/dalpha = T gc - rho / (1 - alpha + 1e-7) (gaussian.cu:716-722)
-                //   = w gc - rho beta,  beta = alpha / (1 - alpha + 1e-7): masked with alpha, like w
-                const float beta = alpha[i] * gs_rcp(1.00000011920928955f - araw[i]);
-                const float sv = fmaf(-rho, beta, wg[i]);
-                Sc0 = fmaf(cur.G0[i], w[i], Sc0);
-                Sc1 = fmaf(cur.G1[i], w[i], Sc1);
-                Sc2 = fmaf(cur.G2[i], w[i], Sc2);
-                S1[i] += sv;
-                Sy[i] = fmaf(sv, dy, Sy[i]);
-                ssum += sv;
-                Sq = fmaf(sv, q[i], Sq);
-                Rout[i] = rho;
-            }
-            Syy = fmaf(ssum * dy, dy, Syy);
-            if (gq == 15) {  // the row's pixel states in front of the next group: T behind the group's last Gaussian
-                f4 Tout;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) Tout[i] = cur.T[i] * pin[i];
-                *reinterpret_cast<f4 *>(s_T + 16 * s + 4 * jq) = Tout;
-                *reinterpret_cast<f4 *>(s_rho + 16 * s + 4 * jq) = Rout;
-            }
-        };
-#endif
-        RowIn ra, rb;
-        if (GS_BWD_ROWS_PF) row_loads(ra, 0);
-        for (int s = 0; s < 16; s += 2) {
-            row_step(ra, rb, s);
-            row_step(rb, ra, s + 1);
+        for (int s = 0; s < 16; s += 2) {  // (two rows per trip: the shape the register allocation was tuned on)
+            row_step(s);
+            row_step(s + 1);
         }
-#if GS_BWD_ROWS_PK
-        S1[0] = S1p[0].x, S1[1] = S1p[0].y, S1[2] = S1p[1].x, S1[3] = S1p[1].y;
-        Sy[0] = Syp[0].x, Sy[1] = Syp[0].y, Sy[2] = Syp[1].x, Sy[3] = Syp[1].y;
-        Sc0 = Scp[0].x + Scp[0].y, Sc1 = Scp[1].x + Scp[1].y, Sc2 = Scp[2].x + Scp[2].y;
-        Sq = Sqp.x + Sqp.y;
-#endif
+        const float S1[4] = {S1p[0].x, S1p[0].y, S1p[1].x, S1p[1].y}, Sy[4] = {Syp[0].x, Syp[0].y, Syp[1].x, Syp[1].y};
+        float Sc0 = Scp[0].x + Scp[0].y, Sc1 = Scp[1].x + Scp[1].y, Sc2 = Scp[2].x + Scp[2].y, Sq = Sqp.x + Sqp.y;
         // ---- close the group: the lane's four pixel columns, then the four pixel quads of the Gaussian
         const float4 cv = rec[1];
         float Sx = 0.f, Sxx = 0.f, Sxy = 0.f, Syt = 0.f, Stot = (S1[0] + S1[1]) + (S1[2] + S1[3]);
@@ -2385,29 +1835,21 @@ raster_backward_rows_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
     }  // work list
 }
 
-// sigmoid=True of the reference API: ceil buckets in the systolic kernel, no tail kernel (a rarely used flag)
+// sigmoid=True of the reference API: the systolic kernel, four buckets per workgroup (a rarely used flag)
 template <int CDIM>
 void launch_bwd_sig(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const BwdOut &O, int64_t max_buckets,
                     hipStream_t stream, int exact) {
     constexpr int WPB = BwdCfg<CDIM>::WPB;
     const int grid = (int)gs_div_up(max_buckets > 0 ? max_buckets : 1, WPB);
     if (exact)
-        hipLaunchKernelGGL((raster_backward_kernel<CDIM, false, true, true>), dim3(grid), dim3(64 * WPB), 0, stream, S, G, I, O);
+        hipLaunchKernelGGL((raster_backward_kernel<CDIM, true>), dim3(grid), dim3(64 * WPB), 0, stream, S, G, I, O);
     else
-        hipLaunchKernelGGL((raster_backward_kernel<CDIM, false, true>), dim3(grid), dim3(64 * WPB), 0, stream, S, G, I, O);
+        hipLaunchKernelGGL((raster_backward_kernel<CDIM, false>), dim3(grid), dim3(64 * WPB), 0, stream, S, G, I, O);
 }
 
-#ifndef GS_BWD_SH_PIXEL
-#define GS_BWD_SH_PIXEL 1  // 0: the systolic kernel for SH as well (A/B switch for tools/ab_variants.py)
-#endif
-#ifndef GS_BWD_PACKED_RGB
-#define GS_BWD_PACKED_RGB 1  // 0: the first, unpacked pixel-parallel kernel for rgb colours (A/B switch)
-#endif
 template <int CDIM, bool FRAME>
 void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const BwdOut &O, int64_t max_buckets,
                 hipStream_t stream) {
-    constexpr int WPB = BwdCfg<CDIM>::WPB;
-    const int grid = (int)gs_div_up(max_buckets > 0 ? max_buckets : 1, WPB);
     // Grid of the one-wave-per-bucket kernels of the frame path: the work list's capacity, but at most GS_BWD_GRID_CAP waves.
     // The kernels walk the list with the grid as the stride, so the cap only decides how many waves come up empty (a frame
     // whose tiles saturate early fills a third of the capacity) or take a second bucket (a frame beyond the cap: the waves
@@ -2417,21 +1859,15 @@ void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const B
 #define GS_BWD_GRID_CAP 40960
 #endif
     const unsigned fgrid = (unsigned)(max_buckets > 0 ? (max_buckets < GS_BWD_GRID_CAP ? max_buckets : GS_BWD_GRID_CAP) : 1);
-    if constexpr (FRAME && ((CDIM == 48 && GS_BWD_SH_MFMA >= 1) || (CDIM == 27 && GS_BWD_SH_MFMA >= 2))) {
-        // one workgroup per GS_BWD_MFMA_TILES tiles (tiles nothing was composited in leave at once)
+    if constexpr (FRAME && CDIM > 3) {  // SH frames: the matrix pipe, one workgroup per work item
         const unsigned mgrid = gs_bwd_mfma_grid(G.ntx * G.nty, max_buckets);
-        const int mwaves = GS_BWD_MFMA_WAVES ? GS_BWD_MFMA_WAVES : (G.ntx * G.nty >= 1024 ? 2 : 4);
-        static_assert((GS_BWD_MFMA_TILES == 1 ? GS_BWD_MFMA_SPLIT : 1) * 4 <= GS_BWD_EXEC_SLOTS, "executed-row counters");
-        if (mwaves == 2)
-            hipLaunchKernelGGL((raster_backward_mfma_sh_kernel<CDIM, 2, GS_BWD_MFMA_TILES>), dim3(mgrid), dim3(128), 0,
-                               stream, S, G, I, O);
+        if (gs_bwd_mfma_waves(G.ntx * G.nty) == 2)
+            hipLaunchKernelGGL((raster_backward_mfma_sh_kernel<CDIM, 2>), dim3(mgrid), dim3(128), 0, stream, S, G, I, O);
         else
-            hipLaunchKernelGGL((raster_backward_mfma_sh_kernel<CDIM, 4, GS_BWD_MFMA_TILES>), dim3(mgrid), dim3(256), 0,
-                               stream, S, G, I, O);
-        // A workgroup walks its tile's buckets four at a time: a 100,000-Gaussian pile in one tile (a degenerate
-        // densification run) would keep ONE workgroup busy for 26 ms.  Frames the caller has flagged for long lists
-        // (GS_FRAME_LONG_LISTS, as for the forward's long-list kernels) leave a tile's buckets beyond the first 32 -- the
-        // part of a list beyond the forward's own 2,048 -- to the one-wave-per-bucket kernel: spread over the device.
+            hipLaunchKernelGGL((raster_backward_mfma_sh_kernel<CDIM, 4>), dim3(mgrid), dim3(256), 0, stream, S, G, I, O);
+        // The hand-over of a tile's buckets from bucket_first on to the one-wave-per-bucket kernel (what frames flagged
+        // GS_FRAME_LONG_LISTS took while ONE workgroup walked a whole tile).  With work items a long list is spread over
+        // the device anyway and gs_stage_raster_backward never sets bucket_first.
         if (I.bucket_first) {
             BwdIn I2 = I;
             I2.bucket_cap = 0;
@@ -2439,22 +1875,14 @@ void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const B
         }
         return;
     }
-    if constexpr (FRAME && CDIM == 3 && GS_BWD_RGB_ROWS) {
-        if (GS_BWD_RGB_ROWS == 1 || I.use_rows) {
+    if constexpr (FRAME && CDIM == 3) {
+        if (I.use_rows) {
             hipLaunchKernelGGL(raster_backward_rows_kernel, dim3(fgrid), dim3(64), 0, stream, S, G, I, O);
             return;
         }
     }
-    if (CDIM == 3 && !GS_BWD_PACKED_RGB) {
-        const int64_t blocks = gs_div_up(max_buckets > 0 ? max_buckets : 1, GS_PP_WPB);
-        hipLaunchKernelGGL((raster_backward_pixel_kernel<FRAME>), dim3((unsigned)blocks), dim3(64 * GS_PP_WPB), 0, stream,
-                           S, G, I, O);
-    } else if (CDIM == 3 || GS_BWD_SH_PIXEL) {
-        hipLaunchKernelGGL((raster_backward_pixel_sh_kernel<CDIM, FRAME>),
-                           dim3(FRAME ? fgrid : (unsigned)(max_buckets > 0 ? max_buckets : 1)), dim3(64), 0, stream, S, G, I, O);
-    } else {
-        hipLaunchKernelGGL((raster_backward_kernel<CDIM, FRAME>), dim3(grid), dim3(64 * WPB), 0, stream, S, G, I, O);
-    }
+    hipLaunchKernelGGL((raster_backward_pixel_sh_kernel<CDIM, FRAME>),
+                       dim3(FRAME ? fgrid : (unsigned)(max_buckets > 0 ? max_buckets : 1)), dim3(64), 0, stream, S, G, I, O);
 }
 
 }  // namespace
@@ -2462,10 +1890,8 @@ void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const B
 // (workgroup, wave) slots the SH backward on the matrix pipe writes its executed-row counters to (0: this colour model
 // takes another kernel): the launch geometry of launch_bwd above
 int gs_bwd_mfma_slots(int color_dim, int n_tiles, int64_t max_buckets) {
-    const bool mfma = (color_dim == 48 && GS_BWD_SH_MFMA >= 1) || (color_dim == 27 && GS_BWD_SH_MFMA >= 2);
-    if (!mfma) return 0;
-    const int mwaves = GS_BWD_MFMA_WAVES ? GS_BWD_MFMA_WAVES : (n_tiles >= 1024 ? 2 : 4);
-    return (int)gs_bwd_mfma_grid(n_tiles, max_buckets) * mwaves;
+    if (color_dim != 27 && color_dim != 48) return 0;
+    return (int)gs_bwd_mfma_grid(n_tiles, max_buckets) * gs_bwd_mfma_waves(n_tiles);
 }
 
 namespace {
@@ -2581,22 +2007,18 @@ int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const ui
     // until then a flag byte per pair, set by scattered one-byte stores = a 32-byte write each, cleared by a memset here)
     hipLaunchKernelGGL(stop_key_kernel, dim3((unsigned)gs_div_up(FG.n_tiles, 256)), dim3(256), 0, stream, ws.tile_nproc,
                        FG.n_tiles, ws.tile_ranges, sorted_ids, ws.rects, (unsigned long long *)ws.stop_keys);
-    // the bucket work list is what the one-wave-per-bucket kernels read; the SH backward on the matrix pipe walks a
-    // tile's buckets itself (one workgroup per tile) and needs none
-    // (GS_FRAME_AUX frames of every colour model take the one-wave-per-bucket pixel kernel: they need the list)
-    const bool per_tile = ((f->color_dim == 48 && GS_BWD_SH_MFMA >= 1) || (f->color_dim == 27 && GS_BWD_SH_MFMA >= 2)) &&
-                          (GS_MFMA_ITEMS || !gs_frame_long_lists(f, FG.n_tiles)) && !(f->flags & GS_FRAME_AUX);  // (no items + flagged frame: the buckets
-                                                                                    // beyond a tile's first 32: hand-over)
-    if (!per_tile)
+    // the bucket work list is what the one-wave-per-bucket kernels read (GS_FRAME_AUX frames of every colour model take
+    // the pixel kernel: they need the list); the SH backward on the matrix pipe walks its own work items, heavy tiles first
+    // where the frame has an order
+    const bool mfma_frame = f->color_dim != 3 && !(f->flags & GS_FRAME_AUX);
+    if (!mfma_frame) {
         gs_launch_bucket_list(ws.tile_nproc, FG.n_tiles, ws.bucket_offsets, ws.counters + GS_CNT_BUCKETS, ws.bucket_info,
                               ws.tile_ranges, 1, stream);
-    const bool mfma_frame = ((f->color_dim == 48 && GS_BWD_SH_MFMA >= 1) || (f->color_dim == 27 && GS_BWD_SH_MFMA >= 2)) &&
-                            !(f->flags & GS_FRAME_AUX);
-    if (mfma_frame && GS_MFMA_ITEMS) {  // the matrix-pipe kernel's work items, heavy tiles first where the frame has an order
-        const uint32_t cap = 0u;  // (work items spread a long list over the device: no hand-over, see gs_stage_raster_backward)
+    } else {
+        const uint32_t cap = 0u;  // (work items spread a long list over the device: no hand-over, see launch_bwd)
         hipLaunchKernelGGL(mfma_items_kernel, dim3(1), dim3(1024), 0, stream, ws.tile_nproc, FG.n_tiles,
-                           (gs_frame_uses_strips(f) && f->N > 0 && GS_BWD_MFMA_ORDER) ? ws.tile_order : nullptr, cap,
-                           (uint32_t)GS_BWD_MFMA_CHUNK, ws.mfma_items, ws.mfma_n_items);
+                           (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr, cap,
+                           (uint32_t)GS_MFMA_ITEM_BUCKETS, ws.mfma_items, ws.mfma_n_items);
     }
     GS_CHECK_LAUNCH();
     return 0;
@@ -2634,22 +2056,12 @@ int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uin
         if (rc) return rc;
     }
     BwdIn I = {f->image_padded, grad_image, ws.ckpt, ws.tile_nproc, ws.bucket_offsets, ws.bucket_info, ws.tile_ranges,
-               (gs_frame_uses_strips(f) && f->N > 0 && GS_BWD_MFMA_ORDER) ? ws.tile_order : nullptr, 0, 0,
-               (f->flags & GS_FRAME_BWD_ROWS) ? 1u : 0u, GS_MFMA_ITEMS ? ws.mfma_items : nullptr,
-               GS_MFMA_ITEMS ? ws.mfma_n_items : nullptr};
-    // One workgroup per TILE (GS_BWD_MFMA_CHUNK = 0, round 4) walks a 100,000-Gaussian pile alone: frames flagged for long lists
-    // then leave a tile's buckets beyond the first GS_BWD_SH_HANDOVER to the one-wave-per-bucket kernel.  With work items
-    // (round 5) a long list is spread over the device anyway: no hand-over, the matrix-pipe kernel takes every bucket.
-#ifndef GS_BWD_SH_HANDOVER
-#define GS_BWD_SH_HANDOVER 32
-#endif
-    if (!GS_MFMA_ITEMS && f->color_dim != 3 && gs_frame_long_lists(f, FG.n_tiles))
-        I.bucket_cap = I.bucket_first = GS_BWD_SH_HANDOVER;
+               (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr, 0, 0,  // (no hand-over: launch_bwd)
+               (f->flags & GS_FRAME_BWD_ROWS) ? 1u : 0u, ws.mfma_items, ws.mfma_n_items};
     BwdOut O = {ws.rows, ws.bwd_exec_rows, ws.pair_offsets, ws.rects, (uint64_t)f->max_pairs, nullptr, nullptr, nullptr, nullptr};
     if (f->flags & GS_FRAME_AUX) {
         // every bucket of the work list (gs_stage_backward_prepare builds it for aux frames of every colour model) on the
         // one-wave-per-bucket pixel kernel, grid as in launch_bwd
-        I.bucket_cap = I.bucket_first = 0;
         const AuxBwdIn X = {(const float2 *)f->aux_padded, gs_frame_aux(f).ckpt, f->grad_depth, f->grad_alpha};
         const int64_t mb = ws.max_buckets;
         const unsigned fgrid = (unsigned)(mb > 0 ? (mb < GS_BWD_GRID_CAP ? mb : GS_BWD_GRID_CAP) : 1);

@@ -58,9 +58,6 @@ struct FwdSmem<3> {
 __device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
 __device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-#ifndef GS_FWD_LEGACY_MUL
-#define GS_FWD_LEGACY_MUL 1  // 0: plain packed multiply (A/B switch for tools/ab_variants.py)
-#endif
 // a * b with DX9 zero rules: 0 x anything (NaN, infinity) = 0 (v_mul_legacy_f32).  Declared as the LLVM intrinsic, NOT
 // as inline assembly: the operand is the result of a transcendental (v_exp_f32), which on gfx940/950 needs a wait state
 // before a VALU instruction may read it -- the compiler inserts it for instructions it knows, not for opaque asm text
@@ -217,7 +214,7 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
             float a9[NB], b9[NB];
             raster_pixel_sh<NB>(id_x, id_y0 + 8 * h, G, a9);
             raster_pixel_sh<NB>(id_x, id_y0 + 8 * h + 4, G, b9);
-            constexpr float KS = GS_SH_PRESCALE ? -GS_LOG2E : 1.0f;  // raster_common.h
+            constexpr float KS = -GS_LOG2E;  // raster_common.h
 #pragma unroll
             for (int k9 = 0; k9 < NB; ++k9) SH[h][k9] = f2{KS * a9[k9], KS * b9[k9]};
         }
@@ -454,7 +451,7 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                     // untouched whatever alpha is -- NaN, infinite --, like the reference, which `break`s before it
                     // evaluates the Gaussian (gaussian.cu:906); a live pixel sees the NaN, as there
                     f2 w;
-                    if constexpr (LEGACY && GS_FWD_LEGACY_MUL)
+                    if constexpr (LEGACY)
                         w = f2{mul_legacy(al.x, T[h].x), mul_legacy(al.y, T[h].y)};
                     else
                         w = al * T[h];
@@ -471,7 +468,7 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                             v1 = pk_fma(SH[h][k9], splat(co[NB + k9]), v1);
                             v2 = pk_fma(SH[h][k9], splat(co[2 * NB + k9]), v2);
                         }
-                        auto sg = [](float v) { return GS_SH_PRESCALE ? gs_rcp(1.0f + gs_exp2(v)) : gs_rcp(1.0f + __expf(-v)); };
+                        auto sg = [](float v) { return gs_rcp(1.0f + gs_exp2(v)); };
                         const f2 c0 = {sg(v0.x), sg(v0.y)}, c1 = {sg(v1.x), sg(v1.y)}, c2 = {sg(v2.x), sg(v2.y)};
                         cr[h] = pk_fma(w, c0, cr[h]);
                         cg[h] = pk_fma(w, c1, cg[h]);
@@ -686,7 +683,7 @@ __global__ void __launch_bounds__(FWD_THREADS) raster_segment_kernel(
             float a9[NB], b9[NB];
             raster_pixel_sh<NB>(id_x, id_y0 + 8 * h, G, a9);
             raster_pixel_sh<NB>(id_x, id_y0 + 8 * h + 4, G, b9);
-            constexpr float KS = GS_SH_PRESCALE ? -GS_LOG2E : 1.0f;  // raster_common.h
+            constexpr float KS = -GS_LOG2E;  // raster_common.h
 #pragma unroll
             for (int k9 = 0; k9 < NB; ++k9) SH[h][k9] = f2{KS * a9[k9], KS * b9[k9]};
         }
@@ -797,7 +794,7 @@ __global__ void __launch_bounds__(FWD_THREADS) raster_segment_kernel(
                             v1 = pk_fma(SH[h][k9], splat(co[NB + k9]), v1);
                             v2 = pk_fma(SH[h][k9], splat(co[2 * NB + k9]), v2);
                         }
-                        auto sg = [](float v) { return GS_SH_PRESCALE ? gs_rcp(1.0f + gs_exp2(v)) : gs_rcp(1.0f + __expf(-v)); };
+                        auto sg = [](float v) { return gs_rcp(1.0f + gs_exp2(v)); };
                         const f2 c0 = {sg(v0.x), sg(v0.y)}, c1 = {sg(v1.x), sg(v1.y)}, c2 = {sg(v2.x), sg(v2.y)};
                         cr[h] = pk_fma(w, c0, cr[h]);
                         cg[h] = pk_fma(w, c1, cg[h]);

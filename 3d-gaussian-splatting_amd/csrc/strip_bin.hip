@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_count_kernel(
     // counts are the first pass's
     if (gate && *gate == 0) return;
     if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
-        tile_order_workgroup(tile_cost, n_tiles, tile_order, SG.ntx, SG.nty);
+        tile_order_workgroup(tile_cost, n_tiles, tile_order);
         return;
     }
     const uint32_t slice = strip_slice_of_block(blockIdx.x, S);

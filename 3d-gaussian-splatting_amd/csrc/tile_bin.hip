@@ -367,11 +367,7 @@ __global__ void __launch_bounds__(BIN_THREADS) bin_scatter_kernel(
                 }
                 walk_rect<DIST>(rcb, g, ntx, load_xy(b, rcb), D, [&](uint32_t tile, uint32_t id, uint32_t d) {
                     const uint32_t slot = atomicAdd(&s_slot[tile], 1u);
-#ifdef GS_DIAG_SCATTER_SMALL  // timing experiment only (tools/ab_variants.py): every store lands in a 128 KiB window
-                    out[slot & 0x3fff] = ((uint64_t)d << 32) | id;
-#else
                     out[slot] = ((uint64_t)d << 32) | id;
-#endif
                 });
             }
         }
@@ -634,9 +630,6 @@ int gs_stage_tile_bin(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stre
     const size_t lds = sizeof(uint32_t) * T, lds_scatter = fused_scan ? 3 * lds : lds;
     // scatter bands: the pairs of one band (8 B each, capacity as the estimate) should stay within ~2.5 MB per XCD
     uint32_t n_bands = (uint32_t)gs_div_up(f->max_pairs * 8, (int64_t)8 * 2560 * 1024);
-#ifdef BIN_BANDS
-    n_bands = BIN_BANDS;  // experiments (tools/ab_variants.py)
-#endif
     if (n_bands < 1) n_bands = 1;
     if (n_bands > 8) n_bands = 8;
     if (n_bands > (uint32_t)G.nty) n_bands = (uint32_t)G.nty;

@@ -430,9 +430,6 @@ __device__ __forceinline__ void tile_sort_body(uint64_t *__restrict__ keys, uint
     // PACKED: the sorted keys are only written on request (GS_FRAME_EMIT_SORTED_KEYS): the raster kernels read the
     // sorted ids alone, and 8 of the 12 bytes this kernel would store per pair are the keys
     auto store = [&](uint32_t i, uint64_t v) {
-#ifdef GS_DIAG_SCATTER_SMALL  // the scatter experiment leaves garbage pairs: keep the ids inside any scene >= 64 k
-        v &= 0xffffffff0000ffffull;
-#endif
         ids[start + i] = (uint32_t)v;
         if (!PACKED || keys) keys[start + i] = ((uint64_t)tile << 32) | (v >> 32);
     };
@@ -802,9 +799,6 @@ __global__ void __launch_bounds__(256, STRIP_SORT_WPE) strip_sort_kernel(
         // GS_CNT_EXCESS stays 0.)
     }
     if (total4 == 0) return;  // uniform
-#ifdef GS_DIAG_STRIP_NO_PLACE  // timing experiments only (tools/ab_variants.py): wrong results
-    return;
-#endif
     // ---- 2. place (depth_bits << 32 | gaussian) and 3. sort.  A half strip of up to CAP pairs holds its four lists in
     // LDS side by side (short lists are then sorted by one wave each, concurrently); otherwise the lists take turns
     // in the LDS window, each placed from the entries in registers and sorted by the workgroup; a single list beyond
@@ -929,11 +923,6 @@ __global__ void __launch_bounds__(256, STRIP_SORT_WPE) strip_sort_kernel(
         // list q at the start of the window, list q + 1 (if paired) behind it
         place(pair ? 3u << q : 1u << q, 0, q == 0 ? n : 0, q == 1 ? n : 0, q == 2 ? n : 0, true, true);
         __syncthreads();
-#ifdef GS_DIAG_STRIP_NO_SORT  // timing experiments only (tools/ab_variants.py): wrong results
-        for (uint32_t i = threadIdx.x; i < n + (pair ? n2 : 0); i += 256) ids[start4[q] + i] = (uint32_t)s_a[i];
-        if (pair) ++q;
-        continue;
-#endif
         if (pair && n + n2 > 256) {
             // both lists by ONE distribution sort (bucket_sort_store, nsplit): adjacent tiles, adjacent output ranges
             const uint32_t start = start4[q];

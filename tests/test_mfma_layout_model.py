@@ -257,7 +257,7 @@ def test_rgb_row_layout_model_equals_the_sequential_recursion():
     T_in[::5, ::3] = 2e-5
     rho_in = rng.normal(size=(16, 16))
 
-    # ---- reference: pixel by pixel, Gaussian by Gaussian (raster_backward_pixel_kernel's arithmetic, float64)
+    # ---- reference: pixel by pixel, Gaussian by Gaussian (raster_backward_pixel_sh_kernel's arithmetic, float64)
     ref = np.zeros((n_g, 10))  # Sx Sy Sxx Sxy Syy Su' (= sum s q) Sopa Sc0 Sc1 Sc2
     T_ref, rho_ref = T_in.copy(), rho_in.copy()
     for y in range(16):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B timing of compile-time variants of libgs_amd.so in ONE gpurun call.
 
-    python tools/ab_variants.py build nolegacy="-DGS_FWD_LEGACY_MUL=0" pf1="-DBIN_PF=1"     # here (CPU, hipcc)
+    python tools/ab_variants.py build wpe3="-DGS_BWD_SH_WPE=3" pf1="-DBIN_PF=1"             # here (CPU, hipcc)
     python tools/ab_variants.py run cfg5 cfg2 > gpurun_out/ab.txt                            # on the GPU box
 
 `build` compiles every variant into build/variants/<name>/libgs_amd.so (git-ignored, but it travels with the gpurun

@@ -29,7 +29,6 @@ FETCH_FACTOR = {
     "raster_backward_pixel_sh_kernel": (1.5, "mixed: 4-KiB checkpoints and image rows stream (x2), records / rectangles / "
                                              "pair offsets are gathered (x1); SH coefficients are contiguous 108 / 192-B "
                                              "runs per Gaussian (between the two)"),
-    "raster_backward_pixel_kernel": (1.5, "as raster_backward_pixel_sh_kernel"),
     "raster_backward_rows_kernel": (1.5, "as raster_backward_pixel_sh_kernel (round 5: the rgb backward in the row layout)"),
     "raster_backward_mfma_sh_kernel": (1.5, "as raster_backward_pixel_sh_kernel (round 4: the SH backward of the frame path)"),
     "raster_backward_kernel": (1.5, "as raster_backward_pixel_sh_kernel"),

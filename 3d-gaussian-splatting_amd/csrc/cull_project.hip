@@ -608,13 +608,13 @@ __global__ void __launch_bounds__(256) frame_project_kernel(
 }
 
 // ---------------------------------------------------------------- S1 + L1a fused (strip variant of sort_mode 2)
-// frame_project_kernel writes a 16-byte rectangle per Gaussian and strip_count_kernel (strip_bin.hip) reads all of them
-// back to histogram the strip entries: 38 MB and a 16-us launch at 2.4 M Gaussians for information that was in
+// Until round 3 frame_project_kernel wrote a 16-byte rectangle per Gaussian and a count kernel of strip_bin.hip read all
+// of them back to histogram the strip entries: 38 MB and a 16-us launch at 2.4 M Gaussians for information that was in
 // registers.  Here ONE workgroup per slice of the Gaussian array (the slices of the level-1 kernels: <= 256, dealt to
 // the XCDs in contiguous runs) projects its Gaussians, 1024 at a time, and counts their strip entries on the spot -- one
-// 64-bit LDS atomic per entry, as there.  The raw parameters of the NEXT round are requested before the current one
-// is projected (16 waves per CU hide the rest).  Same outputs as the two kernels: records, rectangles, the [S][NS] table
-// row, the slice's pair / visible counts; the one extra workgroup of the launch writes the tile dispatch order.
+// 64-bit LDS atomic per entry.  The raw parameters of the NEXT round are requested before the current one is projected
+// (16 waves per CU hide the rest).  Outputs: records, rectangles, the [S][NS] table row of (entries << 32 | pairs) per
+// strip, the slice's pair / visible counts; the one extra workgroup of the launch writes the tile dispatch order.
 // Measured and dropped (round 3, same-box A/B): a COMPACTING variant of this kernel -- every wave tests 64 Gaussians
 // against the frustum (~40 instructions), queues the survivors' raw parameters in a 128-entry LDS ring and runs the
 // long half (~750 instructions) on full waves of survivors only, so that the 21 % culled Gaussians of the 2.4 M scene
@@ -747,11 +747,10 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
     const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, uint4 *__restrict__ surv,
-    uint32_t *__restrict__ slice_nsurv, uint32_t diag) {
+    uint32_t *__restrict__ slice_nsurv) {
     extern __shared__ unsigned long long s_hist[];  // [NS] entries << 32 | pairs of this slice, then the pyramid, then the queue
     __shared__ uint32_t s_acc[2], s_qn, s_ns;
     if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
-        if (diag & 16) return;
         tile_order_workgroup(tile_cost, n_tiles, tile_order);
         return;
     }
@@ -814,7 +813,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     build(s_l3, w3, h3, s_l2, w2, w2, h2);
     uint32_t acc_cnt = 0, acc_vis = 0;
     for (uint32_t c0 = 0; c0 < per_slice; c0 += qcap) {  // uniform: chunks of the slice (one, unless the scene is huge)
-        const uint32_t cn = (diag & 8) ? 0u : (per_slice - c0 < qcap ? per_slice - c0 : qcap);
+        const uint32_t cn = per_slice - c0 < qcap ? per_slice - c0 : qcap;
         if (threadIdx.x == 0) s_qn = 0;
         __syncthreads();  // (also: the pyramid is complete; the previous chunk's queue has been drained)
         // ---- phase A: frustum + occlusion test of every Gaussian of the chunk; survivors are queued
@@ -836,11 +835,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
                     for (int k = 0; k < 3; ++k) s[k] = P.scale_act == 0 ? fabsf(ss[k]) + 1e-4f : gs_exp2(GS_LOG2E * ss[k]);
                     const float smax = fmaxf(s[0], fmaxf(s[1], s[2]));
                     // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
-                    // (`diag`, GS_OCC_DIAG: TIMING-ONLY switches, the frames they render are wrong -- 1: nobody is tested, 2: nobody is
-                    // projected, 4: everybody is skipped, 8: no phase A either, 16: no tile order, 32: phase B loads contiguous
-                    // Gaussians instead of the queued ones, 64: no strip count; tools/batches/gpu_r6n.sh, profiles/r06_n_*)
-                    if ((diag & 4) || (!(diag & 1) && (s[0] + s[1] + s[2] < 3.0e38f) &&
-                                       occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y))) {
+                    if ((s[0] + s[1] + s[2] < 3.0e38f) && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
                         // behind every cut it can reach, or beside the grid: visible, no tile.  NOTHING is written for it (nor
                         // for a Gaussian outside the frustum): the scatter of this pass reads the survivor list, the second
                         // pass re-projects everything -- rects[] of a culled frame is only fresh for the survivors
@@ -886,7 +881,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
         }
         __syncthreads();
         // ---- phase B: the survivors, 1,024 at a time on full waves
-        const uint32_t nq = (diag & 2) ? 0u : s_qn;
+        const uint32_t nq = s_qn;
         RawGaussian cur = {}, nxt = {};
         uint32_t qi = 0, qn_ = 0;
         auto load_survivor = [&](uint32_t k, uint32_t q) {
@@ -910,14 +905,14 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
             return r;
         };
         if (threadIdx.x < nq) {
-            qi = (diag & 32) ? threadIdx.x : s_q[threadIdx.x];
+            qi = s_q[threadIdx.x];
             cur = load_survivor(threadIdx.x, qi);
         }
         settle(cur);
         for (uint32_t base = 0; base < nq; base += STRIP_THREADS) {  // uniform trip count
             const uint32_t k = base + threadIdx.x;
             if (k + STRIP_THREADS < nq) {
-                qn_ = (diag & 32) ? k + STRIP_THREADS : s_q[k + STRIP_THREADS];
+                qn_ = s_q[k + STRIP_THREADS];
                 nxt = load_survivor(k + STRIP_THREADS, qn_);
             }
             uint4 rc = make_uint4(0, 0, 0, 0);
@@ -939,11 +934,11 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
                             make_uint4(rc.x, rc.y, rc.z, (uint32_t)pid);
                 }
             }
-            if (!(diag & 64)) walk_strips<false, true>(rc, pid, SG, cxy, GsDistCull{},
-                                           [&](uint32_t strip, uint32_t, uint32_t, uint32_t np) {
-                                               atomicAdd(&s_hist[strip], (1ull << 32) | np);
-                                           },
-                                           s_cut);
+            walk_strips<false, true>(rc, pid, SG, cxy, GsDistCull{},
+                                     [&](uint32_t strip, uint32_t, uint32_t, uint32_t np) {
+                                         atomicAdd(&s_hist[strip], (1ull << 32) | np);
+                                     },
+                                     s_cut);
             cur = nxt;
             qi = qn_;
         }
@@ -1437,16 +1432,16 @@ static ProjectParams make_params(const gs_frame *f) {
     return P;
 }
 
-// slice_begin / slice_end: the slices of the Gaussian array to project (strip variant with the fused count only:
-// gs_frame_project_slices; every other path projects everything at once: 0, -1)
+// slice_begin / slice_end: the slices of the Gaussian array to project (strip variant only: gs_frame_project_slices;
+// every other path projects everything at once: 0, -1)
 // `second_pass`: the unculled re-run of a GS_FRAME_OCCLUSION_CULL frame's project stage, gated on counters[GS_CNT_RANPAST]
 int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream, int slice_begin, int slice_end,
                      bool second_pass) {
     ProjectParams P = make_params(f);
     // sort_modes 0 / 1 read tiles_touched (emit_pairs_kernel); sort_mode 2 reads the rectangle records only
     uint32_t *touched = f->sort_mode == 2 && gs_frame_geometry(f).n_tiles <= GS_BIN_MAX_TILES ? nullptr : ws.tiles_touched;
-    if (gs_frame_uses_strips(f)) touched = nullptr;
-    if (gs_frame_fused_count(f)) {
+    if (gs_frame_uses_strips(f)) {  // project + strip count in one kernel
+        touched = nullptr;
         gs_frame_geom G = gs_frame_geometry(f);
         const gs_strip_plan plan = gs_strip_plan_for(f->N, G.ntx, G.nty);
         const gs_strip_geom SG = plan.geom;
@@ -1480,7 +1475,6 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
                 if (v >= 64 && v <= (long)GS_OCC_QCAP) qcap_max = (uint32_t)v;
             }
             const uint32_t qcap = plan.per_slice < qcap_max ? plan.per_slice : qcap_max;
-            static const uint32_t diag = getenv("GS_OCC_DIAG") ? (uint32_t)atoi(getenv("GS_OCC_DIAG")) : 0u;  // timing-only builds of the kernel's phases
             size_t lds = sizeof(unsigned long long) * SG.NS + gs_cull_pyramid_bytes(G.ntx, G.nty) + 2 * (size_t)qcap + 16;
             // what is left of the kernel's LDS room holds positions and scales of the chunk's first survivors (24 B each)
             const size_t room = (size_t)GS_BIN_LDS_BYTES - 8 * 4096;
@@ -1495,7 +1489,7 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
                                (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, ws.rects,
                                plan.per_slice, SG, nsl, table, ws.slice_pairs, ws.slice_vis, ws.tile_cost,
                                (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), qcap, stash_cap, ws.surv,
-                               ws.slice_nsurv, diag);
+                               ws.slice_nsurv);
             GS_CHECK_LAUNCH();
             return 0;
         }
@@ -1515,7 +1509,7 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         GS_CHECK_LAUNCH();
         return 0;
     }
-    GS_CHECK_ARG(!second_pass, "the second pass of an occlusion-culled frame belongs to the fused project + count stage");
+    GS_CHECK_ARG(!second_pass, "the second pass of an occlusion-culled frame belongs to the strip variant's project + count stage");
     GS_CHECK_ARG(slice_begin == 0 && slice_end < 0, "this frame's project stage cannot be issued in ranges");
     if (gs_frame_fused_table_count(f)) {
         gs_frame_geom G = gs_frame_geometry(f);

@@ -40,8 +40,6 @@ static int tile_bits(int n_tiles) {
     return b < 1 ? 1 : b;
 }
 
-static bool use_strip_variant(const gs_frame *f);
-
 static int validate(const gs_frame *f) {
     GS_CHECK_ARG(f != nullptr, "frame is null");
     GS_CHECK_ARG(f->N >= 0 && f->N < (1ll << 31), "N out of range");
@@ -58,7 +56,7 @@ static int validate(const gs_frame *f) {
     GS_CHECK_ARG(f->workspace != nullptr && ((uintptr_t)f->workspace & 255) == 0, "workspace null or not 256-byte aligned");
     if (f->tile_culling_method == 0) {
         GS_CHECK_ARG(f->thresh > 0.f && f->thresh < 3.0e38f, "dist: thresh is a squared distance, must be positive");
-        GS_CHECK_ARG(f->sort_mode == 2 && (use_strip_variant(f) || gs_frame_geometry(f).n_tiles <= GS_BIN_MAX_TILES),
+        GS_CHECK_ARG(f->sort_mode == 2 && (gs_frame_uses_strips(f) || gs_frame_geometry(f).n_tiles <= GS_BIN_MAX_TILES),
                      "tile_culling_method dist needs sort_mode 2 (table variant: at most 32768 tiles)");
     } else {
         GS_CHECK_ARG(f->thresh > 0.f && f->thresh < 1.f, "thresh must be in (0,1)");
@@ -122,13 +120,9 @@ extern "C" size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t
 // sort_mode 2: the strip variant needs one LDS counter per strip, the other variants one per tile; grids beyond that
 // (> 8K x 4K pixels) take mode 1.
 static int effective_sort_mode(const gs_frame *f) {
-    if (f->sort_mode == 2 && !use_strip_variant(f) && gs_frame_geometry(f).n_tiles > GS_BIN_MAX_TILES) return 1;
+    if (f->sort_mode == 2 && !gs_frame_uses_strips(f) && gs_frame_geometry(f).n_tiles > GS_BIN_MAX_TILES) return 1;
     return f->sort_mode;
 }
-
-// sort_mode 2 runs the strip variant (strip_bin.hip) unless the caller asks for one of the others or the frame is
-// outside its limits (2^26 Gaussians, GS_STRIP_MAX strips).
-static bool use_strip_variant(const gs_frame *f) { return gs_frame_uses_strips(f); }
 
 // Which double-buffer half holds the sorted (keys, ids) after the radix passes of this mode.
 static int sort_passes(const gs_frame *f) {
@@ -271,8 +265,8 @@ static bool join_prepared(const gs_frame *f, hipStream_t s) {
     return hipStreamWaitEvent(s, a->done, 0) == hipSuccess;
 }
 
-// The forward in two phases: PROJECT (cull + project + activations + level-1 count; with the strip variant's fused count
-// it may be issued as several ranges of slices of the Gaussian array, in any order, slice 0's range first) and REST
+// The forward in two phases: PROJECT (cull + project + activations + level-1 count; in the strip variant it may be
+// issued as several ranges of slices of the Gaussian array, in any order, slice 0's range first) and REST
 // (binning, per-tile sort, compositing).  gs_frame_forward = both; gs_frame_forward_project / _rest expose them to the
 // view-parallel trainer, which projects the NEXT frame's Gaussians range by range as their parameters come out of the
 // optimizer, underneath the gradient exchange of the remaining ranges (gs_dp.py).
@@ -308,7 +302,7 @@ static int frame_forward_impl(const gs_frame *f, hipStream_t s, float *stage_ms,
     const int mode = effective_sort_mode(f);
     if (mode == 2) {
         // counting sort by tile in LDS (stages "scan_emit" and "sort" collapse into this one)
-        const bool strips = use_strip_variant(f);
+        const bool strips = gs_frame_uses_strips(f);
         if (f->N > 0 && (rc = strips ? gs_stage_strip_bin(f, ws, s) : gs_stage_tile_bin(f, ws, s))) return rc;
         tm.mark();
         tm.mark();
@@ -346,8 +340,7 @@ static int frame_forward_impl(const gs_frame *f, hipStream_t s, float *stage_ms,
     tm.mark();  // stage "ranges" = tile ranges (+ the per-tile depth sort in mode 1)
     if ((rc = gs_stage_raster_forward(f, ws, sids, s))) return rc;
     tm.mark();
-    static const bool no_second_pass = getenv("GS_CULL_NO_SECOND_PASS") != nullptr;  // TIMING ONLY: a frame that ran past a cut stays wrong
-    if (mode == 2 && gs_frame_occlusion_cull(f) && !no_second_pass) {
+    if (mode == 2 && gs_frame_occlusion_cull(f)) {
         // The lists of this frame were trimmed by the occlusion cuts of the previous one (gs_frame_layout.h).  If a tile ran
         // past its cut, counters[GS_CNT_RANPAST] is set and the launches below render the frame again from the full
         // lists; otherwise each of them returns at its first instruction (five gated launches: project + count -- the
@@ -369,7 +362,7 @@ extern "C" int gs_frame_forward(const gs_frame *f, gs_stream_t stream) {
 }
 
 // How the project phase of this frame may be cut: *slices = number of slices of the Gaussian array (0: the frame's
-// project stage cannot be issued in ranges -- only the strip variant with the fused count can), *per_slice = Gaussians per
+// project stage cannot be issued in ranges -- only the strip variant's can), *per_slice = Gaussians per
 // slice (a multiple of 256; the last slice may be short).
 extern "C" int gs_frame_project_slices(const gs_frame *f, int32_t *slices, int64_t *per_slice) {
     int rc = validate(f);
@@ -377,7 +370,7 @@ extern "C" int gs_frame_project_slices(const gs_frame *f, int32_t *slices, int64
     GS_CHECK_ARG(slices && per_slice, "null pointer");
     *slices = 0;
     *per_slice = 0;
-    if (f->N > 0 && effective_sort_mode(f) == 2 && gs_frame_fused_count(f)) {
+    if (f->N > 0 && effective_sort_mode(f) == 2 && gs_frame_uses_strips(f)) {
         gs_frame_geom G = gs_frame_geometry(f);
         const gs_strip_plan plan = gs_strip_plan_for(f->N, G.ntx, G.nty);
         *slices = (int32_t)plan.slices;
@@ -691,7 +684,7 @@ extern "C" int gs_frame_binning_variant(const gs_frame *f) {
     if (rc) return rc < 0 ? rc : -rc;
     const int mode = effective_sort_mode(f);
     if (mode != 2) return mode;
-    if (use_strip_variant(f)) return 4;
+    if (gs_frame_uses_strips(f)) return 4;
     return (f->flags & GS_FRAME_SLICE_SORT) ? 3 : 2;
 }
 

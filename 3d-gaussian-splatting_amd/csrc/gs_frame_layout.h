@@ -159,6 +159,8 @@ static inline gs_strip_plan gs_strip_plan_for(int64_t N, int ntx, int nty) {
 // throughput, and the table variant's chain is the shorter one (tools/sweep_n.py --table / --strip, profiles/r03_b_sweep_
 // table_vs_strip.jsonl: 20.2 k against 16.1 k FPS at 10 k Gaussians, equal at 100 k, 9.4 k against 9.7 k at 200 k);
 // GS_FRAME_STRIP_BIN overrides the choice.
+// The strip variant's entry count (level 1a of strip_bin.hip) is taken inside the project stage (cull_project.hip,
+// frame_project_count_kernel / frame_project_cull_count_kernel): no kernel re-reads the rectangles to count.
 #ifndef GS_STRIP_AUTO_MIN_N
 #define GS_STRIP_AUTO_MIN_N 131072
 #endif
@@ -174,16 +176,10 @@ static inline bool gs_frame_uses_strips(const gs_frame *f) {
     return f->N >= GS_STRIP_AUTO_MIN_N || ntx * nty > GS_BIN_MAX_TILES;
 }
 
-// Strip variant: the strip-entry count (level 1a) is taken inside the project stage (cull_project.hip,
-// frame_project_count_kernel) instead of by strip_count_kernel re-reading the rectangles.
-#ifndef GS_FUSED_PROJECT_COUNT
-#define GS_FUSED_PROJECT_COUNT 1  // A/B switch (tools/ab_variants.py)
-#endif
-static inline bool gs_frame_fused_count(const gs_frame *f) { return GS_FUSED_PROJECT_COUNT && gs_frame_uses_strips(f); }
 static inline bool gs_frame_occlusion_cull(const gs_frame *f) {
     if (!((f->flags & GS_FRAME_OCCLUSION_CULL) && !f->training && f->N > 0 && f->tile_culling_method != 0 &&
           !(f->flags & (GS_FRAME_EMIT_SORTED_KEYS | GS_FRAME_LONG_LISTS | GS_FRAME_SERIAL_LONG_LISTS)) &&
-          gs_frame_uses_strips(f) && GS_FUSED_PROJECT_COUNT))
+          gs_frame_uses_strips(f)))
         return false;
     // the level-1 kernels keep the per-tile cuts in LDS next to their strip tables (project + count: histogram, cut pyramid
     // and a queue of up to 16,384 survivors; scatter: cursors + cuts + a staging buffer worth having): 1080p = 70 KiB of
@@ -198,7 +194,7 @@ static inline bool gs_frame_occlusion_cull(const gs_frame *f) {
 // (bin_count_kernel) is taken inside the project stage as well -- five launches per frame instead of six.
 static inline bool gs_frame_fused_table_count(const gs_frame *f) {
     const int ntx = (f->width + GS_TILE - 1) / GS_TILE, nty = (f->height + GS_TILE - 1) / GS_TILE;
-    return GS_FUSED_PROJECT_COUNT && f->sort_mode == 2 && !gs_frame_uses_strips(f) && !(f->flags & GS_FRAME_SLICE_SORT) &&
+    return f->sort_mode == 2 && !gs_frame_uses_strips(f) && !(f->flags & GS_FRAME_SLICE_SORT) &&
            ntx * nty <= GS_BIN_MAX_TILES;
 }
 

@@ -164,9 +164,11 @@ struct BwdIn {
     const uint4 *bucket_info;        // [n_buckets] (tile, first Gaussian, count, start of the tile's list)
     const int32_t *ranges;           // FRAME: [T][2]; REF: accum [T+1]
     const uint32_t *tile_order;      // FRAME, optional: the tiles in descending order of their cost (one workgroup per tile)
-    // Hand-over of long lists: the per-tile SH kernel takes the first bucket_cap buckets of a tile (0: all of them), the
-    // one-wave-per-bucket kernel the buckets from bucket_first on.  Both are 0 since work items (see launch_bwd)
-    uint32_t bucket_cap, bucket_first;
+    // Always 0.  What is left of the long-list hand-over that work items replaced (round 5): the one-wave-per-bucket kernels
+    // skip a tile's buckets below this index.  Kept for the register allocation alone: without this uniform test in
+    // raster_backward_pixel_sh_body five of the ten kernels built from it get more spills (the rgb training kernel its first
+    // two spilled VGPRs; HISTORY.md, the listing at the end of profiles/dead_paths_isa_diff.txt).  To go with the next retuning of that kernel.
+    uint32_t skip_buckets;
     uint32_t use_rows;  // rgb frames: GS_FRAME_BWD_ROWS -- the row-layout kernel instead of the pixel-parallel one (launch_bwd)
     // SH frames on the matrix pipe: the work items (tile, first bucket, buckets) of mfma_items_kernel and their count
     const uint4 *mfma_items;
@@ -558,7 +560,7 @@ __device__ __forceinline__ void raster_backward_pixel_sh_body(RasterSrc S, Raste
     for (uint32_t kb = blockIdx.x; kb < n_work; kb += gridDim.x) {
     const uint4 info = I.bucket_info[kb];
     const uint32_t tile = info.x, base = info.y, r = info.z, start = info.w;
-    if (base < I.bucket_first * GS_BUCKET) continue;  // (uniform) a bucket the per-tile SH kernel has taken: launch_bwd
+    if (base < I.skip_buckets * GS_BUCKET) continue;  // (uniform; never taken: see BwdIn)
     const uint32_t tx = tile % (uint32_t)G.ntx, ty = tile / (uint32_t)G.ntx;
 
     // ---- this lane's Gaussian (lanes >= r re-read the bucket's last one and are zeroed below)
@@ -1127,7 +1129,6 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
         for (int t = 0; t < TPW; ++t) {
             nproc_t[t] = tile0 + t < n_tiles ? I.tile_nproc[tile0 + t] : 0;
             nbk[t] = (nproc_t[t] + GS_BUCKET - 1) / GS_BUCKET;
-            if (I.bucket_cap && nbk[t] > I.bucket_cap) nbk[t] = I.bucket_cap;  // the rest: one wave per bucket (launch_bwd)
             total_bk += nbk[t];
         }
     }
@@ -1498,9 +1499,9 @@ raster_backward_mfma_sh_kernel(RasterSrc S, RasterGeom G, BwdIn I, BwdOut O) {
 }
 
 // The SH backward's work items: (tile, first bucket, buckets <= chunk) in the forward's dispatch order of the tiles (`order`:
-// heavy tiles first; NULL: raster order); `cap`: buckets per tile the matrix-pipe kernel takes at most (long-list frames).
+// heavy tiles first; NULL: raster order).  A long list becomes several items, i.e. several workgroups.
 __global__ void __launch_bounds__(1024) mfma_items_kernel(const uint32_t *__restrict__ tile_nproc, int n_tiles,
-                                                         const uint32_t *__restrict__ order, uint32_t cap, uint32_t chunk,
+                                                         const uint32_t *__restrict__ order, uint32_t chunk,
                                                          uint4 *__restrict__ items, uint32_t *__restrict__ n_items) {
     __shared__ uint32_t s_wave[16];
     __shared__ uint32_t s_carry;
@@ -1510,8 +1511,7 @@ __global__ void __launch_bounds__(1024) mfma_items_kernel(const uint32_t *__rest
     for (int base = 0; base < n_tiles; base += 1024) {
         const int i = base + threadIdx.x;
         const uint32_t tile = i < n_tiles ? (order ? order[i] : (uint32_t)i) : 0u;
-        uint32_t nb = i < n_tiles ? (tile_nproc[tile] + GS_BUCKET - 1) / GS_BUCKET : 0u;
-        if (cap && nb > cap) nb = cap;
+        const uint32_t nb = i < n_tiles ? (tile_nproc[tile] + GS_BUCKET - 1) / GS_BUCKET : 0u;
         const uint32_t v = (nb + chunk - 1) / chunk;
         const uint32_t incl = gs_wave_incl_scan_u32(v);
         if (lane == 63) s_wave[wave] = incl;
@@ -1865,15 +1865,7 @@ void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const B
             hipLaunchKernelGGL((raster_backward_mfma_sh_kernel<CDIM, 2>), dim3(mgrid), dim3(128), 0, stream, S, G, I, O);
         else
             hipLaunchKernelGGL((raster_backward_mfma_sh_kernel<CDIM, 4>), dim3(mgrid), dim3(256), 0, stream, S, G, I, O);
-        // The hand-over of a tile's buckets from bucket_first on to the one-wave-per-bucket kernel (what frames flagged
-        // GS_FRAME_LONG_LISTS took while ONE workgroup walked a whole tile).  With work items a long list is spread over
-        // the device anyway and gs_stage_raster_backward never sets bucket_first.
-        if (I.bucket_first) {
-            BwdIn I2 = I;
-            I2.bucket_cap = 0;
-            hipLaunchKernelGGL((raster_backward_pixel_sh_kernel<CDIM, FRAME>), dim3(fgrid), dim3(64), 0, stream, S, G, I2, O);
-        }
-        return;
+        return;  // (a long list is several work items, spread over the device: nothing is handed to another kernel)
     }
     if constexpr (FRAME && CDIM == 3) {
         if (I.use_rows) {
@@ -2015,9 +2007,8 @@ int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const ui
         gs_launch_bucket_list(ws.tile_nproc, FG.n_tiles, ws.bucket_offsets, ws.counters + GS_CNT_BUCKETS, ws.bucket_info,
                               ws.tile_ranges, 1, stream);
     } else {
-        const uint32_t cap = 0u;  // (work items spread a long list over the device: no hand-over, see launch_bwd)
         hipLaunchKernelGGL(mfma_items_kernel, dim3(1), dim3(1024), 0, stream, ws.tile_nproc, FG.n_tiles,
-                           (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr, cap,
+                           (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr,
                            (uint32_t)GS_MFMA_ITEM_BUCKETS, ws.mfma_items, ws.mfma_n_items);
     }
     GS_CHECK_LAUNCH();
@@ -2056,7 +2047,7 @@ int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uin
         if (rc) return rc;
     }
     BwdIn I = {f->image_padded, grad_image, ws.ckpt, ws.tile_nproc, ws.bucket_offsets, ws.bucket_info, ws.tile_ranges,
-               (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr, 0, 0,  // (no hand-over: launch_bwd)
+               (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr, 0u,
                (f->flags & GS_FRAME_BWD_ROWS) ? 1u : 0u, ws.mfma_items, ws.mfma_n_items};
     BwdOut O = {ws.rows, ws.bwd_exec_rows, ws.pair_offsets, ws.rects, (uint64_t)f->max_pairs, nullptr, nullptr, nullptr, nullptr};
     if (f->flags & GS_FRAME_AUX) {

@@ -8,8 +8,10 @@
 //   level 1 (this file): a STRIP is GS_STRIP_W = 8 consecutive tiles of one tile row.  Every Gaussian emits ONE 8-byte
 //     entry (depth_bits << 32 | first covered tile of the strip << 29 | last << 26 | gaussian) per strip its rectangle
 //     crosses -- 2.1 entries instead of 3.7 pairs per Gaussian -- and the entries are counting-sorted by strip:
-//       strip_count_kernel   <= 256 slices of the Gaussian array, one workgroup each: LDS histogram over the strips of
-//                            (entries << 32 | pairs) in one 64-bit LDS atomic per entry -> row of a [S][NS] table;
+//       (the project stage)  counts while it projects (cull_project.hip, frame_project_count_kernel and
+//                            frame_project_cull_count_kernel): <= 256 slices of the Gaussian array, one workgroup each,
+//                            LDS histogram over the strips of (entries << 32 | pairs) in one 64-bit LDS atomic per
+//                            entry -> row of a [S][NS] table;
 //       strip_colscan_kernel exclusive scan of every column over the slices, strip totals;
 //       strip_scatter_kernel every slice scans the strip totals itself (entry and pair base of every strip: redundant,
 //                            but free of any grid-wide dependency -- a "last workgroup finishes" ticket costs a
@@ -51,68 +53,6 @@ struct SliceLoader {
     }
 };
 
-// ---------------------------------------------------------------- L1a: count
-template <bool DIST>
-__global__ void __launch_bounds__(STRIP_THREADS) strip_count_kernel(
-    const uint4 *__restrict__ rects, const float4 *__restrict__ rec_geom, GsDistCull D, int64_t n, uint32_t per_slice,
-    gs_strip_geom SG, uint32_t S, unsigned long long *__restrict__ table, const uint32_t *__restrict__ block_sums,
-    const uint32_t *__restrict__ block_vis, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
-    const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
-    const unsigned long long *__restrict__ gate) {
-    extern __shared__ unsigned long long s_hist[];  // [NS] entries << 32 | pairs of this slice
-    __shared__ uint32_t s_acc[2];
-    // `gate` (the second, untrimmed pass of a GS_FRAME_OCCLUSION_CULL frame, gs_frame_layout.h): nothing to do unless a tile
-    // ran past its cut.  That pass recounts the entries only -- block_sums == NULL: the slices' rectangle areas and visible
-    // counts are the first pass's
-    if (gate && *gate == 0) return;
-    if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
-        tile_order_workgroup(tile_cost, n_tiles, tile_order);
-        return;
-    }
-    const uint32_t slice = strip_slice_of_block(blockIdx.x, S);
-    const SliceLoader L = {rects, rec_geom, n, (int64_t)slice * per_slice, per_slice};
-    uint4 rc[STRIP_PF];
-#pragma unroll
-    for (int k = 0; k < STRIP_PF; ++k) rc[k] = L.rect(k * STRIP_THREADS);  // in flight while the histogram is cleared
-    for (uint32_t t = threadIdx.x; t < SG.NS; t += STRIP_THREADS) s_hist[t] = 0;
-    if (threadIdx.x < 2) s_acc[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < per_slice; base += STRIP_PF * STRIP_THREADS) {
-        uint4 cur[STRIP_PF];
-#pragma unroll
-        for (int k = 0; k < STRIP_PF; ++k) {
-            cur[k] = rc[k];
-            rc[k] = L.rect(base + (STRIP_PF + k) * STRIP_THREADS);
-        }
-#pragma unroll
-        for (int k = 0; k < STRIP_PF; ++k) {
-            const uint32_t b = base + k * STRIP_THREADS;
-            if (b >= per_slice) break;  // uniform
-            walk_strips<DIST>(cur[k], L.g0 + b + threadIdx.x, SG, L.xy<DIST>(b, cur[k]), D,
-                              [&](uint32_t strip, uint32_t, uint32_t, uint32_t np) {
-                                  atomicAdd(&s_hist[strip], (1ull << 32) | np);
-                              });
-        }
-    }
-    // rectangle areas (= gradient-row slots; == pairs unless DIST) and visible Gaussians of this slice, from the
-    // project stage's per-block sums
-    const int64_t nblk = (n + 255) / 256;
-    for (uint32_t k = threadIdx.x; block_sums && k < per_slice / 256; k += STRIP_THREADS) {
-        const int64_t pb = L.g0 / 256 + k;
-        if (pb < nblk) {
-            atomicAdd(&s_acc[0], block_sums[pb]);
-            atomicAdd(&s_acc[1], block_vis[pb]);
-        }
-    }
-    __syncthreads();
-    unsigned long long *row = table + (size_t)slice * SG.NS;
-    for (uint32_t t = threadIdx.x; t < SG.NS; t += STRIP_THREADS) row[t] = s_hist[t];
-    if (threadIdx.x == 0 && block_sums) {
-        slice_pairs[slice] = s_acc[0];
-        slice_vis[slice] = s_acc[1];
-    }
-}
-
 // ---------------------------------------------------------------- L1b: column scan + strip bases
 // Workgroup = 16 consecutive strips x 16 groups of 16 slices (thread = (group, strip): a group's 16 loads of one
 // slice row are one 128-byte line, and all 16 loads of a thread are in flight at once).  The packed
@@ -121,7 +61,9 @@ __global__ void __launch_bounds__(256) strip_colscan_kernel(
     const unsigned long long *__restrict__ table, unsigned long long *__restrict__ scan, uint32_t S, uint32_t NS,
     unsigned long long *__restrict__ strip_tot, const unsigned long long *__restrict__ gate) {
     static_assert(GS_BIN_SLICES == 256, "16 groups of 16 slices");
-    if (gate && *gate == 0) return;  // (see strip_count_kernel)
+    // `gate` (the second, untrimmed pass of a GS_FRAME_OCCLUSION_CULL frame, gs_frame_layout.h): nothing to do unless a tile
+    // ran past its cut
+    if (gate && *gate == 0) return;
     __shared__ unsigned long long s_tot[16][17];
     const uint32_t col = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const uint32_t t = blockIdx.x * 16 + col;
@@ -187,10 +129,10 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
     unsigned long long *__restrict__ counters, const uint32_t *__restrict__ cut, uint32_t n_tiles,
     const unsigned long long *__restrict__ gate, const uint4 *__restrict__ surv, const uint32_t *__restrict__ slice_nsurv) {
     extern __shared__ unsigned long long s_dyn[];
-    if (gate && *gate == 0) return;  // (see strip_count_kernel)
+    if (gate && *gate == 0) return;  // (see strip_colscan_kernel)
     uint32_t *s_cur = reinterpret_cast<uint32_t *>(s_dyn), *s_gd = s_cur + SG.NS;
     unsigned long long *s_stage = s_dyn + SG.NS;  // 2 NS uint32 = NS uint64
-    // occlusion cuts (the same table the count pass used): staged in LDS behind the `cap` staged entries, every tile row
+    // occlusion cuts (the same table the project stage counted with): staged in LDS behind the `cap` staged entries, every tile row
     // padded to whole strips (walk_strips<.., true>)
     uint32_t *s_cut = reinterpret_cast<uint32_t *>(s_stage + cap);
     if (cut) {
@@ -418,7 +360,8 @@ int gs_stage_cut_dilate(const gs_frame *f, const gs_frame_ws &ws, hipStream_t st
     return 0;
 }
 
-// LDS of the count kernel: 8 B per strip; of the scatter kernel: 8 B per strip + the staging buffer
+// The table of (entries << 32 | pairs) per (slice, strip) is the project stage's.  LDS of the scatter kernel: 8 B per strip
+// + the staging buffer
 // `second_pass`: the untrimmed re-run of a GS_FRAME_OCCLUSION_CULL frame, every kernel gated on counters[GS_CNT_RANPAST]
 int gs_stage_strip_bin(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream, bool second_pass) {
     gs_frame_geom G = gs_frame_geometry(f);
@@ -432,45 +375,27 @@ int gs_stage_strip_bin(const gs_frame *f, const gs_frame_ws &ws, hipStream_t str
     GS_HIP(hipGetDevice(&dev));
     if (dev < 64 && !((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
         std::lock_guard<std::mutex> lock(attr_mu);
-        for (const void *fn : {(const void *)strip_count_kernel<false>, (const void *)strip_count_kernel<true>})
-            GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_STRIP_MAX * 8));
         for (const void *fn : {(const void *)strip_scatter_kernel<false>, (const void *)strip_scatter_kernel<true>})
             GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_BIN_LDS_BYTES));
         attr_done.fetch_or(1ull << dev, std::memory_order_release);
     }
     unsigned long long *table = (unsigned long long *)ws.strip_table, *scan = table + (size_t)GS_BIN_SLICES * SG.NS;
-    const size_t lds_count = sizeof(unsigned long long) * SG.NS;
     const unsigned long long *gate = second_pass ? ws.counters + GS_CNT_RANPAST : nullptr;
     const uint32_t *cut = (!second_pass && gs_frame_occlusion_cull(f)) ? gs_frame_cut_table(f, ws) : nullptr;
     // a culled frame's scatter gives 4 staged entries per strip (32 B: the strip's eight cuts) to the cut table
     const uint32_t cap = cut ? plan.cap - 4 * SG.NS : plan.cap;
     const size_t lds_scatter = sizeof(unsigned long long) * ((size_t)SG.NS + cap) + (cut ? (size_t)32 * SG.NS : 0);
     // (second pass: the table has been rewritten, untrimmed, by the gated re-run of the project stage)
-    const unsigned long long *raw = table;
-#define GS_LAUNCH_STRIP(DIST)                                                                                          \
-    do {                                                                                                               \
-        if (!second_pass && !gs_frame_fused_count(f)) { /* else: counted by the project stage */                         \
-            hipLaunchKernelGGL(strip_count_kernel<DIST>, dim3(plan.slices + 1), dim3(STRIP_THREADS), lds_count, stream,\
-                               ws.rects, ws.rec_geom, D, f->N, plan.per_slice, SG, plan.slices, table, ws.block_sums,  \
-                               ws.block_vis, ws.slice_pairs, ws.slice_vis, ws.tile_cost, (uint32_t)G.n_tiles,          \
-                               ws.tile_order, (const unsigned long long *)nullptr);                                    \
-            GS_CHECK_LAUNCH();                                                                                         \
-        }                                                                                                              \
-        hipLaunchKernelGGL(strip_colscan_kernel, dim3((unsigned)gs_div_up(SG.NS, 16)), dim3(256), 0, stream, raw,      \
-                           scan, plan.slices, SG.NS, (unsigned long long *)ws.strip_tot, gate);                        \
-        GS_CHECK_LAUNCH();                                                                                             \
-        hipLaunchKernelGGL(strip_scatter_kernel<DIST>, dim3(plan.slices), dim3(STRIP_THREADS), lds_scatter, stream,    \
-                           ws.rects, ws.rec_geom, D, f->N, plan.per_slice, SG, plan.slices, cap, scan,                 \
-                           (const unsigned long long *)ws.strip_tot, (unsigned long long *)ws.strip_base,              \
-                           ws.slice_pairs, ws.slice_vis, (uint64_t)f->max_pairs, (unsigned long long *)ws.keys_a,      \
-                           f->training ? ws.pair_offsets : nullptr, ws.counters, cut, (uint32_t)G.n_tiles, gate,       \
-                           cut ? (const uint4 *)ws.surv : (const uint4 *)nullptr, (const uint32_t *)ws.slice_nsurv);    \
-        GS_CHECK_LAUNCH();                                                                                             \
-    } while (0)
-    if (dist)
-        GS_LAUNCH_STRIP(true);
-    else
-        GS_LAUNCH_STRIP(false);
-#undef GS_LAUNCH_STRIP
+    hipLaunchKernelGGL(strip_colscan_kernel, dim3((unsigned)gs_div_up(SG.NS, 16)), dim3(256), 0, stream,
+                       (const unsigned long long *)table, scan, plan.slices, SG.NS, (unsigned long long *)ws.strip_tot, gate);
+    GS_CHECK_LAUNCH();
+    const auto scatter = dist ? strip_scatter_kernel<true> : strip_scatter_kernel<false>;
+    hipLaunchKernelGGL(scatter, dim3(plan.slices), dim3(STRIP_THREADS), lds_scatter, stream, ws.rects, ws.rec_geom, D, f->N,
+                       plan.per_slice, SG, plan.slices, cap, scan, (const unsigned long long *)ws.strip_tot,
+                       (unsigned long long *)ws.strip_base, ws.slice_pairs, ws.slice_vis, (uint64_t)f->max_pairs,
+                       (unsigned long long *)ws.keys_a, f->training ? ws.pair_offsets : nullptr, ws.counters, cut,
+                       (uint32_t)G.n_tiles, gate, cut ? (const uint4 *)ws.surv : (const uint4 *)nullptr,
+                       (const uint32_t *)ws.slice_nsurv);
+    GS_CHECK_LAUNCH();
     return 0;
 }

@@ -99,8 +99,8 @@ __device__ __forceinline__ uint32_t strip_slice_of_block(uint32_t blk, uint32_t 
 // a trainer's consecutive frames of one camera are nearly the same picture, and for an unrelated camera the order is
 // merely arbitrary, as raster order is.  Whatever the costs hold (first frame: uninitialised memory), a counting sort
 // of the tile indices yields a permutation, and the image does not depend on the order: tiles are independent.
-// Runs as one EXTRA workgroup of strip_count_kernel's launch, i.e. underneath the binning, three kernels ahead of its
-// consumer.  256 bins of GS_ORDER_QUANTUM steps; arrival order inside a bin is whatever the LDS atomics make it.
+// Runs as one EXTRA workgroup of the project + count launch (cull_project.hip), i.e. underneath the binning, three
+// kernels ahead of its consumer.  256 bins of GS_ORDER_QUANTUM steps; arrival order inside a bin is whatever the LDS atomics make it.
 #define GS_ORDER_QUANTUM 8
 __device__ __forceinline__ void tile_order_workgroup(const uint32_t *__restrict__ tile_cost, uint32_t T,
                                                      uint32_t *__restrict__ tile_order) {

@@ -560,7 +560,7 @@ class FrameRenderer:
         array (``project_slices()`` of them, ``project_slice_size`` Gaussians each); the range that starts at slice 0
         opens the frame.  gs_train.Trainer calls this slice by slice behind the optimizer of the previous step, so that
         the next frame's cull + project + count runs underneath the gradient exchange of the remaining slices.
-        Returns False -- nothing issued -- when this frame cannot be split (binning variant without the fused count, a
+        Returns False -- nothing issued -- when this frame cannot be split (a binning variant other than the strip variant, a
         pending workspace growth, a capacity check due): the caller then renders it with ``forward``.  The frame is
         completed by ``forward_finish``; no capacity check happens in between (steady-state training frames only).
         ``expect_per_slice``: the slice size the caller converted its Gaussian ranges with (gs_dp.project_slice_size

@@ -162,6 +162,25 @@ gs_densify_classify = _sig("gs_densify_classify", ci, vp, vp, vp, i64, C.POINTER
 gs_densify_apply = _sig("gs_densify_apply", ci, vp, vp, vp, vp, vp, vp, i64, C.POINTER(GsDensifyOpts), vp, vp, i64,
                         vp, vp, vp, vp, vp, i64, vp, vp, sz, vp)
 
+
+class GsSeedOpts(C.Structure):
+    """Mirror of ``struct gs_seed_opts``."""
+
+    _fields_ = [("stride", i32), ("alpha_thresh", f32), ("front_rel", f32), ("scale_factor", f32), ("opa_init", f32),
+                ("scale_activation", i32), ("color_dim", i32)]
+
+
+class GsSeedCamera(C.Structure):
+    """Mirror of ``struct gs_seed_camera``."""
+
+    _fields_ = [("rot", f32 * 9), ("tran", f32 * 3), ("focal_x", f32), ("focal_y", f32), ("width", i32), ("height", i32)]
+
+
+gs_seed_workspace_bytes = _sig("gs_seed_workspace_bytes", sz, i32, i32)
+gs_seed_classify = _sig("gs_seed_classify", ci, vp, vp, vp, i32, i32, C.POINTER(GsSeedOpts), vp, vp, sz, vp)
+gs_seed_apply = _sig("gs_seed_apply", ci, vp, vp, C.POINTER(GsSeedCamera), C.POINTER(GsSeedOpts), vp, vp, vp, vp, vp, i64,
+                     i64, vp, vp, sz, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -176,6 +195,7 @@ EXPORTS = [
     "gs_frame_backward_profile", "gs_adam_step", "gs_adam_step_range", "gs_adam_step_sharded", "gs_frame_overflow_flag", "gs_grad_stat_update", "gs_loss_workspace_bytes", "gs_loss_l1_ssim",
     "gs_loss_depth_workspace_bytes", "gs_loss_depth", "gs_frame_backward_adam_aux",
     "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
+    "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
 ]
 
 

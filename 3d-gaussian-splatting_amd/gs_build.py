@@ -34,6 +34,7 @@ SOURCES = {
     "loss.hip": ["-fno-slp-vectorize"],  # as above: the packer costs ~50 v_mov per row step of the fused kernel
     "densify.hip": ["-ffp-contract=off"],
     "depth_loss.hip": ["-ffp-contract=off"],  # r = D - A z as written: one rounding per operation
+    "seed.hip": ["-ffp-contract=off"],  # z A < (1 - front_rel) D as written: a float32 restatement decides identically
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

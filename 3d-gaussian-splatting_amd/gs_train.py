@@ -690,6 +690,42 @@ class Trainer:
         self.flat.broadcast_params(0)
         return counts
 
+    def _eval_renderer_for_set(self) -> FrameRenderer:
+        """The inference renderer ``test`` and ``seed_from_view`` share (created on first use)."""
+        if getattr(self, "_eval_renderer", None) is None:
+            self._eval_renderer = FrameRenderer(self.flat.flat_param.device, max_pairs=self.renderer.max_pairs,
+                                                training=False, scale_activation=self.scale_activation,
+                                                thresh=self.renderer.thresh)
+            self._eval_renderer.tile_culling_method = self.renderer.tile_culling_method
+            self._eval_renderer.tile_culling_dist_thresh = self.renderer.tile_culling_dist_thresh
+        return self._eval_renderer
+
+    @torch.no_grad()
+    def seed_from_view(self, camera_id: int, i_iter: int, **options) -> int:
+        """Extends the Gaussian set by what view ``camera_id`` measured and the current model does not explain
+        (``gs_seed.seed_from_depth``: its colour target, its range map, the depth / alpha maps of the current model rendered
+        here; ``options``: stride, alpha_thresh, front_rel, scale_factor, opa_init).  Returns the number of Gaussians added.
+        A new set gets a fresh optimizer, as after ``adaptive_control``; when nothing is selected nothing changes -- no
+        rebind, the optimizer state stays.  The Trainer never calls this by itself: a mapping loop calls it per incoming
+        frame, between steps."""
+        from gs_seed import seed_from_depth
+
+        if self.depths is None or self.depths[camera_id] is None:
+            raise RuntimeError(f"view {camera_id} has no depth map (Trainer(depths=...)): nothing to seed from")
+        self.flat.finish_gather()
+        cam, params = self.cameras[camera_id], self.flat.params
+        _, _, depth_map, alpha_map = self._eval_renderer_for_set().forward(*params, cam, aux=True)
+        n_old = self.n_gaussians
+        new = seed_from_depth(self.targets[camera_id], self.depths[camera_id], cam, rendered=(depth_map, alpha_map),
+                              color_dim=int(params[4].shape[1]), scale_activation=self.scale_activation,
+                              append_to=params, **options)
+        added = int(new[0].shape[0]) - n_old
+        if added == 0:
+            return 0
+        self._bind(new, i_iter)
+        self.flat.broadcast_params(0)
+        return added
+
     # ------------------------------------------------------------------ evaluation / viewer hook (SURVEY 8f-4)
     @torch.no_grad()
     def test(self, camera_id, extrinsics=None, intrinsics=None) -> dict:
@@ -712,15 +748,10 @@ class Trainer:
             cam = self.cameras[camera_id]
         else:
             raise RuntimeError("test() needs a camera_id or extrinsics + intrinsics")
-        if getattr(self, "_eval_renderer", None) is None:
-            self._eval_renderer = FrameRenderer(self.flat.flat_param.device, max_pairs=self.renderer.max_pairs,
-                                                training=False, scale_activation=self.scale_activation,
-                                                thresh=self.renderer.thresh)
-            self._eval_renderer.tile_culling_method = self.renderer.tile_culling_method
-            self._eval_renderer.tile_culling_dist_thresh = self.renderer.tile_culling_dist_thresh
+        renderer = self._eval_renderer_for_set()
         tic, toc = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         tic.record()
-        image, _ = self._eval_renderer.forward(*self.flat.params, cam)
+        image, _ = renderer.forward(*self.flat.params, cam)
         toc.record()
         out = {"image": image}
         if camera_id is not None:

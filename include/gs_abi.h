@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_depth +
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_seed_workspace_bytes,
+ *   gs_seed_classify and gs_seed_apply with gs_seed_opts / gs_seed_camera (new Gaussians from an RGB-D frame by
+ *   back-projection of the measured pixels the current model does not explain).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_depth +
  *   gs_loss_depth_workspace_bytes (L1 depth supervision on the GS_FRAME_AUX maps) and gs_frame_backward_adam_aux (the fused
  *   training step for GS_FRAME_AUX frames).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_POSE_GRAD with the
@@ -688,6 +691,57 @@ int gs_densify_apply(const float *pos, const float *quat, const float *scale, co
                      const float *eps1, const float *eps2, int64_t n_eps, float *out_pos, float *out_quat,
                      float *out_scale, float *out_opa, float *out_rgb, int64_t capacity,
                      const int64_t *counts_dev, void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- seeding from an RGB-D frame: new Gaussians where a depth camera saw a surface the model does not explain ----
+ * Two calls around one host read, because the caller sizes the parameter arrays between them (as gs_densify_*):
+ *   gs_seed_classify: decides every LATTICE pixel -- (x, y) with x % stride == stride / 2 and y % stride == stride / 2 -- and
+ *                     writes counts_dev[2] = (selected, lattice pixels that carry a measurement);
+ *   gs_seed_apply   : writes the selected pixels' Gaussians as rows [offset, offset + selected) of pos [.,3], quat [.,4],
+ *                     scale [.,3], opa [.], rgb [., color_dim], arrays of `capacity` rows, in row-major pixel order.  Nothing
+ *                     is written if offset + selected > capacity (counts_dev still holds the need).
+ * range [H,W]: the measured distance from the camera centre (what the GS_FRAME_AUX depth map accumulates; z-depth is
+ * converted by the caller), "no measurement" where it is <= 0, infinite or NaN -- the rule of gs_loss_depth.  image [H,W,3]:
+ * fp32 in [0,1].  depth = sum_i w_i d_i and alpha = sum_i w_i [H,W]: the current model's maps from that camera, both or
+ * neither; NULL: an empty model, every measured lattice pixel is selected.  The decision, in fp32 with one rounding per
+ * operation (a float32 restatement decides identically):
+ *   selected  <=>  measured  and  (no maps  or  A < alpha_thresh  or  z * A < (1 - front_rel) * D)
+ * -- the last: the measurement lies in front of the expected depth D / A by more than the relative margin, without a division.
+ * A selected pixel becomes the Gaussian
+ *   pos   = rot^T (p_c - tran),  p_c = z_cam (u, v, 1),  z_cam = z / sqrt(u u + v v + 1),  (u, v) the renderer's own ray through
+ *           the pixel centre: u = (x + left - padW / 2 + 0.5) / focal_x with the padded size and centred crop of the frame
+ *           path (likewise v), so the Gaussian projects back onto the centre of its pixel;
+ *   quat  = (1, 0, 0, 0);
+ *   scale = isotropic, activated value sigma = scale_factor * stride * z_cam / ((focal_x + focal_y) / 2), stored as the
+ *           inverse of the frame path's activation: max(sigma - 1e-4, 0) for abs (|s| + 1e-4), log(sigma) for exp;
+ *   opa   = logit(opa_init);
+ *   rgb   = logit(c) per channel, c clamped to [1 / 512, 1 - 1 / 512] (half an 8-bit step: |logit| <= 6.24); color_dim 27 /
+ *           48: that logit / 0.28209479177387814 in the DC coefficient of each channel (channel-major 3 x 9 / 3 x 16, as
+ *           utils.py:345-348), every other coefficient 0.
+ * With opa_init > alpha_thresh a pixel that was seeded is not selected again from the same view: its own Gaussian gives it
+ * A >= opa_init at its centre.  Ranks come from wave ballots, per-workgroup counts and a scan -- no atomics: the output is a
+ * pure function of the inputs, bitwise repeatable.  The same workspace and opts go to both calls; quat must be 16-byte
+ * aligned.  Everything is validated before anything is enqueued; all launches on `stream`. */
+typedef struct gs_seed_opts {
+    int32_t stride;           /* >= 1: lattice step in pixels                                                   */
+    float alpha_thresh;       /* a pixel with rendered alpha below this is unexplained                          */
+    float front_rel;          /* ... or one measured in front of the expected depth by more than this share     */
+    float scale_factor;       /* sigma in lattice steps at the point's depth                                    */
+    float opa_init;           /* in (0, 1)                                                                      */
+    int32_t scale_activation; /* 0 = abs, 1 = exp                                                               */
+    int32_t color_dim;        /* 3, 27 or 48                                                                    */
+} gs_seed_opts;
+typedef struct gs_seed_camera { /* as gs_frame carries it */
+    float rot[9], tran[3];    /* world -> camera: p_c = rot p + tran (row-major)                                */
+    float focal_x, focal_y;
+    int32_t width, height;
+} gs_seed_camera;
+size_t gs_seed_workspace_bytes(int32_t H, int32_t W);
+int gs_seed_classify(const float *range, const float *depth, const float *alpha, int32_t H, int32_t W,
+                     const gs_seed_opts *opts, int64_t *counts_dev, void *workspace, size_t workspace_bytes,
+                     gs_stream_t stream);
+int gs_seed_apply(const float *image, const float *range, const gs_seed_camera *cam, const gs_seed_opts *opts, float *pos,
+                  float *quat, float *scale, float *opa, float *rgb, int64_t offset, int64_t capacity,
+                  const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

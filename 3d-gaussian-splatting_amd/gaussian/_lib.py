@@ -146,6 +146,8 @@ gs_loss_workspace_bytes = _sig("gs_loss_workspace_bytes", sz, i32, i32)
 gs_loss_l1_ssim = _sig("gs_loss_l1_ssim", ci, vp, vp, i32, i32, f32, vp, vp, vp, sz, vp)
 gs_loss_depth_workspace_bytes = _sig("gs_loss_depth_workspace_bytes", sz, i32, i32)
 gs_loss_depth = _sig("gs_loss_depth", ci, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp)
+gs_loss_track_workspace_bytes = _sig("gs_loss_track_workspace_bytes", sz, i32, i32)
+gs_loss_track = _sig("gs_loss_track", ci, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, sz, vp)
 
 
 
@@ -196,6 +198,7 @@ EXPORTS = [
     "gs_loss_depth_workspace_bytes", "gs_loss_depth", "gs_frame_backward_adam_aux",
     "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
+    "gs_loss_track_workspace_bytes", "gs_loss_track",
 ]
 
 

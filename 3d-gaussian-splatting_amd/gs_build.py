@@ -35,6 +35,7 @@ SOURCES = {
     "densify.hip": ["-ffp-contract=off"],
     "depth_loss.hip": ["-ffp-contract=off"],  # r = D - A z as written: one rounding per operation
     "seed.hip": ["-ffp-contract=off"],  # z A < (1 - front_rel) D as written: a float32 restatement decides identically
+    "track_loss.hip": ["-ffp-contract=off"],  # r = D / A - z and the gate as written: gs_loss_depth mode 1, bit for bit
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

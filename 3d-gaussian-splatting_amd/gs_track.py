@@ -1,0 +1,189 @@
+"""Camera tracking against a frozen map: the pose of an incoming RGB(-D) frame by rendering the map and descending on the
+pose alone -- what an RGB-D pipeline does once per frame, before any mapping.
+
+One iteration, without autograd:
+
+    posed camera (host, by value) -> forward(training=True, aux=True) -> gs_loss_track (gs_train.TrackLoss)
+      -> backward(part=GS_BWD_RASTER) -> backward(part=GS_BWD_GEOMETRY, grad_pose=...) -> one 64-byte read -> SE(3) step
+
+The colour part of the backward (GS_BWD_COLOR: opacity and colour gradients) is never run: nobody reads it.  dL/drot,
+dL/dtran and the four loss values are views of one 16-float device buffer that a single copy brings into pinned host memory.
+The pose step runs on the host in float64: rot = exp([w]x) R re-linearised at w = 0 every iteration, Adam on (w, tran),
+R <- exp([dw]x) R -- rot stays on SO(3) by construction.  The map's parameters are never written.
+"""
+from __future__ import annotations
+
+import copy
+import math
+from dataclasses import dataclass, field
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from gaussian import _lib
+from gs_frame import FrameRenderer
+from gs_train import TrackLoss
+
+
+@dataclass
+class TrackOptions:
+    """Defaults: the pose fit of tests/test_gpu_pose.py::test_pose_recovery (Adam, lr 2e-3 for both groups decaying to 0.01 x
+    over 300 iterations, the silhouette at alpha 0.5, mean |I - T| per colour element + mean |r| per pixel)."""
+    iterations: int = 300
+    lr_rot: float = 2e-3
+    lr_tran: float = 2e-3
+    lr_final: float = 0.01          # the learning rates decay exponentially to this factor over the run
+    betas: Tuple[float, float] = (0.9, 0.999)
+    eps: float = 1e-8
+    alpha_min: float = 0.5          # a pixel counts where the map's alpha reaches this
+    color_weight: float = 1.0 / 3.0  # x sum_c |I_c - T_c| / (H W): the mean over the colour elements
+    depth_weight: float = 1.0       # x |D / A - z| / (H W)
+    depth_gate: float = 0.0         # <= 0: off; else depth residuals beyond it do not count
+    max_pairs: int = 1 << 20        # the renderer's initial pair capacity (it grows by itself)
+
+
+@dataclass
+class TrackResult:
+    rot: np.ndarray      # [3,3] float64, world -> camera, on SO(3)
+    tran: np.ndarray     # [3] float64
+    loss: float          # the lowest loss seen: the loss of (rot, tran)
+    iterations: int
+    losses: List[float] = field(default_factory=list)  # per iteration, the loss of the pose that iteration rendered
+
+
+def so3_exp(w) -> np.ndarray:
+    """exp([w]x) in float64 (Rodrigues; the series below 1e-8 rad)."""
+    w = np.asarray(w, np.float64).reshape(3)
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (math.sin(th) / th) * K + ((1.0 - math.cos(th)) / (th * th)) * (K @ K)
+
+
+def rot_tangent_grad(grad_rot, rot) -> np.ndarray:
+    """dL/dw at w = 0 of rot(w) = exp([w]x) rot, from G = dL/drot: with M = G rot^T, (M32 - M23, M13 - M31, M21 - M12)."""
+    M = np.asarray(grad_rot, np.float64).reshape(3, 3) @ np.asarray(rot, np.float64).reshape(3, 3).T
+    return np.array([M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]])
+
+
+def predict_constant_velocity(prev, last):
+    """T_pred = T_last T_prev^-1 T_last in float64 for world -> camera poses (rot, tran): the motion between the last two
+    frames, applied once more."""
+    Rp, tp = np.asarray(prev[0], np.float64).reshape(3, 3), np.asarray(prev[1], np.float64).reshape(3)
+    Rl, tl = np.asarray(last[0], np.float64).reshape(3, 3), np.asarray(last[1], np.float64).reshape(3)
+    dR = Rl @ Rp.T               # T_last T_prev^-1 = (dR, tl - dR tp)
+    dt = tl - dR @ tp
+    R = dR @ Rl
+    U, _, Vt = np.linalg.svd(R)  # (two products of rotations: back onto SO(3) to the last bit)
+    return U @ Vt, dR @ tl + dt
+
+
+_SH_REFUSAL = ("pose gradients need rgb colours: with SH colours the image also depends on the pose through "
+               "each pixel's ray direction, which the backward does not differentiate")
+
+
+class Tracker:
+    """``Tracker(params, camera)``: ``params`` = (pos, quat, scale, opa, rgb) of an rgb map, ``camera`` gives the image size,
+    the focal lengths, ``near`` and the pose tracking starts from.  ``track(image, range_map)`` estimates the pose of one
+    incoming frame; without ``init`` it starts from the constant-velocity prediction of the last two tracked poses, else
+    the last pose, else the camera's."""
+
+    def __init__(self, params, camera, options: Optional[TrackOptions] = None, device="cuda"):
+        self.opt = options if options is not None else TrackOptions()
+        self._check_map(params)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("Tracker needs a HIP device; there is no CPU fallback")
+        self.camera = camera
+        self.H, self.W = int(camera.height), int(camera.width)
+        self.renderer = FrameRenderer(self.device, max_pairs=int(self.opt.max_pairs), training=True, occlusion_cull=False,
+                                      auto_grow=True)
+        self.device = self.renderer.device
+        o = self.opt
+        self.loss = TrackLoss(self.H, self.W, o.alpha_min, o.color_weight, o.depth_weight, o.depth_gate, self.device)
+        # grad_rot [0:9], grad_tran [9:12], (loss, colour term, depth term, depth pixels) [12:16]: one read per iteration
+        self._dev = torch.zeros(16, dtype=torch.float32, device=self.device)
+        self._grad_pose = (self._dev[0:9].view(3, 3), self._dev[9:12])
+        self._values = self._dev[12:16]
+        self._host = torch.zeros(16, dtype=torch.float32).pin_memory()
+        self._scratch = None
+        self.set_map(params)
+        self.reset()
+
+    @staticmethod
+    def _check_map(params):
+        if len(params) != 5:
+            raise ValueError("params must be (pos, quat, scale, opa, rgb)")
+        rgb = params[4]
+        if rgb.dim() != 2 or rgb.shape[1] != 3:
+            raise RuntimeError(_SH_REFUSAL)
+
+    def set_map(self, params):
+        """Rebind the map (after the mapper changed or grew the Gaussian set).  The tensors are read, never written."""
+        self._check_map(params)
+        for name, t in zip(("pos", "quat", "scale", "opa", "rgb"), params):
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor")
+        self.params = tuple(t.detach() for t in params)
+        if self._scratch is None or any(s.shape != p.shape for s, p in zip(self._scratch, self.params)):
+            # the per-Gaussian gradient rows the backward writes on its way to the pose gradient: nobody reads them
+            self._scratch = tuple(torch.empty_like(p) for p in self.params)
+
+    def reset(self):
+        """Forget the motion history: the next ``track`` without ``init`` starts from the constructor camera's pose."""
+        self._history: List[Tuple[np.ndarray, np.ndarray]] = []
+
+    def _start_pose(self, init):
+        if init is not None:
+            rot, tran = init
+            to_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))  # noqa: E731
+            return to_np(rot).astype(np.float64).reshape(3, 3), to_np(tran).astype(np.float64).reshape(3)
+        if len(self._history) >= 2:
+            return predict_constant_velocity(self._history[-2], self._history[-1])
+        if self._history:
+            return self._history[-1][0].copy(), self._history[-1][1].copy()
+        return (np.asarray(self.camera.rot, np.float64).reshape(3, 3).copy(),
+                np.asarray(self.camera.tran, np.float64).reshape(3).copy())
+
+    def iteration(self, rot, tran, image, range_map=None):
+        """One forward / loss / pose backward at the pose (rot, tran); the 16 floats land in ``self._host`` (pinned):
+        dL/drot [0:9], dL/dtran [9:12], (loss, colour term, depth term, depth pixels) [12:16].  Returns that buffer."""
+        cam = copy.copy(self.camera)
+        cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
+        cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
+        r = self.renderer
+        img, _, depth, alpha = r.forward(*self.params, cam, training=True, aux=True)
+        with torch.cuda.device(self.device):
+            gi, gd, ga = self.loss(img, depth, alpha, image, range_map, 1.0 / (self.H * self.W), values=self._values)
+        r.backward(gi, out=self._scratch, part=_lib.GS_BWD_RASTER, grad_depth=gd, grad_alpha=ga)
+        r.backward(None, out=self._scratch, part=_lib.GS_BWD_GEOMETRY, grad_pose=self._grad_pose)
+        self._host.copy_(self._dev)  # (device -> pinned host: returns when the 64 bytes have landed)
+        return self._host
+
+    def track(self, image, range_map=None, init=None) -> TrackResult:
+        """``image`` [H,W,3] and ``range_map`` [H,W] (range from the camera centre; <= 0, inf, NaN: no measurement; None:
+        RGB only): contiguous float32 tensors on the tracker's device.  Returns the pose with the lowest loss seen."""
+        o = self.opt
+        R, t = self._start_pose(init)
+        m, v = np.zeros(6), np.zeros(6)  # Adam's moments on (w, tran): kept across iterations, reset per call
+        lr0 = np.array([o.lr_rot] * 3 + [o.lr_tran] * 3)
+        b1, b2 = o.betas
+        best = (math.inf, R, t)
+        losses: List[float] = []
+        for k in range(int(o.iterations)):
+            h = self.iteration(R, t, image, range_map).numpy().astype(np.float64)
+            loss = float(h[12])
+            losses.append(loss)
+            if loss < best[0]:
+                best = (loss, R, t)
+            g = np.concatenate([rot_tangent_grad(h[0:9], R), h[9:12]])
+            m = b1 * m + (1.0 - b1) * g
+            v = b2 * v + (1.0 - b2) * g * g
+            step = lr0 * o.lr_final ** (k / o.iterations) * (m / (1.0 - b1 ** (k + 1))) / (np.sqrt(v / (1.0 - b2 ** (k + 1))) + o.eps)
+            R = so3_exp(-step[:3]) @ R
+            t = t - step[3:]
+        loss, R, t = best
+        self._history = (self._history + [(R, t)])[-2:]
+        return TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)

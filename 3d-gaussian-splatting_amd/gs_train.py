@@ -278,6 +278,51 @@ class DepthLoss:
         return self.grad_depth, self.grad_alpha
 
 
+class TrackLoss:
+    """The loss of camera tracking against a frozen map and its gradients w.r.t. the image, depth and alpha maps of an aux
+    frame (gs_loss_track, include/gs_abi.h): ``scale * (color_weight * sum |I - T| + depth_weight * sum |D / A - z|)`` over
+    the pixels the map covers (A >= ``alpha_min``), the depth term on those that are measured and pass ``depth_gate``
+    (<= 0: off).  Owns the workspace and the three gradient maps; ``values`` = (loss, colour term, depth term, pixels that
+    counted for depth) unless the call names another destination."""
+
+    def __init__(self, height: int, width: int, alpha_min: float = 0.5, color_weight: float = 1.0, depth_weight: float = 1.0,
+                 depth_gate: float = 0.0, device="cuda"):
+        self.H, self.W, self.alpha_min = int(height), int(width), float(alpha_min)
+        self.color_weight, self.depth_weight, self.depth_gate = float(color_weight), float(depth_weight), float(depth_gate)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("TrackLoss needs a HIP device; there is no CPU fallback")
+        nbytes = _lib.gs_loss_track_workspace_bytes(self.H, self.W)
+        self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        self.grad_image = torch.empty(self.H, self.W, 3, dtype=torch.float32, device=self.device)
+        self.grad_depth = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
+        self.grad_alpha = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
+        self.values = torch.zeros(4, dtype=torch.float32, device=self.device)  # stays on the device
+
+    def __call__(self, image: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_image: torch.Tensor,
+                 target_range: Optional[torch.Tensor], scale: float, values: Optional[torch.Tensor] = None):
+        """``target_range``: [H,W] range from the camera centre (<= 0, inf, NaN: no measurement) or None (RGB only);
+        ``values``: four contiguous float32 on the device to receive the values in place of ``self.values``.  Returns
+        (grad_image, grad_depth, grad_alpha)."""
+        maps = [("image", image, 3), ("depth", depth, 0), ("alpha", alpha, 0), ("target_image", target_image, 3)]
+        if target_range is not None:
+            maps.append(("target_range", target_range, 0))
+        for name, t, c in maps:
+            shape = (self.H, self.W, 3) if c else (self.H, self.W)
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape {list(shape)}")
+        values = self.values if values is None else values
+        if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous() or values.numel() != 4:
+            raise RuntimeError("values must be four contiguous float32 on the device")
+        _lib.check(_lib.gs_loss_track(image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
+                                      target_range.data_ptr() if target_range is not None else None, self.H, self.W,
+                                      self.alpha_min, self.color_weight, self.depth_weight, self.depth_gate, float(scale),
+                                      self.grad_image.data_ptr(), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
+                                      values.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                      torch.cuda.current_stream().cuda_stream), "gs_loss_track")
+        return self.grad_image, self.grad_depth, self.grad_alpha
+
+
 def z_to_range(z: torch.Tensor, camera) -> torch.Tensor:
     """Sensor z-depth [H,W] (distance along the optical axis) -> range from the camera centre, what the aux depth map
     measures (d_i = |p_c|): range = z |ray| / ray_z with the renderer's own per-pixel rays (gs_geometry.RayBasis: pixel

@@ -34,7 +34,9 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_seed_workspace_bytes,
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_track +
+ *   gs_loss_track_workspace_bytes (the masked colour + depth loss of camera tracking against a frozen map, one pass).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_seed_workspace_bytes,
  *   gs_seed_classify and gs_seed_apply with gs_seed_opts / gs_seed_camera (new Gaussians from an RGB-D frame by
  *   back-projection of the measured pixels the current model does not explain).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_depth +
@@ -660,6 +662,29 @@ size_t gs_loss_depth_workspace_bytes(int32_t H, int32_t W);
 int gs_loss_depth(const float *depth, const float *alpha, const float *target, int32_t H, int32_t W, int32_t mode,
                   float alpha_min, float scale, float *grad_depth, float *grad_alpha, float *loss_out, void *workspace,
                   size_t workspace_bytes, gs_stream_t stream);
+
+/* The loss of camera tracking against a frozen map, on a GS_FRAME_AUX frame rendered from the pose under estimation: image
+ * [H,W,3], depth D [H,W] and alpha A [H,W] against the incoming frame's target_image [H,W,3] and target_range [H,W] (NULL:
+ * RGB-only tracking; a pixel that is <= 0, infinite or NaN carries no measurement -- the rule of gs_loss_depth).  Per pixel, in
+ * fp32 with one rounding per operation, cs = fl(scale color_weight), ds = fl(scale depth_weight):
+ *   colour: counts iff A >= alpha_min (> 0: the silhouette of the map);  term = cs sum_c |I_c - T_c|,
+ *           grad_image_c = +cs / -cs by the sign of I_c - T_c, 0 where they are equal;
+ *   depth : counts iff the pixel counts for colour, carries a measurement z and, with r = D / A - z, depth_gate <= 0 (off)
+ *           or |r| <= depth_gate;  term = ds |r|,  grad_depth = s (1 / A),  grad_alpha = -s ((D / A) / A),  s = +ds / -ds
+ *           by the sign of r (gs_loss_depth mode 1, bit for bit where ds equals its scale);
+ * every other gradient is written as an exact zero; the masks are constants and are not differentiated.  values_out (device,
+ * 4-byte aligned, may be NULL) receives (loss = colour term + depth term, colour term, depth term, pixels that counted for
+ * depth -- exact up to 2^24).  The caller picks `scale` (finite; 1 / (H W) makes the terms means over the image): no count
+ * pass, no host synchronisation.  The eight maps must be 16-byte aligned, the workspace too.  One streaming pass (four
+ * consecutive pixels per lane) and a one-workgroup reduction in double, fixed order, no atomics: bitwise repeatable.
+ * GS_E_INVALID -- before anything is enqueued -- for a null pointer, H or W <= 0, a misaligned map, alpha_min <= 0 or NaN, a
+ * negative or NaN weight, a scale that is not finite, a workspace that is null, misaligned or too small.  The three gradient
+ * maps are what gs_frame_backward takes as grad_image and gs_frame.grad_depth / grad_alpha. */
+size_t gs_loss_track_workspace_bytes(int32_t H, int32_t W);
+int gs_loss_track(const float *image, const float *depth, const float *alpha, const float *target_image,
+                  const float *target_range, int32_t H, int32_t W, float alpha_min, float color_weight, float depth_weight,
+                  float depth_gate, float scale, float *grad_image, float *grad_depth, float *grad_alpha, float *values_out,
+                  void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 /* ---- densification: Gaussian3ds.adaptive_control (splatter.py:122-228) ----
  * Two calls because the number of split Gaussians decides how many standard-normal draws the split

@@ -55,6 +55,12 @@ __device__ __forceinline__ uint32_t gs_f2u_sat(float v) {
 // wave64 helpers
 __device__ __forceinline__ int gs_lane() { return (int)__lane_id(); }
 
+// The fixed-order sum behind every loss value and pose gradient: a thread adds its own terms in ascending order; a
+// butterfly over the wave (xor 32 ... 1: both partners add the same two values, so both hold the same bits, and after six
+// steps every lane holds the total); lane 0 of each wave stores it to the wave's LDS slot and after a barrier the slots are
+// added in wave order; rows that workgroups left in a workspace: thread t of one 1,024-thread workgroup takes rows t,
+// t + 1024, ... in ascending order in double, then the same.  No atomics (their order is the order in which waves retire):
+// bitwise repeatable.
 __device__ __forceinline__ float gs_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -33,9 +33,10 @@ SOURCES = {
     "adam.hip": ["-ffp-contract=off"],  # same roundings as torch's unfused elementwise kernels
     "loss.hip": ["-fno-slp-vectorize"],  # as above: the packer costs ~50 v_mov per row step of the fused kernel
     "densify.hip": ["-ffp-contract=off"],
-    "depth_loss.hip": ["-ffp-contract=off"],  # r = D - A z as written: one rounding per operation
     "seed.hip": ["-ffp-contract=off"],  # z A < (1 - front_rel) D as written: a float32 restatement decides identically
-    "track_loss.hip": ["-ffp-contract=off"],  # r = D / A - z and the gate as written: gs_loss_depth mode 1, bit for bit
+    # r = D - A z, r = D / A - z and the gate as written: one rounding per operation, and gs_loss_track's depth term is
+    # gs_loss_depth mode 1 bit for bit
+    "map_loss.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

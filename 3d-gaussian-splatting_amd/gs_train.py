@@ -222,30 +222,42 @@ class FusedAdam:
             "gs_adam_step_multi")
 
 
-class ImageLoss:
+class _MapLoss:
+    """What the three loss objects share: the refusal of a non-HIP device, the workspace, the check of an input map."""
+
+    def _setup(self, height: int, width: int, device, workspace_bytes):
+        self.H, self.W, self.device = int(height), int(width), torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
+        self._ws = torch.empty(int(workspace_bytes(self.H, self.W)), dtype=torch.uint8, device=self.device)
+
+    def _new(self, *shape):
+        return torch.empty(*shape, dtype=torch.float32, device=self.device)
+
+    def _check_map(self, name: str, t: torch.Tensor, shape, sep=","):
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [{sep.join(map(str, shape))}]")
+
+
+class ImageLoss(_MapLoss):
     """``(1-w) * L1 + w * (1 - SSIM)`` and its gradient w.r.t. the rendered image (train.py:99-107)."""
 
     def __init__(self, height: int, width: int, ssim_weight: float = 0.1, device="cuda"):
-        self.H, self.W, self.w = int(height), int(width), float(ssim_weight)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("ImageLoss needs a HIP device; there is no CPU fallback")
-        nbytes = _lib.gs_loss_workspace_bytes(self.H, self.W)
-        self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        self.grad = torch.empty(self.H, self.W, 3, dtype=torch.float32, device=self.device)
+        self.w = float(ssim_weight)
+        self._setup(height, width, device, _lib.gs_loss_workspace_bytes)
+        self.grad = self._new(self.H, self.W, 3)
         self.values = torch.zeros(3, dtype=torch.float32, device=self.device)  # (loss, l1, ssim), stays on device
 
     def __call__(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         for name, t in (("pred", pred), ("target", target)):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (self.H, self.W, 3):
-                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [{self.H},{self.W},3]")
+            self._check_map(name, t, (self.H, self.W, 3))
         _lib.check(_lib.gs_loss_l1_ssim(pred.data_ptr(), target.data_ptr(), self.H, self.W, self.w,
                                         self.grad.data_ptr(), self.values.data_ptr(), self._ws.data_ptr(),
                                         self._ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_loss_l1_ssim")
         return self.grad
 
 
-class DepthLoss:
+class DepthLoss(_MapLoss):
     """``scale * sum |r|`` over the measured pixels of a range map and its gradients w.r.t. the depth / alpha maps of an aux
     frame (gs_loss_depth, include/gs_abi.h): ``mode`` "residual" (r = D - A z) or "expected" (r = D / A - z where
     A >= ``alpha_min``).  Owns the workspace and the two gradient maps; ``values`` = (loss, pixels that counted)."""
@@ -255,22 +267,16 @@ class DepthLoss:
     def __init__(self, height: int, width: int, mode: str = "residual", alpha_min: float = 0.5, device="cuda"):
         if mode not in self.MODES:
             raise ValueError(f"depth mode must be 'residual' or 'expected', got {mode!r}")
-        self.H, self.W, self.mode, self.alpha_min = int(height), int(width), self.MODES[mode], float(alpha_min)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("DepthLoss needs a HIP device; there is no CPU fallback")
-        nbytes = _lib.gs_loss_depth_workspace_bytes(self.H, self.W)
-        self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        self.grad_depth = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
-        self.grad_alpha = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
+        self.mode, self.alpha_min = self.MODES[mode], float(alpha_min)
+        self._setup(height, width, device, _lib.gs_loss_depth_workspace_bytes)
+        self.grad_depth, self.grad_alpha = self._new(self.H, self.W), self._new(self.H, self.W)
         self.values = torch.zeros(2, dtype=torch.float32, device=self.device)  # stays on the device
 
     def __call__(self, depth: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor, scale: float):
         """``target``: [H,W] range from the camera centre (<= 0, inf, NaN: no measurement); ``scale``: weight / number of
         measured pixels.  Returns (grad_depth, grad_alpha)."""
         for name, t in (("depth", depth), ("alpha", alpha), ("target", target)):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (self.H, self.W):
-                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [{self.H},{self.W}]")
+            self._check_map(name, t, (self.H, self.W))
         _lib.check(_lib.gs_loss_depth(depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), self.H, self.W, self.mode,
                                       self.alpha_min, float(scale), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
                                       self.values.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
@@ -278,7 +284,7 @@ class DepthLoss:
         return self.grad_depth, self.grad_alpha
 
 
-class TrackLoss:
+class TrackLoss(_MapLoss):
     """The loss of camera tracking against a frozen map and its gradients w.r.t. the image, depth and alpha maps of an aux
     frame (gs_loss_track, include/gs_abi.h): ``scale * (color_weight * sum |I - T| + depth_weight * sum |D / A - z|)`` over
     the pixels the map covers (A >= ``alpha_min``), the depth term on those that are measured and pass ``depth_gate``
@@ -287,16 +293,11 @@ class TrackLoss:
 
     def __init__(self, height: int, width: int, alpha_min: float = 0.5, color_weight: float = 1.0, depth_weight: float = 1.0,
                  depth_gate: float = 0.0, device="cuda"):
-        self.H, self.W, self.alpha_min = int(height), int(width), float(alpha_min)
+        self.alpha_min = float(alpha_min)
         self.color_weight, self.depth_weight, self.depth_gate = float(color_weight), float(depth_weight), float(depth_gate)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("TrackLoss needs a HIP device; there is no CPU fallback")
-        nbytes = _lib.gs_loss_track_workspace_bytes(self.H, self.W)
-        self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        self.grad_image = torch.empty(self.H, self.W, 3, dtype=torch.float32, device=self.device)
-        self.grad_depth = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
-        self.grad_alpha = torch.empty(self.H, self.W, dtype=torch.float32, device=self.device)
+        self._setup(height, width, device, _lib.gs_loss_track_workspace_bytes)
+        self.grad_image = self._new(self.H, self.W, 3)
+        self.grad_depth, self.grad_alpha = self._new(self.H, self.W), self._new(self.H, self.W)
         self.values = torch.zeros(4, dtype=torch.float32, device=self.device)  # stays on the device
 
     def __call__(self, image: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_image: torch.Tensor,
@@ -308,9 +309,7 @@ class TrackLoss:
         if target_range is not None:
             maps.append(("target_range", target_range, 0))
         for name, t, c in maps:
-            shape = (self.H, self.W, 3) if c else (self.H, self.W)
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape {list(shape)}")
+            self._check_map(name, t, (self.H, self.W, 3) if c else (self.H, self.W), sep=", ")
         values = self.values if values is None else values
         if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous() or values.numel() != 4:
             raise RuntimeError("values must be four contiguous float32 on the device")

@@ -183,6 +183,19 @@ gs_seed_classify = _sig("gs_seed_classify", ci, vp, vp, vp, i32, i32, C.POINTER(
 gs_seed_apply = _sig("gs_seed_apply", ci, vp, vp, C.POINTER(GsSeedCamera), C.POINTER(GsSeedOpts), vp, vp, vp, vp, vp, i64,
                      i64, vp, vp, sz, vp)
 
+GS_OVERLAP_MAX_VIEWS = 256
+
+
+class GsOverlapOpts(C.Structure):
+    """Mirror of ``struct gs_overlap_opts``."""
+
+    _fields_ = [("stride", i32), ("near", f32), ("border", i32)]
+
+
+gs_view_overlap_workspace_bytes = _sig("gs_view_overlap_workspace_bytes", sz, i32, i32, i32, i32)
+gs_view_overlap_check_view = _sig("gs_view_overlap_check_view", ci, C.POINTER(GsSeedCamera), i32)
+gs_view_overlap = _sig("gs_view_overlap", ci, vp, C.POINTER(GsSeedCamera), vp, i32, C.POINTER(GsOverlapOpts), vp, vp, sz, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -199,6 +212,7 @@ EXPORTS = [
     "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
     "gs_loss_track_workspace_bytes", "gs_loss_track",
+    "gs_view_overlap_workspace_bytes", "gs_view_overlap_check_view", "gs_view_overlap",
 ]
 
 

@@ -37,12 +37,15 @@ SOURCES = {
     # r = D - A z, r = D / A - z and the gate as written: one rounding per operation, and gs_loss_track's depth term is
     # gs_loss_depth mode 1 bit for bit
     "map_loss.hip": ["-ffp-contract=off"],
+    # the seen / not seen test as written: a float32 restatement decides identically; no SLP packing, as above
+    "overlap.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
 HEADERS = ["gs_common.h", "gs_frame_layout.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
-           "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", os.path.join("..", "..", "include", "gs_abi.h")]
+           "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
+           os.path.join("..", "..", "include", "gs_abi.h")]
 
 
 def _stale(target: str, deps) -> bool:

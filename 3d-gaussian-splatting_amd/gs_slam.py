@@ -1,0 +1,284 @@
+"""Mapping an RGB-D sequence: keyframes, their covisibility, and the track -> decide -> seed -> map loop.
+
+``Slam(camera).step(image, range_map)`` takes the frames of a depth camera one at a time.  The first frame founds the map
+(``gs_seed.seed_from_depth`` into an empty model, a ``gs_train.Trainer`` on that one view).  Every later frame is tracked
+against the frozen map (``gs_track.Tracker``), then asked the covisibility question -- of the surface points this frame
+measured, how many does each keyframe see? (``gs_view_overlap``, csrc/overlap.hip: one call, one host read) -- and becomes a
+keyframe when the last keyframe sees too few of them or too many frames have passed.  A keyframe is added to the running fit
+(``Trainer.add_view``), seeds Gaussians where the map does not explain it (``Trainer.seed_from_view``) and is optimised
+together with the keyframes that share the most points with it.  A frame that is no keyframe leaves the map and the
+optimizer state untouched, bit for bit.
+
+rgb maps only.  Keyframe poses are fixed once set (the pose gradient is not in the fused-Adam backward); the keyframe set
+only grows -- ``KeyframeSet.add`` raises when it is full; there is no loop closure and ``adaptive_control`` is never called.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import time
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+import gs_seed
+from gaussian import _lib
+from gs_track import _SH_REFUSAL, TrackOptions, TrackResult, Tracker
+from gs_train import TrainOptions, Trainer
+
+GS_OVERLAP_MAX_VIEWS = _lib.GS_OVERLAP_MAX_VIEWS
+
+
+def view_overlap(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: int, stride: int = 1, near: float = 0.3,
+                 border: int = 0) -> torch.Tensor:
+    """``gs_view_overlap`` (include/gs_abi.h) -> counts [n_views + 2] int64 on the device: per view the measured lattice pixels
+    of ``range_map`` whose surface point the view sees, then the measured lattice pixels, then those no view sees.  ``table``
+    is the device array of view rows [>= n_views, 16] float32 (``KeyframeSet.table``); ``camera`` the frame's posed camera.
+    No host synchronisation.  The rows of ``table`` are not validated here (``view_row`` does that when a row is made), and
+    a ``border`` that leaves nothing of a view -- 2 border >= its width or height -- is NOT refused by this call: the sizes are
+    in device memory.  ``KeyframeSet.overlap`` holds the border against its smallest view."""
+    if range_map.device.type != "cuda":
+        raise RuntimeError("the overlap count needs a HIP device; there is no CPU fallback")
+    cam = gs_seed.seed_camera(camera)
+    gs_seed._map("range_map", range_map, (cam.height, cam.width))
+    if (table.dtype != torch.float32 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2
+            or table.shape[1] != 16 or table.shape[0] < n_views):
+        raise RuntimeError(f"table must be a contiguous float32 HIP tensor of shape [>= {n_views}, 16]")
+    opts = _lib.GsOverlapOpts(int(stride), float(near), int(border))
+    ws = torch.empty(int(_lib.gs_view_overlap_workspace_bytes(cam.height, cam.width, max(int(stride), 1),
+                                                              min(max(int(n_views), 1), GS_OVERLAP_MAX_VIEWS))),
+                     dtype=torch.uint8, device=range_map.device)
+    counts = torch.empty(max(int(n_views), 0) + 2, dtype=torch.int64, device=range_map.device)
+    _lib.check(_lib.gs_view_overlap(range_map.data_ptr(), C.byref(cam), table.data_ptr(), int(n_views), C.byref(opts),
+                                    counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    torch.cuda.current_stream().cuda_stream), "gs_view_overlap")
+    return counts
+
+
+def view_row(camera) -> np.ndarray:
+    """A camera as one 64-byte row of the view table (``struct gs_seed_camera``), validated: ``gs_view_overlap`` cannot
+    check rows that live in device memory, so the owner of the table does when it appends one."""
+    cam = gs_seed.seed_camera(camera)
+    _lib.check(_lib.gs_view_overlap_check_view(C.byref(cam), 0), "gs_view_overlap_check_view")
+    return np.frombuffer(bytes(cam), np.float32).copy()
+
+
+class KeyframeSet:
+    """The keyframes of a mapping run: posed cameras, colour targets, range maps, and the device table of their 64-byte
+    rows that ``gs_view_overlap`` reads.  It only grows: ``add`` raises ``RuntimeError`` once ``capacity`` keyframes are
+    held (at most GS_OVERLAP_MAX_VIEWS = 256; there is no eviction)."""
+
+    def __init__(self, capacity: int = GS_OVERLAP_MAX_VIEWS, device="cuda"):
+        if not 1 <= int(capacity) <= GS_OVERLAP_MAX_VIEWS:
+            raise ValueError(f"capacity must lie in [1, {GS_OVERLAP_MAX_VIEWS}]")
+        self.capacity = int(capacity)
+        self.cameras, self.images, self.ranges = [], [], []
+        self.table = torch.zeros((self.capacity, 16), dtype=torch.float32, device=device)
+        self._min_size = None
+
+    def __len__(self) -> int:
+        return len(self.cameras)
+
+    def add(self, camera, image: torch.Tensor, range_map: torch.Tensor) -> int:
+        """Appends a keyframe -> its index.  The row is validated on the host and written with one 64-byte copy."""
+        n = len(self.cameras)
+        if n >= self.capacity:
+            raise RuntimeError(f"the keyframe set is full ({self.capacity} views); there is no eviction")
+        row = view_row(camera)
+        self.table[n].copy_(torch.from_numpy(row))
+        self.cameras.append(copy.copy(camera))
+        self.images.append(image)
+        self.ranges.append(range_map)
+        size = min(int(camera.width), int(camera.height))
+        self._min_size = size if self._min_size is None else min(self._min_size, size)
+        return n
+
+    def overlap(self, range_map: torch.Tensor, camera, stride: int = 1, near: float = 0.3, border: int = 0) -> np.ndarray:
+        """counts [len + 2] int64 on the host (``view_overlap``): the one host read of a frame's keyframe decision."""
+        if not self.cameras:
+            raise RuntimeError("the keyframe set is empty")
+        if 2 * int(border) >= self._min_size:
+            raise RuntimeError(f"border {border} leaves nothing of a {self._min_size}-pixel keyframe")
+        return view_overlap(range_map, camera, self.table, len(self.cameras), stride, near, border).cpu().numpy()
+
+
+def select_keyframes(counts: Sequence[int], measured: int, k: int, min_share: float) -> List[int]:
+    """The up to ``k`` views with the highest counts among those with count >= min_share x measured, highest first; ties go
+    to the higher index (the more recent keyframe).  No randomness."""
+    floor = float(min_share) * float(measured)
+    ok = [(int(c), i) for i, c in enumerate(counts) if int(c) >= floor]
+    ok.sort(key=lambda ci: (-ci[0], -ci[1]))
+    return [i for _, i in ok[:max(int(k), 0)]]
+
+
+def is_keyframe(count_last: int, measured: int, frames_since: int, overlap_min: float, every: int) -> bool:
+    """A frame becomes a keyframe when the last keyframe sees less than ``overlap_min`` of its measured points, or
+    ``every`` frames have passed since that keyframe."""
+    return bool(int(count_last) < float(overlap_min) * float(measured) or int(frames_since) >= int(every))
+
+
+def _map_train_options() -> TrainOptions:
+    return TrainOptions(n_iters_warmup=5, depth_weight=0.2)
+
+
+@dataclass
+class SlamOptions:
+    """Nobody has measured good defaults for the mapping side; these come from the only evidence in the tree.
+
+    ``track``: ``gs_track.TrackOptions()`` as they are (the pose fit of tests/test_gpu_pose.py).  ``train``: the Trainer of
+    tests/test_gpu_seed.py::_trainer -- ``n_iters_warmup=5, depth_weight=0.2`` -- whose 90 steps over three views are the only
+    depth-supervised fit from seeds measured here (profiles/seed_rgbd.txt); ``map_iterations_first`` is that run's 30 steps
+    per view.  ``seed``: ``gs_seed.DEFAULTS``.  ``map_iterations`` = 120 is a value fitted to ONE sequence, the eight-frame
+    synthetic arc of tests/test_gpu_slam.py (windows of two and three views): with 30 and with 60 steps per keyframe the
+    loop kept its pose errors within one frame's motion but left the first keyframe's colour loss above its seeded value,
+    with 120 every keyframe ends below it (profiles/slam_sequence.txt).  ``overlap_min``, ``keyframe_every``, ``window`` and
+    ``min_share`` have no evidence behind them yet.
+
+    The learning-rate schedule: ``Slam`` numbers its mapping steps 0, 1, 2, ... over the WHOLE run and passes that count as
+    ``i_iter``, so ``train.n_iters`` is the number of mapping steps over which the "exp" schedule takes the rates down to
+    1 %, not the length of a fit to a fixed set of views.  A sequence has no known length; the default stays
+    ``TrainOptions``' 7001, so that a run of a few hundred mapping steps trains at nearly the full rate (0.72 x after 500).
+    Set it to the expected keyframes x ``map_iterations`` for a sequence that should anneal, or ``lr_decay="none"``."""
+    track: TrackOptions = field(default_factory=TrackOptions)
+    train: TrainOptions = field(default_factory=_map_train_options)
+    seed: dict = field(default_factory=lambda: dict(gs_seed.DEFAULTS))
+    stride: int = 2                 # lattice of the overlap count (the seed lattice is seed["stride"])
+    near: Optional[float] = None    # a point counts for a keyframe beyond this camera z; None: the camera's `near`
+    border: int = 0                 # pixels taken off each side of a keyframe's image in the overlap count
+    overlap_min: float = 0.9        # keyframe when the last keyframe sees less than this share of the measured points ...
+    keyframe_every: int = 5         # ... or this many frames have passed since it
+    window: int = 4                 # views optimised together: the new keyframe + the window - 1 that share most with it
+    min_share: float = 0.1          # ... among those that see at least this share of its measured points
+    map_iterations_first: int = 30  # mapping steps on the first frame
+    map_iterations: int = 120       # mapping steps per later keyframe, round-robin over the window (fitted: see above)
+    max_pairs: int = 1 << 21        # the trainer's initial pair capacity (it grows by itself)
+
+
+@dataclass
+class SlamFrame:
+    rot: np.ndarray                  # [3,3] float64, world -> camera
+    tran: np.ndarray                 # [3] float64
+    tracked: Optional[TrackResult]   # None for the first frame
+    keyframe: bool
+    overlap: Optional[np.ndarray]    # counts [keyframes before this frame + 2]; None for the first frame
+    window: List[int] = field(default_factory=list)   # keyframe indices optimised, the new one first
+    added: int = 0                   # Gaussians seeded
+    map_losses: List[float] = field(default_factory=list)  # the loss of each mapping step
+    seconds: dict = field(default_factory=dict)  # wall time in track / overlap / seed / map (each ends on a host read)
+    pending: int = 0                 # mapping steps that `Slam.map(frame)` has still to take (`begin` sets it)
+
+
+class Slam:
+    """``Slam(camera, options)``: ``camera`` gives the image size, the focal lengths, ``near`` and the pose of the first
+    frame.  ``step(image, range_map, init=None)`` takes one frame -- contiguous float32 HIP tensors [H,W,3] and [H,W]
+    (range from the camera centre; <= 0, inf, NaN: no measurement) -- and returns a ``SlamFrame``.  ``init`` = (rot, tran):
+    the first frame's pose, or where a later frame's tracking starts.  ``params`` is the map, ``keyframes`` the set.
+    ``step`` is ``begin`` -- everything up to and including a keyframe's seeding -- followed by ``map`` -- its mapping steps
+    and the tracker's rebind; a caller that wants to look at the map in between calls the two itself."""
+
+    def __init__(self, camera, options: Optional[SlamOptions] = None, device="cuda"):
+        self.opt = options if options is not None else SlamOptions()
+        # the map is seeded with rgb colours; a `seed` dict that asks for SH rows is refused with the tracker's sentence
+        self._seed = {k: v for k, v in self.opt.seed.items() if k != "color_dim"}
+        if int(self.opt.seed.get("color_dim", 3)) != 3:
+            raise RuntimeError(_SH_REFUSAL)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("Slam needs a HIP device; there is no CPU fallback")
+        self.camera = camera
+        self.near = float(self.opt.near if self.opt.near is not None else camera.near)
+        self.keyframes = KeyframeSet(device=self.device)
+        self.trainer: Optional[Trainer] = None
+        self.tracker: Optional[Tracker] = None
+        self.i_iter = 0          # mapping steps taken so far, over the whole run
+        self.n_frames = 0
+        self._last_keyframe_at = 0
+
+    @property
+    def params(self):
+        return self.trainer.flat.params if self.trainer is not None else None
+
+    def _posed(self, rot, tran):
+        cam = copy.copy(self.camera)
+        cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
+        cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
+        return cam
+
+    def map(self, frame: SlamFrame) -> SlamFrame:
+        """The mapping steps of a keyframe that ``begin`` returned, round-robin over its window starting with the new view,
+        then the tracker's (re)bind to the trainer's parameters.  A frame that is no keyframe has none: nothing happens."""
+        if not frame.keyframe:
+            return frame
+        t0 = time.perf_counter()
+        vals = []
+        for s in range(frame.pending):
+            vals.append(self.trainer.train_step(self.i_iter, frame.window[s % len(frame.window)]).clone())
+            self.i_iter += 1
+        frame.pending = 0
+        frame.map_losses += [float(v) for v in torch.stack(vals)[:, 0].cpu()] if vals else []
+        frame.seconds["map"] = time.perf_counter() - t0
+        # (also with no step taken: seeding gave the trainer new parameter tensors)
+        if self.tracker is None:
+            self.tracker = Tracker(self.trainer.flat.params, self.keyframes.cameras[0], self.opt.track, self.device)
+        else:
+            self.tracker.set_map(self.trainer.flat.params)
+        return frame
+
+    def _first(self, image, range_map, init) -> SlamFrame:
+        o = self.opt
+        rot, tran = init if init is not None else (self.camera.rot, self.camera.tran)
+        to_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))  # noqa: E731
+        rot, tran = to_np(rot).astype(np.float64).reshape(3, 3), to_np(tran).astype(np.float64).reshape(3)
+        cam = self._posed(rot, tran)
+        t0 = time.perf_counter()
+        params = gs_seed.seed_from_depth(image, range_map, cam, color_dim=3, **self._seed)
+        if int(params[0].shape[0]) == 0:
+            raise RuntimeError("the first frame carries no measurement: nothing to found the map on")
+        self.trainer = Trainer(params, [cam], [image], o.train, max_pairs=int(o.max_pairs), depths=[range_map])
+        frame = SlamFrame(rot=rot, tran=tran, tracked=None, keyframe=True, overlap=None, window=[0],
+                          added=int(params[0].shape[0]), pending=int(o.map_iterations_first))
+        self.keyframes.add(cam, image, range_map)
+        frame.seconds["seed"] = time.perf_counter() - t0
+        return frame
+
+    def step(self, image: torch.Tensor, range_map: torch.Tensor, init=None) -> SlamFrame:
+        return self.map(self.begin(image, range_map, init))
+
+    def begin(self, image: torch.Tensor, range_map: torch.Tensor, init=None) -> SlamFrame:
+        """Track, count, decide and -- for a keyframe -- add the view and seed its Gaussians.  ``map(frame)`` must follow
+        before the next frame."""
+        o = self.opt
+        if self.trainer is None:
+            frame = self._first(image, range_map, init)
+            self.n_frames, self._last_keyframe_at = 1, 0
+            return frame
+        t0 = time.perf_counter()
+        res = self.tracker.track(image, range_map, init)
+        t1 = time.perf_counter()
+        cam = self._posed(res.rot, res.tran)
+        n = len(self.keyframes)
+        counts = self.keyframes.overlap(range_map, cam, stride=o.stride, near=self.near, border=o.border)
+        t2 = time.perf_counter()
+        measured = int(counts[n])
+        frames_since = self.n_frames - self._last_keyframe_at
+        frame = SlamFrame(rot=res.rot, tran=res.tran, tracked=res, overlap=counts,
+                          keyframe=is_keyframe(int(counts[n - 1]), measured, frames_since, o.overlap_min, o.keyframe_every))
+        frame.seconds.update(track=t1 - t0, overlap=t2 - t1)
+        if frame.keyframe and n >= self.keyframes.capacity:  # before the trainer or the frame count is touched
+            raise RuntimeError(f"the keyframe set is full ({self.keyframes.capacity} views); there is no eviction")
+        index = self.n_frames
+        self.n_frames += 1
+        if not frame.keyframe:
+            return frame
+        new = self.keyframes.add(cam, image, range_map)
+        added_as = self.trainer.add_view(cam, image, range_map)
+        if added_as != new:
+            raise RuntimeError(f"keyframe {new} became view {added_as} of the trainer: the two lists have diverged")
+        self._last_keyframe_at = index
+        frame.added = self.trainer.seed_from_view(new, self.i_iter, **self._seed)
+        frame.seconds["seed"] = time.perf_counter() - t2
+        frame.window = [new] + select_keyframes(counts[:n], measured, o.window - 1, o.min_share)
+        frame.pending = int(o.map_iterations)
+        return frame

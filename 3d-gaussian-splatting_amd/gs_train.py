@@ -363,24 +363,15 @@ class Trainer:
         if self.opt.depth_mode not in DepthLoss.MODES:
             raise ValueError(f"depth_mode must be 'residual' or 'expected', got {self.opt.depth_mode!r}")
         self.depths, self._depth_inv_n = None, None
+        self._depth_kind, self._depth_device = depth_kind, params[0].device
         if depths is not None:
             if len(depths) != len(targets):
                 raise ValueError("depths must be a list parallel to targets (None for a view without a depth map)")
             self.depths, self._depth_inv_n = [], []
             for cam_, d in zip(cameras, depths):
-                if d is None:
-                    self.depths.append(None)
-                    self._depth_inv_n.append(0.0)
-                    continue
-                if d.dtype != torch.float32 or tuple(d.shape) != (int(cam_.height), int(cam_.width)):
-                    raise ValueError("a depth map must be float32 [H,W] of its camera")
-                d = d.to(params[0].device)
-                if depth_kind == "z":
-                    d = z_to_range(d, cam_)
-                d = d.contiguous()
-                n_valid = int((torch.isfinite(d) & (d > 0)).sum())  # once, here: no count pass in the step
+                d, inv_n = self._view_depth(cam_, d)
                 self.depths.append(d)
-                self._depth_inv_n.append(1.0 / n_valid if n_valid else 0.0)
+                self._depth_inv_n.append(inv_n)
         self._depth_loss = {}
         self.depth_loss = None  # the DepthLoss of the last depth-supervised step (.values: loss, pixels that counted)
         # `fuse_adam`: apply the Adam step inside the backward's last kernel (FrameRenderer.backward_adam: no gradient buffer is
@@ -450,6 +441,35 @@ class Trainer:
         self.grad_counter = None  # "mean" accumulation only: per-Gaussian count of views that saw it (train.py:150)
         self._views_checked = set()  # a new Gaussian set: every view's first frame is capacity-checked again
         self._backward_choice_due = True  # ... and the rgb backward kernel is chosen again, behind its first step
+
+    def _view_depth(self, camera, d: Optional[torch.Tensor]):
+        """One view's measured depth map as the step uses it -> (range map on the device or None, 1 / its measured pixels):
+        the per-view validation and conversion of the constructor and of ``add_view``, stated once."""
+        if d is None:
+            return None, 0.0
+        if d.dtype != torch.float32 or tuple(d.shape) != (int(camera.height), int(camera.width)):
+            raise ValueError("a depth map must be float32 [H,W] of its camera")
+        d = d.to(self._depth_device)
+        if self._depth_kind == "z":
+            d = z_to_range(d, camera)
+        d = d.contiguous()
+        n_valid = int((torch.isfinite(d) & (d > 0)).sum())  # once, here: no count pass in the step
+        return d, (1.0 / n_valid if n_valid else 0.0)
+
+    def add_view(self, camera, target: torch.Tensor, depth: Optional[torch.Tensor] = None) -> int:
+        """Appends a view to a running fit -> its camera id.  ``depth`` goes through the constructor's own per-view
+        validation and conversion (``depth_kind``, the measured-pixel count); a Trainer built without ``depths`` takes
+        ``depth=None`` only.  Nothing else changes -- no rebind, no optimizer reset, no frame abandoned: a step on an earlier
+        view afterwards is the step it would have been."""
+        if depth is not None and self.depths is None:
+            raise ValueError("this Trainer was built without depths: add_view takes depth=None only")
+        d, inv_n = self._view_depth(camera, depth)
+        self.cameras.append(camera)
+        self.targets.append(target)
+        if self.depths is not None:
+            self.depths.append(d)
+            self._depth_inv_n.append(inv_n)
+        return len(self.cameras) - 1
 
     @property
     def n_gaussians(self) -> int:

@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_track +
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_overlap,
+ *   gs_view_overlap_workspace_bytes and gs_view_overlap_check_view with gs_overlap_opts / GS_OVERLAP_MAX_VIEWS (how many of the
+ *   surface points an RGB-D frame measured does each keyframe see: the covisibility count of a mapping loop).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_track +
  *   gs_loss_track_workspace_bytes (the masked colour + depth loss of camera tracking against a frozen map, one pass).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_seed_workspace_bytes,
  *   gs_seed_classify and gs_seed_apply with gs_seed_opts / gs_seed_camera (new Gaussians from an RGB-D frame by
@@ -767,6 +770,45 @@ int gs_seed_classify(const float *range, const float *depth, const float *alpha,
 int gs_seed_apply(const float *image, const float *range, const gs_seed_camera *cam, const gs_seed_opts *opts, float *pos,
                   float *quat, float *scale, float *opa, float *rgb, int64_t offset, int64_t capacity,
                   const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- covisibility: of the surface points a frame measured, how many does each keyframe see? ----
+ * range [H,W] (H, W = cam->height, cam->width): the incoming frame's measured range, "no measurement" where it is <= 0,
+ * infinite or NaN (the rule of gs_seed and gs_loss_depth).  cam: the frame's posed camera, by value, on the host.
+ * views_dev: a DEVICE array of n_views gs_seed_camera rows, 64 bytes = one line per view, 64-byte aligned; the caller keeps
+ * one table and appends a row per keyframe.  counts_dev [n_views + 2] int64 on the device:
+ *   [k]           measured lattice pixels whose point view k sees
+ *   [n_views]     measured lattice pixels
+ *   [n_views + 1] measured lattice pixels that no view sees
+ * over the LATTICE of gs_seed: pixels (x, y) with x % stride == stride / 2 and y % stride == stride / 2.
+ * One point, in fp32 with one rounding per operation (division and square root correctly rounded; a float32 restatement
+ * decides identically; csrc/overlap_point.h is the text, compilable for the host):
+ *   the world point is the one gs_seed_apply writes for the pixel:
+ *     u = (x + left - padW / 2 + 0.5) / focal_x, v likewise;  z_cam = z / sqrt(u u + v v + 1);
+ *     p = rot^T ((u z_cam, v z_cam, z_cam) - tran)
+ *   view k:  q = rot_k p + tran_k, each row summed left to right;  cx = padW_k / 2 - left_k, cy likewise (small exact numbers);
+ *     seen  <=>  q.z > near  and  fl(fx_k q.x) >= fl((border - cx) q.z)  and  fl(fx_k q.x) < fl((W_k - border - cx) q.z)
+ *                and the same two for y
+ *   -- the point lies beyond `near` in front of the view and falls on a pixel of its image at least `border` pixels from
+ *   every side: the inverse of the renderer's pixel coordinate, cross-multiplied, no division.
+ * Two launches on `stream`, no atomics: per-workgroup partial counts go to the workspace as rows of uint32, a second kernel
+ * adds them per view in int64.  The result is a pure function of the inputs, whatever the workspace and counts_dev held.
+ * Refused before anything is enqueued (GS_E_INVALID, gs_last_error): a null pointer, a frame of non-positive size or focal
+ * length, stride < 1, near <= 0 or NaN, border < 0, n_views < 1 or > GS_OVERLAP_MAX_VIEWS, a misaligned or too-small
+ * workspace.  The rows of views_dev are in device memory and cannot be validated here without a read: the owner of the table
+ * validates each row when it appends it -- gs_view_overlap_check_view (host only, nothing enqueued) refuses a view of
+ * non-positive size or focal length and a border with 2 border >= the view's width or height; gs_slam.KeyframeSet calls it. */
+#define GS_OVERLAP_MAX_VIEWS 256
+typedef struct gs_overlap_opts {
+    int32_t stride;   /* >= 1: the lattice of gs_seed (x % stride == stride / 2, y likewise) */
+    float   near;     /* > 0: a point counts for a view only with camera z > near         */
+    int32_t border;   /* >= 0: pixels taken off each side of a view's image               */
+} gs_overlap_opts;
+size_t gs_view_overlap_workspace_bytes(int32_t H, int32_t W, int32_t stride, int32_t n_views);
+int gs_view_overlap_check_view(const gs_seed_camera *view, int32_t border);
+int gs_view_overlap(const float *range, const gs_seed_camera *cam,        /* the incoming frame, by value (host) */
+                    const gs_seed_camera *views_dev, int32_t n_views,     /* DEVICE array, 64 bytes per view     */
+                    const gs_overlap_opts *opts, int64_t *counts_dev,     /* [n_views + 2]                       */
+                    void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

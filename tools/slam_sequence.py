@@ -1,0 +1,84 @@
+"""The whole track / decide / seed / map loop on a synthetic sequence: a ``gs_scene.make_scene`` truth scene, N frames rendered
+along an arc (image, and range = D / A where A >= 0.9), ``gs_slam.Slam`` over them.  Per frame: pose errors against the true
+pose, keyframe flag, window, Gaussians added, milliseconds in track / overlap / seed / map; at the end the colour loss on each
+keyframe.
+
+    python tools/slam_sequence.py [--frames 12] [--width 320 --height 240] [--gaussians 40000] [--step-deg 0.5 --step 0.02]
+"""
+import argparse
+import copy
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "3d-gaussian-splatting_amd")]
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from gs_frame import FrameRenderer  # noqa: E402
+from gs_scene import make_camera, make_scene  # noqa: E402
+from gs_slam import Slam, SlamOptions  # noqa: E402
+from gs_track import so3_exp  # noqa: E402
+from gs_train import ImageLoss  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=12)
+    ap.add_argument("--width", type=int, default=320)
+    ap.add_argument("--height", type=int, default=240)
+    ap.add_argument("--gaussians", type=int, default=40000)
+    ap.add_argument("--step-deg", type=float, default=0.5)
+    ap.add_argument("--step", type=float, default=0.02)
+    ap.add_argument("--keyframe-every", type=int, default=SlamOptions().keyframe_every)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    dev = torch.device("cuda:0")
+    W, H = a.width, a.height
+    scene = make_scene(a.gaussians, W, H, seed=103)
+    truth = [torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+             for x in (scene.pos, scene.quat, scene.scale, scene.opa, scene.rgb)]
+    cam = make_camera(W, H, yaw_deg=2.0)
+    cam.tran = np.array([0.03, -0.01, 0.2], np.float32)
+    g = np.random.default_rng(211)
+    axis, u = g.normal(size=3), g.normal(size=3)
+    dR = so3_exp(axis / np.linalg.norm(axis) * math.radians(a.step_deg))
+    R, t = cam.rot.astype(np.float64), cam.tran.astype(np.float64)
+    dt = u / np.linalg.norm(u) * a.step - (dR @ t - t)
+    poses = [(R, t)]
+    for _ in range(a.frames - 1):
+        R, t = poses[-1]
+        poses.append((dR @ R, dR @ t + dt))
+    renderer = FrameRenderer(dev, max_pairs=1 << 21, training=False, auto_grow=True, occlusion_cull=False)
+
+    def posed(R, t):
+        c = copy.copy(cam)
+        c.rot, c.tran = np.asarray(R, np.float32), np.asarray(t, np.float32)
+        return c
+
+    def err(Ra, ta, Rb, tb):
+        return float(np.linalg.norm(Ra - Rb) / math.sqrt(2.0)), float(np.linalg.norm(ta - tb))
+
+    slam = Slam(posed(*poses[0]), SlamOptions(keyframe_every=a.keyframe_every), dev)
+    print(f"slam sequence: {a.gaussians} truth Gaussians, {W} x {H}, {a.frames} frames, {a.step_deg} degrees and {a.step} per "
+          f"frame, keyframe_every {a.keyframe_every}, defaults otherwise")
+    for f, (R, t) in enumerate(poses):
+        img, _, d, al = renderer.forward(*truth, posed(R, t), training=False, aux=True)
+        rng = torch.where(al >= 0.9, d / al.clamp_min(1e-3), torch.zeros_like(d)).contiguous()
+        fr = slam.step(img.contiguous().clone(), rng)
+        e = err(fr.rot, fr.tran, R, t)
+        ms = ", ".join(f"{k} {1e3 * fr.seconds[k]:.1f}" for k in ("track", "overlap", "seed", "map") if k in fr.seconds)
+        print(f"  frame {f}: rotation error {e[0]:.3e} translation error {e[1]:.3e} keyframe {fr.keyframe} window {fr.window} "
+              f"added {fr.added} Gaussians {slam.trainer.n_gaussians}; ms: {ms}")
+    ev = FrameRenderer(dev, max_pairs=1 << 21, training=False, auto_grow=True)
+    probe = ImageLoss(H, W, slam.opt.train.ssim_weight, dev)
+    for k, (c, target) in enumerate(zip(slam.keyframes.cameras, slam.keyframes.images)):
+        image = ev.forward(*slam.params, c, training=False)[0]
+        probe(image.contiguous(), target)
+        print(f"  keyframe {k}: colour loss {float(probe.values[0]):.5f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
 // aux_depth_backward_body.inc -- the body of frame_aux_depth_backward_kernel and of its GS_FRAME_POSE_GRAD variant
-// frame_aux_depth_pose_backward_kernel (cull_project.hip), expanded in place in both (see frame_project_backward_body.inc).
+// frame_aux_depth_pose_backward_kernel (project_bwd.hip), expanded in place in both (see frame_project_backward_body.inc).
 // Expects in scope: the kernel's parameters, CDIM, `constexpr bool POSE` and, with POSE, `float pt[12]`.  Its `return`s
 // leave the kernel -- or, in the pose variant, the lambda the body is expanded in.  The row walk and the position term are
 // aux_depth_term.inc, shared with the fused optimizer step's AUX variant.

@@ -4,7 +4,8 @@
 // in aux_depth_backward_body.inc (the kernels behind gs_frame_backward) and in the AUX variant of the fused optimizer step
 // (frame_project_backward_body.inc): ONE statement of the row walk, so both add the same rows in the same order.
 // Expects in scope: CDIM, P, D, pid, rc (the visible Gaussian's rectangle record), off, cnt, `const float *rows`, stop_keys,
-// rec_geom, max_pairs, pos.  Leaves gd, p, pc, gc and gpa behind.
+// rec_geom, max_pairs, pos, and GS_PB_SH_BIG (project_bwd.hip, in front of sh_big_rows_kernel).  Leaves gd, p, pc, gc and
+// gpa behind.
     constexpr int RWF = gs_row_floats(CDIM), SLOT = gs_row_aux_depth(CDIM);
     float gd = 0.f;
     if (CDIM != 3 && cnt > (uint64_t)GS_PB_SH_BIG) {

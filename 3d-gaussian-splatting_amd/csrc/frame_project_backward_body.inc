@@ -1,5 +1,5 @@
 // frame_project_backward_body.inc -- the body of frame_project_backward_kernel and of its GS_FRAME_POSE_GRAD variant
-// frame_project_backward_pose_kernel (cull_project.hip), expanded in place in both.  Expects in scope: the kernel's
+// frame_project_backward_pose_kernel (project_bwd.hip), expanded in place in both.  Expects in scope: the kernel's
 // parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE`, `constexpr bool AUX` and `pose_part`.  (Included rather than called: an
 // inlined device function leaves the kernel without the flag with other register assignments than before it existed;
 // expanded in place, it compiles to the same code.)

@@ -127,6 +127,7 @@ __device__ __forceinline__ float gs_det(float a, float b, float c, float d) {
 // a Gaussian centred at (px, py)?  The tile edges are Tiles.create_tiles' (splatter.py:275-293): left(i) =
 // (16 i - pad/2) / focal with an exact integer-valued numerator, right(i) = left(i + 1) bit for bit; the centre is
 // (left + right) / 2 and the test d1 d1 + d2 d2 < thresh, all in fp32 without contraction, as the reference kernel.
+// A frame's values: gs_frame_dist_cull (gs_frame_layout.h, beside the frame geometry it is derived from).
 struct GsDistCull {
     float half_padw, half_padh, fx, fy, thresh;
 };
@@ -150,7 +151,7 @@ __device__ __forceinline__ void gs_conic(float a, float b, float c, float d, flo
     C = a * k;
 }
 
-// One element of torch's _single_tensor_adam (adam.hip; also the fused projection-backward + Adam kernel of cull_project.hip --
+// One element of torch's _single_tensor_adam (adam.hip; also the fused projection-backward + Adam kernel of project_bwd.hip --
 // both translation units are compiled with -ffp-contract=off, so the two paths round alike):
 //   m <- m + (g - m)(1 - b1);  v <- v b2 + (1 - b2) g g;  p <- p - step_size m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 __device__ __forceinline__ void gs_adam_one(float &p, float g, float &m, float &v, float step_size, float one_m_b1,

@@ -273,6 +273,12 @@ static inline gs_frame_geom gs_frame_geometry(const gs_frame *f) {
     G.topmost = f->topmost;
     return G;
 }
+// The "dist" listing test's parameters (GsDistCull, gs_common.h) of a frame: half the padded size in pixels (exact in fp32),
+// the focal lengths and the squared distance threshold.  Every kernel that calls gs_dist_listed is handed this one value.
+inline GsDistCull gs_frame_dist_cull(const gs_frame *f) {
+    const gs_frame_geom G = gs_frame_geometry(f);
+    return {(float)(G.padW / 2), (float)(G.padH / 2), f->focal_x, f->focal_y, f->thresh};
+}
 
 struct gs_frame_ws {
     unsigned long long *counters;  // [GS_CNT_N]

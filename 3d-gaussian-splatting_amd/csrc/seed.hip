@@ -19,7 +19,7 @@
 //                                                                   the pixel (raster_pixel_coord; gs_geometry.RayBasis)
 //   z_cam = z / sqrt(u u + v v + 1),  p_c = (u z_cam, v z_cam, z_cam),  pos = rot^T (p_c - tran)
 //   sigma = scale_factor stride z_cam / ((fx + fy) / 2): `scale_factor` lattice steps at that depth; stored as the inverse of
-//           the renderer's activation (cull_project.hip `activate`): max(sigma - 1e-4, 0) for abs, log sigma for exp
+//           the renderer's activation (project_common.h `activate`): max(sigma - 1e-4, 0) for abs, log sigma for exp
 //   quat = (1, 0, 0, 0),  opa = logit(opa_init),  colour: logit(clamp(c, 1 / 512, 1 - 1 / 512)) per channel (half an 8-bit step
 //           away from 0 and 1: the logit stays within +-6.24); SH: DC = logit / 0.28209479 (utils.py:345-348), the rest zero.
 // The SH rows (27 or 48 floats, all but three of them zero) are written by the whole wave: its selected pixels are consecutive

@@ -368,7 +368,7 @@ int gs_stage_strip_bin(const gs_frame *f, const gs_frame_ws &ws, hipStream_t str
     const gs_strip_plan plan = gs_strip_plan_for(f->N, G.ntx, G.nty);
     const gs_strip_geom SG = plan.geom;
     const bool dist = f->tile_culling_method == 0;
-    GsDistCull D = {(float)(G.padW / 2), (float)(G.padH / 2), f->focal_x, f->focal_y, f->thresh};
+    const GsDistCull D = gs_frame_dist_cull(f);
     static std::mutex attr_mu;
     static std::atomic<uint64_t> attr_done{0};
     int dev = 0;

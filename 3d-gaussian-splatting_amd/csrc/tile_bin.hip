@@ -588,7 +588,7 @@ int gs_stage_tile_bin(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stre
     const gs_bin_plan plan = gs_bin_plan_for(f->N, f->max_pairs, G.n_tiles, (f->flags & GS_FRAME_SLICE_SORT) != 0);
     const uint32_t T = (uint32_t)G.n_tiles;
     const bool dist = f->tile_culling_method == 0;
-    GsDistCull D = {(float)(G.padW / 2), (float)(G.padH / 2), f->focal_x, f->focal_y, f->thresh};
+    const GsDistCull D = gs_frame_dist_cull(f);
     // dynamic LDS above 64 KiB needs the opt-in (gfx950: 160 KiB per workgroup): once per DEVICE (a function
     // attribute belongs to the device's code object), thread-safe
     static std::mutex attr_mu;

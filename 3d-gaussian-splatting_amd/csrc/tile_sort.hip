@@ -1284,7 +1284,7 @@ int gs_stage_strip_sort(const gs_frame *f, const gs_frame_ws &ws, const uint64_t
     const unsigned long long *gate = second_pass ? ws.counters + GS_CNT_RANPAST : nullptr;
     gs_frame_geom G = gs_frame_geometry(f);
     const gs_strip_plan plan = gs_strip_plan_for(f->N, G.ntx, G.nty);
-    GsDistCull D = {(float)(G.padW / 2), (float)(G.padH / 2), f->focal_x, f->focal_y, f->thresh};
+    const GsDistCull D = gs_frame_dist_cull(f);
     const unsigned grid = GS_STRIP_W == 8 ? (unsigned)gs_div_up(plan.geom.NS, 8) * 16 : plan.geom.NS;
     // GS_FRAME_LONG_SORT / GS_FRAME_LONG_LISTS (the caller has seen a long list in an earlier frame): lists beyond the window are queued
     // for big_list_sort_kernel, one workgroup each; otherwise strip_sort_kernel sorts a long list itself and the

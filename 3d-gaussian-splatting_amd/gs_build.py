@@ -2,8 +2,9 @@
 
 ``python gs_build.py`` or ``build()``: every ``csrc/*.hip`` is compiled to an object with
 ``hipcc --offload-arch=gfx950 -O3`` and linked into ``csrc/libgs_amd.so``.  Files whose results
-feed the integer side of the pipeline (depth bits, tile rectangles) are compiled with
-``-ffp-contract=off`` so they match the oracle bit for bit (see cull_project.hip).
+feed the integer side of the pipeline (depth bits, tile rectangles: cull_project.hip, binning.hip) are
+compiled with ``-ffp-contract=off`` so they match the oracle bit for bit; the other files that carry the
+flag say why beside their entry in ``SOURCES``.
 No torch / pybind dependency: the library is a plain C ABI (include/gs_abi.h).
 """
 from __future__ import annotations
@@ -21,6 +22,10 @@ SOURCES = {
     # no SLP packing: the packer turns the 3x3 products into v_pk_mul/v_pk_add + ~140 v_mov shuffles per Gaussian;
     # a packed op has no rate advantage on gfx950, so that is pure issue time (and 66 instead of 45 VGPRs)
     "cull_project.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # uncontracted because the backward is pinned bit for bit by the golden tests, the fused step rounds like adam.hip,
+    # and the AUX position term is fl(gp) + gpa in that order (project_backward / pose_terms contract by pragma);
+    # no SLP packing, as above
+    "project_bwd.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "binning.hip": ["-ffp-contract=off"],
     "radix_sort.hip": [],
     "tile_sort.hip": [],
@@ -43,7 +48,7 @@ SOURCES = {
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
-HEADERS = ["gs_common.h", "gs_frame_layout.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
+HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
            "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
            os.path.join("..", "..", "include", "gs_abi.h")]
 

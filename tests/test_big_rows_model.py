@@ -1,4 +1,4 @@
-"""CPU tier: the contract between the SH big-row pre-pass (cull_project.hip: sh_big_rows_kernel) and the projection backward's row
+"""CPU tier: the contract between the SH big-row pre-pass (project_bwd.hip: sh_big_rows_kernel) and the projection backward's row
 walk, as a NumPy model.
 
 A Gaussian's per-pair gradient rows lie in one contiguous region (emission order); which rows the raster backward wrote

@@ -881,7 +881,7 @@ def test_frame_backward_sh_deep_saturating_tiles(gpu, sh_degree):
 
 def test_frame_backward_screen_filling_gaussians(gpu):
     """Gaussians that touch more than 256 tiles have their per-pair gradient rows summed by the whole workgroup
-    (cull_project.hip, deterministic tree) instead of by one thread: parity with the oracle for a scene that mixes a
+    (project_bwd.hip, deterministic tree) instead of by one thread: parity with the oracle for a scene that mixes a
     few of them -- next to each other in the array and isolated -- with ordinary ones, no SH and SH."""
     for use_sh in (False, True):
         scene, cam = case(3_000, 352, 272, seed=31, use_sh=use_sh)

@@ -348,7 +348,7 @@ def test_rgb_row_layout_model_equals_the_sequential_recursion():
 
 
 def test_fused_adam_hand_over_covers_every_element_once():
-    """The optimizer step fused into the projection backward (cull_project.hip: frame_project_backward_kernel<3, 0, 256, ADAM>,
+    """The optimizer step fused into the projection backward (project_bwd.hip: frame_project_backward_kernel<3, 0, 256, ADAM>,
     round 5): a thread owns a GAUSSIAN, but the [N, 3] arrays are walked by ELEMENT -- lane l of wave w writes its Gaussian's
     three gradients to tr[3 l + k], then lanes with 4 l + 4 <= ne take elements 4 l .. 4 l + 3 of the wave's contiguous run
     (base 3 (pid0 + 64 w)) as one float4, and the lane that straddles the array's end takes the rest one by one.  The model

@@ -357,6 +357,8 @@ def ref_live():
     test_ref_live.test_reference_backward_defect_between_chunks_is_real()
     for use_sh in (False, True):
         test_ref_live.test_sigmoid_flag_forward_and_backward_vs_reference_kernels(use_sh)
+    for use_sh in (False, True):
+        test_ref_live.test_oracle_vs_reference_kernels_general_camera(use_sh)
     np.savez_compressed(os.path.join(HERE, "ref_live.npz"), **test_ref_live.RECORD)
     print("ref_live ok", len(test_ref_live.RECORD))
 

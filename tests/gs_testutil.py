@@ -308,6 +308,109 @@ def aux_case(n, W, H, seed=7, use_sh=False, sh_degree=2, yaw=2.0, **kw):
     return scene, cam
 
 
+def general_rotation(roll, pitch, yaw):
+    """Rz(roll) Rx(pitch) Ry(yaw), degrees, formed in float64 and rounded once to float32."""
+    import math
+
+    a, b, c = (math.radians(v) for v in (roll, pitch, yaw))
+    rz = np.array([[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]])
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, math.cos(b), -math.sin(b)], [0.0, math.sin(b), math.cos(b)]])
+    ry = np.array([[math.cos(c), 0.0, math.sin(c)], [0.0, 1.0, 0.0], [-math.sin(c), 0.0, math.cos(c)]])
+    return (rz @ rx @ ry).astype(np.float32)
+
+
+def general_camera(W, H, roll=35.0, pitch=-12.0, yaw=10.0, fy_ratio=0.85, tran=(0.05, -0.04, 0.25)):
+    """A camera none of whose rotation entries or focal lengths can stand in for another: rot = Rz(roll) Rx(pitch) Ry(yaw)
+    (degrees; formed in float64, rounded once to float32), focal_x = 0.75 W, focal_y = float32(fy_ratio focal_x).
+    make_camera's yaw-only matrix has four exact zeros and an exact one, and fx = fy: a kernel that reads rot[1] for rot[3],
+    drops a y-row term or takes focal_x for focal_y computes the same frame under it.  The asserts below are conditions on
+    the INPUT -- what makes this camera worth a test -- not measurements of anything under test."""
+    rot = general_rotation(roll, pitch, yaw)
+    fx = 0.75 * W
+    fy = float(np.float32(fy_ratio * fx))
+    mags = np.sort(np.abs(rot.astype(np.float64)).ravel())
+    assert mags[0] >= 0.02, ("an entry of rot is (nearly) zero", rot)
+    assert np.diff(mags).min() >= 0.02, ("two entries of rot have (nearly) the same magnitude", rot)
+    r64 = rot.astype(np.float64)
+    assert np.abs(r64.T @ r64 - np.eye(3)).max() <= 1e-6 and np.linalg.det(r64) > 0, rot
+    assert abs(fx - fy) >= 0.1 * fx, (fx, fy)
+    return Camera(W, H, fx, fy, rot, np.asarray(tran, np.float32))
+
+
+def aux_general_case(n, W, H, seed=7, use_sh=False, sh_degree=2, camera=None, **kw):
+    """``aux_case``'s scene seen from ``general_camera`` (``camera``: keyword arguments for it)."""
+    from gs_scene import make_scene
+
+    scene = make_scene(n, W, H, seed=seed, use_sh=use_sh, sh_degree=sh_degree, **kw)
+    return scene, general_camera(W, H, **(camera or {}))
+
+
+# The frames for comparing the HIP frame path with the oracle under general_camera, stated once so that
+# tests/test_general_camera_host.py can prove on the CPU that each is a valid input (enough of the scene in view, pairs to
+# composite, multi-bucket tiles where the GPU test relies on them, few pixels masked for a non-robust stop decision).
+#   n, W, H, seed; sh: 0 = rgb logits, 2 / 3 = SH degree; opa: shift of the opacity logits; exp: log scales for the exp
+#   activation; sigma: make_scene's max_px_sigma; method / dist: tile culling method and its threshold;
+#   deep: the comparison relies on a list beyond one 64-Gaussian bucket; grads: it runs a backward on robust_aux_grads
+def _gc(n, W, H, seed=7, sh=0, opa=0.0, exp=False, sigma=16.0, method="prob2", dist=0.5, deep=False, grads=False):
+    return dict(n=n, W=W, H=H, seed=seed, sh=sh, opa=opa, exp=exp, sigma=sigma, method=method, dist=dist, deep=deep,
+                grads=grads)
+
+
+GENERAL_CASES = {
+    "api_cull": _gc(20_000, 320, 200),
+    "api_tiles": _gc(3_000, 160, 96),
+    "api_draw_rgb": _gc(12_000, 200, 120, seed=5, deep=True),
+    "api_draw_sh2": _gc(12_000, 200, 120, seed=5, sh=2, deep=True),
+    "fwd_256": _gc(10_000, 256, 256, deep=True),
+    "fwd_333": _gc(30_000, 333, 201, deep=True),
+    "fwd_40": _gc(3_000, 40, 200),
+    "fwd_prob": _gc(15_000, 250, 186, seed=29, method="prob", grads=True),
+    "fwd_dist_0.5": _gc(12_000, 250, 186, seed=29, method="dist", dist=0.5, grads=True),
+    "fwd_dist_0.3": _gc(12_000, 333, 201, seed=29, method="dist", dist=0.3, grads=True),
+    "fwd_sh2": _gc(8_000, 160, 96, sh=2),
+    "fwd_sh3": _gc(8_000, 160, 96, sh=3),
+    "aux_rgb": _gc(6_000, 160, 112),
+    "aux_sh2": _gc(6_000, 160, 112, sh=2, deep=True, grads=True),
+    "aux_sh3": _gc(6_000, 160, 112, sh=3),
+    "bwd_rgb": _gc(20_000, 160, 112, seed=11, deep=True, grads=True),
+    "bwd_sh2": _gc(9_000, 160, 112, seed=11, sh=2, deep=True, grads=True),
+    "bwd_sh3": _gc(9_000, 160, 112, seed=11, sh=3, deep=True, grads=True),
+    "bwd_wide": _gc(8_000, 192, 128, seed=47, sigma=48.0, grads=True),
+    "bwd_exp": _gc(5_000, 96, 80, seed=13, exp=True, grads=True),
+    "bwd_dist_sh2": _gc(6_000, 250, 186, seed=29, sh=2, opa=1.0, method="dist", dist=0.5, grads=True),
+    "aux3_rgb": _gc(5_000, 128, 96, seed=13, opa=-4.0, deep=True, grads=True),
+    "aux3_sh2": _gc(5_000, 128, 96, seed=13, sh=2, opa=-4.0, deep=True, grads=True),
+    "adam": _gc(6_000, 160, 112, seed=11),
+    "pose": _gc(5_000, 128, 96, deep=True, grads=True),
+    "pose_identity": _gc(5_000, 128, 96, seed=41),
+}
+_GENERAL_FRAMES = {}
+
+
+def general_case(key):
+    """-> (scene, general_camera, keyword arguments of OracleFrame) of GENERAL_CASES[key], fresh arrays each call."""
+    c = GENERAL_CASES[key]
+    scene, cam = aux_general_case(c["n"], c["W"], c["H"], seed=c["seed"], use_sh=bool(c["sh"]), sh_degree=c["sh"] or 2,
+                                  max_px_sigma=c["sigma"])
+    if c["opa"]:
+        scene.opa += np.float32(c["opa"])
+    of_kw = {}
+    if c["exp"]:
+        scene.scale = np.log(np.abs(scene.scale) + 1e-4).astype(np.float32)
+        of_kw["scale_activation"] = "exp"
+    if c["method"] != "prob2":
+        of_kw.update(tile_culling_method=c["method"], dist_thresh=c["dist"])
+    return scene, cam, of_kw
+
+
+def general_frame(key):
+    """-> (scene, camera, OracleFrame) of GENERAL_CASES[key], computed once per process and shared: read only."""
+    if key not in _GENERAL_FRAMES:
+        scene, cam, of_kw = general_case(key)
+        _GENERAL_FRAMES[key] = (scene, cam, OracleFrame(scene, cam, **of_kw))
+    return _GENERAL_FRAMES[key]
+
+
 def robust_aux_grads(of, rng, image=True):
     """White-noise dL/dimage [H,W,3] (zeros if not ``image``), dL/ddepth, dL/dalpha [H,W] from ``rng`` (a seed or a numpy
     Generator), all three zeroed on the pixels whose early-stop decision is not robust in fp32

@@ -37,9 +37,12 @@ def small_case(n=20000, W=320, H=200, seed=7, use_sh=False):
 
 # ------------------------------------------------------------------ K1 / K2 / legacy
 def test_global_culling_forward_bit_exact(gpu):
+    check_global_culling_forward(gpu, *small_case())
+
+
+def check_global_culling_forward(gpu, scene, cam):
     import gaussian
 
-    scene, cam = small_case()
     qn, sn = activate(scene)
     grid, hw, hh, _ = frame_scalars(cam)
     rp, rc, mk = oracle.global_culling(scene.pos, qn, sn, cam.rot, cam.tran, cam.near, hw, hh)
@@ -56,9 +59,13 @@ def test_global_culling_forward_bit_exact(gpu):
 
 
 def test_global_culling_backward(gpu):
+    check_global_culling_backward(gpu, *small_case())
+
+
+def check_global_culling_backward(gpu, scene, cam):
+    """-> {name: worst err / tol}"""
     import gaussian
 
-    scene, cam = small_case()
     qn, sn = activate(scene)
     grid, hw, hh, _ = frame_scalars(cam)
     _, _, mk = oracle.global_culling(scene.pos, qn, sn, cam.rot, cam.tran, cam.near, hw, hh)
@@ -73,19 +80,25 @@ def test_global_culling_backward(gpu):
     # product taken between magnitudes, oracle.global_culling_backward_scale) -- ~16 fp32 ulp of what is summed
     S = oracle.global_culling_backward_scale(scene.pos, qn, sn, cam.rot, cam.tran, np.abs(gop),
                                              np.abs(goc).reshape(-1, 4), mk)
+    report = {}
     for o, r, sc, name in zip(outs, ref, S, ("pos", "quat", "scale")):
         o = o.cpu().numpy()
         assert np.all(o[mk == 0] == 0), name
         ok, worst, where, _ = grad_close(o, r, sc, rtol=1e-5, kappa=2e-6)
         assert ok, (name, "worst err/tol", worst, "at", where, float(o[where]), float(r[where]), float(sc[where]))
+        report[name] = round(worst, 3)
+    return report
 
 
 def test_world2camera_and_jacobian(gpu):
+    check_world2camera_and_jacobian(gpu, small_case()[1])
+
+
+def check_world2camera_and_jacobian(gpu, cam):
     import gaussian
 
     rng = np.random.default_rng(3)
     pos = rng.normal(size=(1001, 3)).astype(np.float32) + np.array([0, 0, 4], np.float32)
-    _, cam = small_case()
     res = torch.zeros(1001, 3, device=gpu)
     gaussian.world2camera(dev(pos, gpu), dev(cam.rot, gpu), dev(cam.tran, gpu), res)
     ref = oracle.world2camera(pos, cam.rot, cam.tran)
@@ -124,9 +137,12 @@ def _projected(scene, cam):
 
 @pytest.mark.parametrize("method", [2, 1, 0])
 def test_calc_tile_list_and_gather(gpu, method):
+    check_calc_tile_list_and_gather(gpu, *small_case(n=3000 if method != 2 else 20000, W=160, H=96), method)
+
+
+def check_calc_tile_list_and_gather(gpu, scene, cam, method):
     import gaussian
 
-    scene, cam = small_case(n=3000 if method != 2 else 20000, W=160, H=96)
     grid, pos_i, cov = _projected(scene, cam)
     V, T = pos_i.shape[0], grid.n_tiles
     maxp = max(V // 20, 8)  # splatter.py:569
@@ -197,10 +213,14 @@ def _sorted_inputs(scene, cam, thresh=0.05):
 
 @pytest.mark.parametrize("use_sh", [False, True])
 def test_draw_forward_backward(gpu, use_sh):
+    scene, cam = small_case(n=12000, W=200, H=120, seed=5, use_sh=use_sh)
+    check_draw_forward_backward(gpu, _sorted_inputs(scene, cam), use_sh)
+
+
+def check_draw_forward_backward(gpu, of, use_sh):
+    """-> assert_rows_close's report"""
     from renderer import draw
 
-    scene, cam = small_case(n=12000, W=200, H=120, seed=5, use_sh=use_sh)
-    of = _sorted_inputs(scene, cam)
     grid, rays = of.grid, of.rays
     assert of.accum.max() > 0 and np.diff(of.accum).max() > 64  # multi-bucket tiles
     t = [dev(a, gpu).requires_grad_(True) for a in (of.s_pos, of.s_rgb, of.s_opa, of.s_cov.reshape(-1, 2, 2))]
@@ -217,7 +237,9 @@ def test_draw_forward_backward(gpu, use_sh):
                                       lefttop=rays.lefttop, vdx=rays.dx, vdy=rays.dy, with_scale=True)
     got = [x.grad.cpu().numpy() for x in t]
     assert np.all(got[0][:, 2] == 0)  # grad_pos z is never written
-    print("draw_backward rows", "sh" if use_sh else "rgb", assert_rows_close(got, ref, scale, f"use_sh={use_sh}"))
+    report = assert_rows_close(got, ref, scale, f"use_sh={use_sh}")
+    print("draw_backward rows", "sh" if use_sh else "rgb", report)
+    return report
 
 
 @pytest.mark.parametrize("cfg", ["cfg2", "cfg4"])

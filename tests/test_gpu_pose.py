@@ -105,8 +105,12 @@ def _flat(gp):
 # ---------------------------------------------------------------------------------------------------------------- 1. oracle
 @pytest.mark.parametrize("aux", [False, True])
 def test_pose_gradient_matches_fp64_oracle(gpu, aux):
-    scene, cam = case(5000, 128, 96, seed=31)
-    of = OracleFrame(scene, cam)
+    check_pose_gradient(gpu, *case(5000, 128, 96, seed=31), aux)
+
+
+def check_pose_gradient(gpu, scene, cam, aux, of=None):
+    """-> worst err / tol over the twelve components"""
+    of = OracleFrame(scene, cam) if of is None else of
     gimg, gd, ga = _random_grads(of, 37)
     n = scene.n
     # truth: the fp64 rows; the reference's own error: the fp32 oracle's rows, both through the same fp64 projection
@@ -137,6 +141,7 @@ def test_pose_gradient_matches_fp64_oracle(gpu, aux):
     err = np.abs(got - truth)
     assert np.all(err <= tol), (got, truth, err / np.maximum(S, 1e-30), tol / np.maximum(S, 1e-30))
     assert np.abs(truth).max() > 1e-3 * S.max()  # (a gradient that says something)
+    return float((err / tol).max())
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. identities

@@ -72,9 +72,10 @@ def test_depth_loss_matches_fp64(gpu, H, W, mode):
 
 
 # ---------------------------------------------------------------------------------- 2. fused = unfused, bit for bit
-def _fused_pair(gpu, scene, cam, stat, with_image, steps, max_pairs, seed=5, probe=None):
+def _fused_pair(gpu, scene, cam, stat, with_image, steps, max_pairs, seed=5, probe=None, aux=True):
     """`steps` optimizer steps from identical copies through backward_adam(aux) and through backward + FusedAdam.step, random
-    dL/dimage (or None), dL/ddepth, dL/dalpha per step.  Returns the two end states."""
+    dL/dimage (or None), dL/ddepth, dL/dalpha per step.  Returns the two end states.  ``aux=False``: plain frames, dL/dimage
+    alone, through gs_frame_backward_adam."""
     H, W = cam.height, cam.width
     start = to_torch(scene, gpu)
     lrs = [b * 0.5 for b in base_lrs(TrainOptions())]
@@ -85,18 +86,19 @@ def _fused_pair(gpu, scene, cam, stat, with_image, steps, max_pairs, seed=5, pro
         opt = FusedAdam(flat, lrs, grad_stat=stat)
         r = FrameRenderer(gpu, max_pairs=max_pairs, training=True, auto_grow=True)
         for _ in range(steps):
-            r.forward(*flat.params, cam, aux=True)
+            r.forward(*flat.params, cam, aux=aux)
             assert not r.last_frame_overflowed(wait=True)
             if probe is not None:
                 probe(r)
             gimg = torch.randn(H, W, 3, device=gpu, generator=gen) if with_image else None
             gdep = torch.randn(H, W, device=gpu, generator=gen) * 0.1
             galp = torch.randn(H, W, device=gpu, generator=gen)
+            maps = dict(grad_depth=gdep, grad_alpha=galp) if aux else {}
             opt.skip_flag = r.overflow_flag()
             if fuse:
-                r.backward_adam(gimg, opt.fused_descriptor(), grad_depth=gdep, grad_alpha=galp)
+                r.backward_adam(gimg, opt.fused_descriptor(), **maps)
             else:
-                r.backward(gimg, out=flat.grads, grad_depth=gdep, grad_alpha=galp)
+                r.backward(gimg, out=flat.grads, **maps)
                 opt.step()
         assert opt.step_count == steps
         out.append((flat.flat_param.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(),

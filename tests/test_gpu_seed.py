@@ -14,7 +14,7 @@ from gs_colmap import initialize_sh
 from gs_frame import FrameRenderer
 from gs_scene import make_camera, make_scene
 from gs_seed import DEFAULTS, seed_apply, seed_classify, seed_from_depth, seed_options
-from gs_testutil import to_torch
+from gs_testutil import general_rotation, to_torch
 from gs_train import ImageLoss, TrainOptions, Trainer
 from seed_ref import gaussians, lattice, select
 
@@ -22,8 +22,10 @@ pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -24  # one fp32 rounding, relative
 
 
-def _camera(W, H, yaw=17.0, tran=(0.4, -0.3, 0.8)):
+def _camera(W, H, yaw=17.0, tran=(0.4, -0.3, 0.8), general=False):
     cam = make_camera(W, H, yaw_deg=yaw)
+    if general:  # gs_testutil.general_camera's rotation: no entry of rot zero, one, or equal in magnitude to another
+        cam.rot = general_rotation(35.0, -12.0, 10.0)
     cam.focal_y = 0.8 * W  # fx != fy
     cam.tran = np.asarray(tran, np.float32)
     return cam
@@ -70,8 +72,18 @@ def test_seed_matches_the_restatement(gpu, H, W, stride):
       colour logits <= (2 + 4 |logit|) x 2^-24: 1 - c and the quotient (the logarithm turns their relative error into an absolute
                 one), logf within 2 ulp of its result.
     quat exact.  Measured maxima on an MI355X, as shares of the bounds: profiles/seed_rgbd.txt."""
+    _check_seed_matches_the_restatement(gpu, H, W, stride, _camera(W, H))
+
+
+def test_seed_matches_the_restatement_under_a_general_rotation(gpu):
+    """The same statement at 187 x 250, stride 2, with a rotation about no single axis: under test_seed_matches_the_restatement's
+    yaw-only matrix (four exact zeros, an exact one) rot^T and rot give the same y row, and a kernel that reads one entry of
+    rot for another can place every Gaussian where it belongs."""
+    _check_seed_matches_the_restatement(gpu, 187, 250, 2, _camera(250, 187, general=True))
+
+
+def _check_seed_matches_the_restatement(gpu, H, W, stride, cam):
     D, A, z, img = _inputs(H, W, seed=H + W + stride)
-    cam = _camera(W, H)
     at, fr, sf, p0 = 0.5, 0.1, 0.7, 0.9
     sel, meas = select(z, D, A, stride, at, fr)
     n_sel, n_meas = int(sel.sum()), int(meas.sum())

@@ -11,7 +11,7 @@ import pytest
 import oracle
 from oracle import ref
 from gs_scene import make_camera, make_scene
-from gs_testutil import OracleFrame, activate, frame_scalars, rel_err
+from gs_testutil import OracleFrame, activate, frame_scalars, general_camera, rel_err
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_live.npz")
 RECORD = None  # a dict while tests/golden/make_golden.py::ref_live records the fixture
@@ -52,6 +52,56 @@ def test_oracle_vs_reference_kernels_fresh_seed(seed):
     img, = reference(f"draw_seed{seed}", lambda: ref.draw(of.s_pos, of.s_rgb, of.s_opa, of.s_cov, of.accum, grid.padded_height,
                                                          grid.padded_width, grid.focal_x, grid.focal_y, fast=True))
     assert np.array_equal(img.view(np.uint32), of.padded.view(np.uint32))
+
+
+@pytest.mark.parametrize("use_sh", [False, True])
+def test_oracle_vs_reference_kernels_general_camera(use_sh):
+    """The yardstick itself off the y axis: every other comparison of the oracle with the reference's kernels runs under a
+    camera yawed by at most 3 degrees with fx = fy, whose rotation has four exact zeros and an exact one.  Under
+    gs_testutil.general_camera (roll, pitch and yaw, fx != fy: no entry of rot and neither focal length can stand in for
+    another) the oracle's cull + project and its backward equal the reference kernels' bit for bit, as does the image drawn
+    with that camera's ray basis; the compositing backward agrees to 1e-6 inside one shared-memory chunk (the reference
+    is not defined beyond: test_reference_backward_defect_between_chunks_is_real)."""
+    cam = general_camera(80, 64)
+    scene = make_scene(1500, 80, 64, seed=33, use_sh=use_sh)
+    tag = f"general_sh{int(use_sh)}"
+    qn, sn = activate(scene)
+    grid, hw, hh, _ = frame_scalars(cam)
+    a = oracle.global_culling(scene.pos, qn, sn, cam.rot, cam.tran, cam.near, hw, hh)
+    b = reference(f"cull_{tag}", lambda: ref.global_culling(scene.pos, qn, sn, cam.rot, cam.tran, cam.near, hw, hh))
+    assert np.array_equal(a[2], b[2]) and 0.3 * scene.n < a[2].sum() < scene.n
+    assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32))
+    assert np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
+    rng = np.random.default_rng(3)
+    gop = rng.normal(size=(scene.n, 3)).astype(np.float32)
+    goc = rng.normal(size=(scene.n, 2, 2)).astype(np.float32)
+    ga = oracle.global_culling_backward(scene.pos, qn, sn, cam.rot, cam.tran, gop, goc, a[2])
+    gb = reference(f"cull_backward_{tag}", lambda: ref.global_culling_backward(scene.pos, qn, sn, cam.rot, cam.tran, gop,
+                                                                               goc, a[2]))
+    for x, y, name in zip(ga, gb, ("pos", "quat", "scale")):
+        assert np.array_equal(np.asarray(x, np.float32).view(np.uint32), y.view(np.uint32)), name
+        assert np.abs(y).max() > 0
+    of = OracleFrame(scene, cam)
+    r = of.rays
+    kw = dict(use_sh=use_sh, fast=True, rays_o=r.rays_o, lefttop=r.lefttop, vdx=r.dx, vdy=r.dy)
+    assert 64 < np.diff(of.accum).max() <= 1200
+    img, = reference(f"draw_{tag}", lambda: ref.draw(of.s_pos, of.s_rgb, of.s_opa, of.s_cov, of.accum, grid.padded_height,
+                                                     grid.padded_width, grid.focal_x, grid.focal_y, **kw))
+    assert np.array_equal(img.view(np.uint32), of.padded.view(np.uint32)) and img.max() > 0.1
+    # the compositing backward where the reference is well defined: one chunk per tile, no pixel stops
+    small = make_scene(400, 80, 64, seed=34, use_sh=use_sh)
+    small.opa -= 3.0
+    of = OracleFrame(small, cam)
+    r = of.rays
+    kw = dict(use_sh=use_sh, fast=True, rays_o=r.rays_o, lefttop=r.lefttop, vdx=r.dx, vdy=r.dy)
+    assert 32 < np.diff(of.accum).max() <= 160
+    g = rng.normal(size=of.padded.shape).astype(np.float32)
+    da = oracle.draw_backward(of.s_pos, of.s_rgb, of.s_opa, of.s_cov, of.accum, of.padded, g, grid.focal_x, grid.focal_y,
+                              **kw)
+    db = reference(f"draw_backward_{tag}", lambda: ref.draw_backward(of.s_pos, of.s_rgb, of.s_opa, of.s_cov, of.accum,
+                                                                     of.padded, g, grid.focal_x, grid.focal_y, **kw))
+    for x, y, name in zip(da, db, ("pos", "rgb", "opa", "cov")):
+        assert rel_err(x, y) < 1e-6, (name, rel_err(x, y))
 
 
 def test_reference_backward_defect_between_chunks_is_real():

@@ -352,7 +352,9 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
 // arrive in no spatial order: measured, 92.7 against 79 us), so this kernel COMPACTS:
 //   phase A, every Gaussian of the slice: position and scale only (24 of 56 bytes), the exact frustum test, and a
 //     conservative occlusion test (occluded_everywhere) -- ~120 instructions; the survivors' indices are queued in LDS;
-//   phase B, full waves of survivors: the unchanged project_one + the trimmed strip count of the culled frame.
+//   phase B, full waves of survivors: the unchanged project_one + the trimmed strip walk of the culled frame, which counts
+//     every level-1 entry and stores it, with its strip and its rank in the slice's run of that strip, in the slice's
+//     staging region: the level-1 placement of this pass is a permutation of the staged entries (strip_bin.hip).
 // A Gaussian that fails the occlusion test would have lost every pair to the trimming of walk_strips<.., true>: the
 // emitted lists are exactly those of the lane-masked kernel, and the frame's second pass (a tile ran past its cut) starts
 // from a gated re-run of frame_project_count_kernel, which rewrites records, rectangles and the strip table untrimmed.
@@ -412,10 +414,10 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
     unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
-    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, uint4 *__restrict__ surv,
-    uint32_t *__restrict__ slice_nsurv) {
+    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, unsigned long long *__restrict__ stage_ent,
+    uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
     extern __shared__ unsigned long long s_hist[];  // [NS] entries << 32 | pairs of this slice, then the pyramid, then the queue
-    __shared__ uint32_t s_acc[2], s_qn, s_ns;
+    __shared__ uint32_t s_acc[2], s_qn, s_ne;
     if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
         tile_order_workgroup(tile_cost, n_tiles, tile_order);
         return;
@@ -460,7 +462,10 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
             if (t0 + k * STRIP_THREADS < st0 * SG.nty) s_cut[t0 + k * STRIP_THREADS] = v[k];
     }
     if (threadIdx.x < 2) s_acc[threadIdx.x] = 0;
-    if (threadIdx.x == 2) s_ns = 0;
+    if (threadIdx.x == 2) s_ne = 0;
+    // this slice's region of the entry staging (gs_frame_layout.h, gs_cull_stage_cap): `ecap` entries and their tags
+    unsigned long long *const ent = stage_ent + (size_t)slice * ecap;
+    uint32_t *const tag = stage_tag + (size_t)slice * ecap;
     auto build = [&](uint32_t *dst, uint32_t dw, uint32_t dh, const uint32_t *src, uint32_t sst, uint32_t sw, uint32_t sh) {
         __syncthreads();
         for (uint32_t t = threadIdx.x; t < dw * dh; t += STRIP_THREADS) {
@@ -503,7 +508,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
                     // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
                     if ((s[0] + s[1] + s[2] < 3.0e38f) && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
                         // behind every cut it can reach, or beside the grid: visible, no tile.  NOTHING is written for it (nor
-                        // for a Gaussian outside the frustum): the scatter of this pass reads the survivor list, the second
+                        // for a Gaussian outside the frustum): this pass places the entries phase B stages, the second
                         // pass re-projects everything -- rects[] of a culled frame is only fresh for the survivors
                         acc_vis += 1;
                     } else {
@@ -588,21 +593,23 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
             if (k < nq) rc = project_one(cur, pid, P, rec_geom, nullptr, rects, vis, cxy);
             acc_cnt += rc.w;
             acc_vis += vis;
-            {   // survivors that touch a tile: (rectangle, depth, Gaussian) appended to the slice's compact list
-                const bool has = rc.w != 0;
-                const unsigned long long hb = __ballot(has);
-                if (hb) {  // (uniform per wave)
-                    uint32_t wbase = 0;
-                    if (lane == 0) wbase = atomicAdd(&s_ns, (uint32_t)__popcll(hb));
-                    wbase = __shfl(wbase, 0, 64);
-                    if (has)
-                        surv[g0 + wbase + (uint32_t)__popcll(hb & ((1ull << lane) - 1ull))] =
-                            make_uint4(rc.x, rc.y, rc.z, (uint32_t)pid);
-                }
-            }
+            // Every entry is counted AND kept: the LDS add returns the entry's rank inside this slice's run of its strip,
+            // which with the column scan is its final position -- the permutation that follows (strip_bin.hip) neither walks
+            // the rectangle nor reads the cut table again.  Slot in the slice's staging region: the lanes that arrive
+            // together claim consecutive slots with one LDS add (they are whoever the walk has active here: the lowest of
+            // them adds).  An entry beyond the region is not stored; the slice is withdrawn below.
             walk_strips<false, true>(rc, pid, SG, cxy, GsDistCull{},
-                                     [&](uint32_t strip, uint32_t, uint32_t, uint32_t np) {
-                                         atomicAdd(&s_hist[strip], (1ull << 32) | np);
+                                     [&](uint32_t strip, uint32_t lo32, uint32_t d, uint32_t np) {
+                                         const uint32_t rank = (uint32_t)(atomicAdd(&s_hist[strip], (1ull << 32) | np) >> 32);
+                                         const unsigned long long act = __ballot(true);
+                                         uint32_t wbase = 0;
+                                         if (lane == __ffsll((long long)act) - 1) wbase = atomicAdd(&s_ne, (uint32_t)__popcll(act));
+                                         wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+                                         const uint32_t slot = wbase + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+                                         if (slot < ecap) {
+                                             ent[slot] = ((unsigned long long)d << 32) | lo32;
+                                             tag[slot] = strip_tag(strip, rank);
+                                         }
                                      },
                                      s_cut);
             cur = nxt;
@@ -616,12 +623,17 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
         atomicAdd(&s_acc[1], acc_vis);
     }
     __syncthreads();
+    // A slice whose entries did not fit its staging region publishes NO entries (an empty table row: nothing downstream
+    // of this pass reads a slot that was not written) and marks itself; the permutation raises counters[GS_CNT_RANPAST] for
+    // it, and the gated second pass renders the frame from the full lists.
+    const uint32_t ne = s_ne;
+    const bool fits = ne <= ecap;
     unsigned long long *row = table + (size_t)slice * SG.NS;
-    for (uint32_t t = threadIdx.x; t < SG.NS; t += STRIP_THREADS) row[t] = s_hist[t];
+    for (uint32_t t = threadIdx.x; t < SG.NS; t += STRIP_THREADS) row[t] = fits ? s_hist[t] : 0ull;
     if (threadIdx.x == 0) {
         slice_pairs[slice] = s_acc[0];
         slice_vis[slice] = s_acc[1];
-        slice_nsurv[slice] = s_ns;
+        slice_entries[slice] = fits ? ne : GS_STAGE_OVER;
     }
 }
 
@@ -782,8 +794,9 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
             hipLaunchKernelGGL(frame_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, f->pos,
                                (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, ws.rects,
                                plan.per_slice, SG, nsl, table, ws.slice_pairs, ws.slice_vis, ws.tile_cost,
-                               (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), qcap, stash_cap, ws.surv,
-                               ws.slice_nsurv);
+                               (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), qcap, stash_cap,
+                               (unsigned long long *)ws.keys_b, ws.vals_b, gs_cull_stage_cap(f->max_pairs, plan.slices),
+                               ws.slice_entries);
             GS_CHECK_LAUNCH();
             return 0;
         }

@@ -697,6 +697,23 @@ extern "C" int gs_frame_debug_rects(const gs_frame *f, const uint32_t **rects) {
     return 0;
 }
 
+extern "C" int gs_frame_debug_cull_stage(const gs_frame *f, const uint64_t **entries, const uint32_t **tags,
+                                         const uint32_t **slice_entries, int32_t *slices, int64_t *cap) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG(entries && tags && slice_entries && slices && cap, "null pointer");
+    GS_CHECK_ARG(effective_sort_mode(f) == 2 && gs_frame_occlusion_cull(f), "not an occlusion-culled frame");
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
+    gs_frame_geom G = gs_frame_geometry(f);
+    const gs_strip_plan plan = gs_strip_plan_for(f->N, G.ntx, G.nty);
+    *entries = ws.keys_b;
+    *tags = ws.vals_b;
+    *slice_entries = ws.slice_entries;
+    *slices = (int32_t)plan.slices;
+    *cap = gs_cull_stage_cap(f->max_pairs, plan.slices);
+    return 0;
+}
+
 extern "C" int gs_frame_debug_views(const gs_frame *f, const uint64_t **sorted_keys, const uint32_t **sorted_ids,
                                     const int32_t **tile_ranges, const float **rec_geom, const float **rec_cov,
                                     const float **rec_color, const uint32_t **tiles_touched) {

@@ -94,9 +94,8 @@ static inline bool gs_frame_long_lists(const gs_frame *f, int n_tiles) {
 // from the full lists.  No host synchronisation, the image is exact either way.  Not for training frames (the backward
 // owns the full emission order), frames that export their sorted keys, the "dist" listing, segmented long lists, or
 // the table / radix variants.
-// LDS a culled frame's level-1 kernels add to their strip tables: the cuts, every tile row padded to whole strips --
-static inline size_t gs_cull_lds_bytes(int64_t ns) { return (size_t)ns * 4 * 8; }
-// -- and, in the project stage (frame_project_cull_count_kernel), three more levels of the cut pyramid behind them
+// LDS the project stage of a culled frame (frame_project_cull_count_kernel) adds to its strip table: the cuts, every tile row
+// padded to whole strips, and three more levels of the cut pyramid behind them
 static inline size_t gs_cull_pyramid_bytes(int ntx, int nty) {
     const int nsx = (ntx + 7) / 8;  // (GS_STRIP_W, defined below)
     size_t b = (size_t)nsx * 8 * nty * 4;
@@ -107,6 +106,19 @@ static inline size_t gs_cull_pyramid_bytes(int ntx, int nty) {
     }
     return b;
 }
+// Staging of the first pass's level-1 entries.  The project stage of a culled frame stores every entry it counts (8 bytes)
+// with a 4-byte tag (strip, rank in the slice's run of the strip: strip_common.h); a permutation puts them in strip order
+// (strip_bin.hip).  The staging borrows two buffers a culled frame has no other use for until the permutation has read
+// them -- keys_b (such a frame exports no sorted keys; the per-tile sort's scratch) for the entries, vals_b (the big-list
+// sort's scratch) for the tags -- cut into one region of gs_cull_stage_cap entries per slice: slice s owns
+// [s x cap, (s + 1) x cap) of both.  A frame that fits its workspace has at most max_pairs entries in all; a slice with more
+// entries than its region stores none beyond it, publishes an empty row of the strip table and GS_STAGE_OVER as its count,
+// and the permutation raises counters[GS_CNT_RANPAST]: the gated second pass renders the frame from the full lists.
+static inline uint32_t gs_cull_stage_cap(int64_t max_pairs, uint32_t slices) {
+    const int64_t c = max_pairs / (int64_t)(slices ? slices : 1);
+    return c < 0x7fffffff ? (uint32_t)c : 0x7fffffffu;
+}
+#define GS_STAGE_OVER 0xffffffffu
 #define GS_NO_CUT 0xffffffffu
 #define GS_CUT_MARGIN 0.0625f
 // GS_FRAME_CULL_DILATE (a camera that moved a little since the table was recorded): a tile's cut is the deepest cut of its
@@ -182,13 +194,12 @@ static inline bool gs_frame_occlusion_cull(const gs_frame *f) {
           gs_frame_uses_strips(f)))
         return false;
     // the level-1 kernels keep the per-tile cuts in LDS next to their strip tables (project + count: histogram, cut pyramid
-    // and a queue of up to 16,384 survivors; scatter: cursors + cuts + a staging buffer worth having): 1080p = 70 KiB of
-    // 160; beyond ~1,900 strips (~15 k tiles: 4K images) the frame is not culled
+    // and a queue of up to 16,384 survivors): 1080p = 70 KiB of 160; beyond ~1,900 strips (~15 k tiles: 4K images) the frame
+    // is not culled
     const int ntx = (f->width + GS_TILE - 1) / GS_TILE, nty = (f->height + GS_TILE - 1) / GS_TILE;
     const int64_t ns = (int64_t)((ntx + GS_STRIP_W - 1) / GS_STRIP_W) * nty;
     const int64_t room = (int64_t)GS_BIN_LDS_BYTES - 8 * 4096;
-    return 8 * ns + (int64_t)gs_cull_pyramid_bytes(ntx, nty) + 2 * 16384 + 16 <= room &&
-           8 * ns + (int64_t)gs_cull_lds_bytes(ns) + 8 * 4096 <= room;
+    return 8 * ns + (int64_t)gs_cull_pyramid_bytes(ntx, nty) + 2 * 16384 + 16 <= room;
 }
 // Table variant (small scenes: a frame is a chain of dependent launches of ~7 us each): the per-(slice, tile) count
 // (bin_count_kernel) is taken inside the project stage as well -- five launches per frame instead of six.
@@ -290,8 +301,7 @@ struct gs_frame_ws {
     float4 *rec_conic;             // (A, B, C, -)
     uint32_t *tiles_touched;       // [N]
     uint4 *rects;                  // [N] (y0 | y1 << 16, x0 | x1 << 16, depth bits, tiles touched): all the binning needs
-    uint4 *surv;                   // [N] inference workspaces: compacted survivor rectangles of an occlusion-culled frame
-    uint32_t *slice_nsurv;         // [slices] their count per slice
+    uint32_t *slice_entries;       // [slices] occlusion-culled frames, first pass: level-1 entries every slice staged (below)
     uint32_t *block_sums;          // [ceil(N/256)] pairs emitted by each 256-Gaussian block
     uint32_t *block_vis;           // [ceil(N/256)] visible Gaussians of each block
     uint32_t *block_offsets;       // [ceil(N/256)]
@@ -379,11 +389,7 @@ static inline gs_frame_ws gs_frame_carve(void *base, int64_t N, int64_t max_pair
     ws.rec_conic = ws.rec_geom ? ws.rec_geom + 3 : nullptr;
     ws.tiles_touched = (uint32_t *)take(sizeof(uint32_t) * N);
     ws.rects = (uint4 *)take(sizeof(uint4) * N);
-    // occlusion-culled inference frames (first pass): the rectangles of the Gaussians that were projected AND touch a tile,
-    // compacted per slice of the Gaussian array -- (y range, x range, depth bits, Gaussian) at [slice x per_slice, +
-    // slice_nsurv[slice]) -- what the level-1 scatter of such a frame reads instead of all N rectangle records
-    ws.surv = (uint4 *)take(training ? 0 : sizeof(uint4) * N);
-    ws.slice_nsurv = (uint32_t *)take(sizeof(uint32_t) * GS_BIN_MAX_SLICES);
+    ws.slice_entries = (uint32_t *)take(sizeof(uint32_t) * GS_BIN_MAX_SLICES);
     ws.block_sums = (uint32_t *)take(sizeof(uint32_t) * nblk);
     ws.block_vis = (uint32_t *)take(sizeof(uint32_t) * nblk);
     ws.block_offsets = (uint32_t *)take(sizeof(uint32_t) * nblk);

@@ -19,6 +19,9 @@
 //                            bases and the frame counters), places its entries by strip in an LDS staging buffer (ds_add_rtn cursors)
 //                            and copies each (slice, strip) run to its final place with consecutive lanes: a run
 //                            is ~15 entries = one 128-byte line, written by one instruction.
+//                            First pass of an occlusion-culled frame (gs_frame_layout.h): the project stage has staged
+//                            every entry with its strip and its rank in the (slice, strip) run, so the STAGED variant of
+//                            the kernel is a permutation -- same bases, no rectangle, no cut table, no walk.
 //   level 2 (tile_sort.hip, strip_sort_kernel): one workgroup per half strip (four tiles) reads the strip's entries
 //     (contiguous), expands them into its tiles' pair lists INSIDE LDS, sorts every list by (depth_bits, gaussian) there
 //     and writes only the sorted ids: the unsorted pairs never exist in HBM (table variant: 8 B written + 8 B read per
@@ -116,53 +119,52 @@ __device__ __forceinline__ uint32_t strip_block_excl_scan(uint32_t v, uint32_t *
     return off + incl - v;
 }
 
+// STAGED (first pass of an occlusion-culled frame): the slice's entries lie in its staging region -- `ecap` 8-byte entries in
+// stage_ent and their tags in stage_tag from slice x ecap, slice_entries[slice] of them (GS_STAGE_OVER: the slice did not fit
+// and published none; the frame is rendered again by the second pass, which slice 0 arranges by raising
+// counters[GS_CNT_RANPAST]) -- and entry i belongs at s_gd[strip of its tag] + rank of its tag.
 // Dynamic LDS: s_cur[NS] (staging cursor of every strip, ends up at the END of the strip's run), s_gd[NS] (final
 // index of staging slot 0 of the strip's run, i.e. entry i of the staging buffer belongs at s_gd[strip] + i), then
 // `cap` staged entries.  Entries beyond `cap` (a slice that does not fit) are stored straight to their final place.
-template <bool DIST>
+template <bool DIST, bool STAGED = false>
 __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
     const uint4 *__restrict__ rects, const float4 *__restrict__ rec_geom, GsDistCull D, int64_t n, uint32_t per_slice,
     gs_strip_geom SG, uint32_t S, uint32_t cap, const unsigned long long *__restrict__ scan,
     const unsigned long long *__restrict__ strip_tot, unsigned long long *__restrict__ strip_base,
     const uint32_t *__restrict__ slice_pairs, const uint32_t *__restrict__ slice_vis, uint64_t max_pairs,
     unsigned long long *__restrict__ out, uint32_t *__restrict__ pair_offsets,
-    unsigned long long *__restrict__ counters, const uint32_t *__restrict__ cut, uint32_t n_tiles,
-    const unsigned long long *__restrict__ gate, const uint4 *__restrict__ surv, const uint32_t *__restrict__ slice_nsurv) {
+    unsigned long long *__restrict__ counters, const unsigned long long *__restrict__ gate,
+    const unsigned long long *__restrict__ stage_ent, const uint32_t *__restrict__ stage_tag, uint32_t ecap,
+    const uint32_t *__restrict__ slice_entries) {
+    static_assert(!STAGED || !DIST, "the occlusion cull is not combined with the \"dist\" listing");
     extern __shared__ unsigned long long s_dyn[];
     if (gate && *gate == 0) return;  // (see strip_colscan_kernel)
     uint32_t *s_cur = reinterpret_cast<uint32_t *>(s_dyn), *s_gd = s_cur + SG.NS;
     unsigned long long *s_stage = s_dyn + SG.NS;  // 2 NS uint32 = NS uint64
-    // occlusion cuts (the same table the project stage counted with): staged in LDS behind the `cap` staged entries, every tile row
-    // padded to whole strips (walk_strips<.., true>)
-    uint32_t *s_cut = reinterpret_cast<uint32_t *>(s_stage + cap);
-    if (cut) {
-        // (eight loads in flight per thread -- one at a time, each waited for, cost eight load latencies; barriers follow below)
-        const uint32_t stride = SG.nsx * GS_STRIP_W;
-        for (uint32_t t0 = threadIdx.x; t0 < stride * SG.nty; t0 += 8 * STRIP_THREADS) {
-            uint32_t v[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) {
-                const uint32_t t = t0 + k * STRIP_THREADS, iy = t / stride, ix = t - iy * stride;
-                const bool in = iy < SG.nty && ix < SG.ntx;
-                v[k] = cut[in ? iy * SG.ntx + ix : 0u];
-                v[k] = in ? v[k] : GS_NO_CUT;
-            }
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k)
-                if (t0 + k * STRIP_THREADS < stride * SG.nty) s_cut[t0 + k * STRIP_THREADS] = v[k];
-        }
-    }
     __shared__ uint32_t s_wave[STRIP_THREADS / 64];
     __shared__ unsigned long long s_wave64[4 * (STRIP_THREADS / 64)];
     const uint32_t slice = strip_slice_of_block(blockIdx.x, gridDim.x);
-    // `surv` (first pass of an occlusion-culled frame): the slice's rectangles come from the compact list the project stage
-    // left -- (y range, x range, depth, Gaussian) of the Gaussians it projected that touch a tile, slice_nsurv[slice] of them
-    // at the slice's own offset -- instead of from all per_slice rectangle records, most of which were not even written
-    const uint32_t count = surv ? slice_nsurv[slice] : per_slice;
-    const SliceLoader L = {surv ? surv : rects, rec_geom, n, (int64_t)slice * per_slice, count};
+    const SliceLoader L = {rects, rec_geom, n, (int64_t)slice * per_slice, per_slice};
     uint4 rc[STRIP_PF];
+    // STAGED: the region's first slots are requested whatever they hold (inside the region: readable), their count with them
+    const unsigned long long *ent = stage_ent + (size_t)slice * ecap;
+    const uint32_t *tag = stage_tag + (size_t)slice * ecap;
+    unsigned long long pe[STRIP_PF];
+    uint32_t pt[STRIP_PF], ne = 0;
 #pragma unroll
-    for (int k = 0; k < STRIP_PF; ++k) rc[k] = L.rect(k * STRIP_THREADS);  // in flight during the set-up below
+    for (int k = 0; k < STRIP_PF; ++k) {  // in flight during the set-up below
+        if constexpr (STAGED) {
+            const uint32_t i = k * STRIP_THREADS + threadIdx.x;
+            pe[k] = i < ecap ? ent[i] : 0ull;
+            pt[k] = i < ecap ? tag[i] : 0u;
+        } else {
+            rc[k] = L.rect(k * STRIP_THREADS);
+        }
+    }
+    if constexpr (STAGED) {
+        ne = slice_entries[slice];
+        ne = ne == GS_STAGE_OVER ? 0u : (ne < ecap ? ne : ecap);
+    }
     // ---- strip totals -> entry / pair base of every strip, frame totals (every workgroup computes all of them)
     const uint32_t per = (SG.NS + STRIP_THREADS - 1) / STRIP_THREADS;
     const uint32_t t0 = threadIdx.x * per < SG.NS ? threadIdx.x * per : SG.NS, t1 = t0 + per < SG.NS ? t0 + per : SG.NS;
@@ -224,6 +226,9 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
     }
     const bool overflow = M > max_pairs || R > max_pairs;  // not enough room: the frame is left empty, the true count reported
     if (slice == 0) {
+        // STAGED: a slice that did not fit its staging region asks for the second pass, as a tile that runs past its cut does
+        unsigned long long redo = 0;
+        if constexpr (STAGED) redo = __syncthreads_or(threadIdx.x < S && slice_entries[threadIdx.x] == GS_STAGE_OVER) ? 1 : 0;
         for (uint32_t t = t0; t < t1; ++t) {
             const unsigned long long x = t == t0 ? tot0 : strip_tot[t];
             strip_base[t] = overflow ? 0ull : (be << 32) | bp;  // both < 2^30 when the frame fits
@@ -242,10 +247,37 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
             counters[GS_CNT_EXCESS] = 0;   // ... and the pairs beyond the first GS_LONG_MIN of their tile's list
             counters[GS_CNT_MAXWALK] = 0;  // raster_forward_kernel: longest walk a tile's wave made, steps beyond GS_LONG_MIN
             counters[GS_CNT_EXCESS_WALK] = 0;
-            if (!gate) counters[GS_CNT_RANPAST] = 0;  // raised by a tile that ran past its occlusion cut (raster_fwd.hip)
+            if (!gate) counters[GS_CNT_RANPAST] = redo;  // raised by a tile that ran past its occlusion cut (raster_fwd.hip)
         }
     }
     if (overflow) return;  // uniform
+    if constexpr (STAGED) {
+        // ---- final index of the first entry of this slice's run of every strip, then the permutation
+        uint32_t eb = (uint32_t)be;
+        for (uint32_t t = t0; t < t1; ++t) {
+            const unsigned long long tot = t == t0 ? tot0 : strip_tot[t], a = t == t0 ? a0 : row[t];
+            s_gd[t] = eb + (uint32_t)(a >> 32);
+            eb += (uint32_t)(tot >> 32);
+        }
+        __syncthreads();
+        for (uint32_t base = 0; base < ne; base += STRIP_PF * STRIP_THREADS) {  // uniform trip count
+            unsigned long long ce[STRIP_PF];
+            uint32_t ct[STRIP_PF];
+#pragma unroll
+            for (int k = 0; k < STRIP_PF; ++k) {
+                ce[k] = pe[k];
+                ct[k] = pt[k];
+                const uint32_t i = base + (STRIP_PF + k) * STRIP_THREADS + threadIdx.x;
+                pe[k] = i < ne ? ent[i] : 0ull;
+                pt[k] = i < ne ? tag[i] : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < STRIP_PF; ++k)
+                if (base + k * STRIP_THREADS + threadIdx.x < ne)
+                    out[s_gd[ct[k] & ((1u << STRIP_TAG_BITS) - 1u)] + (ct[k] >> STRIP_TAG_BITS)] = ce[k];
+        }
+        return;
+    }
     // ---- run lengths of this slice = next slice's scanned value - this one's -> local starts (exclusive scan over strips)
     uint32_t mine = 0;
     {
@@ -277,7 +309,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
     }
     __syncthreads();
     // ---- place
-    for (uint32_t base = 0; base < count; base += STRIP_PF * STRIP_THREADS) {  // uniform trip counts (barriers inside)
+    for (uint32_t base = 0; base < per_slice; base += STRIP_PF * STRIP_THREADS) {  // uniform trip counts (barriers inside)
         uint4 cur[STRIP_PF];
 #pragma unroll
         for (int k = 0; k < STRIP_PF; ++k) {
@@ -287,7 +319,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
 #pragma unroll
         for (int k = 0; k < STRIP_PF; ++k) {
             const uint32_t b = base + k * STRIP_THREADS;
-            if (b >= count) break;  // uniform
+            if (b >= per_slice) break;  // uniform
             const uint32_t i = b + threadIdx.x;
             if (pair_offsets) {  // uniform: prefix sum of the rectangle areas in Gaussian order
                 const uint32_t ex = strip_block_excl_scan(cur[k].w, s_wave, dummy);
@@ -302,19 +334,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) strip_scatter_kernel(
                 else
                     out[s_gd[strip] + slot] = e;
             };
-            if (cut) {  // (uniform; a "dist" frame is never culled)
-                if constexpr (!DIST) {
-                    uint4 e = cur[k];
-                    int64_t gid = L.g0 + i;
-                    if (surv) {  // (uniform) a list entry: the Gaussian rides in .w, the area follows from the ranges
-                        gid = e.w;
-                        e.w = ((e.x >> 16) - (e.x & 0xffff)) * ((e.y >> 16) - (e.y & 0xffff));
-                    }
-                    walk_strips<false, true>(e, gid, SG, make_float2(0.f, 0.f), D, place, s_cut);
-                }
-            } else {
-                walk_strips<DIST>(cur[k], L.g0 + i, SG, L.xy<DIST>(b, cur[k]), D, place);
-            }
+            walk_strips<DIST>(cur[k], L.g0 + i, SG, L.xy<DIST>(b, cur[k]), D, place);
         }
     }
     __syncthreads();
@@ -381,21 +401,21 @@ int gs_stage_strip_bin(const gs_frame *f, const gs_frame_ws &ws, hipStream_t str
     }
     unsigned long long *table = (unsigned long long *)ws.strip_table, *scan = table + (size_t)GS_BIN_SLICES * SG.NS;
     const unsigned long long *gate = second_pass ? ws.counters + GS_CNT_RANPAST : nullptr;
-    const uint32_t *cut = (!second_pass && gs_frame_occlusion_cull(f)) ? gs_frame_cut_table(f, ws) : nullptr;
-    // a culled frame's scatter gives 4 staged entries per strip (32 B: the strip's eight cuts) to the cut table
-    const uint32_t cap = cut ? plan.cap - 4 * SG.NS : plan.cap;
-    const size_t lds_scatter = sizeof(unsigned long long) * ((size_t)SG.NS + cap) + (cut ? (size_t)32 * SG.NS : 0);
+    // first pass of an occlusion-culled frame: the project stage has staged the entries, the permutation needs no LDS staging
+    const bool staged = !second_pass && gs_frame_occlusion_cull(f);
+    const uint32_t cap = staged ? 0u : plan.cap;
+    const size_t lds_scatter = sizeof(unsigned long long) * ((size_t)SG.NS + cap);
     // (second pass: the table has been rewritten, untrimmed, by the gated re-run of the project stage)
     hipLaunchKernelGGL(strip_colscan_kernel, dim3((unsigned)gs_div_up(SG.NS, 16)), dim3(256), 0, stream,
                        (const unsigned long long *)table, scan, plan.slices, SG.NS, (unsigned long long *)ws.strip_tot, gate);
     GS_CHECK_LAUNCH();
-    const auto scatter = dist ? strip_scatter_kernel<true> : strip_scatter_kernel<false>;
+    const auto scatter = staged ? strip_scatter_kernel<false, true> : dist ? strip_scatter_kernel<true> : strip_scatter_kernel<false>;
     hipLaunchKernelGGL(scatter, dim3(plan.slices), dim3(STRIP_THREADS), lds_scatter, stream, ws.rects, ws.rec_geom, D, f->N,
                        plan.per_slice, SG, plan.slices, cap, scan, (const unsigned long long *)ws.strip_tot,
                        (unsigned long long *)ws.strip_base, ws.slice_pairs, ws.slice_vis, (uint64_t)f->max_pairs,
-                       (unsigned long long *)ws.keys_a, f->training ? ws.pair_offsets : nullptr, ws.counters, cut,
-                       (uint32_t)G.n_tiles, gate, cut ? (const uint4 *)ws.surv : (const uint4 *)nullptr,
-                       (const uint32_t *)ws.slice_nsurv);
+                       (unsigned long long *)ws.keys_a, f->training ? ws.pair_offsets : nullptr, ws.counters, gate,
+                       (const unsigned long long *)ws.keys_b, (const uint32_t *)ws.vals_b,
+                       gs_cull_stage_cap(f->max_pairs, plan.slices), (const uint32_t *)ws.slice_entries);
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -81,6 +81,17 @@ __device__ __forceinline__ void walk_strips(const uint4 rc, int64_t g, const gs_
     }
 }
 
+// ---------------------------------------------------------------- staged entries of an occlusion-culled frame's first pass
+// The project stage of such a frame (cull_project.hip, frame_project_cull_count_kernel) keeps every level-1 entry it counts:
+// the 8-byte entry and a 4-byte tag = strip | rank << 13, rank = the entry's position inside its slice's run of that strip
+// (what the counting LDS add returned).  13 bits hold a strip index at the limit (GS_STRIP_MAX = 8,192 strips per frame), the
+// other 19 a rank at the limit: a Gaussian has at most one entry per strip, so rank < per_slice <= 2^(GS_STRIP_ID_BITS - 8)
+// = 2^18 (256 slices of a scene below 2^26 Gaussians, rounded up to a multiple of 256).
+#define STRIP_TAG_BITS 13
+static_assert(GS_STRIP_MAX <= (1 << STRIP_TAG_BITS), "a tag holds the strip index in its low bits");
+static_assert(GS_BIN_SLICES == 256 && GS_STRIP_ID_BITS - 8 + STRIP_TAG_BITS <= 32, "... and the rank above it");
+__device__ __forceinline__ uint32_t strip_tag(uint32_t strip, uint32_t rank) { return strip | (rank << STRIP_TAG_BITS); }
+
 // same XCD-contiguous dealing of slices to workgroups as the table variant (tile_bin.hip): the runs of neighbouring
 // slices are neighbours in memory, so the partial lines at run boundaries meet in one L2
 __device__ __forceinline__ uint32_t strip_slice_of_block(uint32_t blk, uint32_t B) {

@@ -52,7 +52,7 @@ extern "C" {
  *   gs_frame fields depth / alpha / aux_padded / aux_workspace / aux_workspace_bytes / grad_depth / grad_alpha (read only
  *   when the flag is set) and gs_frame_aux_workspace_bytes.
  * 8 (round 6): gs_frame_is_occlusion_culled; an occlusion-culled frame's first pass projects only the Gaussians that are not
- * behind every cut they can reach and writes rectangle records for those only (workspace layout: + the survivor list).
+ * behind every cut they can reach and writes rectangle records for those only.
  *   GS_FRAME_CULL_DILATE.
  * 7 (round 6): GS_FRAME_LONG_SORT, GS_FRAME_OCCLUSION_CULL + gs_frame_cull_fallback_async; gs_frame_stats_serial (the frame the
  * counters belong to).
@@ -486,6 +486,14 @@ int gs_frame_binning_variant(const gs_frame *f);
  * `depth bits != 0`); the 64-byte record (rec_geom / rec_cov / rec_color above) of a culled Gaussian is NOT written and
  * holds whatever an earlier frame left there. */
 int gs_frame_debug_rects(const gs_frame *f, const uint32_t **rects);
+
+/* Where the FIRST PASS of an occlusion-culled frame (gs_frame_is_occlusion_culled) stages its level-1 entries, for tests of
+ * that path: slice s of the Gaussian array owns slots [s x *cap, (s + 1) x *cap) of *entries (8 bytes each) and *tags
+ * (4 bytes each), both borrowed from the sort buffers of the workspace and overwritten by the rest of the frame, and wrote
+ * (*slice_entries)[s] of them -- 0xffffffff: the slice had more than *cap entries, stored none beyond its slots and sent the
+ * frame to its second pass.  Fails for a frame description that is not culled. */
+int gs_frame_debug_cull_stage(const gs_frame *f, const uint64_t **entries, const uint32_t **tags,
+                              const uint32_t **slice_entries, int32_t *slices, int64_t *cap);
 
 /* [T] uint32: how many Gaussians of its list each tile's forward actually composited before all of its pixels had
  * stopped (a multiple of 64 except for the last chunk), kept by TRAINING forwards for the backward.  Measurement

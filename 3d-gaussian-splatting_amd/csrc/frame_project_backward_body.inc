@@ -1,11 +1,13 @@
-// frame_project_backward_body.inc -- the body of frame_project_backward_kernel and of its GS_FRAME_POSE_GRAD variant
-// frame_project_backward_pose_kernel (project_bwd.hip), expanded in place in both.  Expects in scope: the kernel's
-// parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE`, `constexpr bool AUX` and `pose_part`.  (Included rather than called: an
+// frame_project_backward_body.inc -- the body of frame_project_backward_kernel, of its GS_FRAME_POSE_GRAD variant
+// frame_project_backward_pose_kernel and of the fused step's variants frame_project_backward_adam_aux_kernel and
+// frame_project_backward_adam_pose_kernel (project_bwd.hip), expanded in place in all of them.  Expects in scope: the kernel's
+// parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE`, `constexpr bool AUX`, `pose_part` and `pose_part_aux`.  (Included rather than called: an
 // inlined device function leaves the kernel without the flag with other register assignments than before it existed;
 // expanded in place, it compiles to the same code.)
     static_assert(ADAM == 0 || PART == 0, "the fused optimizer step: everything in one kernel");
-    static_assert(!POSE || (CDIM == 3 && PART != 2 && ADAM == 0), "pose gradients: rgb colours, geometry part, no fused step");
-    static_assert(!AUX || (ADAM != 0 && !POSE), "the depth map's position term is added here only in front of the fused step");
+    static_assert(!POSE || (CDIM == 3 && (ADAM == 0 ? PART != 2 : PART == 0)),
+                  "pose gradients: rgb colours; the geometry part, or everything in front of the fused step");
+    static_assert(!AUX || ADAM != 0, "the depth map's position term is added here only in front of the fused step");
     // rgb rows (round 4): only rows that EXIST are fetched.  71 % of the pairs of the 2.4 M scene lie behind their
     // tile's stop point and their rows are uninitialised memory; round 3 streamed all of them through LDS and looked at
     // the flags afterwards (PMC: 916 MB of traffic against 316 MB algorithmic).  Whether the row of pair (tile, g) was
@@ -428,6 +430,13 @@
 #pragma unroll
         for (int e = 0; e < 12; ++e) pose[e] = 0.f;
     }
+    // (POSE in front of the fused step, AUX frames: the depth map's pose terms, a second row per workgroup -- what
+    // frame_aux_depth_pose_backward_kernel leaves behind gs_frame_backward)
+    [[maybe_unused]] float pt[POSE && AUX ? 12 : 1];
+    if constexpr (POSE && AUX) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) pt[e] = 0.f;
+    }
     if (vis && PART != 2) {
         float p[3], sraw[3], q[4], s[3];
         load3(pos, pid, p);
@@ -437,7 +446,7 @@
         activate(qraw, sraw, P.scale_act, q, s);
         float gi[3] = {d0.x, d0.y, 0.0f}, g2[4] = {d0.z, d0.w, d1.x, d1.y}, gq[4], gs[3];
         project_backward(p, q, s, P.cam, gi, g2, gp, gq, gs);
-        if constexpr (POSE) pose_terms(p, q, s, P.cam, gi, g2, pose);
+        if constexpr (POSE) pose_terms<POSE && AUX>(p, q, s, P.cam, gi, g2, pose);
         // q_hat = q / |q|  ->  dq = (dq_hat - q_hat (q_hat . dq_hat)) / |q|
         const float inr = gs_rsq(qraw[0] * qraw[0] + qraw[1] * qraw[1] + qraw[2] * qraw[2] + qraw[3] * qraw[3]);
         float dt = q[0] * gq[0] + q[1] * gq[1] + q[2] * gq[2] + q[3] * gq[3];
@@ -465,6 +474,9 @@
             gopa = d1.z * g.w * (1.0f - g.w);
         }
     }
+    // (POSE: both sums hold a __syncthreads -- every thread of the workgroup, the fused step's skipped frames included.  The
+    // projection's row is summed here, in front of the depth map's row walk: its twelve registers are free by then)
+    if constexpr (POSE) pose_block_sum<BLOCK>(pose, pose_part + (size_t)blockIdx.x * 12);
     if constexpr (AUX) {
         // GS_FRAME_AUX frames in front of the fused step (gs_frame_backward_adam_aux): what frame_aux_depth_backward_kernel adds
         // to the stored grad_pos behind this kernel is added to gp here -- the same row walk (aux_depth_term.inc), and
@@ -477,14 +489,24 @@
 #include "aux_depth_term.inc"
 #pragma unroll
                 for (int c = 0; c < 3; ++c) ga[c] = gpa[c];
+                if constexpr (POSE) {  // gc p^T, gc: aux_depth_backward_body.inc
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) pt[r * 3 + c] = gc[r] * p[c];
+                        pt[9 + r] = gc[r];
+                    }
+                }
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) gp[c] = gp[c] + ga[c];
         }
     }
     if constexpr (POSE) {
-        pose_block_sum<BLOCK>(pose, pose_part + (size_t)blockIdx.x * 12);
-        if (!valid) return;
+        if constexpr (AUX) pose_block_sum<BLOCK, 1>(pt, pose_part_aux + (size_t)blockIdx.x * 12);
+        if constexpr (ADAM == 0) {
+            if (!valid) return;
+        }  // (the fused step's LDS hand-over needs every lane of the wave: its invalid threads leave in the epilogue)
     }
     if constexpr (ADAM != 0) {
         // ---- the optimizer step of the wave's 64 x 14 parameters (gs_adam_one: torch's _single_tensor_adam); a culled

@@ -552,6 +552,41 @@ extern "C" int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_i
     return gs_stage_project_backward_adam(f, ws, adam, s, true);
 }
 
+// The fused step of a GS_FRAME_POSE_GRAD training frame (rgb colours), with or without GS_FRAME_AUX: the raster backward, the
+// projection backward with the pose terms and the optimizer step in one kernel, the pose gradient's reduction.  The map takes
+// the step gs_frame_backward + gs_adam_step give it, f->grad_rot / f->grad_tran what that gs_frame_backward writes, bit for bit.
+extern "C" int gs_frame_backward_adam_pose(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
+                                           gs_stream_t stream) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG((f->flags & GS_FRAME_POSE_GRAD) != 0,
+                 "the frame is not flagged GS_FRAME_POSE_GRAD (gs_frame_backward_adam / _adam_aux take frames without a pose gradient)");
+    if (f->color_dim != 3) {
+        gs_set_error("gs_frame_backward_adam_pose: GS_FRAME_POSE_GRAD needs rgb colours (color_dim 3): with SH colours the image "
+                     "also depends on the pose through the pixels' ray directions");
+        return GS_E_UNSUPPORTED;
+    }
+    const bool aux = (f->flags & GS_FRAME_AUX) != 0;
+    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam_pose needs a training forward (image_padded kept)");
+    GS_CHECK_ARG(adam && (aux || grad_image), "null pointer");
+    if ((rc = gs_validate_adam_fused(f, adam))) return rc;  // before anything is enqueued
+    hipStream_t s = (hipStream_t)stream;
+    if (f->N == 0) {  // no partial sums: zeros, written all the same (frame_backward_impl)
+        GS_HIP(hipMemsetAsync(f->grad_rot, 0, 9 * sizeof(float), s));
+        GS_HIP(hipMemsetAsync(f->grad_tran, 0, 3 * sizeof(float), s));
+        return 0;
+    }
+    if (!grad_image && (rc = zero_image(sizeof(float) * 3 * (size_t)f->width * (size_t)f->height, &grad_image))) return rc;
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
+    uint64_t *skeys, *okeys;
+    uint32_t *sids;
+    sorted_buffers(f, ws, &skeys, &sids, &okeys);
+    const bool prepared = join_prepared(f, s);
+    if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
+    if ((rc = gs_stage_project_backward_adam(f, ws, adam, s, aux, true))) return rc;
+    return gs_stage_pose_finalize(f, ws, s);
+}
+
 extern "C" int gs_frame_backward_part(const gs_frame *f, const float *grad_image, float *grad_pos, float *grad_quat,
                                       float *grad_scale, float *grad_opa, float *grad_rgb, int32_t part,
                                       gs_stream_t stream) {

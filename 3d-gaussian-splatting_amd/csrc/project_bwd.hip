@@ -115,6 +115,13 @@ __device__ __forceinline__ void project_backward(const float p[3], const float q
 // and folds into it).  With p_c = rot p + tran and cov2d = J rot C rot^T J^T, C = (R S)(R S)^T, J held fixed as above:
 //   dL/dtran = gc,   dL/drot = gc p^T + J^T (G + G^T) J rot C,   G = dL/dcov2d (g2: G00, G01, G10, G11).
 // J^T (G + G^T) J rot C = J^T K (RS)(RS)^T with K = (G + G^T) (J rot) [2x3]: ~80 FMAs.
+// U0_EXPLICIT (the fused step's AUX + POSE variant only): everything here contracts by pragma, and which product of a b + c d
+// the compiler fuses follows the operand order its optimizer leaves, which depends on the code around the call.  In every
+// other kernel that expands this function U[a][0] comes out as fma(K2, RS6, fma(K1, RS3, fl(K0 RS0))); with the depth map's
+// row walk in the same kernel the first two products change places -- the one sum of this function that moves, found by
+// comparing the kernels' machine code -- and the pose row loses its last bit against frame_project_backward_pose_kernel.
+// The flag states that sum the way the other kernels have it.  tests/test_gpu_pose_adam.py compares the rows bit for bit.
+template <bool U0_EXPLICIT = false>
 __device__ __forceinline__ void pose_terms(const float p[3], const float q[4], const float s[3], const Cam &cam,
                                            const float gi[3], const float g2[4], float t[12]) {
     float pc[3];
@@ -147,7 +154,14 @@ __device__ __forceinline__ void pose_terms(const float p[3], const float q[4], c
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) U[a * 3 + k] = K[a * 3 + 0] * RS[0 * 3 + k] + K[a * 3 + 1] * RS[1 * 3 + k] + K[a * 3 + 2] * RS[2 * 3 + k];
+        for (int k = 0; k < 3; ++k) {
+            if (U0_EXPLICIT && k == 0) {
+                const float first = K[a * 3 + 0] * RS[0];
+                U[a * 3] = __builtin_fmaf(K[a * 3 + 2], RS[6], __builtin_fmaf(K[a * 3 + 1], RS[3], first));
+            } else {
+                U[a * 3 + k] = K[a * 3 + 0] * RS[0 * 3 + k] + K[a * 3 + 1] * RS[1 * 3 + k] + K[a * 3 + 2] * RS[2 * 3 + k];
+            }
+        }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -167,8 +181,9 @@ __device__ __forceinline__ void pose_terms(const float p[3], const float q[4], c
 // GS_FRAME_POSE_GRAD: the workgroup's sum of every thread's 12 pose terms -> row[0..11] (one row per workgroup, summed by
 // pose_grad_finalize_kernel).  A fixed order, no atomics -- bitwise repeatable like every other gradient here: a butterfly
 // over the wave (both partners add the same two values: every lane holds the same bits), then the waves in index order.
-// Every thread of the workgroup must call it.
-template <int BLOCK>
+// Every thread of the workgroup must call it.  SLOT: a kernel that sums two rows (the fused step's AUX + POSE variant) gives
+// each its own LDS array, so the second sum's writes cannot overtake the first one's reads.
+template <int BLOCK, int SLOT = 0>
 __device__ __forceinline__ void pose_block_sum(float t[12], float *__restrict__ row) {
     __shared__ float s_pose[BLOCK / 64][12];
 #pragma unroll
@@ -471,7 +486,7 @@ __global__ void __launch_bounds__(BLOCK) frame_project_backward_kernel(
     float4 *__restrict__ grad_quat, float *__restrict__ grad_scale, float *__restrict__ grad_opa,
     float *__restrict__ grad_rgb, AdamFusedDev A = AdamFusedDev{}) {
     constexpr bool POSE = false, AUX = false;
-    [[maybe_unused]] float *const pose_part = nullptr;
+    [[maybe_unused]] float *const pose_part = nullptr, *const pose_part_aux = nullptr;
 #include "frame_project_backward_body.inc"
 }
 
@@ -490,7 +505,7 @@ __global__ void __launch_bounds__(BLOCK) frame_project_backward_adam_aux_kernel(
     constexpr int PART = 0;
     constexpr bool POSE = false, AUX = true;
     const int64_t g_first = 0;
-    [[maybe_unused]] float *const pose_part = nullptr;
+    [[maybe_unused]] float *const pose_part = nullptr, *const pose_part_aux = nullptr;
     // (no gradient is stored: the names the body's unfused tail mentions)
     [[maybe_unused]] float *const grad_pos = nullptr, *const grad_scale = nullptr, *const grad_opa = nullptr, *const grad_rgb = nullptr;
     [[maybe_unused]] float4 *const grad_quat = nullptr;
@@ -514,6 +529,33 @@ __global__ void __launch_bounds__(256) frame_project_backward_pose_kernel(
     constexpr bool POSE = true, AUX = false;
     const int64_t g_first = 0;
     [[maybe_unused]] const AdamFusedDev A{};
+    [[maybe_unused]] float *const pose_part_aux = nullptr;
+#include "frame_project_backward_body.inc"
+}
+
+// GS_FRAME_POSE_GRAD training frames with the fused step (gs_frame_backward_adam_pose), plain (AUX false) or GS_FRAME_AUX: the
+// ADAM = 1 / 2 step of frame_project_backward_kernel<3, 0, 256, .> / frame_project_backward_adam_aux_kernel<3, 256, .> with the
+// pose terms of frame_project_backward_pose_kernel<0> -- and, AUX, of frame_aux_depth_pose_backward_kernel -- formed from the
+// position, quaternion and scale the thread loaded BEFORE the step, and summed over the workgroup in front of the epilogue.
+// One row of 12 partial sums per workgroup into pose_part, AUX: a second one into pose_part_aux -- the layout the two
+// unfused kernels leave, so pose_grad_finalize_kernel runs as it is.  Threads past N add zeros to both sums, take part in
+// the epilogue's hand-overs and leave where it lets them.  A kernel of its own name: the others keep their code.
+template <bool AUX, int ADAM>
+__global__ void __launch_bounds__(256) frame_project_backward_adam_pose_kernel(
+    const float *pos, const float4 *quat, const float *scale,
+    int64_t n, ProjectParams P, const float4 *__restrict__ rec_geom,
+    const float4 *__restrict__ rec_color, const float4 *__restrict__ rows,
+    const unsigned long long *__restrict__ stop_keys, const float *opa_raw,
+    const float *rgb_raw, GsDistCull D,
+    const uint32_t *__restrict__ pair_offsets, const uint4 *__restrict__ rects, uint64_t max_pairs, AdamFusedDev A,
+    float *__restrict__ pose_part, float *__restrict__ pose_part_aux) {
+    static_assert(ADAM != 0, "the fused step's variant");
+    constexpr int CDIM = 3, PART = 0, BLOCK = 256;
+    constexpr bool POSE = true;
+    const int64_t g_first = 0;
+    // (no gradient is stored: the names the body's unfused tail mentions)
+    [[maybe_unused]] float *const grad_pos = nullptr, *const grad_scale = nullptr, *const grad_opa = nullptr, *const grad_rgb = nullptr;
+    [[maybe_unused]] float4 *const grad_quat = nullptr;
 #include "frame_project_backward_body.inc"
 }
 
@@ -556,8 +598,9 @@ static void for_color_dim(int color_dim, Fn fn) {
         fn(Int<3>{});
 }
 
-// One launch of frame_project_backward_kernel, frame_project_backward_adam_aux_kernel or frame_project_backward_pose_kernel
-// over the Gaussians below `n`: the arguments the three have in common, then `tail` (what each takes behind max_pairs).
+// One launch of frame_project_backward_kernel, frame_project_backward_adam_aux_kernel, frame_project_backward_pose_kernel or
+// frame_project_backward_adam_pose_kernel over the Gaussians below `n`: the arguments they have in common, then `tail` (what
+// each takes behind max_pairs).
 template <class Kernel, class... Tail>
 static void launch_project_backward(Kernel kernel, unsigned grid, int block, hipStream_t stream, const gs_frame *f,
                                     const gs_frame_ws &ws, int64_t n, Tail... tail) {
@@ -655,10 +698,12 @@ int gs_validate_adam_fused(const gs_frame *f, const gs_adam_fused *a) {
 }
 
 int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream,
-                                   bool aux) {
+                                   bool aux, bool pose) {
     int vrc = gs_validate_adam_fused(f, a);
     if (vrc) return vrc;
+    GS_CHECK_ARG(!pose || f->color_dim == 3, "the fused step with a pose gradient needs rgb colours");
     if (f->N <= 0) return 0;
+    const gs_frame_pose_ws pw = gs_frame_pose_carve(pose ? f->pose_workspace : nullptr, f->N);
     // bias corrections on the host in double, as torch does (adam.hip: adam_step_impl)
     const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step), bc2 = 1.0 - pow((double)a->beta2, (double)a->step);
     AdamFusedDev A;
@@ -689,8 +734,18 @@ int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, con
         const unsigned grid = (unsigned)gs_div_up(f->N, BLK);
         auto launch = [&](auto mode) {
             constexpr int MODE = decltype(mode)::value;
-            // aux: GS_FRAME_AUX (gs_frame_backward_adam_aux), the variant that adds the depth map's position term in front of the step
-            if (aux)
+            // aux: GS_FRAME_AUX (gs_frame_backward_adam_aux), the variant that adds the depth map's position term in front of the step;
+            // pose: GS_FRAME_POSE_GRAD (gs_frame_backward_adam_pose), grid = pw.rows: one row (aux: two) of partial sums per workgroup
+            if (pose) {
+                if constexpr (CD == 3) {
+                    if (aux)
+                        launch_project_backward(frame_project_backward_adam_pose_kernel<true, MODE>, grid, BLK, stream, f, ws,
+                                                f->N, A, pw.proj, pw.aux);
+                    else
+                        launch_project_backward(frame_project_backward_adam_pose_kernel<false, MODE>, grid, BLK, stream, f, ws,
+                                                f->N, A, pw.proj, pw.aux);
+                }
+            } else if (aux)
                 launch_project_backward(frame_project_backward_adam_aux_kernel<CD, BLK, MODE>, grid, BLK, stream, f, ws, f->N, A);
             else
                 launch_project_backward(frame_project_backward_kernel<CD, 0, BLK, MODE>, grid, BLK, stream, f, ws, f->N,

@@ -675,13 +675,16 @@ class FrameRenderer:
         f.grad_alpha = grad_alpha.data_ptr() if grad_alpha is not None else None
         return grad_depth, grad_alpha
 
-    def backward_adam(self, grad_image, adam, grad_depth=None, grad_alpha=None):
+    def backward_adam(self, grad_image, adam, grad_depth=None, grad_alpha=None, grad_pose=None):
         """``backward`` with the optimizer step fused into its last kernel (gs_frame_backward_adam, include/
         gs_abi.h): the frame's own parameter tensors are updated in place, no gradient is written.  ``adam``: a filled
         ``gaussian._lib.GsAdamFused`` (gs_train.FusedAdam.fused_descriptor).
         After ``forward(..., aux=True)`` the step goes through gs_frame_backward_adam_aux: ``grad_depth`` / ``grad_alpha``
         [H,W] are dL/d(depth), dL/d(alpha) (None = zero), and ``grad_image`` may be None (zero) as well -- bit for bit
-        what ``backward(grad_image, grad_depth=..., grad_alpha=...)`` + the optimizer's step give."""
+        what ``backward(grad_image, grad_depth=..., grad_alpha=...)`` + the optimizer's step give.
+        ``grad_pose`` = (grad_rot [3,3], grad_tran [3]) as in ``backward``: the step goes through
+        gs_frame_backward_adam_pose, which also writes the gradient of the frame's pose -- that of the parameters the frame
+        was rendered with, bit for bit what ``backward(..., grad_pose=...)`` writes.  rgb colours only."""
         f = self._frame
         if f is None or not f.training:
             raise RuntimeError("backward_adam() needs a preceding forward(training=True)")
@@ -693,6 +696,22 @@ class FrameRenderer:
         for ptr, t in zip((f.pos, f.quat, f.scale, f.opa, f.rgb), self._keep[:5]):
             if int(ptr or 0) != t.data_ptr():
                 raise RuntimeError("backward_adam(): the frame was rendered from tensors that are no longer alive")
+        if grad_pose is not None:
+            if aux:
+                grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
+            if grad_image is not None:
+                grad_image = grad_image.contiguous()
+                if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
+                    raise RuntimeError("grad_image must be float32 [H,W,3]")
+            elif not aux:
+                raise RuntimeError("grad_image may be None for frames rendered with aux=True only")
+            g = self._pose_frame(f, grad_pose, 0)  # (refuses SH colours)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.gs_frame_backward_adam_pose(C.byref(g), grad_image.data_ptr() if grad_image is not None
+                                                            else None, C.byref(adam), self._stream().cuda_stream),
+                           "gs_frame_backward_adam_pose")
+            self._bwd_serial = self._frame_serial
+            return
         if aux:
             grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
             if grad_image is not None:

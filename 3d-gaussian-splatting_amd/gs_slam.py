@@ -9,8 +9,12 @@ keyframe when the last keyframe sees too few of them or too many frames have pas
 together with the keyframes that share the most points with it.  A frame that is no keyframe leaves the map and the
 optimizer state untouched, bit for bit.
 
-rgb maps only.  Keyframe poses are fixed once set (the pose gradient is not in the fused-Adam backward); the keyframe set
-only grows -- ``KeyframeSet.add`` raises when it is full; there is no loop closure and ``adaptive_control`` is never called.
+rgb maps only.  By default a keyframe's pose is fixed once set.  With ``SlamOptions.refine_poses`` the mapping steps of a
+keyframe also refine the poses of its window (``Trainer.free_pose``: the fused step's pose variant,
+gs_frame_backward_adam_pose, delivers the pose gradient of every step, the Tracker's pose optimizer takes it) -- every view of
+the window except keyframe 0, which fixes the gauge; ``KeyframeSet.set_pose`` carries the result into the view table and the
+tracker's motion history starts from the refined pose.  The keyframe set only grows -- ``KeyframeSet.add`` raises when it is
+full; there is no loop closure and ``adaptive_control`` is never called.
 """
 from __future__ import annotations
 
@@ -18,7 +22,7 @@ import copy
 import ctypes as C
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -95,6 +99,18 @@ class KeyframeSet:
         self._min_size = size if self._min_size is None else min(self._min_size, size)
         return n
 
+    def set_pose(self, index: int, rot, tran):
+        """Replaces the pose of keyframe ``index`` (a mapper refined it): the camera by a copy with (rot, tran) in float32,
+        its 64-byte row of the device table by the validated row of that copy."""
+        if not 0 <= int(index) < len(self.cameras):
+            raise IndexError(f"no keyframe {index}")
+        cam = copy.copy(self.cameras[index])
+        cam.rot = np.array(rot, np.float32).reshape(3, 3)
+        cam.tran = np.array(tran, np.float32).reshape(3)
+        row = view_row(cam)  # (validated before anything is written)
+        self.table[index].copy_(torch.from_numpy(row))
+        self.cameras[index] = cam
+
     def overlap(self, range_map: torch.Tensor, camera, stride: int = 1, near: float = 0.3, border: int = 0) -> np.ndarray:
         """counts [len + 2] int64 on the host (``view_overlap``): the one host read of a frame's keyframe decision."""
         if not self.cameras:
@@ -154,6 +170,13 @@ class SlamOptions:
     map_iterations_first: int = 30  # mapping steps on the first frame
     map_iterations: int = 120       # mapping steps per later keyframe, round-robin over the window (fitted: see above)
     max_pairs: int = 1 << 21        # the trainer's initial pair capacity (it grows by itself)
+    # Joint refinement of the window's poses with the map (off: the loop is bit for bit the one without the option).  The
+    # rates are TrackOptions' 2e-3 x 0.1, held constant: a window view takes some 30 - 60 pose steps per keyframe, which lets
+    # it travel ~1e-2 (rad, scene units) at most and jitter by ~2e-4 -- an order below one frame's motion on the arc of
+    # tests/test_gpu_pose_adam.py.  No evidence beyond that arc (profiles/pose_refine.txt).
+    refine_poses: bool = False
+    pose_lr_rot: float = 2e-4
+    pose_lr_tran: float = 2e-4
 
 
 @dataclass
@@ -168,6 +191,9 @@ class SlamFrame:
     map_losses: List[float] = field(default_factory=list)  # the loss of each mapping step
     seconds: dict = field(default_factory=dict)  # wall time in track / overlap / seed / map (each ends on a host read)
     pending: int = 0                 # mapping steps that `Slam.map(frame)` has still to take (`begin` sets it)
+    # refine_poses: keyframe index -> (rot, tran) float64 of every window view whose pose the mapping steps moved (never
+    # keyframe 0); rot / tran above then report this frame's own refined pose
+    refined: Dict[int, Tuple[np.ndarray, np.ndarray]] = field(default_factory=dict)
 
 
 class Slam:
@@ -212,11 +238,28 @@ class Slam:
         if not frame.keyframe:
             return frame
         t0 = time.perf_counter()
+        o, tr = self.opt, self.trainer
+        # refine_poses: every view of the window but keyframe 0 (the gauge) is free for these steps
+        freed = [v for v in frame.window if v != 0] if (o.refine_poses and frame.pending > 0) else []
+        before = {v: (tr.cameras[v].rot, tr.cameras[v].tran) for v in freed}
+        for v in freed:
+            tr.free_pose(v, o.pose_lr_rot, o.pose_lr_tran)
         vals = []
         for s in range(frame.pending):
             vals.append(self.trainer.train_step(self.i_iter, frame.window[s % len(frame.window)]).clone())
             self.i_iter += 1
         frame.pending = 0
+        for v in freed:
+            rot, tran = tr.pose(v)  # (float64; settles the last step's update)
+            tr.fix_pose(v)
+            cam = tr.cameras[v]
+            if not (np.array_equal(cam.rot, before[v][0]) and np.array_equal(cam.tran, before[v][1])):
+                self.keyframes.set_pose(v, cam.rot, cam.tran)  # the float32 pose the trainer renders: the two agree
+                frame.refined[v] = (rot, tran)
+        if frame.window and frame.window[0] in frame.refined:
+            frame.rot, frame.tran = frame.refined[frame.window[0]]
+            if frame.tracked is not None:  # the next frame's constant-velocity prediction starts from the refined pose
+                self.tracker.set_last_pose(frame.rot, frame.tran)
         frame.map_losses += [float(v) for v in torch.stack(vals)[:, 0].cpu()] if vals else []
         frame.seconds["map"] = time.perf_counter() - t0
         # (also with no step taken: seeding gave the trainer new parameter tensors)

@@ -84,6 +84,73 @@ _SH_REFUSAL = ("pose gradients need rgb colours: with SH colours the image also 
                "each pixel's ray direction, which the backward does not differentiate")
 
 
+class PoseAdam:
+    """The pose optimizer, stated once (Tracker.track, gs_train.Trainer's free poses): a world -> camera pose (rot on SO(3),
+    tran) in float64 on the host and Adam on its six tangent numbers.  One ``step``: g = (dL/dw at w = 0 of rot(w) =
+    exp([w]x) rot, dL/dtran), Adam's moments and bias corrections on g, then rot <- exp([-dw]x) rot, tran <- tran - dt --
+    rot stays on SO(3) by construction.  ``k`` counts the steps taken."""
+
+    def __init__(self, rot, tran, lr_rot: float, lr_tran: float, betas: Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-8):
+        self.rot = np.array(rot, np.float64).reshape(3, 3)
+        self.tran = np.array(tran, np.float64).reshape(3)
+        self.lr0 = np.array([lr_rot] * 3 + [lr_tran] * 3)
+        self.betas = (betas[0], betas[1])
+        self.eps = eps
+        self.m, self.v = np.zeros(6), np.zeros(6)
+        self.k = 0
+
+    def step(self, grad_rot, grad_tran, lr_scale: float = 1.0):
+        """``grad_rot`` [9] / [3,3] = dL/drot, ``grad_tran`` [3] = dL/dtran (float64); ``lr_scale`` multiplies both learning
+        rates for this step.  Returns the new (rot, tran)."""
+        b1, b2 = self.betas
+        g = np.concatenate([rot_tangent_grad(grad_rot, self.rot), np.asarray(grad_tran, np.float64).reshape(3)])
+        self.k += 1
+        self.m = b1 * self.m + (1.0 - b1) * g
+        self.v = b2 * self.v + (1.0 - b2) * g * g
+        step = self.lr0 * lr_scale * (self.m / (1.0 - b1 ** self.k)) / (np.sqrt(self.v / (1.0 - b2 ** self.k)) + self.eps)
+        self.rot = so3_exp(-step[:3]) @ self.rot
+        self.tran = self.tran - step[3:]
+        return self.rot, self.tran
+
+
+class FreePose:
+    """A pose that a training loop refines without waiting for its gradient (gs_train.Trainer.free_pose): the step's backward
+    writes dL/drot, dL/dtran into ``grad_pose`` (views of ``dev``), ``deliver`` sends the 48 bytes to pinned host memory behind
+    it, and ``settle`` -- called by whoever reads the pose next -- waits for that copy and takes the ``PoseAdam`` step.  As
+    long as every reader settles first, that is exactly the step taken at once.  Without a device (``device=None``) the
+    gradient is written into ``host`` directly: the same bookkeeping on the host alone."""
+
+    def __init__(self, adam: PoseAdam, device=None):
+        self.adam = adam
+        self.pending = False
+        self.host = torch.zeros(12, dtype=torch.float32)  # grad_rot [0:9], grad_tran [9:12]
+        self.dev = self.grad_pose = self.event = None
+        if device is not None:
+            self.host = self.host.pin_memory()
+            self.dev = torch.zeros(12, dtype=torch.float32, device=device)
+            self.grad_pose = (self.dev[0:9].view(3, 3), self.dev[9:12])
+            self.event = torch.cuda.Event()
+
+    def deliver(self):
+        """Behind the step that wrote the gradient, on the stream that ran it: no host synchronisation."""
+        if self.dev is not None:
+            self.host.copy_(self.dev, non_blocking=True)
+            self.event.record()
+        self.pending = True
+
+    def settle(self) -> bool:
+        """Take the pending step, if any -> whether the pose moved (was stepped)."""
+        if not self.pending:
+            return False
+        self.pending = False
+        if self.event is not None:
+            self.event.synchronize()
+        h = self.host.numpy().astype(np.float64)
+        self.adam.step(h[0:9], h[9:12])
+        return True
+
+
 class Tracker:
     """``Tracker(params, camera)``: ``params`` = (pos, quat, scale, opa, rgb) of an rgb map, ``camera`` gives the image size,
     the focal lengths, ``near`` and the pose tracking starts from.  ``track(image, range_map)`` estimates the pose of one
@@ -135,6 +202,13 @@ class Tracker:
         """Forget the motion history: the next ``track`` without ``init`` starts from the constructor camera's pose."""
         self._history: List[Tuple[np.ndarray, np.ndarray]] = []
 
+    def set_last_pose(self, rot, tran):
+        """Replace the last tracked pose of the motion history (a mapper refined the pose of the frame just tracked): the
+        constant-velocity prediction of the next ``track`` starts from it."""
+        if not self._history:
+            raise RuntimeError("set_last_pose() needs a tracked frame")
+        self._history[-1] = (np.array(rot, np.float64).reshape(3, 3), np.array(tran, np.float64).reshape(3))
+
     def _start_pose(self, init):
         if init is not None:
             rot, tran = init
@@ -167,9 +241,7 @@ class Tracker:
         RGB only): contiguous float32 tensors on the tracker's device.  Returns the pose with the lowest loss seen."""
         o = self.opt
         R, t = self._start_pose(init)
-        m, v = np.zeros(6), np.zeros(6)  # Adam's moments on (w, tran): kept across iterations, reset per call
-        lr0 = np.array([o.lr_rot] * 3 + [o.lr_tran] * 3)
-        b1, b2 = o.betas
+        adam = PoseAdam(R, t, o.lr_rot, o.lr_tran, o.betas, o.eps)  # Adam's moments on (w, tran): kept across iterations, reset per call
         best = (math.inf, R, t)
         losses: List[float] = []
         for k in range(int(o.iterations)):
@@ -178,12 +250,7 @@ class Tracker:
             losses.append(loss)
             if loss < best[0]:
                 best = (loss, R, t)
-            g = np.concatenate([rot_tangent_grad(h[0:9], R), h[9:12]])
-            m = b1 * m + (1.0 - b1) * g
-            v = b2 * v + (1.0 - b2) * g * g
-            step = lr0 * o.lr_final ** (k / o.iterations) * (m / (1.0 - b1 ** (k + 1))) / (np.sqrt(v / (1.0 - b2 ** (k + 1))) + o.eps)
-            R = so3_exp(-step[:3]) @ R
-            t = t - step[3:]
+            R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / o.iterations))
         loss, R, t = best
         self._history = (self._history + [(R, t)])[-2:]
         return TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)

@@ -17,11 +17,12 @@ schedule) is SURVEY 8f-2; data loading and the viewer stay out of scope (8f-3, 8
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 import math
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -422,6 +423,7 @@ class Trainer:
         self._overflow_warned = 0
         self._lambdas, self._base = lr_lambdas(self.opt), base_lrs(self.opt)
         self._loss = {}
+        self._free = {}  # camera id -> _FreePose: gs_track.FreePose: the views whose pose is refined with the map (free_pose)
         self._bind(params, 0)
 
     def _bind(self, params: Sequence[torch.Tensor], i_iter: int):
@@ -471,6 +473,57 @@ class Trainer:
             self._depth_inv_n.append(inv_n)
         return len(self.cameras) - 1
 
+    # ------------------------------------------------------------------ free poses (joint refinement of poses and map)
+    def free_pose(self, camera_id: int, lr_rot: float, lr_tran: float, betas: Tuple[float, float] = (0.9, 0.999),
+                  eps: float = 1e-8):
+        """From now on every ``train_step`` on view ``camera_id`` also moves that view's pose: the step's backward delivers
+        dL/drot, dL/dtran of the parameters the frame was rendered with (``FrameRenderer.backward_adam(grad_pose=...)``:
+        the fused step's pose variant, or ``backward(grad_pose=...)`` + the optimizer where the step cannot be fused), and
+        ``gs_track.PoseAdam`` -- the Tracker's optimizer: Adam on the six tangent numbers in float64 on the host, rot <-
+        exp([-dw]x) rot -- takes one step on it.  Moments and step count start at zero, the pose at the view's camera.  rgb
+        maps only; a step on a free view under view parallelism raises (the slice backward has no pose gradient).
+
+        No host synchronisation in the loop: the 48 bytes travel to pinned memory behind the step, and the pose update is
+        applied at the view's NEXT use by any reader (``train_step`` on it, ``seed_from_view``, ``test``, ``pose``,
+        ``fix_pose``), which waits for the copy there -- nobody reads the pose in between, so this is exactly eager
+        application.  ``cameras[camera_id]`` is then REPLACED by a copy with the new pose in float32: the caller's camera
+        object is never written.  A step on a frame that overflowed its pair capacity delivers zero gradients; with Adam's
+        moments that still moves the pose, as a zero-gradient step moves a culled Gaussian."""
+        from gs_track import _SH_REFUSAL, FreePose, PoseAdam
+
+        rgb = self.flat.params[4]
+        if rgb.dim() != 2 or rgb.shape[1] != 3:
+            raise RuntimeError(_SH_REFUSAL)
+        self._settle_pose(camera_id)
+        rot, tran = self.pose(camera_id)
+        self._free[camera_id] = FreePose(PoseAdam(rot, tran, lr_rot, lr_tran, betas, eps), self.flat.flat_param.device)
+
+    def fix_pose(self, camera_id: int):
+        """Ends ``free_pose``: the pending update is applied, the view keeps the pose it has, its optimizer state is dropped."""
+        self._settle_pose(camera_id)
+        self._free.pop(camera_id, None)
+
+    def pose(self, camera_id: int):
+        """(rot [3,3], tran [3]) of view ``camera_id`` in float64: a free view's own float64 pose (its camera carries the
+        float32 rounding of it), else the camera's."""
+        self._settle_pose(camera_id)
+        fp = self._free.get(camera_id)
+        if fp is not None:
+            return fp.adam.rot.copy(), fp.adam.tran.copy()
+        cam = self.cameras[camera_id]
+        return (np.array(cam.rot, np.float64).reshape(3, 3), np.array(cam.tran, np.float64).reshape(3))
+
+    def _settle_pose(self, camera_id):
+        """Apply the pose update a free view's last step left pending (waits for that step's 48-byte copy)."""
+        fp = self._free.get(camera_id)
+        if fp is None or not fp.settle():
+            return
+        rot, tran = fp.adam.rot, fp.adam.tran
+        cam = copy.copy(self.cameras[camera_id])
+        cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
+        cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
+        self.cameras[camera_id] = cam
+
     @property
     def n_gaussians(self) -> int:
         return int(self.flat.params[0].shape[0])
@@ -519,6 +572,12 @@ class Trainer:
         only_delete = past and i_iter % o.n_adaptive_control == 0
         control = only_delete and i_iter < o.adaptive_control_end_iter
         accum_start = past and (i_iter + o.grad_accum_iters - 1) % o.n_adaptive_control == 0
+        free = self._free.get(camera_id) if self._free else None
+        if free is not None:
+            if self.flat.collective_active():
+                raise RuntimeError(f"view {camera_id} has a free pose: the view-parallel step's slice backward has no pose "
+                                   "gradient (fix_pose first, or train on one rank)")
+            self._settle_pose(camera_id)  # the pose its previous step left pending
         cam, target = self.cameras[camera_id], self.targets[camera_id]
         flat, r = self.flat, self.renderer
         flat.finish_gather()  # reduce-scatter mode: parameter all-gathers of the previous step that nobody waited for yet
@@ -625,6 +684,20 @@ class Trainer:
                     flat.finish_slice_gather(j)  # ... the next slice's reduce-scatter + Adam
                     ahead = self._project_ahead(j, next_camera_id)
             # (gathers nobody waited for are waited for where the parameters are read next: finish_gather)
+        elif free is not None:
+            # a free pose: the same step with the pose gradient of this frame -- gs_frame_backward_adam_pose where the step
+            # fuses (rgb maps: free_pose refuses others), else the unfused backward with the flag; the map's step is bit for
+            # bit the one of the branches below
+            if self._can_fuse_adam() and flat.params[4].shape[1] == 3:
+                r.backward_adam(grad_image, self.optimizer.fused_descriptor(), grad_pose=free.grad_pose, **aux_grads)
+            else:
+                r.backward(grad_image, out=flat.grads, grad_pose=free.grad_pose, **aux_grads)
+                local_terms(0, flat.n)
+                if self.view_stat is not None and seen is not None:
+                    self.view_stat.add_seen(seen)
+                self.optimizer.step()
+            with torch.cuda.device(flat.flat_param.device):
+                free.deliver()  # 48 bytes -> pinned host behind the step; read at the view's next use
         elif self._can_fuse_adam():
             # one kernel less and no gradient round trip through memory: the per-Gaussian sums, the projection / activation
             # backward and the Adam update of the Gaussian's 14 parameters (+ the |pos.grad| statistic) in one launch
@@ -777,6 +850,7 @@ class Trainer:
         if self.depths is None or self.depths[camera_id] is None:
             raise RuntimeError(f"view {camera_id} has no depth map (Trainer(depths=...)): nothing to seed from")
         self.flat.finish_gather()
+        self._settle_pose(camera_id)
         cam, params = self.cameras[camera_id], self.flat.params
         _, _, depth_map, alpha_map = self._eval_renderer_for_set().forward(*params, cam, aux=True)
         n_old = self.n_gaussians
@@ -809,6 +883,7 @@ class Trainer:
                          float(intrinsics["focal_y"]), to_np(extrinsics["rot"]).reshape(3, 3),
                          to_np(extrinsics["tran"]).reshape(3), near=getattr(self.cameras[0], "near", 0.3) if self.cameras else 0.3)
         elif camera_id is not None:
+            self._settle_pose(camera_id)
             cam = self.cameras[camera_id]
         else:
             raise RuntimeError("test() needs a camera_id or extrinsics + intrinsics")

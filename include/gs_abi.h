@@ -34,7 +34,9 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_overlap,
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_backward_adam_pose (the
+ *   fused training step for GS_FRAME_POSE_GRAD frames, with or without GS_FRAME_AUX: the pose gradient of a mapping step).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_overlap,
  *   gs_view_overlap_workspace_bytes and gs_view_overlap_check_view with gs_overlap_opts / GS_OVERLAP_MAX_VIEWS (how many of the
  *   surface points an RGB-D frame measured does each keyframe see: the covisibility count of a mapping loop).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_track +
@@ -71,7 +73,7 @@ extern "C" {
 #define GS_E_INVALID (-1)   /* bad argument (null pointer, negative size, bad enum)   */
 #define GS_E_UNSUPPORTED (-2) /* a valid request this entry point does not implement (gs_frame_backward_adam of a
                                  GS_FRAME_AUX frame -- gs_frame_backward_adam_aux takes those -- or of a
-                                 GS_FRAME_POSE_GRAD frame; gs_frame_backward_slice of a
+                                 GS_FRAME_POSE_GRAD frame -- gs_frame_backward_adam_pose takes those --; gs_frame_backward_slice of a
                                  GS_FRAME_POSE_GRAD frame; any backward of a GS_FRAME_POSE_GRAD frame with SH colours) */
 #define GS_E_CAPACITY (-3)  /* workspace too small for this frame                     */
 
@@ -302,7 +304,9 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        through each pixel's ray direction, which is not differentiated -- every backward of
                                        such a frame returns GS_E_UNSUPPORTED.  gs_frame_backward_slice returns
                                        GS_E_UNSUPPORTED (a frame in slices has no point at which all partial sums are in)
-                                       and so does gs_frame_backward_adam.  All refusals come before anything is enqueued.
+                                       and so do gs_frame_backward_adam and gs_frame_backward_adam_aux: the fused training
+                                       step of a flagged frame is gs_frame_backward_adam_pose, which writes both as well.
+                                       All refusals come before anything is enqueued.
                                        Frames without the flag run exactly the kernels they ran before it existed. */
 
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
@@ -637,6 +641,20 @@ int gs_frame_backward_adam(const gs_frame *f, const float *grad_image, const gs_
  * that is not a training frame, a NULL or invalid `adam`; GS_E_UNSUPPORTED with GS_FRAME_POSE_GRAD.  Everything is checked
  * before anything is enqueued.  rgb and SH colours (color_dim 3 / 27 / 48). */
 int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam, gs_stream_t stream);
+
+/* The same step for GS_FRAME_POSE_GRAD training frames, with or without GS_FRAME_AUX (joint refinement of a keyframe's pose
+ * and the map): the raster backward, ONE kernel that sums the rows, forms every Gaussian's pose terms from the position,
+ * quaternion and scale it loaded before the step, sums them per workgroup and steps the 14 parameters, and the reduction of
+ * the partial rows into f->grad_rot / f->grad_tran.  The pose gradient belongs to the parameters the frame was rendered
+ * with.  Every updated parameter, both moments and the grad_stat fold are bit for bit what gs_frame_backward of the flagged
+ * frame + gs_adam_step give, and grad_rot / grad_tran are bit for bit what that gs_frame_backward writes (the same partial
+ * rows in the same layout: one per workgroup of 256 Gaussians, with GS_FRAME_AUX a second one for the depth map's term).
+ * With GS_FRAME_AUX the call reads f->grad_depth / f->grad_alpha and grad_image may be NULL, as in
+ * gs_frame_backward_adam_aux.  An overflowed frame takes no step (skip_if_nonzero) and gets zero pose gradients; N = 0
+ * writes zero pose gradients.  GS_E_INVALID for a frame without GS_FRAME_POSE_GRAD, a frame that is not a training frame, a
+ * NULL or invalid `adam`; GS_E_UNSUPPORTED with SH colours (color_dim 27 / 48: the image also depends on the pose through
+ * the pixels' ray directions).  Everything is checked before anything is enqueued. */
+int gs_frame_backward_adam_pose(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam, gs_stream_t stream);
 
 /* Device address of the frame's overflow counter (inside the caller's workspace; 64-bit, 0 = the last forward of this
  * frame description fitted its pair capacity, else the pair count it would have needed).  No launch, no copy. */

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/gs_abi.h"
 
 #define GS_WAVE 64
@@ -40,6 +42,21 @@ void gs_set_error(const char *fmt, ...);
 
 static inline int64_t gs_div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t gs_align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+
+// A compile-time integer handed to a generic lambda: how a stage picks the instantiation of its kernel
+template <int V>
+using gs_int = std::integral_constant<int, V>;
+
+// fn(gs_int<48>), fn(gs_int<27>) or fn(gs_int<3>): a colour dimension the caller has validated to be one of the three
+template <class Fn>
+static inline void gs_for_color_dim(int color_dim, Fn fn) {
+    if (color_dim == 48)
+        fn(gs_int<48>{});
+    else if (color_dim == 27)
+        fn(gs_int<27>{});
+    else
+        fn(gs_int<3>{});
+}
 
 // ---- device helpers ---------------------------------------------------------------------
 #ifdef __HIPCC__

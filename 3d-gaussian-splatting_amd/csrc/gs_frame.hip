@@ -393,6 +393,20 @@ extern "C" int gs_frame_forward_profile(const gs_frame *f, float *stage_ms_host,
     return frame_forward_impl(f, (hipStream_t)stream, stage_ms_host);
 }
 
+// GS_FRAME_POSE_GRAD with SH colours: what every backward entry point answers
+static int refuse_sh_pose(const char *entry) {
+    gs_set_error("%s: GS_FRAME_POSE_GRAD needs rgb colours (color_dim 3): with SH colours the image also depends on the pose "
+                 "through the pixels' ray directions", entry);
+    return GS_E_UNSUPPORTED;
+}
+
+// GS_FRAME_POSE_GRAD frame without Gaussians: no partial sums, the pose gradient is zeros, written all the same
+static int zero_pose_grad(const gs_frame *f, hipStream_t s) {
+    GS_HIP(hipMemsetAsync(f->grad_rot, 0, 9 * sizeof(float), s));
+    GS_HIP(hipMemsetAsync(f->grad_tran, 0, 3 * sizeof(float), s));
+    return 0;
+}
+
 // part: 0 = the whole backward; GS_BWD_RASTER (1) = the raster backward only (per-pair gradient rows), then any of
 // GS_BWD_GEOMETRY (2) = grad_pos / quat / scale and GS_BWD_COLOR (4) = grad_opa / rgb from those rows, in any order.
 static int frame_backward_impl(const gs_frame *f, const float *grad_image, float *grad_pos, float *grad_quat,
@@ -413,24 +427,14 @@ static int frame_backward_impl(const gs_frame *f, const float *grad_image, float
     GS_CHECK_ARG(((uintptr_t)grad_quat & 15) == 0, "grad_quat must be 16-byte aligned");
     const bool pose = (f->flags & GS_FRAME_POSE_GRAD) != 0;
     if (pose) {  // (everything refused before anything is enqueued)
-        if (f->color_dim != 3) {
-            gs_set_error("gs_frame_backward: GS_FRAME_POSE_GRAD needs rgb colours (color_dim 3): with SH colours the image "
-                         "also depends on the pose through the pixels' ray directions");
-            return GS_E_UNSUPPORTED;
-        }
+        if (f->color_dim != 3) return refuse_sh_pose("gs_frame_backward");
         if (part == -1 || g_begin != 0 || g_end != f->N) {
             gs_set_error("gs_frame_backward_slice: GS_FRAME_POSE_GRAD frames are not supported");
             return GS_E_UNSUPPORTED;
         }
     }
     const bool pose_out = pose && (part == 0 || part == GS_BWD_GEOMETRY);  // the parts that write grad_rot / grad_tran
-    if (f->N == 0) {
-        if (pose_out) {  // no partial sums: zeros, written all the same
-            GS_HIP(hipMemsetAsync(f->grad_rot, 0, 9 * sizeof(float), s));
-            GS_HIP(hipMemsetAsync(f->grad_tran, 0, 3 * sizeof(float), s));
-        }
-        return 0;
-    }
+    if (f->N == 0) return pose_out ? zero_pose_grad(f, s) : 0;
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
     uint64_t *skeys, *okeys;
     uint32_t *sids;
@@ -472,33 +476,6 @@ extern "C" int gs_frame_backward(const gs_frame *f, const float *grad_image, flo
                                (hipStream_t)stream, nullptr);
 }
 
-extern "C" int gs_frame_backward_adam(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
-                                      gs_stream_t stream) {
-    int rc = validate(f);
-    if (rc) return rc;
-    if (f->flags & GS_FRAME_AUX) {
-        gs_set_error("gs_frame_backward_adam: GS_FRAME_AUX frames are not supported (use gs_frame_backward + an optimizer step)");
-        return GS_E_UNSUPPORTED;
-    }
-    if (f->flags & GS_FRAME_POSE_GRAD) {
-        gs_set_error("gs_frame_backward_adam: GS_FRAME_POSE_GRAD frames are not supported (use gs_frame_backward + an "
-                     "optimizer step)");
-        return GS_E_UNSUPPORTED;
-    }
-    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam needs a training forward (image_padded kept)");
-    GS_CHECK_ARG(grad_image && adam, "null pointer");
-    if ((rc = gs_validate_adam_fused(f, adam))) return rc;  // before anything is enqueued
-    if (f->N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
-    uint64_t *skeys, *okeys;
-    uint32_t *sids;
-    sorted_buffers(f, ws, &skeys, &sids, &okeys);
-    const bool prepared = join_prepared(f, s);
-    if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
-    return gs_stage_project_backward_adam(f, ws, adam, s);
-}
-
 // An all-zero [bytes] device buffer for a NULL grad_image of gs_frame_backward_adam_aux: the raster backward reads dL/dimage
 // of every pixel, and its kernels are left as they are.  One buffer per device, owned by the library, allocated (and
 // cleared, once) at the first call that needs it and grown when a larger image arrives; only ever read afterwards.  Growing
@@ -525,66 +502,72 @@ static int zero_image(size_t bytes, const float **out) {
     return 0;
 }
 
-// gs_frame_backward_adam for GS_FRAME_AUX training frames: the raster backward takes f->grad_depth / f->grad_alpha with
-// grad_image, and the projection backward's fused step adds the depth map's position term before it steps.
-extern "C" int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
-                                          gs_stream_t stream) {
-    int rc = validate(f);
-    if (rc) return rc;
-    GS_CHECK_ARG((f->flags & GS_FRAME_AUX) != 0, "the frame is not flagged GS_FRAME_AUX (gs_frame_backward_adam takes plain frames)");
-    if (f->flags & GS_FRAME_POSE_GRAD) {
-        gs_set_error("gs_frame_backward_adam_aux: GS_FRAME_POSE_GRAD frames are not supported (use gs_frame_backward + an "
-                     "optimizer step)");
-        return GS_E_UNSUPPORTED;
+// The fused step: the raster backward, then the projection backward with the optimizer step in its epilogue, in the variant
+// f->flags ask for (gs_stage_project_backward_adam).  GS_FRAME_AUX: the raster backward takes f->grad_depth / f->grad_alpha with
+// grad_image (which may be NULL: zeros) and the step adds the depth map's position term; GS_FRAME_POSE_GRAD: the pose terms
+// with the step, then their reduction into f->grad_rot / f->grad_tran.  Behind validate(f) and the flag preconditions of the
+// entry point `entry`, which the refusals name; everything is refused before anything is enqueued.
+static int frame_backward_adam_impl(const char *entry, const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
+                                    hipStream_t s) {
+    const bool aux = (f->flags & GS_FRAME_AUX) != 0, pose = (f->flags & GS_FRAME_POSE_GRAD) != 0;
+    if (!(f->training && f->image_padded)) {
+        gs_set_error("%s: invalid argument: %s needs a training forward (image_padded kept)", entry, entry);
+        return GS_E_INVALID;
     }
-    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam_aux needs a training forward (image_padded kept)");
-    GS_CHECK_ARG(adam, "null pointer");
-    if ((rc = gs_validate_adam_fused(f, adam))) return rc;  // before anything is enqueued
-    if (f->N == 0) return 0;
+    if (!(adam && (aux || grad_image))) {
+        gs_set_error("%s: invalid argument: null pointer", entry);
+        return GS_E_INVALID;
+    }
+    int rc = gs_validate_adam_fused(f, adam);  // (a call rejected behind the raster backward would leave the caller's step counter ahead)
+    if (rc) return rc;
+    if (f->N == 0) return pose ? zero_pose_grad(f, s) : 0;
     if (!grad_image && (rc = zero_image(sizeof(float) * 3 * (size_t)f->width * (size_t)f->height, &grad_image))) return rc;
-    hipStream_t s = (hipStream_t)stream;
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
     uint64_t *skeys, *okeys;
     uint32_t *sids;
     sorted_buffers(f, ws, &skeys, &sids, &okeys);
     const bool prepared = join_prepared(f, s);
     if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
-    return gs_stage_project_backward_adam(f, ws, adam, s, true);
+    if ((rc = gs_stage_project_backward_adam(f, ws, adam, s))) return rc;
+    return pose ? gs_stage_pose_finalize(f, ws, s) : 0;
 }
 
-// The fused step of a GS_FRAME_POSE_GRAD training frame (rgb colours), with or without GS_FRAME_AUX: the raster backward, the
-// projection backward with the pose terms and the optimizer step in one kernel, the pose gradient's reduction.  The map takes
-// the step gs_frame_backward + gs_adam_step give it, f->grad_rot / f->grad_tran what that gs_frame_backward writes, bit for bit.
+// a flag this entry point does not take
+static int refuse_flag(const char *entry, const char *flag) {
+    gs_set_error("%s: %s frames are not supported (use gs_frame_backward + an optimizer step)", entry, flag);
+    return GS_E_UNSUPPORTED;
+}
+
+// plain training frames
+extern "C" int gs_frame_backward_adam(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
+                                      gs_stream_t stream) {
+    int rc = validate(f);
+    if (rc) return rc;
+    if (f->flags & GS_FRAME_AUX) return refuse_flag(__func__, "GS_FRAME_AUX");
+    if (f->flags & GS_FRAME_POSE_GRAD) return refuse_flag(__func__, "GS_FRAME_POSE_GRAD");
+    return frame_backward_adam_impl(__func__, f, grad_image, adam, (hipStream_t)stream);
+}
+
+// GS_FRAME_AUX training frames
+extern "C" int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
+                                          gs_stream_t stream) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG((f->flags & GS_FRAME_AUX) != 0, "the frame is not flagged GS_FRAME_AUX (gs_frame_backward_adam takes plain frames)");
+    if (f->flags & GS_FRAME_POSE_GRAD) return refuse_flag(__func__, "GS_FRAME_POSE_GRAD");
+    return frame_backward_adam_impl(__func__, f, grad_image, adam, (hipStream_t)stream);
+}
+
+// GS_FRAME_POSE_GRAD training frames (rgb colours), with or without GS_FRAME_AUX.  The map takes the step gs_frame_backward +
+// gs_adam_step give it, f->grad_rot / f->grad_tran what that gs_frame_backward writes, bit for bit.
 extern "C" int gs_frame_backward_adam_pose(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam,
                                            gs_stream_t stream) {
     int rc = validate(f);
     if (rc) return rc;
     GS_CHECK_ARG((f->flags & GS_FRAME_POSE_GRAD) != 0,
                  "the frame is not flagged GS_FRAME_POSE_GRAD (gs_frame_backward_adam / _adam_aux take frames without a pose gradient)");
-    if (f->color_dim != 3) {
-        gs_set_error("gs_frame_backward_adam_pose: GS_FRAME_POSE_GRAD needs rgb colours (color_dim 3): with SH colours the image "
-                     "also depends on the pose through the pixels' ray directions");
-        return GS_E_UNSUPPORTED;
-    }
-    const bool aux = (f->flags & GS_FRAME_AUX) != 0;
-    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_adam_pose needs a training forward (image_padded kept)");
-    GS_CHECK_ARG(adam && (aux || grad_image), "null pointer");
-    if ((rc = gs_validate_adam_fused(f, adam))) return rc;  // before anything is enqueued
-    hipStream_t s = (hipStream_t)stream;
-    if (f->N == 0) {  // no partial sums: zeros, written all the same (frame_backward_impl)
-        GS_HIP(hipMemsetAsync(f->grad_rot, 0, 9 * sizeof(float), s));
-        GS_HIP(hipMemsetAsync(f->grad_tran, 0, 3 * sizeof(float), s));
-        return 0;
-    }
-    if (!grad_image && (rc = zero_image(sizeof(float) * 3 * (size_t)f->width * (size_t)f->height, &grad_image))) return rc;
-    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
-    uint64_t *skeys, *okeys;
-    uint32_t *sids;
-    sorted_buffers(f, ws, &skeys, &sids, &okeys);
-    const bool prepared = join_prepared(f, s);
-    if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
-    if ((rc = gs_stage_project_backward_adam(f, ws, adam, s, aux, true))) return rc;
-    return gs_stage_pose_finalize(f, ws, s);
+    if (f->color_dim != 3) return refuse_sh_pose(__func__);
+    return frame_backward_adam_impl(__func__, f, grad_image, adam, (hipStream_t)stream);
 }
 
 extern "C" int gs_frame_backward_part(const gs_frame *f, const float *grad_image, float *grad_pos, float *grad_quat,

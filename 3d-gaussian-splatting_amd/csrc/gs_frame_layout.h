@@ -520,9 +520,9 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
 int gs_stage_project_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, float *grad_quat,
                               float *grad_scale, float *grad_opa, float *grad_rgb, int part, int64_t g_begin,
                               int64_t g_end, hipStream_t stream);
-// aux: GS_FRAME_AUX frames; pose: GS_FRAME_POSE_GRAD frames (rgb colours), the partial rows of the pose gradient with the step
-int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream,
-                                   bool aux = false, bool pose = false);
+// the variant f->flags ask for: GS_FRAME_AUX, GS_FRAME_POSE_GRAD (rgb colours: the partial rows of the pose gradient with the
+// step); `a` has passed gs_validate_adam_fused
+int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream);
 int gs_validate_adam_fused(const gs_frame *f, const gs_adam_fused *a);
 int gs_stage_scan_emit(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
 int gs_stage_tile_sort(const gs_frame *f, const gs_frame_ws &ws, uint64_t *keys, uint32_t *ids, uint64_t *scratch,

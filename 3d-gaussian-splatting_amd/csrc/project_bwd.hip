@@ -583,21 +583,6 @@ extern "C" int gs_global_culling_backward(const float *pos, const float *quat, c
 }
 
 // ================================================================= frame stages (internal)
-// A compile-time integer handed to a generic lambda: how a stage picks the instantiation of its kernel
-template <int V>
-using Int = std::integral_constant<int, V>;
-
-// fn(Int<48>), fn(Int<27>) or fn(Int<3>): the frame's colour dimension
-template <class Fn>
-static void for_color_dim(int color_dim, Fn fn) {
-    if (color_dim == 48)
-        fn(Int<48>{});
-    else if (color_dim == 27)
-        fn(Int<27>{});
-    else
-        fn(Int<3>{});
-}
-
 // One launch of frame_project_backward_kernel, frame_project_backward_adam_aux_kernel, frame_project_backward_pose_kernel or
 // frame_project_backward_adam_pose_kernel over the Gaussians below `n`: the arguments they have in common, then `tail` (what
 // each takes behind max_pairs).
@@ -616,16 +601,13 @@ int gs_stage_sh_big_rows(const gs_frame *f, const gs_frame_ws &ws, hipStream_t s
     const int blocks = 512;
     const int64_t per_block = gs_div_up(f->N, blocks);  // (the kernel walks its slice 1,024 Gaussians at a time)
     const gs_frame_geom G = gs_frame_geometry(f);
-    auto launch = [&](auto cd) {
-        hipLaunchKernelGGL(sh_big_rows_kernel<decltype(cd)::value>, dim3(blocks), dim3(1024), 0, stream, ws.rects,
-                           ws.pair_offsets, ws.rows, (const unsigned long long *)ws.stop_keys, ws.rec_geom, (uint32_t)G.ntx,
-                           (uint32_t)G.n_tiles, f->tile_culling_method, gs_frame_dist_cull(f), f->N, (uint64_t)f->max_pairs,
-                           per_block);
-    };
-    if (f->color_dim == 48)
-        launch(Int<48>{});
-    else
-        launch(Int<27>{});
+    gs_for_color_dim(f->color_dim, [&](auto cd) {
+        constexpr int CD = decltype(cd)::value;
+        if constexpr (CD != 3)  // (rgb frames returned above: no such kernel)
+            hipLaunchKernelGGL(sh_big_rows_kernel<CD>, dim3(blocks), dim3(1024), 0, stream, ws.rects, ws.pair_offsets, ws.rows,
+                               (const unsigned long long *)ws.stop_keys, ws.rec_geom, (uint32_t)G.ntx, (uint32_t)G.n_tiles,
+                               f->tile_culling_method, gs_frame_dist_cull(f), f->N, (uint64_t)f->max_pairs, per_block);
+    });
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -636,7 +618,7 @@ int gs_stage_aux_depth_backward(const gs_frame *f, const gs_frame_ws &ws, float 
                                 hipStream_t stream) {
     if (g_end <= g_begin) return 0;
     const unsigned grid = (unsigned)gs_div_up(g_end - g_begin, 256);
-    for_color_dim(f->color_dim, [&](auto cd) {
+    gs_for_color_dim(f->color_dim, [&](auto cd) {
         hipLaunchKernelGGL(frame_aux_depth_backward_kernel<decltype(cd)::value>, dim3(grid), dim3(256), 0, stream, f->pos,
                            g_end, g_begin, make_params(f), ws.rec_geom, ws.rows, (const unsigned long long *)ws.stop_keys,
                            gs_frame_dist_cull(f), ws.pair_offsets, ws.rects, (uint64_t)f->max_pairs, grad_pos);
@@ -664,9 +646,9 @@ int gs_stage_project_backward_pose(const gs_frame *f, const gs_frame_ws &ws, flo
                                 f->N, grad_pos, (float4 *)grad_quat, grad_scale, grad_opa, grad_rgb, pw.proj);
     };
     if (part == 1)
-        launch(Int<1>{});
+        launch(gs_int<1>{});
     else
-        launch(Int<0>{});
+        launch(gs_int<0>{});
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -697,10 +679,11 @@ int gs_validate_adam_fused(const gs_frame *f, const gs_adam_fused *a) {
     return 0;
 }
 
-int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream,
-                                   bool aux, bool pose) {
-    int vrc = gs_validate_adam_fused(f, a);
-    if (vrc) return vrc;
+int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, const gs_adam_fused *a, hipStream_t stream) {
+    // (no gs_validate_adam_fused here: every caller has run it, before it enqueued the raster backward)
+    // aux: the variant that adds the depth map's position term in front of the step (gs_frame_backward_adam_aux);
+    // pose: the partial rows of the pose gradient with the step (gs_frame_backward_adam_pose), one row (aux: two) per workgroup
+    const bool aux = (f->flags & GS_FRAME_AUX) != 0, pose = (f->flags & GS_FRAME_POSE_GRAD) != 0;
     GS_CHECK_ARG(!pose || f->color_dim == 3, "the fused step with a pose gradient needs rgb colours");
     if (f->N <= 0) return 0;
     const gs_frame_pose_ws pw = gs_frame_pose_carve(pose ? f->pose_workspace : nullptr, f->N);
@@ -729,13 +712,11 @@ int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, con
     A.skip_if_nonzero = (const unsigned long long *)a->skip_if_nonzero;
     // (11 + C) parameters x 16 bytes of arrays: beyond the Infinity Cache the moments stream with non-temporal accesses (adam.hip)
     const bool nt = (unsigned long long)f->N * (unsigned long long)(11 + f->color_dim) * 16ull > (300ull << 20);
-    for_color_dim(f->color_dim, [&](auto cd) {
+    gs_for_color_dim(f->color_dim, [&](auto cd) {
         constexpr int CD = decltype(cd)::value, BLK = CD == 3 ? 256 : 128;
         const unsigned grid = (unsigned)gs_div_up(f->N, BLK);
         auto launch = [&](auto mode) {
             constexpr int MODE = decltype(mode)::value;
-            // aux: GS_FRAME_AUX (gs_frame_backward_adam_aux), the variant that adds the depth map's position term in front of the step;
-            // pose: GS_FRAME_POSE_GRAD (gs_frame_backward_adam_pose), grid = pw.rows: one row (aux: two) of partial sums per workgroup
             if (pose) {
                 if constexpr (CD == 3) {
                     if (aux)
@@ -752,9 +733,9 @@ int gs_stage_project_backward_adam(const gs_frame *f, const gs_frame_ws &ws, con
                                         (int64_t)0, nullptr, nullptr, nullptr, nullptr, nullptr, A);
         };
         if (nt)
-            launch(Int<2>{});
+            launch(gs_int<2>{});
         else
-            launch(Int<1>{});
+            launch(gs_int<1>{});
     });
     GS_CHECK_LAUNCH();
     return 0;
@@ -765,7 +746,7 @@ int gs_stage_project_backward(const gs_frame *f, const gs_frame_ws &ws, float *g
                               float *grad_scale, float *grad_opa, float *grad_rgb, int part, int64_t g_begin,
                               int64_t g_end, hipStream_t stream) {
     if (g_end <= g_begin) return 0;
-    for_color_dim(f->color_dim, [&](auto cd) {
+    gs_for_color_dim(f->color_dim, [&](auto cd) {
         constexpr int CD = decltype(cd)::value, BLK = CD == 3 ? 256 : 128;
         auto launch = [&](auto pt) {
             launch_project_backward(frame_project_backward_kernel<CD, decltype(pt)::value>,
@@ -773,11 +754,11 @@ int gs_stage_project_backward(const gs_frame *f, const gs_frame_ws &ws, float *g
                                     (float4 *)grad_quat, grad_scale, grad_opa, grad_rgb, AdamFusedDev{});
         };
         if (part == 1)
-            launch(Int<1>{});
+            launch(gs_int<1>{});
         else if (part == 2)
-            launch(Int<2>{});
+            launch(gs_int<2>{});
         else
-            launch(Int<0>{});
+            launch(gs_int<0>{});
     });
     GS_CHECK_LAUNCH();
     return 0;

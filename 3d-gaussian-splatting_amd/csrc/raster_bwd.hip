@@ -1847,18 +1847,22 @@ void launch_bwd_sig(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, con
         hipLaunchKernelGGL((raster_backward_kernel<CDIM, false>), dim3(grid), dim3(64 * WPB), 0, stream, S, G, I, O);
 }
 
-template <int CDIM, bool FRAME>
-void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const BwdOut &O, int64_t max_buckets,
-                hipStream_t stream) {
-    // Grid of the one-wave-per-bucket kernels of the frame path: the work list's capacity, but at most GS_BWD_GRID_CAP waves.
-    // The kernels walk the list with the grid as the stride, so the cap only decides how many waves come up empty (a frame
-    // whose tiles saturate early fills a third of the capacity) or take a second bucket (a frame beyond the cap: the waves
-    // are still 8 x the device's resident slots, i.e. fresh waves keep arriving while others are in their load phase -- what
-    // the measured-and-dropped persistent grids of round 2 lacked).
+// Grid of the one-wave-per-bucket kernels of the frame path: the work list's capacity, but at most GS_BWD_GRID_CAP waves.
+// The kernels walk the list with the grid as the stride, so the cap only decides how many waves come up empty (a frame
+// whose tiles saturate early fills a third of the capacity) or take a second bucket (a frame beyond the cap: the waves
+// are still 8 x the device's resident slots, i.e. fresh waves keep arriving while others are in their load phase -- what
+// the measured-and-dropped persistent grids of round 2 lacked).
 #ifndef GS_BWD_GRID_CAP
 #define GS_BWD_GRID_CAP 40960
 #endif
-    const unsigned fgrid = (unsigned)(max_buckets > 0 ? (max_buckets < GS_BWD_GRID_CAP ? max_buckets : GS_BWD_GRID_CAP) : 1);
+unsigned bwd_frame_grid(int64_t max_buckets) {
+    return (unsigned)(max_buckets > 0 ? (max_buckets < GS_BWD_GRID_CAP ? max_buckets : GS_BWD_GRID_CAP) : 1);
+}
+
+template <int CDIM, bool FRAME>
+void launch_bwd(const RasterSrc &S, const RasterGeom &G, const BwdIn &I, const BwdOut &O, int64_t max_buckets,
+                hipStream_t stream) {
+    const unsigned fgrid = bwd_frame_grid(max_buckets);
     if constexpr (FRAME && CDIM > 3) {  // SH frames: the matrix pipe, one workgroup per work item
         const unsigned mgrid = gs_bwd_mfma_grid(G.ntx * G.nty, max_buckets);
         if (gs_bwd_mfma_waves(G.ntx * G.nty) == 2)
@@ -2050,24 +2054,17 @@ int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uin
                (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr, 0u,
                (f->flags & GS_FRAME_BWD_ROWS) ? 1u : 0u, ws.mfma_items, ws.mfma_n_items};
     BwdOut O = {ws.rows, ws.bwd_exec_rows, ws.pair_offsets, ws.rects, (uint64_t)f->max_pairs, nullptr, nullptr, nullptr, nullptr};
-    if (f->flags & GS_FRAME_AUX) {
-        // every bucket of the work list (gs_stage_backward_prepare builds it for aux frames of every colour model) on the
-        // one-wave-per-bucket pixel kernel, grid as in launch_bwd
-        const AuxBwdIn X = {(const float2 *)f->aux_padded, gs_frame_aux(f).ckpt, f->grad_depth, f->grad_alpha};
-        const int64_t mb = ws.max_buckets;
-        const unsigned fgrid = (unsigned)(mb > 0 ? (mb < GS_BWD_GRID_CAP ? mb : GS_BWD_GRID_CAP) : 1);
-        if (f->color_dim == 48)
-            hipLaunchKernelGGL(raster_aux_backward_kernel<48>, dim3(fgrid), dim3(64), 0, stream, S, G, I, O, X);
-        else if (f->color_dim == 27)
-            hipLaunchKernelGGL(raster_aux_backward_kernel<27>, dim3(fgrid), dim3(64), 0, stream, S, G, I, O, X);
-        else
-            hipLaunchKernelGGL(raster_aux_backward_kernel<3>, dim3(fgrid), dim3(64), 0, stream, S, G, I, O, X);
-    } else if (f->color_dim == 48)
-        launch_bwd<48, true>(S, G, I, O, ws.max_buckets, stream);
-    else if (f->color_dim == 27)
-        launch_bwd<27, true>(S, G, I, O, ws.max_buckets, stream);
-    else
-        launch_bwd<3, true>(S, G, I, O, ws.max_buckets, stream);
+    gs_for_color_dim(f->color_dim, [&](auto cd) {
+        constexpr int CD = decltype(cd)::value;
+        if (f->flags & GS_FRAME_AUX) {
+            // every bucket of the work list (gs_stage_backward_prepare builds it for aux frames of every colour model) on the
+            // one-wave-per-bucket pixel kernel
+            const AuxBwdIn X = {(const float2 *)f->aux_padded, gs_frame_aux(f).ckpt, f->grad_depth, f->grad_alpha};
+            hipLaunchKernelGGL(raster_aux_backward_kernel<CD>, dim3(bwd_frame_grid(ws.max_buckets)), dim3(64), 0, stream, S, G,
+                               I, O, X);
+        } else
+            launch_bwd<CD, true>(S, G, I, O, ws.max_buckets, stream);
+    });
     GS_CHECK_LAUNCH();
     // SH rows of Gaussians that cover hundreds of tiles are summed here, once, by whole workgroups (project_bwd.hip)
     return gs_stage_sh_big_rows(f, ws, stream);

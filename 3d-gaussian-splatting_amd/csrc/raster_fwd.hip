@@ -1070,46 +1070,34 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
     const uint32_t *cut_in = culled && !second_pass ? gs_frame_cut_table(f, ws) : nullptr;
     unsigned long long *ranpast = ws.counters + GS_CNT_RANPAST;
     const unsigned long long *gate = second_pass ? ranpast : nullptr;
-#define GS_LAUNCH_FRAME_FWD(CD)                                                                                        \
-    do {                                                                                                               \
-        if (f->training)                                                                                               \
-            launch_fwd<CD, true, true, false>(S, G, ws.tile_ranges, f->image_padded, f->image, ws.ckpt, ws.tile_nproc, \
-                                              0, stream, cs, cf, order, cost, nullptr, nullptr, ranpast, nullptr);     \
-        else                                                                                                           \
-            launch_fwd<CD, true, false, false>(S, G, ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, 0,   \
-                                               stream, cs, cf, order, cost, cut_in, ws.cut, ranpast, gate);            \
-    } while (0)
     if (aux) {
         if (!fwd_plan().order) order = nullptr;
         const uint32_t T = (uint32_t)FG.n_tiles;
         const uint32_t grid = gate ? (T < 1024u ? T : 1024u) : fwd_grid(T);
         const gs_frame_aux_ws aw = gs_frame_aux(f);
         AuxFwdOut X = {(float2 *)f->aux_padded, f->depth, f->alpha, aw.ckpt};
-#define GS_LAUNCH_AUX_FWD(CD)                                                                                           \
-    do {                                                                                                                \
-        if (f->training)                                                                                                \
-            hipLaunchKernelGGL((raster_aux_forward_kernel<CD, true>), dim3(grid), dim3(FWD_THREADS), 0, stream, S, G,    \
-                               ws.tile_ranges, f->image_padded, f->image, ws.ckpt, ws.tile_nproc, T, order, cost,       \
-                               nullptr, nullptr, ranpast, nullptr, X);                                                  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((raster_aux_forward_kernel<CD, false>), dim3(grid), dim3(FWD_THREADS), 0, stream, S, G,   \
-                               ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, T, order, cost, cut_in,     \
-                               ws.cut, ranpast, gate, X);                                                               \
-    } while (0)
-        if (f->color_dim == 48)
-            GS_LAUNCH_AUX_FWD(48);
-        else if (f->color_dim == 27)
-            GS_LAUNCH_AUX_FWD(27);
-        else
-            GS_LAUNCH_AUX_FWD(3);
-#undef GS_LAUNCH_AUX_FWD
-    } else if (f->color_dim == 48)
-        GS_LAUNCH_FRAME_FWD(48);
-    else if (f->color_dim == 27)
-        GS_LAUNCH_FRAME_FWD(27);
-    else
-        GS_LAUNCH_FRAME_FWD(3);
-#undef GS_LAUNCH_FRAME_FWD
+        gs_for_color_dim(f->color_dim, [&](auto cd) {
+            constexpr int CD = decltype(cd)::value;
+            if (f->training)
+                hipLaunchKernelGGL((raster_aux_forward_kernel<CD, true>), dim3(grid), dim3(FWD_THREADS), 0, stream, S, G,
+                                   ws.tile_ranges, f->image_padded, f->image, ws.ckpt, ws.tile_nproc, T, order, cost, nullptr,
+                                   nullptr, ranpast, nullptr, X);
+            else
+                hipLaunchKernelGGL((raster_aux_forward_kernel<CD, false>), dim3(grid), dim3(FWD_THREADS), 0, stream, S, G,
+                                   ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, T, order, cost, cut_in, ws.cut,
+                                   ranpast, gate, X);
+        });
+    } else {
+        gs_for_color_dim(f->color_dim, [&](auto cd) {
+            constexpr int CD = decltype(cd)::value;
+            if (f->training)
+                launch_fwd<CD, true, true, false>(S, G, ws.tile_ranges, f->image_padded, f->image, ws.ckpt, ws.tile_nproc, 0,
+                                                  stream, cs, cf, order, cost, nullptr, nullptr, ranpast, nullptr);
+            else
+                launch_fwd<CD, true, false, false>(S, G, ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, 0, stream,
+                                                   cs, cf, order, cost, cut_in, ws.cut, ranpast, gate);
+        });
+    }
     GS_CHECK_LAUNCH();
     if (dense) {
         const uint32_t T = (uint32_t)FG.n_tiles, cap = (uint32_t)gs_seg_items_cap(f->max_pairs, FG.n_tiles);
@@ -1117,35 +1105,23 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
         hipLaunchKernelGGL(seg_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.cont_flag, ws.tile_ranges, T, cap,
                            ws.seg_item_base, ws.seg_items, n_items);
         GS_CHECK_LAUNCH();
-#define GS_LAUNCH_SEG(CD, CK)                                                                                          \
-    do {                                                                                                               \
-        hipLaunchKernelGGL((raster_segment_kernel<CD, CK, 1>), dim3(cap), dim3(FWD_THREADS), 0, stream, S, G,          \
-                           ws.tile_ranges, ws.seg_items, n_items, ws.cont_state, ws.seg_P, ws.seg_C, ws.seg_nproc,    \
-                           ws.ckpt);                                                                                   \
-        hipLaunchKernelGGL((raster_segment_kernel<CD, CK, 2>), dim3(cap), dim3(FWD_THREADS), 0, stream, S, G,          \
-                           ws.tile_ranges, ws.seg_items, n_items, ws.cont_state, ws.seg_P, ws.seg_C, ws.seg_nproc,    \
-                           ws.ckpt);                                                                                   \
-        hipLaunchKernelGGL((seg_combine_kernel<CK>), dim3(T, CK ? 16 : 1), dim3(256), 0, stream, G, ws.tile_ranges,     \
-                           ws.cont_flag,                                                                               \
-                           ws.seg_item_base, ws.cont_state, ws.seg_C, ws.seg_nproc, ws.ckpt, ws.tile_nproc,           \
-                           f->image_padded, f->image);                                                                 \
-    } while (0)
-        if (f->training) {
-            if (f->color_dim == 48)
-                GS_LAUNCH_SEG(48, true);
-            else if (f->color_dim == 27)
-                GS_LAUNCH_SEG(27, true);
+        gs_for_color_dim(f->color_dim, [&](auto cd) {
+            constexpr int CD = decltype(cd)::value;
+            auto launch = [&](auto ck) {  // CK: a training frame keeps its checkpoints
+                constexpr bool CK = decltype(ck)::value;
+                hipLaunchKernelGGL((raster_segment_kernel<CD, CK, 1>), dim3(cap), dim3(FWD_THREADS), 0, stream, S, G,
+                                   ws.tile_ranges, ws.seg_items, n_items, ws.cont_state, ws.seg_P, ws.seg_C, ws.seg_nproc, ws.ckpt);
+                hipLaunchKernelGGL((raster_segment_kernel<CD, CK, 2>), dim3(cap), dim3(FWD_THREADS), 0, stream, S, G,
+                                   ws.tile_ranges, ws.seg_items, n_items, ws.cont_state, ws.seg_P, ws.seg_C, ws.seg_nproc, ws.ckpt);
+                hipLaunchKernelGGL((seg_combine_kernel<CK>), dim3(T, CK ? 16 : 1), dim3(256), 0, stream, G, ws.tile_ranges,
+                                   ws.cont_flag, ws.seg_item_base, ws.cont_state, ws.seg_C, ws.seg_nproc, ws.ckpt, ws.tile_nproc,
+                                   f->image_padded, f->image);
+            };
+            if (f->training)
+                launch(std::true_type{});
             else
-                GS_LAUNCH_SEG(3, true);
-        } else {
-            if (f->color_dim == 48)
-                GS_LAUNCH_SEG(48, false);
-            else if (f->color_dim == 27)
-                GS_LAUNCH_SEG(27, false);
-            else
-                GS_LAUNCH_SEG(3, false);
-        }
-#undef GS_LAUNCH_SEG
+                launch(std::false_type{});
+        });
     }
     GS_CHECK_LAUNCH();
     return 0;

@@ -300,15 +300,10 @@ extern "C" int gs_seed_apply(const float *image, const float *range, const gs_se
     const SeedOut O = {pos, quat, scale, opa, rgb};
     hipStream_t s = (hipStream_t)stream;
     const long long *cnt = (const long long *)counts_dev;
-    if (opts->color_dim == 3)
-        hipLaunchKernelGGL(seed_apply_kernel<3>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P, O, offset, capacity,
-                           w.masks, w.block_counts, cnt);
-    else if (opts->color_dim == 27)
-        hipLaunchKernelGGL(seed_apply_kernel<27>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P, O, offset, capacity,
-                           w.masks, w.block_counts, cnt);
-    else
-        hipLaunchKernelGGL(seed_apply_kernel<48>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P, O, offset, capacity,
-                           w.masks, w.block_counts, cnt);
+    gs_for_color_dim(opts->color_dim, [&](auto cd) {
+        hipLaunchKernelGGL(seed_apply_kernel<decltype(cd)::value>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P, O,
+                           offset, capacity, w.masks, w.block_counts, cnt);
+    });
     GS_CHECK_LAUNCH();
     return 0;
 }

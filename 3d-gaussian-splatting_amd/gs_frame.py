@@ -675,6 +675,18 @@ class FrameRenderer:
         f.grad_alpha = grad_alpha.data_ptr() if grad_alpha is not None else None
         return grad_depth, grad_alpha
 
+    @staticmethod
+    def _checked_grad_image(f, grad_image, none_ok: bool):
+        """dL/d(image), contiguous and checked (float32 [H,W,3]); None (= zero) where the frame's backward takes it."""
+        if grad_image is None:
+            if not none_ok:
+                raise RuntimeError("grad_image may be None for frames rendered with aux=True only")
+            return None
+        grad_image = grad_image.contiguous()
+        if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
+            raise RuntimeError("grad_image must be float32 [H,W,3]")
+        return grad_image
+
     def backward_adam(self, grad_image, adam, grad_depth=None, grad_alpha=None, grad_pose=None):
         """``backward`` with the optimizer step fused into its last kernel (gs_frame_backward_adam, include/
         gs_abi.h): the frame's own parameter tensors are updated in place, no gradient is written.  ``adam``: a filled
@@ -696,37 +708,15 @@ class FrameRenderer:
         for ptr, t in zip((f.pos, f.quat, f.scale, f.opa, f.rgb), self._keep[:5]):
             if int(ptr or 0) != t.data_ptr():
                 raise RuntimeError("backward_adam(): the frame was rendered from tensors that are no longer alive")
-        if grad_pose is not None:
-            if aux:
-                grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
-            if grad_image is not None:
-                grad_image = grad_image.contiguous()
-                if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
-                    raise RuntimeError("grad_image must be float32 [H,W,3]")
-            elif not aux:
-                raise RuntimeError("grad_image may be None for frames rendered with aux=True only")
-            g = self._pose_frame(f, grad_pose, 0)  # (refuses SH colours)
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.gs_frame_backward_adam_pose(C.byref(g), grad_image.data_ptr() if grad_image is not None
-                                                            else None, C.byref(adam), self._stream().cuda_stream),
-                           "gs_frame_backward_adam_pose")
-            self._bwd_serial = self._frame_serial
-            return
         if aux:
-            grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
-            if grad_image is not None:
-                grad_image = grad_image.contiguous()
-                if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
-                    raise RuntimeError("grad_image must be float32 [H,W,3]")
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.gs_frame_backward_adam_aux(C.byref(f), grad_image.data_ptr() if grad_image is not None
-                                                           else None, C.byref(adam), self._stream().cuda_stream),
-                           "gs_frame_backward_adam_aux")
-            self._bwd_serial = self._frame_serial
-            return
+            grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)  # (kept alive until the call below)
+        grad_image = self._checked_grad_image(f, grad_image, none_ok=aux)
+        if grad_pose is not None:
+            f = self._pose_frame(f, grad_pose, 0)  # (refuses SH colours)
+        name = "gs_frame_backward_adam" + ("_pose" if grad_pose is not None else "_aux" if aux else "")
         with torch.cuda.device(self.device):
-            _lib.check(_lib.gs_frame_backward_adam(C.byref(f), grad_image.contiguous().data_ptr(), C.byref(adam),
-                                                   self._stream().cuda_stream), "gs_frame_backward_adam")
+            _lib.check(getattr(_lib, name)(C.byref(f), grad_image.data_ptr() if grad_image is not None else None,
+                                           C.byref(adam), self._stream().cuda_stream), name)
         self._bwd_serial = self._frame_serial
 
     def backward(self, grad_image, out=None, part: int = 0, grad_depth=None, grad_alpha=None, grad_pose=None):
@@ -753,14 +743,12 @@ class FrameRenderer:
         aux = bool(f.flags & _lib.GS_FRAME_AUX)
         if not aux and (grad_depth is not None or grad_alpha is not None):
             raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
-        if aux and part in (0, _lib.GS_BWD_RASTER):
-            grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
+        if part in (0, _lib.GS_BWD_RASTER):
+            if aux:
+                grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
+            grad_image = self._checked_grad_image(f, grad_image, none_ok=aux)
             if grad_image is None:
                 grad_image = torch.zeros(f.height, f.width, 3, device=self.device, dtype=torch.float32)
-        if part in (0, _lib.GS_BWD_RASTER):
-            grad_image = grad_image.contiguous()
-            if grad_image.dtype != torch.float32 or tuple(grad_image.shape) != (f.height, f.width, 3):
-                raise RuntimeError("grad_image must be float32 [H,W,3]")
         for t, ref in zip(out, (pos, quat, scale, opa, rgb)):
             if t.shape != ref.shape or t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("gradient destinations must match the parameters")

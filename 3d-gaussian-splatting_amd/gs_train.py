@@ -684,31 +684,24 @@ class Trainer:
                     flat.finish_slice_gather(j)  # ... the next slice's reduce-scatter + Adam
                     ahead = self._project_ahead(j, next_camera_id)
             # (gathers nobody waited for are waited for where the parameters are read next: finish_gather)
-        elif free is not None:
-            # a free pose: the same step with the pose gradient of this frame -- gs_frame_backward_adam_pose where the step
-            # fuses (rgb maps: free_pose refuses others), else the unfused backward with the flag; the map's step is bit for
-            # bit the one of the branches below
-            if self._can_fuse_adam() and flat.params[4].shape[1] == 3:
-                r.backward_adam(grad_image, self.optimizer.fused_descriptor(), grad_pose=free.grad_pose, **aux_grads)
+        else:
+            # a free pose: the same step with the pose gradient of this frame, written by whichever backward the step takes
+            grad_pose = free.grad_pose if free is not None else None
+            if self._can_fuse_adam() and (free is None or flat.params[4].shape[1] == 3):
+                # one kernel less and no gradient round trip through memory: the per-Gaussian sums, the projection / activation
+                # backward and the Adam update of the Gaussian's 14 parameters (+ the |pos.grad| statistic) in one launch
+                # (gs_frame_backward_adam; a depth-supervised frame: _adam_aux, the same step with the depth map's position
+                # term; a free pose: _adam_pose, rgb maps only -- free_pose refuses others)
+                r.backward_adam(grad_image, self.optimizer.fused_descriptor(), grad_pose=grad_pose, **aux_grads)
             else:
-                r.backward(grad_image, out=flat.grads, grad_pose=free.grad_pose, **aux_grads)
+                r.backward(grad_image, out=flat.grads, grad_pose=grad_pose, **aux_grads)
                 local_terms(0, flat.n)
                 if self.view_stat is not None and seen is not None:
                     self.view_stat.add_seen(seen)
-                self.optimizer.step()
-            with torch.cuda.device(flat.flat_param.device):
-                free.deliver()  # 48 bytes -> pinned host behind the step; read at the view's next use
-        elif self._can_fuse_adam():
-            # one kernel less and no gradient round trip through memory: the per-Gaussian sums, the projection / activation
-            # backward and the Adam update of the Gaussian's 14 parameters (+ the |pos.grad| statistic) in one launch
-            # (a depth-supervised frame: gs_frame_backward_adam_aux, the same step with the depth map's position term)
-            r.backward_adam(grad_image, self.optimizer.fused_descriptor(), **aux_grads)
-        else:
-            r.backward(grad_image, out=flat.grads, **aux_grads)
-            local_terms(0, flat.n)
-            if self.view_stat is not None and seen is not None:
-                self.view_stat.add_seen(seen)
-            self.optimizer.step()  # also: accum_max_grad = max(|pos.grad|, accum) or += |pos.grad| (train.py:144-153)
+                self.optimizer.step()  # also: accum_max_grad = max(|pos.grad|, accum) or += |pos.grad| (train.py:144-153)
+            if free is not None:
+                with torch.cuda.device(flat.flat_param.device):
+                    free.deliver()  # 48 bytes -> pinned host behind the step; read at the view's next use
         if seen is not None and self.view_stat is None:
             self.grad_counter = seen if self.grad_counter is None else self.grad_counter + seen
         settle_backward_choice()

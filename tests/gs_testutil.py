@@ -1,11 +1,60 @@
 """Shared helpers for the parity tests: oracle-side frame pipeline and comparisons."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 import oracle
 from gs_geometry import RayBasis, TileGrid
 from gs_scene import Camera, Scene
+
+
+FAKE = 1 << 40  # a device address that is never dereferenced
+
+
+def fake_frame(pose=False, aux=False, color_dim=3, training=1, N=1000, W=128, H=96):
+    """A well-formed frame descriptor with fake (never dereferenced) device addresses: only host-side entry points that
+    validate and return before any launch may be called with it."""
+    from gaussian import _lib
+
+    f = _lib.GsFrame()
+    f.N, f.color_dim, f.scale_activation = N, color_dim, 0
+    f.pos, f.quat, f.scale, f.opa, f.rgb = FAKE, FAKE + 4096, FAKE + 8192, FAKE + 12288, FAKE + 16384
+    f.rot = (C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
+    f.near_plane, f.half_width, f.half_height = 0.01, 1.0, 1.0
+    f.width, f.height, f.focal_x, f.focal_y = W, H, 0.75 * W, 0.75 * W
+    f.thresh, f.max_pairs, f.sort_mode, f.tile_culling_method = 0.05, 50_000, 2, 2
+    f.workspace = FAKE + (1 << 30)
+    f.workspace_bytes = _lib.gs_frame_workspace_bytes(f.N, f.max_pairs, W, H, color_dim, training)
+    f.training = training
+    f.image, f.image_padded = FAKE + (2 << 30), FAKE + (3 << 30)
+    if aux:
+        f.flags |= _lib.GS_FRAME_AUX
+        f.aux_workspace = FAKE + (4 << 30)
+        f.aux_workspace_bytes = _lib.gs_frame_aux_workspace_bytes(f.max_pairs, W, H, training)
+        f.aux_padded = FAKE + (5 << 30)
+    if pose:
+        f.flags |= _lib.GS_FRAME_POSE_GRAD
+        f.grad_rot, f.grad_tran = FAKE + (6 << 30), FAKE + (6 << 30) + 64
+        f.pose_workspace = FAKE + (7 << 30)
+        f.pose_workspace_bytes = _lib.gs_frame_pose_workspace_bytes(f.N)
+    return f
+
+
+def fake_adam(good=True):
+    """A gs_adam_fused that passes gs_validate_adam_fused (fake, 16-byte aligned moments) -- or, good=False, one that does
+    not (all-zero: step 0)."""
+    from gaussian import _lib
+
+    a = _lib.GsAdamFused()
+    if good:
+        for k in range(5):
+            a.exp_avg[k] = FAKE + (8 << 30) + k * 65536
+            a.exp_avg_sq[k] = FAKE + (9 << 30) + k * 65536
+            a.lr[k] = 1e-3
+        a.beta1, a.beta2, a.eps, a.step = 0.9, 0.99, 1e-8, 1
+    return a
 
 
 def sigmoid32(x):

@@ -12,29 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GS_E_INVALID, GS_E_UNSUPPORTED = -1, -2
 
 
-def _frame(aux=False, training=1, W=128, H=96):
-    """A well-formed frame descriptor with fake (never dereferenced) device addresses: only host-side entry points that
-    validate and return before any launch may be called with it."""
-    from gaussian import _lib
-
-    f = _lib.GsFrame()
-    f.N, f.color_dim, f.scale_activation = 1000, 3, 0
-    fake = 1 << 40
-    f.pos, f.quat, f.scale, f.opa, f.rgb = fake, fake + 4096, fake + 8192, fake + 12288, fake + 16384
-    f.rot = (C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
-    f.near_plane, f.half_width, f.half_height = 0.01, 1.0, 1.0
-    f.width, f.height, f.focal_x, f.focal_y = W, H, 0.75 * W, 0.75 * W
-    f.thresh, f.max_pairs, f.sort_mode, f.tile_culling_method = 0.05, 50_000, 2, 2
-    f.workspace = fake + (1 << 30)
-    f.workspace_bytes = _lib.gs_frame_workspace_bytes(f.N, f.max_pairs, W, H, 3, training)
-    f.training = training
-    f.image, f.image_padded = fake + (2 << 30), fake + (3 << 30)
-    if aux:
-        f.flags = _lib.GS_FRAME_AUX
-        f.aux_workspace = fake + (4 << 30)
-        f.aux_workspace_bytes = _lib.gs_frame_aux_workspace_bytes(f.max_pairs, W, H, training)
-        f.aux_padded = fake + (5 << 30)
-    return f
+from gs_testutil import fake_frame as _frame  # (plain unless aux=True)
 
 
 def test_aux_workspace_size_query():

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_pose_host import FAKE, GS_E_INVALID, GS_E_UNSUPPORTED, _frame
-from test_rgbd_host import _adam
+from gs_testutil import FAKE, fake_adam as _adam
+from test_pose_host import GS_E_INVALID, GS_E_UNSUPPORTED, _frame
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GIMG = FAKE + (9 << 30)

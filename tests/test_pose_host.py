@@ -3,43 +3,20 @@ of a flagged frame, the refusals (SH colours, the slice and fused-Adam backwards
 trailing fields, and the register / scratch budgets of the new kernels read from the built code objects.  No kernel is
 launched here: every call below is refused or answered on the host before anything is enqueued."""
 import ctypes as C
+import functools
 import os
 import shutil
 import subprocess
 
 import pytest
 
+from gs_testutil import FAKE, fake_frame
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GS_E_INVALID, GS_E_UNSUPPORTED = -1, -2
-FAKE = 1 << 40
 
 
-def _frame(pose=True, aux=False, color_dim=3, training=1, N=1000, W=128, H=96):
-    """A well-formed frame descriptor with fake (never dereferenced) device addresses (tests/test_aux_host.py::_frame)."""
-    from gaussian import _lib
-
-    f = _lib.GsFrame()
-    f.N, f.color_dim, f.scale_activation = N, color_dim, 0
-    f.pos, f.quat, f.scale, f.opa, f.rgb = FAKE, FAKE + 4096, FAKE + 8192, FAKE + 12288, FAKE + 16384
-    f.rot = (C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
-    f.near_plane, f.half_width, f.half_height = 0.01, 1.0, 1.0
-    f.width, f.height, f.focal_x, f.focal_y = W, H, 0.75 * W, 0.75 * W
-    f.thresh, f.max_pairs, f.sort_mode, f.tile_culling_method = 0.05, 50_000, 2, 2
-    f.workspace = FAKE + (1 << 30)
-    f.workspace_bytes = _lib.gs_frame_workspace_bytes(f.N, f.max_pairs, W, H, color_dim, training)
-    f.training = training
-    f.image, f.image_padded = FAKE + (2 << 30), FAKE + (3 << 30)
-    if aux:
-        f.flags |= _lib.GS_FRAME_AUX
-        f.aux_workspace = FAKE + (4 << 30)
-        f.aux_workspace_bytes = _lib.gs_frame_aux_workspace_bytes(f.max_pairs, W, H, training)
-        f.aux_padded = FAKE + (5 << 30)
-    if pose:
-        f.flags |= _lib.GS_FRAME_POSE_GRAD
-        f.grad_rot, f.grad_tran = FAKE + (6 << 30), FAKE + (6 << 30) + 64
-        f.pose_workspace = FAKE + (7 << 30)
-        f.pose_workspace_bytes = _lib.gs_frame_pose_workspace_bytes(f.N)
-    return f
+_frame = functools.partial(fake_frame, pose=True)
 
 
 def _grads():

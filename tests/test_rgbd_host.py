@@ -3,51 +3,19 @@ ctypes bindings, the depth loss's workspace size query and argument checks, ever
 pointers (each comes before anything is enqueued), gs_frame_backward_adam's unchanged refusal of aux frames, the z -> range
 conversion, and the register / scratch budgets of the new kernels read from the built code objects.  No kernel is launched."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+from gs_testutil import FAKE, fake_adam as _adam, fake_frame
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GS_E_INVALID, GS_E_UNSUPPORTED = -1, -2
-FAKE = 1 << 40
 
 
-def _frame(aux=True, training=1, W=128, H=96, color_dim=3):
-    """A well-formed frame descriptor with fake (never dereferenced) device addresses, as tests/test_aux_host.py builds it."""
-    from gaussian import _lib
-
-    f = _lib.GsFrame()
-    f.N, f.color_dim, f.scale_activation = 1000, color_dim, 0
-    f.pos, f.quat, f.scale, f.opa, f.rgb = FAKE, FAKE + 4096, FAKE + 8192, FAKE + 12288, FAKE + 16384
-    f.rot = (C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
-    f.near_plane, f.half_width, f.half_height = 0.01, 1.0, 1.0
-    f.width, f.height, f.focal_x, f.focal_y = W, H, 0.75 * W, 0.75 * W
-    f.thresh, f.max_pairs, f.sort_mode, f.tile_culling_method = 0.05, 50_000, 2, 2
-    f.workspace = FAKE + (1 << 30)
-    f.workspace_bytes = _lib.gs_frame_workspace_bytes(f.N, f.max_pairs, W, H, color_dim, training)
-    f.training = training
-    f.image, f.image_padded = FAKE + (2 << 30), FAKE + (3 << 30)
-    if aux:
-        f.flags = _lib.GS_FRAME_AUX
-        f.aux_workspace = FAKE + (4 << 30)
-        f.aux_workspace_bytes = _lib.gs_frame_aux_workspace_bytes(f.max_pairs, W, H, training)
-        f.aux_padded = FAKE + (5 << 30)
-    return f
-
-
-def _adam(good=True):
-    """A gs_adam_fused that passes gs_validate_adam_fused (fake, 16-byte aligned moments) -- or, good=False, one that does not."""
-    from gaussian import _lib
-
-    a = _lib.GsAdamFused()
-    if good:
-        for k in range(5):
-            a.exp_avg[k] = FAKE + (6 << 30) + k * 65536
-            a.exp_avg_sq[k] = FAKE + (7 << 30) + k * 65536
-            a.lr[k] = 1e-3
-        a.beta1, a.beta2, a.eps, a.step = 0.9, 0.99, 1e-8, 1
-    return a
+_frame = functools.partial(fake_frame, aux=True)
 
 
 def test_symbols_exist_and_are_bound():

@@ -175,10 +175,7 @@ __device__ __forceinline__ uint32_t dist_rect(float cx, float cy, const ProjectP
     return (y1 - y0) * (x1 - x0);
 }
 
-// Raw parameters of one Gaussian (what S1 reads: 56 bytes with rgb logits, 44 with SH)
-struct RawGaussian {
-    float p[3], sraw[3], qraw[4], opa, rgb[3];
-};
+// (RawGaussian, StaticGaussian and make_static: project_common.h)
 __device__ __forceinline__ RawGaussian load_raw(const float *__restrict__ pos, const float4 *__restrict__ quat,
                                                 const float *__restrict__ scale, const float *__restrict__ opa,
                                                 const float *__restrict__ rgb, int64_t pid, int color_dim) {
@@ -202,14 +199,41 @@ __device__ __forceinline__ void settle(const RawGaussian &r) {
                  "v"(r.qraw[1]), "v"(r.qraw[2]), "v"(r.qraw[3]), "v"(r.opa), "v"(r.rgb[0]), "v"(r.rgb[1]), "v"(r.rgb[2]));
 }
 
-// S1 for one Gaussian: activations -> project -> tile rectangle -> 64-byte record (visible Gaussians only) + the
+__device__ __forceinline__ void settle(const StaticGaussian &g) {
+    asm volatile("" ::"v"(g.p[0]), "v"(g.p[1]), "v"(g.p[2]), "v"(g.opa_act), "v"(g.RSSR[0]), "v"(g.RSSR[1]), "v"(g.RSSR[2]),
+                 "v"(g.RSSR[3]), "v"(g.RSSR[4]), "v"(g.RSSR[5]), "v"(g.RSSR[6]), "v"(g.RSSR[7]), "v"(g.RSSR[8]), "v"(g.col[0]),
+                 "v"(g.col[1]), "v"(g.col[2]));
+}
+
+// The scene pack (include/gs_abi.h, GS_FRAME_SCENE_PACK): the camera-independent half of every Gaussian, computed once by
+// scene_pack_build_kernel and read by the PACKED project kernels of the inference frames that follow.  Plane B, one aligned
+// 64-byte record per Gaussian: {p.xyz, sigmoid(opa)} {RSSR[0..3]} {RSSR[4..7]} {RSSR[8], col.rgb}; plane A, a float4 per
+// Gaussian: {p.xyz, smax}, what phase A of the occlusion-culled kernel streams.
+__device__ __forceinline__ StaticGaussian load_static(const float4 *__restrict__ pack_b, int64_t pid) {
+    const float4 *rec = pack_b + pid * 4;
+    const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+    StaticGaussian g;
+    g.p[0] = a.x; g.p[1] = a.y; g.p[2] = a.z; g.opa_act = a.w;
+    g.RSSR[0] = b.x; g.RSSR[1] = b.y; g.RSSR[2] = b.z; g.RSSR[3] = b.w;
+    g.RSSR[4] = c.x; g.RSSR[5] = c.y; g.RSSR[6] = c.z; g.RSSR[7] = c.w;
+    g.RSSR[8] = d.x; g.col[0] = d.y; g.col[1] = d.z; g.col[2] = d.w;
+    return g;
+}
+__device__ __forceinline__ void store_static(float4 *__restrict__ pack_b, int64_t pid, const StaticGaussian &g) {
+    float4 *rec = pack_b + pid * 4;
+    rec[0] = make_float4(g.p[0], g.p[1], g.p[2], g.opa_act);
+    rec[1] = make_float4(g.RSSR[0], g.RSSR[1], g.RSSR[2], g.RSSR[3]);
+    rec[2] = make_float4(g.RSSR[4], g.RSSR[5], g.RSSR[6], g.RSSR[7]);
+    rec[3] = make_float4(g.RSSR[8], g.col[0], g.col[1], g.col[2]);
+}
+
+// S1 for one Gaussian, camera half: project -> tile rectangle -> 64-byte record (visible Gaussians only) + the
 // 16-byte rectangle record (every Gaussian).  Returns the rectangle record; `vis` = passed the frustum test; `cxy` = the
 // projected centre (the "dist" listing test of the binning needs it).
-__device__ __forceinline__ uint4 project_one(const RawGaussian &in, int64_t pid, const ProjectParams &P,
+__device__ __forceinline__ uint4 project_one(const StaticGaussian &in, int64_t pid, const ProjectParams &P,
                                              float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched,
                                              uint4 *__restrict__ rects, uint32_t &vis, float2 &cxy) {
-    float q[4], s[3], pi[3], cv[4];
-    activate(in.qraw, in.sraw, P.scale_act, q, s);
+    float pc[3], pi[3], cv[4];
     uint32_t cnt = 0;
     vis = 0;
     cxy = make_float2(0.f, 0.f);
@@ -219,7 +243,8 @@ __device__ __forceinline__ uint4 project_one(const RawGaussian &in, int64_t pid,
     // (rects[i].z, the depth bits, is 0 exactly for culled Gaussians: visible ones lie beyond the near plane) --
     // and NOT its 64-byte record: nothing reads the record of a Gaussian that is in no tile's list (21 % of the
     // Gaussians of the 2.4 M scene: 33 of this stage's 337 MB).  The record of a culled Gaussian is unspecified.
-    if (project(in.p, q, s, P.cam, P.near_plane, P.half_w, P.half_h, pi, cv)) {
+    if (project_cull(in.p, P.cam, P.near_plane, P.half_w, P.half_h, pc, pi)) {
+        project_cov_static(pc, in.RSSR, P.cam, pi, cv);
         vis = 1;
         uint32_t y0, y1, x0, x1;
         cnt = P.cull_method == 0 ? dist_rect(pi[0], pi[1], P, y0, y1, x0, x1)
@@ -227,13 +252,11 @@ __device__ __forceinline__ uint4 project_one(const RawGaussian &in, int64_t pid,
         rc = make_uint2(y0 | (y1 << 16), x0 | (x1 << 16));
         depth = pi[2];
         cxy = make_float2(pi[0], pi[1]);
-        float4 col = make_float4(0, 0, 0, 0);
-        if (P.color_dim == 3)
-            col = make_float4(sigmoid_f(in.rgb[0]), sigmoid_f(in.rgb[1]), sigmoid_f(in.rgb[2]), 0.0f);
+        const float4 col = make_float4(in.col[0], in.col[1], in.col[2], 0.0f);
         float cA = 0.f, cB = 0.f, cC = 0.f;
         gs_conic(cv[0], cv[1], cv[2], cv[3], cA, cB, cC);
         float4 *rec = rec_geom + pid * GS_REC_STRIDE;  // one 64-byte record per Gaussian
-        rec[0] = make_float4(pi[0], pi[1], pi[2], sigmoid_f(in.opa));
+        rec[0] = make_float4(pi[0], pi[1], pi[2], in.opa_act);
         rec[1] = make_float4(cv[0], cv[1], cv[2], cv[3]);
         rec[2] = col;
         rec[3] = make_float4(cA, cB, cC, 0.f);
@@ -242,6 +265,29 @@ __device__ __forceinline__ uint4 project_one(const RawGaussian &in, int64_t pid,
     const uint4 out = make_uint4(rc.x, rc.y, __float_as_uint(depth), cnt);
     rects[pid] = out;
     return out;
+}
+// S1 from the raw parameters: load_raw -> make_static (activations, R S S R^T) -> the camera half
+__device__ __forceinline__ uint4 project_one(const RawGaussian &in, int64_t pid, const ProjectParams &P,
+                                             float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched,
+                                             uint4 *__restrict__ rects, uint32_t &vis, float2 &cxy) {
+    return project_one(make_static(in, P.scale_act, P.color_dim), pid, P, rec_geom, tiles_touched, rects, vis, cxy);
+}
+
+// One Gaussian per thread, grid-stride: both planes of the scene pack from the raw parameters (a stream: 56 B in, 80 B out).
+// smax = the largest activated scale, NaN unless all three are finite (s0 + s1 + s2 < 3e38 as phase A of the raw kernel asks):
+// the packed kernel's guard is then `smax < 3e38`, and a Gaussian with a non-finite scale is projected as it is there.
+__global__ void __launch_bounds__(256) scene_pack_build_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, int scale_act, int color_dim,
+    float4 *__restrict__ pack_a, float4 *__restrict__ pack_b) {
+    for (int64_t pid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pid < n; pid += (int64_t)gridDim.x * blockDim.x) {
+        float s[3];
+        const StaticGaussian g = make_static(load_raw(pos, quat, scale, opa, rgb, pid, color_dim), scale_act, color_dim, s);
+        float smax = fmaxf(s[0], fmaxf(s[1], s[2]));
+        if (!(s[0] + s[1] + s[2] < 3.0e38f)) smax = __uint_as_float(0x7fc00000u);
+        pack_a[pid] = make_float4(g.p[0], g.p[1], g.p[2], smax);
+        store_static(pack_b, pid, g);
+    }
 }
 
 __global__ void __launch_bounds__(256) frame_project_kernel(
@@ -286,10 +332,14 @@ __global__ void __launch_bounds__(256) frame_project_kernel(
 // long half (~750 instructions) on full waves of survivors only, so that the 21 % culled Gaussians of the 2.4 M scene
 // stop paying for it lane-masked.  Bit-identical outputs, 21 % fewer long-half wave passes -- and 89 - 92 us against
 // 81 - 82 us for the kernel below (parameters loaded by index in the long half instead of queued: 93 us).
-template <bool DIST>
-__global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
+// PACKED: the frame carries a scene pack -- the kernel streams plane B (64 B per Gaussian in one aligned line, instead of 56 B
+// from five arrays) and runs the camera half alone.
+// (One body, two kernels: frame_project_count_kernel<DIST> reads the raw arrays and keeps its name and signature,
+// frame_packed_project_count_kernel<DIST> is the PACKED instantiation.)
+template <bool DIST, bool PACKED>
+__device__ __forceinline__ void project_count_body(
     const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
-    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    const float *__restrict__ opa, const float *__restrict__ rgb, const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
     float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
     uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
     uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
@@ -308,8 +358,12 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
     const uint32_t slice = slice0 + strip_slice_of_block(blockIdx.x, S);
     const int64_t g0 = (int64_t)slice * per_slice;
     auto in_range = [&](uint32_t i) { return i < per_slice && g0 + i < n; };
-    RawGaussian cur = {}, nxt = {};
-    if (in_range(threadIdx.x)) cur = load_raw(pos, quat, scale, opa, rgb, g0 + threadIdx.x, P.color_dim);
+    auto load = [&](int64_t pid) {
+        if constexpr (PACKED) return load_static(pack_b, pid);
+        else return load_raw(pos, quat, scale, opa, rgb, pid, P.color_dim);
+    };
+    decltype(load(0)) cur = {}, nxt = {};
+    if (in_range(threadIdx.x)) cur = load(g0 + threadIdx.x);
     for (uint32_t t = threadIdx.x; t < SG.NS; t += STRIP_THREADS) s_hist[t] = 0;
     if (threadIdx.x < 2) s_acc[threadIdx.x] = 0;
     __syncthreads();
@@ -317,7 +371,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
     uint32_t acc_cnt = 0, acc_vis = 0;
     for (uint32_t base = 0; base < per_slice; base += STRIP_THREADS) {  // uniform trip count
         const uint32_t i = base + threadIdx.x;
-        if (in_range(i + STRIP_THREADS)) nxt = load_raw(pos, quat, scale, opa, rgb, g0 + i + STRIP_THREADS, P.color_dim);
+        if (in_range(i + STRIP_THREADS)) nxt = load(g0 + i + STRIP_THREADS);
         uint4 rc = make_uint4(0, 0, 0, 0);
         uint32_t vis = 0;
         float2 cxy = make_float2(0.f, 0.f);
@@ -342,6 +396,28 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
         slice_pairs[slice] = s_acc[0];
         slice_vis[slice] = s_acc[1];
     }
+}
+
+template <bool DIST>
+__global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
+    uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
+    uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
+    uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
+    project_count_body<DIST, false>(pos, quat, scale, opa, rgb, nullptr, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+                                    tile_cost, n_tiles, tile_order, gate);
+}
+template <bool DIST>
+__global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_count_kernel(
+    const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
+    uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
+    uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
+    uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
+    project_count_body<DIST, true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_b, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+                                    tile_cost, n_tiles, tile_order, gate);
 }
 
 // ---------------------------------------------------------------- S1 + L1a of an occlusion-culled frame (first pass)
@@ -408,9 +484,16 @@ __device__ __forceinline__ bool occluded_everywhere(const float pi[3], float z, 
     return dbits > m;
 }
 
-__global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel(
+// PACKED (the frame carries a scene pack): phase A streams plane A -- one 16-byte load per Gaussian, position and the largest
+// activated scale, 38 MB instead of 58 and no exponential --, phase B gathers the survivor's one 64-byte line of plane B and
+// runs the camera half alone.  No stash: nothing phase A read is needed again.  Queue, pyramid, strip walk, staging and every
+// output are those of the raw variant.
+// (One body, two kernels, as above: frame_project_cull_count_kernel and frame_packed_project_cull_count_kernel.)
+template <bool PACKED>
+__device__ __forceinline__ void project_cull_count_body(
     const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
-    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    const float *__restrict__ opa, const float *__restrict__ rgb, const float4 *__restrict__ pack_a,
+    const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
     float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
     unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
@@ -440,8 +523,14 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     auto fetch_at = [&](float (&pp)[3], float (&ss)[3], uint32_t i) {
         int64_t g = g0 + i;
         g = g < n ? g : n - 1;
-        load3(pos, g, pp);
-        load3(scale, g, ss);
+        if constexpr (PACKED) {  // (ss[0] = smax; ss[1], ss[2] are never read)
+            const float4 v = pack_a[g];
+            pp[0] = v.x; pp[1] = v.y; pp[2] = v.z; ss[0] = v.w;
+            ss[1] = ss[2] = 0.f;
+        } else {
+            load3(pos, g, pp);
+            load3(scale, g, ss);
+        }
     };
     float pa[3], sa[3], pb[3], sb[3];
     fetch_at(pa, sa, threadIdx.x);
@@ -501,12 +590,20 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
                 float pc[3], pi[3];
                 if (project_cull(pp, P.cam, P.near_plane, P.half_w, P.half_h, pc, pi)) {
                     const float dep = sqrtf(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);  // == project_cov's pos_i[2]
-                    float s[3];
+                    float smax;
+                    bool finite;
+                    if constexpr (PACKED) {  // (the pack holds NaN for a Gaussian whose scales are not all finite)
+                        smax = ss[0];
+                        finite = smax < 3.0e38f;
+                    } else {
+                        float s[3];
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) s[k] = P.scale_act == 0 ? fabsf(ss[k]) + 1e-4f : gs_exp2(GS_LOG2E * ss[k]);
-                    const float smax = fmaxf(s[0], fmaxf(s[1], s[2]));
-                    // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
-                    if ((s[0] + s[1] + s[2] < 3.0e38f) && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
+                        for (int k = 0; k < 3; ++k) s[k] = P.scale_act == 0 ? fabsf(ss[k]) + 1e-4f : gs_exp2(GS_LOG2E * ss[k]);
+                        smax = fmaxf(s[0], fmaxf(s[1], s[2]));
+                        // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
+                        finite = s[0] + s[1] + s[2] < 3.0e38f;
+                    }
+                    if (finite && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
                         // behind every cut it can reach, or beside the grid: visible, no tile.  NOTHING is written for it (nor
                         // for a Gaussian outside the frustum): this pass places the entries phase B stages, the second
                         // pass re-projects everything -- rects[] of a culled frame is only fresh for the survivors
@@ -524,7 +621,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
                 if (surv) {
                     const uint32_t slot = wbase + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
                     s_q[slot] = (uint16_t)i;
-                    if (slot < stash_cap) {
+                    if (!PACKED && slot < stash_cap) {
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
                             s_stash[c * stash_cap + slot] = pp[c];
@@ -553,28 +650,32 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
         __syncthreads();
         // ---- phase B: the survivors, 1,024 at a time on full waves
         const uint32_t nq = s_qn;
-        RawGaussian cur = {}, nxt = {};
-        uint32_t qi = 0, qn_ = 0;
         auto load_survivor = [&](uint32_t k, uint32_t q) {
-            RawGaussian r;
             const int64_t pid = g0 + c0 + q;
-            if (k < stash_cap) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    r.p[c] = s_stash[c * stash_cap + k];
-                    r.sraw[c] = s_stash[(3 + c) * stash_cap + k];
-                }
+            if constexpr (PACKED) {
+                return load_static(pack_b, pid);
             } else {
-                load3(pos, pid, r.p);
-                load3(scale, pid, r.sraw);
+                RawGaussian r;
+                if (k < stash_cap) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        r.p[c] = s_stash[c * stash_cap + k];
+                        r.sraw[c] = s_stash[(3 + c) * stash_cap + k];
+                    }
+                } else {
+                    load3(pos, pid, r.p);
+                    load3(scale, pid, r.sraw);
+                }
+                const float4 q4 = quat[pid];
+                r.qraw[0] = q4.x; r.qraw[1] = q4.y; r.qraw[2] = q4.z; r.qraw[3] = q4.w;
+                r.opa = opa[pid];
+                r.rgb[0] = r.rgb[1] = r.rgb[2] = 0.f;
+                if (P.color_dim == 3) load3(rgb, pid, r.rgb);
+                return r;
             }
-            const float4 q4 = quat[pid];
-            r.qraw[0] = q4.x; r.qraw[1] = q4.y; r.qraw[2] = q4.z; r.qraw[3] = q4.w;
-            r.opa = opa[pid];
-            r.rgb[0] = r.rgb[1] = r.rgb[2] = 0.f;
-            if (P.color_dim == 3) load3(rgb, pid, r.rgb);
-            return r;
         };
+        decltype(load_survivor(0, 0)) cur = {}, nxt = {};
+        uint32_t qi = 0, qn_ = 0;
         if (threadIdx.x < nq) {
             qi = s_q[threadIdx.x];
             cur = load_survivor(threadIdx.x, qi);
@@ -637,6 +738,27 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     }
 }
 
+__global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
+    unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
+    const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
+    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, unsigned long long *__restrict__ stage_ent,
+    uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
+    project_cull_count_body<false>(pos, quat, scale, opa, rgb, nullptr, nullptr, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
+                                   qcap, stash_cap, stage_ent, stage_tag, ecap, slice_entries);
+}
+__global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_cull_count_kernel(
+    const float4 *__restrict__ pack_a, const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
+    unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
+    const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
+    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, unsigned long long *__restrict__ stage_ent,
+    uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
+    project_cull_count_body<true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_a, pack_b, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
+                                   qcap, stash_cap, stage_ent, stage_tag, ecap, slice_entries);
+}
 
 // ---------------------------------------------------------------- S1 + B1 fused (table variant of sort_mode 2: small scenes)
 // The same fusion for the table variant, which small scenes take: a frame of 10,000 Gaussians is six dependent launches
@@ -737,6 +859,33 @@ extern "C" int gs_global_culling(const float *pos, const float *quat, const floa
     return 0;
 }
 
+// ================================================================= scene pack
+extern "C" size_t gs_scene_pack_bytes(int64_t N, size_t *a_bytes, size_t *b_bytes) {
+    // 16 N and 64 N bytes, each rounded up to whole 256-byte units
+    const size_t a = N < 0 ? 0 : ((size_t)N * 16 + 255) / 256 * 256, b = N < 0 ? 0 : ((size_t)N * 64 + 255) / 256 * 256;
+    if (a_bytes) *a_bytes = a;
+    if (b_bytes) *b_bytes = b;
+    return a + b;
+}
+
+extern "C" int gs_scene_pack_build(const float *pos, const float *quat, const float *scale, const float *opa, const float *rgb,
+                                   int64_t N, int32_t color_dim, int32_t scale_activation, void *pack_a, void *pack_b,
+                                   gs_stream_t stream) {
+    GS_CHECK_ARG(N >= 0 && N < (1ll << 31), "N out of range");
+    GS_CHECK_ARG(color_dim == 3 || color_dim == 27 || color_dim == 48, "color_dim must be 3, 27 or 48");
+    GS_CHECK_ARG(scale_activation == 0 || scale_activation == 1, "scale_activation must be 0 (abs) or 1 (exp)");
+    if (N == 0) return 0;
+    GS_CHECK_ARG(pos && quat && scale && opa && rgb && pack_a && pack_b, "null pointer");
+    GS_CHECK_ARG(((uintptr_t)quat & 15) == 0, "quat must be 16-byte aligned");
+    GS_CHECK_ARG(((uintptr_t)pack_a & 15) == 0 && ((uintptr_t)pack_b & 63) == 0,
+                 "pack_a must be 16-byte aligned, pack_b 64-byte aligned");
+    hipLaunchKernelGGL(scene_pack_build_kernel, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, pos,
+                       (const float4 *)quat, scale, opa, rgb, N, (int)scale_activation, (int)color_dim, (float4 *)pack_a,
+                       (float4 *)pack_b);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
 // ================================================================= frame stages (internal)
 // slice_begin / slice_end: the slices of the Gaussian array to project (strip variant only: gs_frame_project_slices;
 // every other path projects everything at once: 0, -1)
@@ -759,7 +908,8 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         if (dev < 64 && !((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
             std::lock_guard<std::mutex> lock(attr_mu);
             for (const void *fn : {(const void *)frame_project_count_kernel<false>, (const void *)frame_project_count_kernel<true>,
-                                   (const void *)frame_project_cull_count_kernel})
+                                   (const void *)frame_packed_project_count_kernel<false>, (const void *)frame_packed_project_count_kernel<true>,
+                                   (const void *)frame_project_cull_count_kernel, (const void *)frame_packed_project_cull_count_kernel})
                 // (the kernels also hold ~17 KiB of static LDS -- the tile-order workgroup's bins --: the strip histogram, and the
                 // cut pyramid + survivor queue behind it in a culled frame, get what gs_frame_occlusion_cull's room rule allows)
                 GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_BIN_LDS_BYTES - 8 * 4096));
@@ -769,6 +919,10 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         if (slice_end < 0) slice_end = (int)plan.slices;
         GS_CHECK_ARG(slice_begin >= 0 && slice_begin < slice_end && slice_end <= (int)plan.slices, "bad slice range");
         const uint32_t nsl = (uint32_t)(slice_end - slice_begin);
+        // GS_FRAME_SCENE_PACK: the PACKED kernels read the caller's two planes (validated in gs_frame.hip) instead of the raw arrays
+        const bool packed = gs_frame_scene_pack(f);
+        const float4 *pack_a = packed ? (const float4 *)gs_frame_scene_fields(f)->scene_pack_a : nullptr;
+        const float4 *pack_b = packed ? (const float4 *)gs_frame_scene_fields(f)->scene_pack_b : nullptr;
         if (gs_frame_occlusion_cull(f) && !second_pass) {
             // GS_FRAME_OCCLUSION_CULL, first pass: Gaussians behind every cut they can reach are not projected, the level-1
             // entries of the others are trimmed by the cut table the previous frame of this workspace left
@@ -786,33 +940,47 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
             const size_t room = (size_t)GS_BIN_LDS_BYTES - 8 * 4096;
             uint32_t stash_cap = room > lds ? (uint32_t)((room - lds) / 24) & ~63u : 0u;
             if (stash_cap > qcap) stash_cap = (qcap + 63u) & ~63u;
+            if (packed) stash_cap = 0;  // (the packed variant has no stash; GS_OCC_STASH is ignored)
             if (const char *e = getenv("GS_OCC_STASH")) {
                 const long v = atol(e);
                 if (v >= 0 && (uint32_t)v < stash_cap) stash_cap = (uint32_t)v & ~63u;
             }
             lds += (size_t)stash_cap * 24;
-            hipLaunchKernelGGL(frame_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, f->pos,
-                               (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, ws.rects,
-                               plan.per_slice, SG, nsl, table, ws.slice_pairs, ws.slice_vis, ws.tile_cost,
-                               (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), qcap, stash_cap,
-                               (unsigned long long *)ws.keys_b, ws.vals_b, gs_cull_stage_cap(f->max_pairs, plan.slices),
-                               ws.slice_entries);
+#define GS_CULL_TAIL                                                                                                   \
+    f->N, P, ws.rec_geom, ws.rects, plan.per_slice, SG, nsl, table, ws.slice_pairs, ws.slice_vis, ws.tile_cost,        \
+        (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), qcap, stash_cap, (unsigned long long *)ws.keys_b, \
+        ws.vals_b, gs_cull_stage_cap(f->max_pairs, plan.slices), ws.slice_entries
+            if (packed)
+                hipLaunchKernelGGL(frame_packed_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, pack_a,
+                                   pack_b, GS_CULL_TAIL);
+            else
+                hipLaunchKernelGGL(frame_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, f->pos,
+                                   (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_CULL_TAIL);
+#undef GS_CULL_TAIL
             GS_CHECK_LAUNCH();
             return 0;
         }
         const size_t lds = sizeof(unsigned long long) * SG.NS;
         const uint32_t extra = (slice_begin == 0 && !second_pass) ? 1u : 0u;  // the tile-order workgroup rides with the first range
         const unsigned long long *gate = second_pass ? ws.counters + GS_CNT_RANPAST : nullptr;
+#define GS_COUNT_TAIL                                                                                                  \
+    f->N, P, ws.rec_geom, touched, ws.rects, D, plan.per_slice, SG, nsl, (uint32_t)slice_begin, table, ws.slice_pairs, \
+        ws.slice_vis, ws.tile_cost, (uint32_t)G.n_tiles, ws.tile_order, gate
 #define GS_LAUNCH_PROJECT_COUNT(DIST)                                                                                  \
-    hipLaunchKernelGGL(frame_project_count_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, stream,          \
-                       f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, touched,       \
-                       ws.rects, D, plan.per_slice, SG, nsl, (uint32_t)slice_begin, table, ws.slice_pairs,             \
-                       ws.slice_vis, ws.tile_cost, (uint32_t)G.n_tiles, ws.tile_order, gate)
+    do {                                                                                                               \
+        if (packed)                                                                                                    \
+            hipLaunchKernelGGL(frame_packed_project_count_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds,   \
+                               stream, pack_b, GS_COUNT_TAIL);                                                         \
+        else                                                                                                           \
+            hipLaunchKernelGGL(frame_project_count_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, stream,  \
+                               f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_COUNT_TAIL);              \
+    } while (0)
         if (f->tile_culling_method == 0)
             GS_LAUNCH_PROJECT_COUNT(true);
         else
             GS_LAUNCH_PROJECT_COUNT(false);
 #undef GS_LAUNCH_PROJECT_COUNT
+#undef GS_COUNT_TAIL
         GS_CHECK_LAUNCH();
         return 0;
     }

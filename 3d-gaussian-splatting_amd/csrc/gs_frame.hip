@@ -64,7 +64,7 @@ static int validate(const gs_frame *f) {
     GS_CHECK_ARG((f->flags & ~(GS_FRAME_EMIT_SORTED_KEYS | GS_FRAME_SLICE_SORT | GS_FRAME_TABLE_BIN |
                                GS_FRAME_SERIAL_LONG_LISTS | GS_FRAME_LONG_LISTS | GS_FRAME_STRIP_BIN |
                                GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR |
-                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD)) == 0,
+                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD | GS_FRAME_SCENE_PACK)) == 0,
                  "unknown flag bits");
     GS_CHECK_ARG(f->sort_mode >= 0 && f->sort_mode <= 2,
                  "sort_mode must be 0 (full LSD radix), 1 (tile-bit radix + per-tile LDS sort) or 2 (LDS counting sort "
@@ -90,6 +90,20 @@ static int validate(const gs_frame *f) {
         if (f->pose_workspace_bytes < pose_need) {
             gs_set_error("gs_frame: GS_FRAME_POSE_GRAD: pose workspace too small (%zu < %zu bytes)", f->pose_workspace_bytes,
                          pose_need);
+            return GS_E_INVALID;
+        }
+    }
+    if (f->flags & GS_FRAME_SCENE_PACK) {  // (trailing fields, as above; checked whether or not this frame's path reads the pack)
+        GS_CHECK_ARG(!f->training, "GS_FRAME_SCENE_PACK: training frames read the raw arrays (training must be 0)");
+        const gs_frame_scene *sp = gs_frame_scene_fields(f);
+        GS_CHECK_ARG(sp->scene_pack_a != nullptr && sp->scene_pack_b != nullptr, "GS_FRAME_SCENE_PACK: scene_pack_a / scene_pack_b null");
+        GS_CHECK_ARG(((uintptr_t)sp->scene_pack_a & 15) == 0, "GS_FRAME_SCENE_PACK: scene_pack_a must be 16-byte aligned");
+        GS_CHECK_ARG(((uintptr_t)sp->scene_pack_b & 63) == 0, "GS_FRAME_SCENE_PACK: scene_pack_b must be 64-byte aligned");
+        size_t need_a = 0, need_b = 0;
+        (void)gs_scene_pack_bytes(f->N, &need_a, &need_b);
+        if (sp->scene_pack_a_bytes < need_a || sp->scene_pack_b_bytes < need_b) {
+            gs_set_error("gs_frame: GS_FRAME_SCENE_PACK: scene_pack_a_bytes / scene_pack_b_bytes too small (%zu < %zu or %zu < %zu bytes)",
+                         sp->scene_pack_a_bytes, need_a, sp->scene_pack_b_bytes, need_b);
             return GS_E_INVALID;
         }
     }
@@ -670,6 +684,11 @@ extern "C" int gs_frame_is_occlusion_culled(const gs_frame *f, int32_t *culled) 
     GS_CHECK_ARG(f && culled, "null argument");
     *culled = (effective_sort_mode(f) == 2 && gs_frame_occlusion_cull(f)) ? 1 : 0;
     return 0;
+}
+
+extern "C" int gs_frame_reads_scene_pack(const gs_frame *f) {
+    if (!f || f->training || f->N <= 0 || effective_sort_mode(f) != 2) return 0;
+    return gs_frame_uses_strips(f) ? 1 : 0;
 }
 
 extern "C" int gs_frame_debug_tile_nproc(const gs_frame *f, const uint32_t **tile_nproc) {

@@ -201,6 +201,15 @@ static inline bool gs_frame_occlusion_cull(const gs_frame *f) {
     const int64_t room = (int64_t)GS_BIN_LDS_BYTES - 8 * 4096;
     return 8 * ns + (int64_t)gs_cull_pyramid_bytes(ntx, nty) + 2 * 16384 + 16 <= room;
 }
+// GS_FRAME_SCENE_PACK: does this frame read the caller's scene pack?  Inference frames of the strip variant only (the project +
+// count kernels of cull_project.hip have a packed variant; every other path reads the raw arrays and ignores the flag).
+// (the four fields behind the descriptor of a flagged frame: include/gs_abi.h, gs_frame_scene)
+static inline const gs_frame_scene *gs_frame_scene_fields(const gs_frame *f) {
+    return reinterpret_cast<const gs_frame_scene *>(f);
+}
+static inline bool gs_frame_scene_pack(const gs_frame *f) {
+    return (f->flags & GS_FRAME_SCENE_PACK) && !f->training && f->N > 0 && gs_frame_uses_strips(f);
+}
 // Table variant (small scenes: a frame is a chain of dependent launches of ~7 us each): the per-(slice, tile) count
 // (bin_count_kernel) is taken inside the project stage as well -- five launches per frame instead of six.
 static inline bool gs_frame_fused_table_count(const gs_frame *f) {

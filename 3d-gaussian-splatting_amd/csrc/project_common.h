@@ -2,7 +2,10 @@
 // transform and the EWA covariance projection (world2camera, gaussian.cu:49-99; jacobian, :10-47; the forward half of
 // global_culling_kernel, :1182-1336), the activations, and the per-frame parameter block the kernels of both files take
 // by value.  Every expression is written in the reference's source order; both files are compiled with
-// -ffp-contract=off, each for its own reason (see their headers).  Nothing here is used by one side only.
+// -ffp-contract=off, each for its own reason (see their headers).  The forward's per-Gaussian work is stated once, in two
+// halves: make_static (what depends on the Gaussian alone; a scene pack caches its result, cull_project.hip) and the camera
+// half (project_cull + project_cov_static), so that a packed frame evaluates the same expressions on the same inputs in the
+// same order as a raw one.
 #pragma once
 #include <math.h>
 #include "gs_common.h"
@@ -84,13 +87,18 @@ __device__ __forceinline__ bool project_cull(const float p[3], const Cam &cam, f
     pos_i[1] = pc[1] / pc[2];
     return !(fabsf(pos_i[0]) >= half_w || fabsf(pos_i[1]) >= half_h);
 }
-__device__ __forceinline__ void project_cov(const float pc[3], const float q[4], const float s[3], const Cam &cam,
-                                            float pos_i[3], float cov[4]) {
-    pos_i[2] = sqrtf(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);
-    float R[9], S[9] = {s[0], 0, 0, 0, s[1], 0, 0, 0, s[2]}, RS[9], RSSR[9], J[9], JW[9], JWC[9], JWCWJ[9];
+// project_cov in two halves: static_cov = what depends on the Gaussian alone (R S S R^T), project_cov_static = depth + what the
+// camera adds.  Each half is the reference's expressions in the reference's order: the halves share no intermediate.
+__device__ __forceinline__ void static_cov(const float q[4], const float s[3], float RSSR[9]) {
+    float R[9], S[9] = {s[0], 0, 0, 0, s[1], 0, 0, 0, s[2]}, RS[9];
     quat_to_R(q[0], q[1], q[2], q[3], R);
     mm3(R, S, RS);
     mm3_nt(RS, RS, RSSR);
+}
+__device__ __forceinline__ void project_cov_static(const float pc[3], const float RSSR[9], const Cam &cam, float pos_i[3],
+                                                   float cov[4]) {
+    pos_i[2] = sqrtf(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);
+    float J[9], JW[9], JWC[9], JWCWJ[9];
     jacobian_rows(pc, J);
     mm3(J, cam.rot, JW);
     mm3(JW, RSSR, JWC);
@@ -99,6 +107,12 @@ __device__ __forceinline__ void project_cov(const float pc[3], const float q[4],
     cov[1] = JWCWJ[1];
     cov[2] = JWCWJ[3];
     cov[3] = JWCWJ[4];
+}
+__device__ __forceinline__ void project_cov(const float pc[3], const float q[4], const float s[3], const Cam &cam,
+                                            float pos_i[3], float cov[4]) {
+    float RSSR[9];
+    static_cov(q, s, RSSR);
+    project_cov_static(pc, RSSR, cam, pos_i, cov);
 }
 __device__ __forceinline__ bool project(const float p[3], const float q[4], const float s[3],
                                         const Cam &cam, float near_plane, float half_w, float half_h,
@@ -145,6 +159,37 @@ __device__ __forceinline__ void activate(const float qraw[4], const float sraw[3
     for (int k = 0; k < 4; ++k) q[k] = qraw[k] / nr;
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] = scale_act == 0 ? fabsf(sraw[k]) + 1e-4f : expf(sraw[k]);
+}
+
+// Raw parameters of one Gaussian (what S1 reads: 56 bytes with rgb logits, 44 with SH)
+struct RawGaussian {
+    float p[3], sraw[3], qraw[4], opa, rgb[3];
+};
+// The camera-independent half of S1 for one Gaussian: position, R S S R^T (all nine entries), the activated opacity and
+// the rgb colour (zero with SH colours, which the compositing evaluates per pixel).  It is what a scene pack stores
+// (cull_project.hip): the camera half below it takes this and nothing else of the Gaussian.
+struct StaticGaussian {
+    float p[3], RSSR[9], opa_act, col[3];
+};
+// `s`: the activated scales as well (the scene pack keeps the largest)
+__device__ __forceinline__ StaticGaussian make_static(const RawGaussian &in, int scale_act, int color_dim, float s[3]) {
+    StaticGaussian g;
+    float q[4];
+    activate(in.qraw, in.sraw, scale_act, q, s);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g.p[k] = in.p[k];
+    static_cov(q, s, g.RSSR);
+    g.opa_act = sigmoid_f(in.opa);
+    g.col[0] = g.col[1] = g.col[2] = 0.f;
+    if (color_dim == 3) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.col[k] = sigmoid_f(in.rgb[k]);
+    }
+    return g;
+}
+__device__ __forceinline__ StaticGaussian make_static(const RawGaussian &in, int scale_act, int color_dim) {
+    float s[3];
+    return make_static(in, scale_act, color_dim, s);
 }
 
 // Grid of the grid-stride reference-API kernels (section A of both files)

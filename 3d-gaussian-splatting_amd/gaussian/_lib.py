@@ -49,6 +49,13 @@ class GsFrame(C.Structure):
     ]
 
 
+class GsFrameScene(GsFrame):
+    """Mirror of ``struct gs_frame_scene``: a ``gs_frame`` followed by the GS_FRAME_SCENE_PACK fields (read by the library
+    only when the flag is set).  An instance is accepted wherever a ``GsFrame`` is (same address, the fields behind it)."""
+
+    _fields_ = [("scene_pack_a", vp), ("scene_pack_b", vp), ("scene_pack_a_bytes", sz), ("scene_pack_b_bytes", sz)]
+
+
 GS_FRAME_EMIT_SORTED_KEYS = 1
 GS_FRAME_SLICE_SORT = 2
 GS_FRAME_TABLE_BIN = 4
@@ -62,6 +69,7 @@ GS_FRAME_CULL_DILATE = 512
 GS_FRAME_CULL_DILATE_NEAR = 1024
 GS_FRAME_AUX = 2048
 GS_FRAME_POSE_GRAD = 4096
+GS_FRAME_SCENE_PACK = 8192
 
 
 def _sig(name, restype, *argtypes):
@@ -93,6 +101,9 @@ gs_sort_pairs_bits = _sig("gs_sort_pairs_bits", ci, vp, vp, vp, vp, vp, i64, ci,
 gs_frame_workspace_bytes = _sig("gs_frame_workspace_bytes", sz, i64, i64, i32, i32, i32, i32)
 gs_frame_aux_workspace_bytes = _sig("gs_frame_aux_workspace_bytes", sz, i64, i32, i32, i32)
 gs_frame_pose_workspace_bytes = _sig("gs_frame_pose_workspace_bytes", sz, i64)
+gs_scene_pack_bytes = _sig("gs_scene_pack_bytes", sz, i64, C.POINTER(sz), C.POINTER(sz))
+gs_scene_pack_build = _sig("gs_scene_pack_build", ci, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp)
+gs_frame_reads_scene_pack = _sig("gs_frame_reads_scene_pack", ci, C.POINTER(GsFrame))
 gs_frame_forward = _sig("gs_frame_forward", ci, C.POINTER(GsFrame), vp)
 gs_frame_backward = _sig("gs_frame_backward", ci, C.POINTER(GsFrame), vp, vp, vp, vp, vp, vp, vp)
 gs_frame_backward_part = _sig("gs_frame_backward_part", ci, C.POINTER(GsFrame), vp, vp, vp, vp, vp, vp, i32, vp)
@@ -216,6 +227,7 @@ EXPORTS = [
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
     "gs_loss_track_workspace_bytes", "gs_loss_track",
     "gs_view_overlap_workspace_bytes", "gs_view_overlap_check_view", "gs_view_overlap",
+    "gs_scene_pack_bytes", "gs_scene_pack_build", "gs_frame_reads_scene_pack",
 ]
 
 

@@ -19,6 +19,7 @@ import copy
 import ctypes as C
 import os
 import sys
+import weakref
 from dataclasses import dataclass
 from typing import Optional
 
@@ -54,7 +55,8 @@ class FrameRenderer:
                  sort_mode: int = 2, tile_culling_method: str = "prob2", tile_culling_dist_thresh: float = 0.5,
                  emit_sorted_keys: bool = False, slice_sort: bool = False, table_bin: bool = False,
                  serial_long_lists: bool = False, long_lists: Optional[bool] = None, bwd_rows: Optional[bool] = None,
-                 force_strips: Optional[bool] = None, occlusion_cull: Optional[bool] = None):
+                 force_strips: Optional[bool] = None, occlusion_cull: Optional[bool] = None,
+                 scene_pack: Optional[bool] = None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("FrameRenderer needs a HIP device; there is no CPU fallback")
@@ -85,6 +87,18 @@ class FrameRenderer:
         # culled frame counts the pairs that were emitted.
         self.occlusion_cull = False if (occlusion_cull is None and os.environ.get("GS_NO_CULL", "") == "1") else occlusion_cull  # (GS_NO_CULL=1: A/B runs)
         self._cut_key = None  # (workspace address, width, height) of the inference forward that left the current cut table behind
+        # GS_FRAME_SCENE_PACK (include/gs_abi.h): an inference renderer draws the same trained scene again and again while only
+        # the camera changes, so the camera-independent half of the projection (activations, R S S R^T, sigmoids) is computed
+        # once into a pack of 80 bytes per Gaussian (192 MB at 2.4 M) that the project stage of the following inference
+        # frames reads instead of the raw arrays -- bit for bit the same frame.  None: automatic (_scene_pack_step: built in
+        # front of the SECOND consecutive inference frame of the same tensors, so a one-off render never pays for it, and
+        # dropped as soon as a tensor is replaced or written); False: never.  Training frames never read a pack.
+        self.scene_pack = False if (scene_pack is None and os.environ.get("GS_NO_SCENE_PACK", "") == "1") else scene_pack  # (GS_NO_SCENE_PACK=1: A/B runs)
+        if self.scene_pack not in (None, False):
+            raise ValueError("scene_pack must be None (automatic) or False (never)")
+        self._pack = None       # the current pack: {"key", "a", "b", the planes' aligned addresses and sizes, "event", "streams"}
+        self._pack_seen = None  # key of the last inference frame that had no pack (the next one with the same key builds it)
+        self._pack_cur = None   # the pack the frame being described carries (enters the descriptor and its cache key)
         # does the cull pay on this scene?  (_cull_probe: asynchronous, tagged counter copies of an unculled and a culled frame)
         self._cull_off_until = 0      # frame serial from which the cull is allowed (again)
         self._cull_backoff = 256      # frames it is switched off for when it did not pay; doubles up to 4,096
@@ -122,7 +136,7 @@ class FrameRenderer:
         self._aux_keep = None  # (depth, alpha, aux_padded) of the last forward, kept for its backward
         self._pose_ws: Optional[torch.Tensor] = None  # GS_FRAME_POSE_GRAD backwards: the per-workgroup partial sums
         self._stats_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
-        self._frame: Optional[_lib.GsFrame] = None
+        self._frame: Optional[_lib.GsFrameScene] = None
         self._frame_serial = 0  # counts forwards: autograd checks that backward() belongs to the latest one
         self._cam_cache = {}
         self._keep = None
@@ -134,7 +148,7 @@ class FrameRenderer:
         self.overflowed_frames = 0  # frames that were rendered empty / truncated and could not be redone (see forward)
 
     # ------------------------------------------------------------------ frame descriptor
-    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrame:
+    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameScene:
         # A viewer or a benchmark renders the same tensors from the same camera object again and again: the descriptor
         # of the previous call is reused as long as nothing it was built from has changed (tensor identities and
         # storage, camera object, renderer settings) -- the validation below, ~40 ctypes stores and a library call cost
@@ -157,23 +171,24 @@ class FrameRenderer:
                self.emit_sorted_keys, self.slice_sort, self.table_bin, self.force_strips, self.serial_long_lists,
                self.long_lists, self._long_lists_seen, self._long_sort_seen, self.bwd_rows, self._bwd_rows_seen,
                self.occlusion_cull, self._cut_key, getattr(self, "_cut_ck", None), self._frame_serial >= self._cull_off_until,
+               self._pack_cur["planes"] if (self._pack_cur is not None and not training) else None,
                bool(aux), self._aux_ws.data_ptr() if (aux and self._aux_ws is not None) else 0,
                self._ws.data_ptr() if self._ws is not None else 0)
         cached = getattr(self, "_desc_cache", None)
         if cached is not None and cached[0] == key:
-            f = _lib.GsFrame()
-            C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFrame))
+            f = _lib.GsFrameScene()
+            C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFrameScene))
             self._grid = cached[3]
             return f
         f = self._describe_uncached(pos, quat, scale, opa, rgb, camera, training, aux)
         # (the key is taken again: building the descriptor may have (re)allocated the workspaces)
         key = key[:-2] + (self._aux_ws.data_ptr() if aux else 0, self._ws.data_ptr())
-        keep = _lib.GsFrame()
-        C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFrame))
+        keep = _lib.GsFrameScene()
+        C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFrameScene))
         self._desc_cache = (key, keep, None, self._grid)
         return f
 
-    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrame:
+    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameScene:
         n = int(pos.shape[0])
         color_dim = int(rgb.shape[1]) if rgb.dim() == 2 else 1
         if color_dim not in (3, 27, 48):  # rgb logits, SH degree 2 (the reference's), SH degree 3 (extension)
@@ -204,7 +219,7 @@ class FrameRenderer:
             else:
                 zero3 = np.zeros(3, np.float32)
                 rays = RayBasis(zero3, zero3, zero3, zero3)
-            c = _lib.GsFrame()
+            c = _lib.GsFrameScene()
             c.rot = (C.c_float * 9)(*np.asarray(camera.rot, np.float32).reshape(9))
             c.tran = (C.c_float * 3)(*np.asarray(camera.tran, np.float32).reshape(3))
             c.near_plane, c.half_width, c.half_height = float(camera.near), half_w, half_h
@@ -220,8 +235,8 @@ class FrameRenderer:
                 self._cam_cache.clear()
             cached = self._cam_cache[ck] = (c, grid)
         proto, grid = cached
-        f = _lib.GsFrame()
-        C.memmove(C.byref(f), C.byref(proto), C.sizeof(_lib.GsFrame))
+        f = _lib.GsFrameScene()
+        C.memmove(C.byref(f), C.byref(proto), C.sizeof(_lib.GsFrameScene))
         f.N, f.color_dim, f.scale_activation = n, color_dim, self.scale_activation
         f.pos, f.quat, f.scale, f.opa, f.rgb = (t.data_ptr() for t in (pos, quat, scale, opa, rgb))
         # "dist": the squared distance threshold of splatter.py:577
@@ -277,8 +292,78 @@ class FrameRenderer:
                 f.flags |= _lib.GS_FRAME_CULL_DILATE  # a pose near the recorded one: every tile's cut from its 3 x 3 neighbourhood
                 if shift <= self.CULL_NEAR_SHIFT_PX:
                     f.flags |= _lib.GS_FRAME_CULL_DILATE_NEAR  # ... pushed back by 1.125 instead of 1.375 in depth
+        pk = self._pack_cur
+        if pk is not None and not training and _lib.gs_frame_reads_scene_pack(C.byref(f)):
+            f.scene_pack_a, f.scene_pack_b, f.scene_pack_a_bytes, f.scene_pack_b_bytes = pk["planes"]
+            f.flags |= _lib.GS_FRAME_SCENE_PACK
         self._grid = grid
         return f
+
+    # ------------------------------------------------------------------ scene pack
+    @staticmethod
+    def _scene_pack_state(tensors):
+        """What a pack is valid for besides the tensor objects themselves: every tensor's version counter, address and shape.
+        None when a tensor keeps no version counter (inference tensors): no pack then."""
+        try:
+            return tuple((t._version, t.data_ptr(), tuple(t.shape)) for t in tensors)
+        except RuntimeError:
+            return None
+
+    def _scene_pack_key_matches(self, key, tensors, state, color_dim) -> bool:
+        # Tensor IDENTITY is part of the key: a freed tensor's address and version 0 can both come back in a new tensor of
+        # the same shape.  (Weak references are compared through their referents with `is`: `==` on tensors is element-wise.)
+        return (key is not None and state is not None and key[1] == state and key[2] == (self.scale_activation, color_dim)
+                and all(r() is t for r, t in zip(key[0], tensors)))
+
+    def _scene_pack_step(self, pos, quat, scale, opa, rgb, training):
+        """Decide which pack, if any, the frame about to be described carries (``self._pack_cur``); build one in front of the
+        second consecutive inference frame of the same tensors.  A training frame carries none and leaves the state alone."""
+        self._pack_cur = None
+        if training or self.scene_pack is False:
+            return
+        tensors = (pos, quat, scale, opa, rgb)
+        color_dim = int(rgb.shape[1]) if rgb.dim() == 2 else 1
+        state = self._scene_pack_state(tensors)
+        cur = self._stream()
+        capturing = torch.cuda.is_current_stream_capturing()
+        pk = self._pack
+        if pk is not None and self._scene_pack_key_matches(pk["key"], tensors, state, color_dim):
+            if cur.cuda_stream not in pk["streams"]:
+                if capturing:
+                    return  # (no wait for an outside event inside a capture: this frame reads the raw arrays)
+                cur.wait_event(pk["event"])  # another stream than the build's: wait once for the event recorded behind it
+                pk["a"].record_stream(cur)
+                pk["b"].record_stream(cur)
+                pk["streams"].add(cur.cuda_stream)
+            self._pack_cur = pk
+            return
+        self._pack = None  # a tensor was replaced or written (or never packed): whatever pack there was is stale
+        prev = self._frame
+        if (state is not None and not capturing and self._scene_pack_key_matches(self._pack_seen, tensors, state, color_dim)
+                and prev is not None and not prev.training and int(prev.N) == int(pos.shape[0])
+                and _lib.gs_frame_reads_scene_pack(C.byref(prev))):
+            # the second consecutive inference frame of these tensors, and the first was one that would have read a pack
+            n = int(pos.shape[0])
+            a_bytes, b_bytes = C.c_size_t(), C.c_size_t()
+            _lib.gs_scene_pack_bytes(n, C.byref(a_bytes), C.byref(b_bytes))
+            a = torch.empty(a_bytes.value + 256, dtype=torch.uint8, device=self.device)
+            b = torch.empty(b_bytes.value + 256, dtype=torch.uint8, device=self.device)
+            pa, pb = (a.data_ptr() + 255) // 256 * 256, (b.data_ptr() + 255) // 256 * 256
+            _lib.check(_lib.gs_scene_pack_build(*(t.data_ptr() for t in tensors), n, color_dim, self.scale_activation, pa, pb,
+                                                cur.cuda_stream), "gs_scene_pack_build")
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._pack = self._pack_cur = {
+                "key": (tuple(weakref.ref(t) for t in tensors), state, (self.scale_activation, color_dim)),
+                "a": a, "b": b, "planes": (pa, pb, a_bytes.value, b_bytes.value), "event": ev, "streams": {cur.cuda_stream}}
+            self._pack_seen = None
+            return
+        self._pack_seen = None if state is None else (tuple(weakref.ref(t) for t in tensors), state,
+                                                      (self.scale_activation, color_dim))
+
+    def scene_pack_active(self) -> bool:
+        """Did the last frame read a scene pack (GS_FRAME_SCENE_PACK) instead of the raw parameter arrays?"""
+        return self._frame is not None and bool(self._frame.flags & _lib.GS_FRAME_SCENE_PACK)
 
     def _stream(self):
         return torch.cuda.current_stream(self.device)
@@ -505,6 +590,7 @@ class FrameRenderer:
         sync_check = self.auto_grow is True or (self.auto_grow == "async" and (not training or not self._checked_once))
         if self.auto_grow == "async":
             self._poll_async_counters()
+        self._scene_pack_step(pos, quat, scale, opa, rgb, training)
         while True:
             f = self._describe(pos, quat, scale, opa, rgb, camera, training, aux)
             g = self._grid
@@ -575,6 +661,7 @@ class FrameRenderer:
                 if (cur is None or not cur.training or self.auto_grow is True or not self._checked_once
                         or cur.max_pairs != self.max_pairs or cur.N != pos.shape[0]):
                     return False
+                self._pack_cur = None  # (a training frame)
                 f = self._describe(pos, quat, scale, opa, rgb, camera, True)
                 if f.workspace != cur.workspace:
                     return False
@@ -717,6 +804,9 @@ class FrameRenderer:
         with torch.cuda.device(self.device):
             _lib.check(getattr(_lib, name)(C.byref(f), grad_image.data_ptr() if grad_image is not None else None,
                                            C.byref(adam), self._stream().cuda_stream), name)
+        # the library stepped the parameters through raw pointers: tell torch, so that whoever keys on the tensors' version
+        # counters (a renderer's scene pack) sees them change -- all three fused entry points pass through here
+        torch.autograd.graph.increment_version(self._keep[:5])
         self._bwd_serial = self._frame_serial
 
     def backward(self, grad_image, out=None, part: int = 0, grad_depth=None, grad_alpha=None, grad_pose=None):
@@ -781,8 +871,8 @@ class FrameRenderer:
         need = _lib.gs_frame_pose_workspace_bytes(int(f.N))
         if self._pose_ws is None or self._pose_ws.numel() < need + 256:
             self._pose_ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
-        g = _lib.GsFrame()
-        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFrame))
+        g = _lib.GsFrameScene()
+        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFrameScene))
         base = self._pose_ws.data_ptr()
         g.pose_workspace = (base + 255) // 256 * 256
         g.pose_workspace_bytes = self._pose_ws.numel() - (g.pose_workspace - base)
@@ -795,6 +885,8 @@ class FrameRenderer:
         {stage: ms}; the raster stage is exactly one kernel launch."""
         training = self.training if training is None else training
         self._begun = None
+        with torch.cuda.device(self.device):
+            self._scene_pack_step(pos, quat, scale, opa, rgb, training)
         f = self._describe(pos, quat, scale, opa, rgb, camera, training, aux)
         g = self._grid
         image = torch.empty(g.height, g.width, 3, device=self.device, dtype=torch.float32)

@@ -86,6 +86,9 @@ def seed_apply(image: torch.Tensor, rng: torch.Tensor, camera, opts, out: Sequen
     _lib.check(_lib.gs_seed_apply(image.data_ptr(), rng.data_ptr(), C.byref(cam), C.byref(opts),
                                   *(t.data_ptr() for t in out), int(offset), cap, counts.data_ptr(), ws.data_ptr(),
                                   ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_seed_apply")
+    # rows written through raw pointers into tensors the caller may already have rendered from (a set with spare capacity):
+    # advance their version counters, which a renderer's scene pack is keyed on
+    torch.autograd.graph.increment_version(tuple(out))
 
 
 def seed_from_depth(image: torch.Tensor, depth: torch.Tensor, camera, *,

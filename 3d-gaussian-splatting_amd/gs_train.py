@@ -183,6 +183,9 @@ class FusedAdam:
             0, len(ORDER), self._ends, self._lr, self.betas[0], self.betas[1], self.eps, self.step_count,
             self.accum_grad.data_ptr() if self.accum_grad is not None else None, b, e, self.stat_mode, self.skip_flag,
             torch.cuda.current_stream().cuda_stream), "gs_adam_step")
+        # the kernel wrote the flat buffer through a raw pointer: advance its version counter (shared by all its views, the
+        # five parameter tensors among them), which a renderer's scene pack is keyed on
+        torch.autograd.graph.increment_version(f.flat_param)
 
     def fused_descriptor(self, advance: bool = True):
         """The ``gs_adam_fused`` argument of ``FrameRenderer.backward_adam`` for ONE optimizer step over everything
@@ -221,6 +224,7 @@ class FusedAdam:
             self.eps, self.step_count, self.accum_grad.data_ptr() if self.accum_grad is not None else None, b, e,
             self.stat_mode, self.skip_flag, float(grad_scale), torch.cuda.current_stream().cuda_stream),
             "gs_adam_step_multi")
+        torch.autograd.graph.increment_version(f.flat_param)  # (as in `step`)
 
 
 class _MapLoss:

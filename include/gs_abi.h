@@ -47,6 +47,10 @@ extern "C" {
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_depth +
  *   gs_loss_depth_workspace_bytes (L1 depth supervision on the GS_FRAME_AUX maps) and gs_frame_backward_adam_aux (the fused
  *   training step for GS_FRAME_AUX frames).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_SCENE_PACK with
+ *   gs_frame_scene -- a gs_frame followed by scene_pack_a / scene_pack_b / scene_pack_a_bytes / scene_pack_b_bytes, read only
+ *   when the flag is set; gs_frame itself is unchanged --, gs_scene_pack_bytes, gs_scene_pack_build and
+ *   gs_frame_reads_scene_pack.
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_POSE_GRAD with the
  *   trailing gs_frame fields grad_rot / grad_tran / pose_workspace / pose_workspace_bytes (behind the GS_FRAME_AUX fields,
  *   read only when the flag is set) and gs_frame_pose_workspace_bytes.
@@ -309,6 +313,26 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        All refusals come before anything is enqueued.
                                        Frames without the flag run exactly the kernels they ran before it existed. */
 
+#define GS_FRAME_SCENE_PACK 8192      /* the frame carries a SCENE PACK (the descriptor is a gs_frame_scene, below: built by
+                                       gs_scene_pack_build): the camera-independent half of the projection of every Gaussian
+                                       -- activations, R S S R^T, the activated opacity and rgb colour, 80 bytes per Gaussian
+                                       (192 MB at 2.4 M) --, which the project stage of an inference frame of the strip
+                                       variant then reads INSTEAD of the raw arrays.  The frame is bit for bit the frame
+                                       rendered without the flag: the same expressions on the same inputs in the same
+                                       order, half of them evaluated once instead of once per frame.
+                                       THE CALLER PROMISES that the pack was built from exactly the arrays this frame names
+                                       (pos, quat, scale, opa, rgb, N), with this frame's color_dim and scale_activation, and
+                                       that none of the arrays has been written since.  The library cannot check it (the
+                                       check would be the pass over memory the pack removes), and unlike a stale cut table
+                                       of GS_FRAME_OCCLUSION_CULL, which costs a second pass, a stale pack renders a WRONG
+                                       IMAGE.  The raw arrays must still be valid: the paths below read them.
+                                       GS_E_INVALID, before anything is enqueued, for a flagged training frame, a NULL
+                                       plane, a plane shorter than gs_scene_pack_bytes says, scene_pack_a not 16-byte or
+                                       scene_pack_b not 64-byte aligned.  Ignored (the raw arrays are read) by the table /
+                                       slice-sorted / radix variants and by gs_frame_forward_project's frames, which are
+                                       training frames; gs_frame_reads_scene_pack tells.  Frames without the flag run
+                                       exactly the kernels they ran before it existed. */
+
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
  * splatter.py does (Tiles, RayInfo, frustum guard band); rot/tran are passed by value. */
 typedef struct gs_frame {
@@ -382,6 +406,18 @@ typedef struct gs_frame {
     size_t pose_workspace_bytes;
 } gs_frame;
 
+/* GS_FRAME_SCENE_PACK: the descriptor of a flagged frame continues behind gs_frame with four more fields.  A caller that sets
+ * the flag passes &s.frame of a gs_frame_scene to the entry points, all of which keep taking `const gs_frame *`; the library
+ * reads the four fields only when the flag is set, which is the rule the GS_FRAME_AUX and GS_FRAME_POSE_GRAD fields follow.
+ * They are a struct of their own and not members of gs_frame so that sizeof(gs_frame) and its last member stay what every
+ * client of version 8 was built against. */
+typedef struct gs_frame_scene {
+    gs_frame frame;           /* first member: (const gs_frame_scene *)f == f                                              */
+    const void *scene_pack_a; /* 16-byte aligned, >= a_bytes of gs_scene_pack_bytes(N, ...)                                 */
+    const void *scene_pack_b; /* 64-byte aligned, >= b_bytes                                                                */
+    size_t scene_pack_a_bytes, scene_pack_b_bytes;
+} gs_frame_scene;
+
 /* Bytes of workspace needed for N Gaussians, `max_pairs` pairs, a width x height image. */
 size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int32_t height,
                                 int32_t color_dim, int32_t training);
@@ -394,6 +430,18 @@ size_t gs_frame_aux_workspace_bytes(int64_t max_pairs, int32_t width, int32_t he
 /* Bytes of pose workspace a GS_FRAME_POSE_GRAD frame of N Gaussians needs (host-only, no device call): one row of 12 floats
  * per 256 Gaussians for the projection backward and one for the aux depth backward, and a small header.  0 when N < 0. */
 size_t gs_frame_pose_workspace_bytes(int64_t N);
+
+/* Scene pack (GS_FRAME_SCENE_PACK).  gs_scene_pack_bytes: bytes of the two planes for N Gaussians (host-only): 16 N and 64 N,
+ * each rounded up to 256; returns their sum, 0 (and zeros) when N < 0; either out pointer may be NULL.
+ * gs_scene_pack_build: writes both planes from the raw arrays on `stream` (one kernel, 56 B in and 80 B out per Gaussian); pack_a
+ * 16-byte, pack_b 64-byte aligned, of at least those sizes.
+ * gs_frame_reads_scene_pack (host-only): 1 exactly when the frame AS DESCRIBED, flagged or not, is one whose project stage would
+ * read a pack -- an inference frame of the strip variant with N > 0 --, else 0 (also for a NULL frame): a caller need not build
+ * 80 bytes per Gaussian for a frame that would ignore them. */
+size_t gs_scene_pack_bytes(int64_t N, size_t *a_bytes, size_t *b_bytes);
+int gs_scene_pack_build(const float *pos, const float *quat, const float *scale, const float *opa, const float *rgb, int64_t N,
+                        int32_t color_dim, int32_t scale_activation, void *pack_a, void *pack_b, gs_stream_t stream);
+int gs_frame_reads_scene_pack(const gs_frame *f);
 
 /* Forward frame.  Launches everything on `stream`, never synchronises, and keeps no state of its own.
  * With f->training AND f->async the zero-fill of the per-pair gradient rows and the backward's bucket list are

@@ -210,6 +210,26 @@ gs_view_overlap_workspace_bytes = _sig("gs_view_overlap_workspace_bytes", sz, i3
 gs_view_overlap_check_view = _sig("gs_view_overlap_check_view", ci, C.POINTER(GsSeedCamera), i32)
 gs_view_overlap = _sig("gs_view_overlap", ci, vp, C.POINTER(GsSeedCamera), vp, i32, C.POINTER(GsOverlapOpts), vp, vp, sz, vp)
 
+GS_PRUNE_MAX_ARRAYS = 16
+
+
+class GsPruneOpts(C.Structure):
+    """Mirror of ``struct gs_prune_opts``."""
+
+    _fields_ = [("opa_logit_min", f32), ("scale_max", f32), ("scale_activation", i32)]
+
+
+class GsPruneArrays(C.Structure):
+    """Mirror of ``struct gs_prune_arrays``."""
+
+    _fields_ = [("n", i32), ("width", i32 * GS_PRUNE_MAX_ARRAYS), ("src", vp * GS_PRUNE_MAX_ARRAYS),
+                ("dst", vp * GS_PRUNE_MAX_ARRAYS)]
+
+
+gs_prune_workspace_bytes = _sig("gs_prune_workspace_bytes", sz, i64)
+gs_prune_classify = _sig("gs_prune_classify", ci, vp, vp, i64, C.POINTER(GsPruneOpts), vp, vp, sz, vp)
+gs_prune_apply = _sig("gs_prune_apply", ci, C.POINTER(GsPruneArrays), i64, i64, i64, vp, vp, sz, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -228,6 +248,7 @@ EXPORTS = [
     "gs_loss_track_workspace_bytes", "gs_loss_track",
     "gs_view_overlap_workspace_bytes", "gs_view_overlap_check_view", "gs_view_overlap",
     "gs_scene_pack_bytes", "gs_scene_pack_build", "gs_frame_reads_scene_pack",
+    "gs_prune_workspace_bytes", "gs_prune_classify", "gs_prune_apply",
 ]
 
 

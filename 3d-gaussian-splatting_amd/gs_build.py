@@ -44,6 +44,8 @@ SOURCES = {
     "map_loss.hip": ["-ffp-contract=off"],
     # the seen / not seen test as written: a float32 restatement decides identically; no SLP packing, as above
     "overlap.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # the keep test (opa > t and ||act(scale)|| < s) as written: densify.hip's delete rule, decided identically
+    "map_edit.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

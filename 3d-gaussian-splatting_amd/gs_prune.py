@@ -1,0 +1,96 @@
+"""Pruning the Gaussian set: remove rows by one per-row decision and move every array that shares the row index.
+
+``prune_rows(scale, opa, arrays, opa_min=..., scale_max=..., scale_activation=...)`` keeps the Gaussians with
+sigmoid(opa) > ``opa_min`` and ||act(scale)|| < ``scale_max`` -- the delete rule of ``gs_densify.adaptive_control`` with both
+thresholds as arguments -- and returns every array of ``arrays`` (up to sixteen: parameters, optimizer moments, a statistic;
+rows of any width) compacted to the kept rows, in order (include/gs_abi.h, gs_prune_classify / gs_prune_apply;
+csrc/map_edit.hip).  Three HIP launches and one host read of the counts in between (a control step, like
+``gs_seed.seed_from_depth``); bitwise repeatable.  ``gs_train.Trainer.prune`` is the hook that prunes a running fit and takes
+its optimizer state along.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from gaussian import _lib
+
+SCALE_ACT = {"abs": 0, "exp": 1}
+# opa_min 0.005: a quarter of the 0.02 the reference prunes below (gs_densify; utils.py:350-351), which it applies inside a
+# schedule that also resets opacities; a mapping loop has no such schedule and its seeds start at opa_init = 0.9, so the floor
+# only takes what training has driven out of the image.  scale_max inf: no scale test.  No run has been fitted to either.
+DEFAULTS = dict(opa_min=0.005, scale_max=math.inf)
+MAX_ARRAYS = _lib.GS_PRUNE_MAX_ARRAYS
+
+
+def opa_logit(p: float) -> float:
+    """A probability in (0, 1) as the raw logit the kernel compares, computed in double (inverse_sigmoid, utils.py:350-351)."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"opa_min must lie in (0, 1), got {p!r}")
+    return -math.log(1.0 / p - 1.0)
+
+
+def prune_options(opa_min: float = DEFAULTS["opa_min"], scale_max: Optional[float] = DEFAULTS["scale_max"],
+                  scale_activation: str = "abs") -> "_lib.GsPruneOpts":
+    return _lib.GsPruneOpts(opa_logit(opa_min), math.inf if scale_max is None else float(scale_max),
+                            SCALE_ACT[scale_activation])
+
+
+def _rows(name: str, t: torch.Tensor, n: Optional[int] = None) -> int:
+    """A contiguous float32 HIP tensor of rows -> floats per row."""
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() < 1 or (n is not None and t.shape[0] < n):
+        raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor" + (f" of at least {n} rows" if n is not None else ""))
+    return int(math.prod(t.shape[1:]))
+
+
+def prune_classify(scale: torch.Tensor, opa: torch.Tensor, opts) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The decision pass: -> (counts [2] int64 on the device = (kept, removed), workspace)."""
+    if scale.device.type != "cuda":
+        raise RuntimeError("pruning needs a HIP device; there is no CPU fallback")
+    n = int(scale.shape[0])
+    if _rows("scale", scale) != 3 or _rows("opa", opa) != 1 or int(opa.shape[0]) != n:
+        raise RuntimeError(f"scale must be [N,3] and opa [N] of the same N, got {list(scale.shape)} and {list(opa.shape)}")
+    ws = torch.empty(int(_lib.gs_prune_workspace_bytes(n)), dtype=torch.uint8, device=scale.device)
+    counts = torch.zeros(2, dtype=torch.int64, device=scale.device)
+    _lib.check(_lib.gs_prune_classify(scale.data_ptr(), opa.data_ptr(), n, C.byref(opts), counts.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_prune_classify")
+    return counts, ws
+
+
+def prune_apply(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], n: int, counts: torch.Tensor, ws: torch.Tensor,
+                dst_offset: int = 0, capacity: Optional[int] = None):
+    """The move, ONE launch for all arrays: the kept rows of every ``src[k]`` (``n`` rows) become rows [dst_offset, dst_offset +
+    kept) of ``dst[k]`` (``capacity`` rows, default: the shortest dst).  Writes nothing if they do not fit."""
+    if len(src) != len(dst) or not 1 <= len(src) <= MAX_ARRAYS:
+        raise RuntimeError(f"prune_apply moves 1 .. {MAX_ARRAYS} arrays, a dst for every src; got {len(src)} and {len(dst)}")
+    cap = min(int(t.shape[0]) for t in dst) if capacity is None else int(capacity)
+    a = _lib.GsPruneArrays()
+    a.n = len(src)
+    for k, (s, d) in enumerate(zip(src, dst)):
+        w = _rows(f"src[{k}]", s, int(n))
+        if _rows(f"dst[{k}]", d, cap) != w:
+            raise RuntimeError(f"array {k}: src rows hold {w} floats, dst rows {_rows('dst', d)}")
+        a.width[k], a.src[k], a.dst[k] = max(w, 0), s.data_ptr() or None, d.data_ptr() or None
+    _lib.check(_lib.gs_prune_apply(C.byref(a), int(n), int(dst_offset), cap, counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   torch.cuda.current_stream().cuda_stream), "gs_prune_apply")
+    # rows written through raw pointers: advance the version counters (a renderer's scene pack is keyed on them)
+    torch.autograd.graph.increment_version(tuple(dst))
+
+
+def prune_rows(scale: torch.Tensor, opa: torch.Tensor, arrays: Sequence[torch.Tensor], *,
+               opa_min: float = DEFAULTS["opa_min"], scale_max: Optional[float] = DEFAULTS["scale_max"],
+               scale_activation: str = "abs") -> Tuple[List[torch.Tensor], int, int]:
+    """-> (the arrays compacted to the kept rows, kept, removed).  ``scale`` [N,3] and ``opa`` [N] decide (raw parameters);
+    ``arrays``: up to sixteen float32 tensors of N rows each, ``scale`` and ``opa`` among them if they are to travel."""
+    opts = prune_options(opa_min, scale_max, scale_activation)
+    n = int(scale.shape[0])
+    counts, ws = prune_classify(scale, opa, opts)
+    kept, removed = (int(v) for v in counts.tolist())  # the one host synchronisation
+    out = [torch.empty((kept,) + tuple(t.shape[1:]), dtype=torch.float32, device=scale.device) for t in arrays]
+    if kept:
+        prune_apply([t.detach() for t in arrays], out, n, counts, ws)
+    return out, kept, removed

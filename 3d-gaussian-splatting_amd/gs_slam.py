@@ -15,6 +15,13 @@ gs_frame_backward_adam_pose, delivers the pose gradient of every step, the Track
 the window except keyframe 0, which fixes the gauge; ``KeyframeSet.set_pose`` carries the result into the view table and the
 tracker's motion history starts from the refined pose.  The keyframe set only grows -- ``KeyframeSet.add`` raises when it is
 full; there is no loop closure and ``adaptive_control`` is never called.
+
+Two options edit the map without resetting Adam, both off by default.  ``SlamOptions.carry_optimizer``: a keyframe's seeding
+keeps the old rows' moments and the step count (``Trainer.seed_from_view(carry_state=True)``) instead of starting a fresh
+optimizer for the whole map.  ``SlamOptions.prune_every`` = k: behind the mapping steps of every k-th keyframe the Gaussians
+whose opacity training drove below ``prune_opa_min`` (or whose extent reached ``prune_scale_max``) are removed
+(``Trainer.prune``, csrc/map_edit.hip: one compaction of parameters, moments and statistic), before the tracker is bound to
+the map.
 """
 from __future__ import annotations
 
@@ -156,7 +163,12 @@ class SlamOptions:
     ``i_iter``, so ``train.n_iters`` is the number of mapping steps over which the "exp" schedule takes the rates down to
     1 %, not the length of a fit to a fixed set of views.  A sequence has no known length; the default stays
     ``TrainOptions``' 7001, so that a run of a few hundred mapping steps trains at nearly the full rate (0.72 x after 500).
-    Set it to the expected keyframes x ``map_iterations`` for a sequence that should anneal, or ``lr_decay="none"``."""
+    Set it to the expected keyframes x ``map_iterations`` for a sequence that should anneal, or ``lr_decay="none"``.
+
+    ``carry_optimizer`` and ``prune_every`` are off: with them off the loop issues exactly the calls it issued before they
+    existed.  ``prune_opa_min`` = 0.005 and ``prune_scale_max`` = None (no scale test) have no evidence behind them: 0.005 is a
+    quarter of the 0.02 the reference prunes below inside its own densification schedule (``gs_prune.DEFAULTS``); what the
+    options did on the eight-frame arc is in profiles/slam_carry.txt."""
     track: TrackOptions = field(default_factory=TrackOptions)
     train: TrainOptions = field(default_factory=_map_train_options)
     seed: dict = field(default_factory=lambda: dict(gs_seed.DEFAULTS))
@@ -177,6 +189,11 @@ class SlamOptions:
     refine_poses: bool = False
     pose_lr_rot: float = 2e-4
     pose_lr_tran: float = 2e-4
+    # Map edits that keep the optimizer state (off: the loop is call for call the one without the options)
+    carry_optimizer: bool = False   # a keyframe's seeding keeps the old rows' Adam moments and the step count
+    prune_every: int = 0            # prune behind the mapping steps of every k-th keyframe (0: never)
+    prune_opa_min: float = 0.005    # ... the Gaussians with sigmoid(opa) <= this (no evidence: see above)
+    prune_scale_max: Optional[float] = None  # ... or ||act(scale)|| >= this; None: no scale test
 
 
 @dataclass
@@ -194,6 +211,7 @@ class SlamFrame:
     # refine_poses: keyframe index -> (rot, tran) float64 of every window view whose pose the mapping steps moved (never
     # keyframe 0); rot / tran above then report this frame's own refined pose
     refined: Dict[int, Tuple[np.ndarray, np.ndarray]] = field(default_factory=dict)
+    pruned: int = 0                  # Gaussians removed behind this keyframe's mapping steps (prune_every)
 
 
 class Slam:
@@ -262,6 +280,11 @@ class Slam:
                 self.tracker.set_last_pose(frame.rot, frame.tran)
         frame.map_losses += [float(v) for v in torch.stack(vals)[:, 0].cpu()] if vals else []
         frame.seconds["map"] = time.perf_counter() - t0
+        if o.prune_every > 0 and len(self.keyframes) % int(o.prune_every) == 0:
+            t0 = time.perf_counter()
+            frame.pruned = tr.prune(self.i_iter, opa_min=o.prune_opa_min, scale_max=o.prune_scale_max,
+                                    carry_state=bool(o.carry_optimizer))
+            frame.seconds["prune"] = time.perf_counter() - t0
         # (also with no step taken: seeding gave the trainer new parameter tensors)
         if self.tracker is None:
             self.tracker = Tracker(self.trainer.flat.params, self.keyframes.cameras[0], self.opt.track, self.device)
@@ -320,7 +343,10 @@ class Slam:
         if added_as != new:
             raise RuntimeError(f"keyframe {new} became view {added_as} of the trainer: the two lists have diverged")
         self._last_keyframe_at = index
-        frame.added = self.trainer.seed_from_view(new, self.i_iter, **self._seed)
+        if o.carry_optimizer:
+            frame.added = self.trainer.seed_from_view(new, self.i_iter, carry_state=True, **self._seed)
+        else:
+            frame.added = self.trainer.seed_from_view(new, self.i_iter, **self._seed)
         frame.seconds["seed"] = time.perf_counter() - t2
         frame.window = [new] + select_keyframes(counts[:n], measured, o.window - 1, o.min_share)
         frame.pending = int(o.map_iterations)

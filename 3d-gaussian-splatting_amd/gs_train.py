@@ -144,6 +144,15 @@ class FusedAdam:
                                 (C.c_int64 * n_r)(*offs)))
         return off if self.sharded else flat.flat_param.numel()
 
+    def moment_rows(self, name: str):
+        """(exp_avg, exp_avg_sq) of parameter tensor ``name`` as views shaped like it -- a replicated optimizer only, whose
+        moments mirror the flat buffer (a sharded one keeps 1 / world of them, packed by slice)."""
+        if self.sharded:
+            raise RuntimeError("a sharded optimizer's moments are not addressable by row")
+        lo, hi = self.flat.offsets[name]
+        shape = self.flat.params[("pos", "quat", "scale", "opa", "rgb").index(name)].shape
+        return self.exp_avg[lo:hi].view(shape), self.exp_avg_sq[lo:hi].view(shape)
+
     def reslice(self):
         """After ``flat.set_slices``: a replicated optimizer's moments mirror the flat buffer, so only the unit tables
         change; a sharded one packs its moments by slice and cannot follow."""
@@ -344,6 +353,14 @@ def z_to_range(z: torch.Tensor, camera) -> torch.Tensor:
     return (z.to(torch.float64) * torch.from_numpy(factor).to(z.device)).to(torch.float32)
 
 
+@dataclass
+class _Carry:
+    """What ``Trainer._bind`` takes over from the optimizer it replaces when the Gaussian set is EDITED rather than replaced:
+    the step count, and ``fill(flat, optimizer)``, which writes the rows that travel into the new (zeroed) buffers."""
+    step_count: int
+    fill: Callable
+
+
 class Trainer:
     """One view per step on this rank; gradients are averaged over ranks when torch.distributed is up.
 
@@ -430,9 +447,12 @@ class Trainer:
         self._free = {}  # camera id -> _FreePose: gs_track.FreePose: the views whose pose is refined with the map (free_pose)
         self._bind(params, 0)
 
-    def _bind(self, params: Sequence[torch.Tensor], i_iter: int):
+    def _bind(self, params: Sequence[torch.Tensor], i_iter: int, carry: Optional[_Carry] = None):
         """(Re)creates the flat bucket and the optimizer for a (new) Gaussian set: train.py:59-67 / :169-179 --
-        the reference also starts a fresh torch.optim.Adam after every adaptive_control."""
+        the reference also starts a fresh torch.optim.Adam after every adaptive_control.  ``carry`` (an edit of the set:
+        ``prune``, ``seed_from_view(carry_state=True)``): the new optimizer keeps the old step count and ``carry.fill`` writes
+        the carried rows of the moments and the statistic into its zeroed buffers (pad rows stay zero); everything else is
+        the rebind it always was."""
         force = getattr(getattr(self, "flat", None), "force_collective", False)
         self.flat = FlatGaussianParams(params, world_size=self.world_size, exchange=self.exchange,
                                        force_collective=force, n_slices=self.n_slices)
@@ -447,6 +467,9 @@ class Trainer:
         self.grad_counter = None  # "mean" accumulation only: per-Gaussian count of views that saw it (train.py:150)
         self._views_checked = set()  # a new Gaussian set: every view's first frame is capacity-checked again
         self._backward_choice_due = True  # ... and the rgb backward kernel is chosen again, behind its first step
+        if carry is not None:
+            self.optimizer.step_count = int(carry.step_count)
+            carry.fill(self.flat, self.optimizer)
 
     def _view_depth(self, camera, d: Optional[torch.Tensor]):
         """One view's measured depth map as the step uses it -> (range map on the device or None, 1 / its measured pixels):
@@ -835,15 +858,70 @@ class Trainer:
         return self._eval_renderer
 
     @torch.no_grad()
-    def seed_from_view(self, camera_id: int, i_iter: int, **options) -> int:
+    def _refuse_carry(self, what: str):
+        """The optimizer state can travel with the rows only where one rank holds all of it, addressed by row."""
+        if self.optimizer.sharded or self.world_size > 1 or self.view_stat is not None or self.grad_counter is not None:
+            raise RuntimeError(f"{what} cannot carry the optimizer state of a sharded optimizer (exchange='reduce_scatter'), "
+                               "of several ranks (world_size > 1) or of a per-view statistic (per_view_stat, a 'mean' view "
+                               "counter): their moments are not row-addressable from one rank; pass carry_state=False")
+
+    @torch.no_grad()
+    def prune(self, i_iter: int, *, opa_min: float, scale_max: Optional[float] = math.inf, carry_state: bool = True) -> int:
+        """Removes the Gaussians with sigmoid(opa) <= ``opa_min`` or ||act(scale)|| >= ``scale_max`` (``gs_prune``: the delete
+        rule of ``adaptive_control`` with both thresholds as arguments; None / inf: no scale test) -> the number removed.
+        With ``carry_state`` the kept rows take their Adam moments and their densification statistic with them and the step
+        count stays: ONE ``gs_prune_apply`` moves the five parameter arrays, the ten moment arrays and the statistic straight
+        into the new flat buffer and the new optimizer's buffers.  ``carry_state=False``: the fresh optimizer of every other
+        rebind.  When nothing is removed nothing changes -- no rebind; one host read either way.  A prune that would remove
+        every Gaussian is refused.  The Trainer never calls this by itself."""
+        from gs_prune import prune_apply, prune_classify, prune_options
+
+        if carry_state:
+            self._refuse_carry("prune(carry_state=True)")
+        opts = prune_options(opa_min, scale_max, self.scale_activation)
+        self.flat.finish_gather()
+        old_flat, old_opt = self.flat, self.optimizer
+        params, n = old_flat.params, old_flat.n
+        counts, ws = prune_classify(params[2], params[3], opts)
+        kept, removed = (int(v) for v in counts.tolist())  # the one host synchronisation
+        if removed == 0:
+            return 0
+        if kept == 0:
+            raise RuntimeError(f"prune(opa_min={opa_min}, scale_max={scale_max}) would remove all {n} Gaussians")
+        names = ("pos", "quat", "scale", "opa", "rgb")
+
+        def fill(flat, optimizer):
+            src, dst = list(params), list(flat.params)
+            if carry_state:
+                for name in names:
+                    src += old_opt.moment_rows(name)
+                    dst += optimizer.moment_rows(name)
+                if old_opt.accum_grad is not None:
+                    src.append(old_opt.accum_grad)
+                    dst.append(optimizer.accum_grad)
+            prune_apply(src, dst, n, counts, ws, capacity=kept)
+
+        # placeholders give the new flat buffer its shapes; the rows arrive with `fill`, not through a temporary set
+        shapes = [torch.empty((kept,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device) for t in params]
+        self._bind(shapes, i_iter, carry=_Carry(old_opt.step_count if carry_state else 0, fill))
+        self.flat.broadcast_params(0)
+        return removed
+
+    @torch.no_grad()
+    def seed_from_view(self, camera_id: int, i_iter: int, carry_state: bool = False, **options) -> int:
         """Extends the Gaussian set by what view ``camera_id`` measured and the current model does not explain
         (``gs_seed.seed_from_depth``: its colour target, its range map, the depth / alpha maps of the current model rendered
         here; ``options``: stride, alpha_thresh, front_rel, scale_factor, opa_init).  Returns the number of Gaussians added.
         A new set gets a fresh optimizer, as after ``adaptive_control``; when nothing is selected nothing changes -- no
-        rebind, the optimizer state stays.  The Trainer never calls this by itself: a mapping loop calls it per incoming
-        frame, between steps."""
+        rebind, the optimizer state stays.  ``carry_state=True``: the old rows keep their Adam moments and statistic, the
+        appended rows start from zeros, the step count stays (ten block copies, the regions shift in the flat layout).  A new
+        row then meets bias corrections near 1 with zero moments: its first update is lr 0.1 g / (0.1 |g| + eps), the
+        magnitude of a fresh Adam's first step, so no per-row step count is kept.  The Trainer never calls this by itself: a
+        mapping loop calls it per incoming frame, between steps."""
         from gs_seed import seed_from_depth
 
+        if carry_state:
+            self._refuse_carry("seed_from_view(carry_state=True)")
         if self.depths is None or self.depths[camera_id] is None:
             raise RuntimeError(f"view {camera_id} has no depth map (Trainer(depths=...)): nothing to seed from")
         self.flat.finish_gather()
@@ -857,7 +935,19 @@ class Trainer:
         added = int(new[0].shape[0]) - n_old
         if added == 0:
             return 0
-        self._bind(new, i_iter)
+        carry = None
+        if carry_state:
+            old_opt = self.optimizer
+
+            def fill(flat, optimizer):
+                for name in ("pos", "quat", "scale", "opa", "rgb"):
+                    for d, s in zip(optimizer.moment_rows(name), old_opt.moment_rows(name)):
+                        d[:n_old].copy_(s)
+                if old_opt.accum_grad is not None:
+                    optimizer.accum_grad[:n_old].copy_(old_opt.accum_grad)
+
+            carry = _Carry(old_opt.step_count, fill)
+        self._bind(new, i_iter, carry=carry)
         self.flat.broadcast_params(0)
         return added
 

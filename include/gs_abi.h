@@ -34,7 +34,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_backward_adam_pose (the
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_prune_workspace_bytes,
+ *   gs_prune_classify and gs_prune_apply with gs_prune_opts / gs_prune_arrays / GS_PRUNE_MAX_ARRAYS (remove Gaussians by one
+ *   per-row decision and move every array that shares the row index -- parameters, optimizer moments, the densification
+ *   statistic -- in one stable compaction).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_backward_adam_pose (the
  *   fused training step for GS_FRAME_POSE_GRAD frames, with or without GS_FRAME_AUX: the pose gradient of a mapping step).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_overlap,
  *   gs_view_overlap_workspace_bytes and gs_view_overlap_check_view with gs_overlap_opts / GS_OVERLAP_MAX_VIEWS (how many of the
@@ -883,6 +887,47 @@ int gs_view_overlap(const float *range, const gs_seed_camera *cam,        /* the
                     const gs_seed_camera *views_dev, int32_t n_views,     /* DEVICE array, 64 bytes per view     */
                     const gs_overlap_opts *opts, int64_t *counts_dev,     /* [n_views + 2]                       */
                     void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- editing the map: remove rows by one per-row decision, move everything that shares the row index ----
+ * Two calls around one host read, because the caller sizes the destination arrays between them (as gs_densify_* and
+ * gs_seed_*):
+ *   gs_prune_classify: decides every row and writes counts_dev[2] = (kept, removed);
+ *   gs_prune_apply   : the kept row with kept-rank r (the number of kept rows before it: the compaction is stable) goes to row
+ *                      dst_offset + r of EVERY dst[k]; rows in front of dst_offset and behind dst_offset + kept are not
+ *                      touched.  Nothing is written if dst_offset + kept > capacity (counts_dev still holds the need).
+ * The decision, in fp32 with one rounding per operation (a float32 restatement decides identically up to expf):
+ *   keep  <=>  opa[i] > opa_logit_min  and  norm < scale_max
+ *   norm = sqrtf(a a + b b + c c),  (a, b, c) = |scale[i]| per axis (scale_activation 0) or expf(scale[i]) (1)
+ * -- the delete rule of gs_densify_classify with both thresholds as arguments (there: logit(0.02) and delete_thresh).  A NaN
+ * in opa[i] or scale[i] means not kept.  scale_max = +inf switches the second test off for every finite norm (a norm that
+ * overflowed to +inf is still not kept).  opa is the raw logit; a caller that thinks in probabilities converts on the host.
+ * arrays: up to GS_PRUNE_MAX_ARRAYS arrays of fp32 rows, N rows in each src, `capacity` rows in each dst, any width >= 1
+ * (1, 3, 4, 27 and 48 occur); every array is moved by the same kernel in the same launch: a workgroup writes the destination
+ * span of its 256 source rows with consecutive lanes on consecutive floats, whatever the width.  No dst may be a src (the
+ * move is not in place) and no dst may overlap any src (not checked beyond equality).  Ranks come from wave ballots,
+ * per-workgroup counts and a scan -- no atomics: the result is a pure function of the inputs, whatever the workspace held.
+ * The same workspace goes to both calls (8-byte aligned, gs_prune_workspace_bytes(N): one bit and an eighth of a count per
+ * row).  Refused before anything is enqueued (GS_E_INVALID, gs_last_error): a null pointer (a src may be null only with
+ * N = 0, a dst only with capacity = 0), N < 0 or >= 2^31, n outside 1 .. GS_PRUNE_MAX_ARRAYS, a width < 1, a dst[k] equal to a
+ * src[j], a non-finite opa_logit_min, a NaN scale_max, an unknown activation, a misaligned or too-small workspace, a negative
+ * dst_offset or capacity.  N = 0 is valid: counts (0, 0), nothing moves.  All launches on `stream`. */
+#define GS_PRUNE_MAX_ARRAYS 16
+typedef struct gs_prune_opts {
+    float opa_logit_min;      /* keep needs opa[i] > this (raw logit; finite)                                   */
+    float scale_max;          /* keep needs ||act(scale[i])|| < this; +inf switches the test off                */
+    int32_t scale_activation; /* 0 = abs, 1 = exp                                                               */
+} gs_prune_opts;
+typedef struct gs_prune_arrays {   /* n arrays of fp32 rows that share the row index */
+    int32_t n;                     /* 1 .. GS_PRUNE_MAX_ARRAYS */
+    int32_t width[GS_PRUNE_MAX_ARRAYS];     /* floats per row, >= 1 */
+    const float *src[GS_PRUNE_MAX_ARRAYS];  /* N rows each */
+    float *dst[GS_PRUNE_MAX_ARRAYS];        /* `capacity` rows each; must not overlap any src */
+} gs_prune_arrays;
+size_t gs_prune_workspace_bytes(int64_t N);
+int gs_prune_classify(const float *scale, const float *opa, int64_t N, const gs_prune_opts *opts, int64_t *counts_dev,
+                      void *workspace, size_t workspace_bytes, gs_stream_t stream);
+int gs_prune_apply(const gs_prune_arrays *arrays, int64_t N, int64_t dst_offset, int64_t capacity,
+                   const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -427,8 +427,10 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_count_kern
 // of the projection.  Lane-masking them out gains nothing (a wave skips only what all of its 64 lanes skip, and Gaussians
 // arrive in no spatial order: measured, 92.7 against 79 us), so this kernel COMPACTS:
 //   phase A, every Gaussian of the slice: position and scale only (24 of 56 bytes), the exact frustum test, and a
-//     conservative occlusion test (occluded_everywhere) -- ~120 instructions; the survivors' indices are queued in LDS;
-//   phase B, full waves of survivors: the unchanged project_one + the trimmed strip walk of the culled frame, which counts
+//     conservative occlusion test (occluded_everywhere) -- ~120 instructions; the survivors' indices go to an LDS ring of
+//     the wave that tested them;
+//   phase B, full waves of survivors (a wave drains its ring whenever it holds 64: the two phases interleave, wave by
+//     wave): the unchanged project_one + the trimmed strip walk of the culled frame, which counts
 //     every level-1 entry and stores it, with its strip and its rank in the slice's run of that strip, in the slice's
 //     staging region: the level-1 placement of this pass is a permutation of the staged entries (strip_bin.hip).
 // A Gaussian that fails the occlusion test would have lost every pair to the trimming of walk_strips<.., true>: the
@@ -436,7 +438,6 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_count_kern
 // from a gated re-run of frame_project_count_kernel, which rewrites records, rectangles and the strip table untrimmed.
 // The cut pyramid: level 0 = the per-tile cuts (rows padded to whole strips, what walk_strips reads), level l = the LARGEST
 // cut of each block of 2^l x 2^l tiles (GS_NO_CUT -- a tile that did not saturate -- is the largest value there is).
-#define GS_OCC_QCAP 16384u   // Gaussians per chunk of a slice: their in-chunk indices are queued as 16-bit words
 #define GS_OCC_LEVELS 4      // pyramid levels 0..3: rectangles of up to 16 x 16 tiles are tested with <= 3 x 3 look-ups
 struct OccPyramid {
     const uint32_t *t0;           // level 0
@@ -484,10 +485,18 @@ __device__ __forceinline__ bool occluded_everywhere(const float pi[3], float z, 
     return dbits > m;
 }
 
+// Measured and dropped (profiles/cull_waves_ab.txt): this kernel with ONE survivor queue per workgroup -- every wave of phase A
+// claimed its slots with a returning LDS add on one word, a barrier, then phase B on the queue, 1,024 survivors at a time.
+// All 16 waves of the CU's one workgroup streamed at the same moment and then all of them waited for the same sparse gather.
+// Now every wave compacts for itself and projects its survivors as soon as it has 64 of them: no wave waits for another one
+// before the end of the slice, and on a SIMD one wave's gather lies under the other waves' stream.
+#define GS_OCC_RING 128u     // slots of a wave's survivor ring: a round adds at most 64, 64 are drained whenever 64 are present
+#define GS_OCC_TAIL (16u * 63u)  // the leftovers of the 16 waves (fewer than 64 each), pooled at the end of the slice
+
 // PACKED (the frame carries a scene pack): phase A streams plane A -- one 16-byte load per Gaussian, position and the largest
-// activated scale, 38 MB instead of 58 and no exponential --, phase B gathers the survivor's one 64-byte line of plane B and
-// runs the camera half alone.  No stash: nothing phase A read is needed again.  Queue, pyramid, strip walk, staging and every
-// output are those of the raw variant.
+// activated scale, 38 MB instead of 58 and no exponential --, the drain gathers the survivor's one 64-byte line of plane B and
+// runs the camera half alone.  The ring carries indices only: nothing phase A read is needed again.  Pyramid, strip walk,
+// staging and every output are those of the raw variant.
 // (One body, two kernels, as above: frame_project_cull_count_kernel and frame_packed_project_cull_count_kernel.)
 template <bool PACKED>
 __device__ __forceinline__ void project_cull_count_body(
@@ -497,30 +506,31 @@ __device__ __forceinline__ void project_cull_count_body(
     float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
     unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
-    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, unsigned long long *__restrict__ stage_ent,
+    const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
     uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
-    extern __shared__ unsigned long long s_hist[];  // [NS] entries << 32 | pairs of this slice, then the pyramid, then the queue
-    __shared__ uint32_t s_acc[2], s_qn, s_ne;
+    extern __shared__ unsigned long long s_hist[];  // [NS] entries << 32 | pairs of this slice, then the pyramid, rings and tail
+    __shared__ uint32_t s_acc[2], s_tn, s_ne;
     if (blockIdx.x >= S) {  // the one extra workgroup of the launch (uniform)
         tile_order_workgroup(tile_cost, n_tiles, tile_order);
         return;
     }
     const uint32_t slice = strip_slice_of_block(blockIdx.x, S);
     const int64_t g0 = (int64_t)slice * per_slice;
-    const int lane = threadIdx.x & 63;
-    // ---- LDS: histogram | cut pyramid | survivor queue
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // ---- LDS: histogram | cut pyramid | 16 survivor rings | pooled tail | (raw variant) the ring slots' positions and scales
     uint32_t *s_cut = reinterpret_cast<uint32_t *>(s_hist + SG.NS);
     const uint32_t st0 = SG.nsx * GS_STRIP_W;
     const uint32_t w1 = (SG.ntx + 1) / 2, h1 = (SG.nty + 1) / 2, w2 = (w1 + 1) / 2, h2 = (h1 + 1) / 2, w3 = (w2 + 1) / 2,
                    h3 = (h2 + 1) / 2;
     uint32_t *s_l1 = s_cut + st0 * SG.nty, *s_l2 = s_l1 + w1 * h1, *s_l3 = s_l2 + w2 * h2;
-    uint16_t *s_q = reinterpret_cast<uint16_t *>(s_l3 + w3 * h3);
-    // the first `stash_cap` survivors of a chunk keep their position and scale in LDS (six planes of stash_cap floats): phase B
-    // then gathers only the 32 bytes phase A did not read -- 17 % of the array still touches 62 % of its 64-byte lines
-    float *s_stash = reinterpret_cast<float *>(s_q + ((qcap + 1) & ~1u));
+    uint32_t *s_tail = s_l3 + w3 * h3 + (STRIP_THREADS / 64) * GS_OCC_RING;
+    uint32_t *const ring = s_l3 + w3 * h3 + wave * GS_OCC_RING;  // this wave's: slice-relative indices of its survivors
+    // the first `par_slots` slots of every ring keep position and scale as well (six planes of par_slots floats per wave): the
+    // drain then gathers only the 32 bytes phase A did not read -- 17 % of the array still touches 62 % of its 64-byte lines
+    float *const par = reinterpret_cast<float *>(s_tail + GS_OCC_TAIL) + wave * 6 * par_slots;
     const OccPyramid Y = {s_cut, st0 * SG.nty, w1 * h1, w2 * h2, st0, w1 - st0, w2 - w1, w3 - w2};
     // the first two rounds of positions and scales are requested before the set-up (their latency runs underneath it)
-    auto fetch_at = [&](float (&pp)[3], float (&ss)[3], uint32_t i) {
+    auto fetch = [&](float (&pp)[3], float (&ss)[3], uint32_t i) {
         int64_t g = g0 + i;
         g = g < n ? g : n - 1;
         if constexpr (PACKED) {  // (ss[0] = smax; ss[1], ss[2] are never read)
@@ -533,8 +543,8 @@ __device__ __forceinline__ void project_cull_count_body(
         }
     };
     float pa[3], sa[3], pb[3], sb[3];
-    fetch_at(pa, sa, threadIdx.x);
-    fetch_at(pb, sb, threadIdx.x + STRIP_THREADS);
+    fetch(pa, sa, threadIdx.x);
+    fetch(pb, sb, threadIdx.x + STRIP_THREADS);
     for (uint32_t t = threadIdx.x; t < SG.NS; t += STRIP_THREADS) s_hist[t] = 0;
     // (eight loads of the cut table in flight per thread: one at a time, each waited for, was 8 x the latency of a load)
     for (uint32_t t0 = threadIdx.x; t0 < st0 * SG.nty; t0 += 8 * STRIP_THREADS) {
@@ -552,6 +562,7 @@ __device__ __forceinline__ void project_cull_count_body(
     }
     if (threadIdx.x < 2) s_acc[threadIdx.x] = 0;
     if (threadIdx.x == 2) s_ne = 0;
+    if (threadIdx.x == 3) s_tn = 0;
     // this slice's region of the entry staging (gs_frame_layout.h, gs_cull_stage_cap): `ecap` entries and their tags
     unsigned long long *const ent = stage_ent + (size_t)slice * ecap;
     uint32_t *const tag = stage_tag + (size_t)slice * ecap;
@@ -571,150 +582,198 @@ __device__ __forceinline__ void project_cull_count_body(
     build(s_l1, w1, h1, s_cut, st0, SG.ntx, SG.nty);
     build(s_l2, w2, h2, s_l1, w1, w1, h1);
     build(s_l3, w3, h3, s_l2, w2, w2, h2);
+    __syncthreads();  // the pyramid is complete; from here to the pooled tail no wave waits for another one
     uint32_t acc_cnt = 0, acc_vis = 0;
-    for (uint32_t c0 = 0; c0 < per_slice; c0 += qcap) {  // uniform: chunks of the slice (one, unless the scene is huge)
-        const uint32_t cn = per_slice - c0 < qcap ? per_slice - c0 : qcap;
-        if (threadIdx.x == 0) s_qn = 0;
-        __syncthreads();  // (also: the pyramid is complete; the previous chunk's queue has been drained)
-        // ---- phase A: frustum + occlusion test of every Gaussian of the chunk; survivors are queued
-        // The phase is a 58 MB stream (24 B in per Gaussian, nothing out) at one workgroup per CU: three rounds of positions
-        // and scales are kept in flight.  That takes THREE NAMED register sets and a loop unrolled by three -- rotating one
-        // set into the next at the end of a round (`cur = nxt`) makes the move wait for the newest load (first version:
-        // s_waitcnt vmcnt(0) in every round, 30 us for the bare stream) -- and loads whose control flow is uniform (a lane
-        // beyond the chunk loads the array's last Gaussian and drops it), so that the waitcnt pass counts them exactly.
-        auto in_chunk = [&](uint32_t i) { return i < cn && g0 + c0 + i < n; };
-        auto fetch = [&](float (&pp)[3], float (&ss)[3], uint32_t i) { fetch_at(pp, ss, c0 + i); };
-        auto test = [&](const float (&pp)[3], const float (&ss)[3], uint32_t i) {
-            bool surv = false;
-            if (in_chunk(i)) {
-                float pc[3], pi[3];
-                if (project_cull(pp, P.cam, P.near_plane, P.half_w, P.half_h, pc, pi)) {
-                    const float dep = sqrtf(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);  // == project_cov's pos_i[2]
-                    float smax;
-                    bool finite;
-                    if constexpr (PACKED) {  // (the pack holds NaN for a Gaussian whose scales are not all finite)
-                        smax = ss[0];
-                        finite = smax < 3.0e38f;
-                    } else {
-                        float s[3];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) s[k] = P.scale_act == 0 ? fabsf(ss[k]) + 1e-4f : gs_exp2(GS_LOG2E * ss[k]);
-                        smax = fmaxf(s[0], fmaxf(s[1], s[2]));
-                        // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
-                        finite = s[0] + s[1] + s[2] < 3.0e38f;
-                    }
-                    if (finite && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
-                        // behind every cut it can reach, or beside the grid: visible, no tile.  NOTHING is written for it (nor
-                        // for a Gaussian outside the frustum): this pass places the entries phase B stages, the second
-                        // pass re-projects everything -- rects[] of a culled frame is only fresh for the survivors
-                        acc_vis += 1;
-                    } else {
-                        surv = true;
-                    }
-                }
-            }
-            const unsigned long long b = __ballot(surv);
-            if (b) {  // (uniform per wave)
-                uint32_t wbase = 0;
-                if (lane == 0) wbase = atomicAdd(&s_qn, (uint32_t)__popcll(b));
-                wbase = __shfl(wbase, 0, 64);
-                if (surv) {
-                    const uint32_t slot = wbase + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-                    s_q[slot] = (uint16_t)i;
-                    if (!PACKED && slot < stash_cap) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            s_stash[c * stash_cap + slot] = pp[c];
-                            s_stash[(3 + c) * stash_cap + slot] = ss[c];
-                        }
-                    }
-                }
-            }
-        };
-        float pq[3], sq[3];
-        if (c0 != 0) {  // (the first chunk's were requested in front of the set-up)
-            fetch(pa, sa, threadIdx.x);
-            fetch(pb, sb, threadIdx.x + STRIP_THREADS);
-        }
-        for (uint32_t base = 0; base < cn; base += 3 * STRIP_THREADS) {  // uniform trip count, uniform exits
-            const uint32_t i = base + threadIdx.x;
-            fetch(pq, sq, i + 2 * STRIP_THREADS);
-            test(pa, sa, i);
-            if (base + STRIP_THREADS >= cn) break;
-            fetch(pa, sa, i + 3 * STRIP_THREADS);
-            test(pb, sb, i + STRIP_THREADS);
-            if (base + 2 * STRIP_THREADS >= cn) break;
-            fetch(pb, sb, i + 4 * STRIP_THREADS);
-            test(pq, sq, i + 2 * STRIP_THREADS);
-        }
-        __syncthreads();
-        // ---- phase B: the survivors, 1,024 at a time on full waves
-        const uint32_t nq = s_qn;
-        auto load_survivor = [&](uint32_t k, uint32_t q) {
-            const int64_t pid = g0 + c0 + q;
-            if constexpr (PACKED) {
-                return load_static(pack_b, pid);
-            } else {
-                RawGaussian r;
-                if (k < stash_cap) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        r.p[c] = s_stash[c * stash_cap + k];
-                        r.sraw[c] = s_stash[(3 + c) * stash_cap + k];
-                    }
+    uint32_t head = 0, tail = 0;  // (wave-uniform) the ring holds the survivors [head, tail), slot = position mod GS_OCC_RING
+    // the ring is written and read by this wave alone: LDS runs a wave's accesses in order, the compiler is told to keep them so
+    auto ring_order = [] {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    // ---- the test of phase A: frustum + occlusion test of 64 Gaussians; the survivors go to the wave's ring
+    // The phase is a stream (PACKED: 16 B in per Gaussian, nothing out) at one workgroup per CU: three rounds of positions and
+    // scales are kept in flight.  That takes THREE NAMED register sets and a loop unrolled by three -- rotating one set into
+    // the next at the end of a round (`cur = nxt`) makes the move wait for the newest load (first version: s_waitcnt vmcnt(0)
+    // in every round, 30 us for the bare stream) -- and loads whose control flow is uniform (a lane beyond the slice loads the
+    // array's last Gaussian and drops it), so that the waitcnt pass counts them exactly.
+    auto in_slice = [&](uint32_t i) { return i < per_slice && g0 + i < n; };
+    auto test = [&](const float (&pp)[3], const float (&ss)[3], uint32_t i) {
+        bool surv = false;
+        if (in_slice(i)) {
+            float pc[3], pi[3];
+            if (project_cull(pp, P.cam, P.near_plane, P.half_w, P.half_h, pc, pi)) {
+                const float dep = sqrtf(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);  // == project_cov's pos_i[2]
+                float smax;
+                bool finite;
+                if constexpr (PACKED) {  // (the pack holds NaN for a Gaussian whose scales are not all finite)
+                    smax = ss[0];
+                    finite = smax < 3.0e38f;
                 } else {
-                    load3(pos, pid, r.p);
-                    load3(scale, pid, r.sraw);
+                    float s[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) s[k] = P.scale_act == 0 ? fabsf(ss[k]) + 1e-4f : gs_exp2(GS_LOG2E * ss[k]);
+                    smax = fmaxf(s[0], fmaxf(s[1], s[2]));
+                    // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
+                    finite = s[0] + s[1] + s[2] < 3.0e38f;
                 }
-                const float4 q4 = quat[pid];
-                r.qraw[0] = q4.x; r.qraw[1] = q4.y; r.qraw[2] = q4.z; r.qraw[3] = q4.w;
-                r.opa = opa[pid];
-                r.rgb[0] = r.rgb[1] = r.rgb[2] = 0.f;
-                if (P.color_dim == 3) load3(rgb, pid, r.rgb);
-                return r;
+                if (finite && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
+                    // behind every cut it can reach, or beside the grid: visible, no tile.  NOTHING is written for it (nor
+                    // for a Gaussian outside the frustum): this pass places the entries the drain stages, the second
+                    // pass re-projects everything -- rects[] of a culled frame is only fresh for the survivors
+                    acc_vis += 1;
+                } else {
+                    surv = true;
+                }
             }
-        };
-        decltype(load_survivor(0, 0)) cur = {}, nxt = {};
-        uint32_t qi = 0, qn_ = 0;
-        if (threadIdx.x < nq) {
-            qi = s_q[threadIdx.x];
-            cur = load_survivor(threadIdx.x, qi);
         }
-        settle(cur);
-        for (uint32_t base = 0; base < nq; base += STRIP_THREADS) {  // uniform trip count
-            const uint32_t k = base + threadIdx.x;
-            if (k + STRIP_THREADS < nq) {
-                qn_ = s_q[k + STRIP_THREADS];
-                nxt = load_survivor(k + STRIP_THREADS, qn_);
+        // no atomic, no shuffle: the wave's count is the ballot's population (an SGPR), a lane's slot the survivors below it
+        const unsigned long long b = __ballot(surv);
+        if (surv) {
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+            const uint32_t slot = (tail + below) & (GS_OCC_RING - 1);
+            ring[slot] = i;
+            if (!PACKED && slot < par_slots) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    par[c * par_slots + slot] = pp[c];
+                    par[(3 + c) * par_slots + slot] = ss[c];
+                }
             }
-            uint4 rc = make_uint4(0, 0, 0, 0);
-            uint32_t vis = 0;
-            float2 cxy = make_float2(0.f, 0.f);
-            const int64_t pid = g0 + c0 + qi;
-            if (k < nq) rc = project_one(cur, pid, P, rec_geom, nullptr, rects, vis, cxy);
-            acc_cnt += rc.w;
-            acc_vis += vis;
-            // Every entry is counted AND kept: the LDS add returns the entry's rank inside this slice's run of its strip,
-            // which with the column scan is its final position -- the permutation that follows (strip_bin.hip) neither walks
-            // the rectangle nor reads the cut table again.  Slot in the slice's staging region: the lanes that arrive
-            // together claim consecutive slots with one LDS add (they are whoever the walk has active here: the lowest of
-            // them adds).  An entry beyond the region is not stored; the slice is withdrawn below.
-            walk_strips<false, true>(rc, pid, SG, cxy, GsDistCull{},
-                                     [&](uint32_t strip, uint32_t lo32, uint32_t d, uint32_t np) {
-                                         const uint32_t rank = (uint32_t)(atomicAdd(&s_hist[strip], (1ull << 32) | np) >> 32);
-                                         const unsigned long long act = __ballot(true);
-                                         uint32_t wbase = 0;
-                                         if (lane == __ffsll((long long)act) - 1) wbase = atomicAdd(&s_ne, (uint32_t)__popcll(act));
-                                         wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
-                                         const uint32_t slot = wbase + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
-                                         if (slot < ecap) {
-                                             ent[slot] = ((unsigned long long)d << 32) | lo32;
-                                             tag[slot] = strip_tag(strip, rank);
-                                         }
-                                     },
-                                     s_cut);
-            cur = nxt;
-            qi = qn_;
+        }
+        tail += (uint32_t)__popcll(b);
+    };
+    // ---- the drain (phase B on this wave's own survivors): the unchanged project_one + the trimmed strip walk of the culled
+    // frame, which counts every level-1 entry and stores it, with its strip and its rank in the slice's run of that strip, in
+    // the slice's staging region
+    // `slot`: the survivor's ring slot (raw variant: below par_slots its position and scale are in LDS; GS_OCC_RING: not queued
+    // with them, gathered again)
+    auto load_survivor = [&](uint32_t slot, uint32_t q) {
+        const int64_t pid = g0 + q;
+        if constexpr (PACKED) {
+            return load_static(pack_b, pid);
+        } else {
+            RawGaussian r;
+            if (slot < par_slots) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    r.p[c] = par[c * par_slots + slot];
+                    r.sraw[c] = par[(3 + c) * par_slots + slot];
+                }
+            } else {
+                load3(pos, pid, r.p);
+                load3(scale, pid, r.sraw);
+            }
+            const float4 q4 = quat[pid];
+            r.qraw[0] = q4.x; r.qraw[1] = q4.y; r.qraw[2] = q4.z; r.qraw[3] = q4.w;
+            r.opa = opa[pid];
+            r.rgb[0] = r.rgb[1] = r.rgb[2] = 0.f;
+            if (P.color_dim == 3) load3(rgb, pid, r.rgb);
+            return r;
+        }
+    };
+    using Survivor = decltype(load_survivor(0, 0));
+    auto project_walk = [&](const Survivor &g, uint32_t q, bool active) {
+        uint4 rc = make_uint4(0, 0, 0, 0);
+        uint32_t vis = 0;
+        float2 cxy = make_float2(0.f, 0.f);
+        const int64_t pid = g0 + q;
+        if (active) rc = project_one(g, pid, P, rec_geom, nullptr, rects, vis, cxy);
+        acc_cnt += rc.w;
+        acc_vis += vis;
+        // Every entry is counted AND kept: the LDS add returns the entry's rank inside this slice's run of its strip,
+        // which with the column scan is its final position -- the permutation that follows (strip_bin.hip) neither walks
+        // the rectangle nor reads the cut table again.  Slot in the slice's staging region: the lanes that arrive
+        // together claim consecutive slots with one LDS add (they are whoever the walk has active here: the lowest of
+        // them adds).  An entry beyond the region is not stored; the slice is withdrawn below.
+        walk_strips<false, true>(rc, pid, SG, cxy, GsDistCull{},
+                                 [&](uint32_t strip, uint32_t lo32, uint32_t d, uint32_t np) {
+                                     const uint32_t rank = (uint32_t)(atomicAdd(&s_hist[strip], (1ull << 32) | np) >> 32);
+                                     const unsigned long long act = __ballot(true);
+                                     uint32_t wbase = 0;
+                                     if ((int)lane == __ffsll((long long)act) - 1) wbase = atomicAdd(&s_ne, (uint32_t)__popcll(act));
+                                     wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+                                     const uint32_t slot = wbase + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+                                     if (slot < ecap) {
+                                         ent[slot] = ((unsigned long long)d << 32) | lo32;
+                                         tag[slot] = strip_tag(strip, rank);
+                                     }
+                                 },
+                                 s_cut);
+    };
+    // A drain is cut in two: `request` takes the 64 oldest survivors off the ring and asks for their records, `finish` -- one
+    // round of the test later, so that the gather's latency lies under it -- projects them (in one piece: 48.4 against 47.5 us
+    // at 2.4 M Gaussians).  Both are wave-uniform branches: all 64 lanes are active in either.
+    Survivor cur = {};
+    uint32_t qi = 0;
+    bool pending = false;  // (wave-uniform) `cur` / `qi` hold a requested, not yet projected survivor per lane
+    auto request = [&] {
+        if (tail - head >= 64u) {
+            ring_order();
+            const uint32_t slot = (head + lane) & (GS_OCC_RING - 1);
+            qi = ring[slot];
+            ring_order();  // (the next test's stores may reach these slots)
+            head += 64u;
+            cur = load_survivor(slot, qi);
+            pending = true;
+        }
+    };
+    auto finish = [&] {
+        if (pending) {
+            project_walk(cur, qi, true);
+            pending = false;
+        }
+    };
+    // The set the NEXT round tests is waited for before a drain's loads are requested behind it and before its stores go out:
+    // where the two sides of a uniform branch meet, the waitcnt pass keeps the smaller count of "loads issued since", and the
+    // wait for a set that was requested before the branch would take the gather (or the stores) with it.
+    auto settle_set = [&](const float (&pp)[3], const float (&ss)[3]) {
+        if constexpr (PACKED) asm volatile("" ::"v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(ss[0]));
+        else asm volatile("" ::"v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(ss[0]), "v"(ss[1]), "v"(ss[2]));
+    };
+    float pq[3], sq[3];
+    for (uint32_t base = 0; base < per_slice; base += 3 * STRIP_THREADS) {  // uniform trip count, uniform exits
+        const uint32_t i = base + threadIdx.x;
+        fetch(pq, sq, i + 2 * STRIP_THREADS);
+        test(pa, sa, i);
+        settle_set(pb, sb);
+        finish();
+        request();
+        if (base + STRIP_THREADS >= per_slice) break;
+        fetch(pa, sa, i + 3 * STRIP_THREADS);
+        test(pb, sb, i + STRIP_THREADS);
+        settle_set(pq, sq);
+        finish();
+        request();
+        if (base + 2 * STRIP_THREADS >= per_slice) break;
+        fetch(pb, sb, i + 4 * STRIP_THREADS);
+        test(pq, sq, i + 2 * STRIP_THREADS);
+        settle_set(pa, sa);
+        finish();
+        request();
+    }
+    finish();
+    // ---- the pooled tail: every wave has fewer than 64 survivors left; they are pooled (one LDS add per wave) and projected
+    // by the first waves as full waves, the last of them ragged.  Every wave of the workgroup arrives here, Gaussians or not.
+    {
+        const uint32_t left = tail - head;  // < 64
+        uint32_t tbase = 0;
+        if (left) {  // (uniform per wave)
+            if (lane == 0) tbase = atomicAdd(&s_tn, left);
+            tbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)tbase);
+            ring_order();
+            if (lane < left) s_tail[tbase + lane] = ring[(head + lane) & (GS_OCC_RING - 1)];
+        }
+    }
+    __syncthreads();
+    {
+        const uint32_t nt = s_tn;
+        if (wave * 64u < nt) {  // (uniform per wave)
+            const uint32_t k = threadIdx.x;
+            const bool active = k < nt;
+            const uint32_t q = active ? s_tail[k] : 0u;
+            Survivor g = {};
+            if (active) g = load_survivor(GS_OCC_RING, q);
+            project_walk(g, q, active);
         }
     }
     acc_cnt = gs_wave_sum_u32(acc_cnt);
@@ -744,20 +803,20 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
     unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
-    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, unsigned long long *__restrict__ stage_ent,
+    const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
     uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
     project_cull_count_body<false>(pos, quat, scale, opa, rgb, nullptr, nullptr, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
-                                   qcap, stash_cap, stage_ent, stage_tag, ecap, slice_entries);
+                                   par_slots, stage_ent, stage_tag, ecap, slice_entries);
 }
 __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_cull_count_kernel(
     const float4 *__restrict__ pack_a, const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
     float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
     unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
-    const uint32_t *__restrict__ cut, uint32_t qcap, uint32_t stash_cap, unsigned long long *__restrict__ stage_ent,
+    const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
     uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
     project_cull_count_body<true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_a, pack_b, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
-                                   qcap, stash_cap, stage_ent, stage_tag, ecap, slice_entries);
+                                   par_slots, stage_ent, stage_tag, ecap, slice_entries);
 }
 
 // ---------------------------------------------------------------- S1 + B1 fused (table variant of sort_mode 2: small scenes)
@@ -927,28 +986,26 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
             // GS_FRAME_OCCLUSION_CULL, first pass: Gaussians behind every cut they can reach are not projected, the level-1
             // entries of the others are trimmed by the cut table the previous frame of this workspace left
             GS_CHECK_ARG(slice_begin == 0 && nsl == plan.slices, "an occlusion-culled frame is projected in one piece");
-            // (GS_OCC_QCAP / GS_OCC_STASH: smaller chunks / stash, read per frame -- the parity tests walk the several-chunks and
-            // beyond-the-stash paths at sizes a test can afford; a slice has more than 16,384 Gaussians only beyond 4.2 M)
-            uint32_t qcap_max = GS_OCC_QCAP;
-            if (const char *e = getenv("GS_OCC_QCAP")) {
-                const long v = atol(e);
-                if (v >= 64 && v <= (long)GS_OCC_QCAP) qcap_max = (uint32_t)v;
-            }
-            const uint32_t qcap = plan.per_slice < qcap_max ? plan.per_slice : qcap_max;
-            size_t lds = sizeof(unsigned long long) * SG.NS + gs_cull_pyramid_bytes(G.ntx, G.nty) + 2 * (size_t)qcap + 16;
-            // what is left of the kernel's LDS room holds positions and scales of the chunk's first survivors (24 B each)
+            // LDS behind the strip histogram: the cut pyramid, the 16 waves' survivor rings, the pooled tail -- 12 KiB where the
+            // workgroup-wide 16-bit queue took up to 32 KiB: gs_frame_occlusion_cull's room rule, which still reserves that, holds
+            size_t lds = sizeof(unsigned long long) * SG.NS + gs_cull_pyramid_bytes(G.ntx, G.nty) +
+                         sizeof(uint32_t) * ((STRIP_THREADS / 64) * GS_OCC_RING + GS_OCC_TAIL);
+            // raw variant: what is left of the kernel's LDS room holds position and scale (24 B) of the first slots of every ring
             const size_t room = (size_t)GS_BIN_LDS_BYTES - 8 * 4096;
-            uint32_t stash_cap = room > lds ? (uint32_t)((room - lds) / 24) & ~63u : 0u;
-            if (stash_cap > qcap) stash_cap = (qcap + 63u) & ~63u;
-            if (packed) stash_cap = 0;  // (the packed variant has no stash; GS_OCC_STASH is ignored)
+            uint32_t par_slots = room > lds ? (uint32_t)((room - lds) / (24 * (STRIP_THREADS / 64))) : 0u;
+            if (par_slots > GS_OCC_RING) par_slots = GS_OCC_RING;
+            if (packed) par_slots = 0;  // (the packed variant queues indices only; GS_OCC_STASH is ignored)
+            // GS_OCC_STASH, read per frame: fewer parameter slots in the workgroup's rings (a sixteenth of the value per wave) --
+            // the parity tests walk the gathered-again path with it.  GS_OCC_QCAP chunked the 16-bit queue this kernel no longer
+            // has: still accepted, without effect.
             if (const char *e = getenv("GS_OCC_STASH")) {
                 const long v = atol(e);
-                if (v >= 0 && (uint32_t)v < stash_cap) stash_cap = (uint32_t)v & ~63u;
+                if (v >= 0 && (uint32_t)(v / (STRIP_THREADS / 64)) < par_slots) par_slots = (uint32_t)(v / (STRIP_THREADS / 64));
             }
-            lds += (size_t)stash_cap * 24;
+            lds += (size_t)par_slots * 24 * (STRIP_THREADS / 64);
 #define GS_CULL_TAIL                                                                                                   \
     f->N, P, ws.rec_geom, ws.rects, plan.per_slice, SG, nsl, table, ws.slice_pairs, ws.slice_vis, ws.tile_cost,        \
-        (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), qcap, stash_cap, (unsigned long long *)ws.keys_b, \
+        (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), par_slots, (unsigned long long *)ws.keys_b,       \
         ws.vals_b, gs_cull_stage_cap(f->max_pairs, plan.slices), ws.slice_entries
             if (packed)
                 hipLaunchKernelGGL(frame_packed_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, pack_a,

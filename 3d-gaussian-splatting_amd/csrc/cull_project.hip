@@ -230,6 +230,8 @@ __device__ __forceinline__ void store_static(float4 *__restrict__ pack_b, int64_
 // S1 for one Gaussian, camera half: project -> tile rectangle -> 64-byte record (visible Gaussians only) + the
 // 16-byte rectangle record (every Gaussian).  Returns the rectangle record; `vis` = passed the frustum test; `cxy` = the
 // projected centre (the "dist" listing test of the binning needs it).
+// PP: the frame carries an off-centre principal point (project_common.h, project_cull<PP>)
+template <bool PP = false>
 __device__ __forceinline__ uint4 project_one(const StaticGaussian &in, int64_t pid, const ProjectParams &P,
                                              float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched,
                                              uint4 *__restrict__ rects, uint32_t &vis, float2 &cxy) {
@@ -243,7 +245,7 @@ __device__ __forceinline__ uint4 project_one(const StaticGaussian &in, int64_t p
     // (rects[i].z, the depth bits, is 0 exactly for culled Gaussians: visible ones lie beyond the near plane) --
     // and NOT its 64-byte record: nothing reads the record of a Gaussian that is in no tile's list (21 % of the
     // Gaussians of the 2.4 M scene: 33 of this stage's 337 MB).  The record of a culled Gaussian is unspecified.
-    if (project_cull(in.p, P.cam, P.near_plane, P.half_w, P.half_h, pc, pi)) {
+    if (project_cull<PP>(in.p, P, pc, pi)) {
         project_cov_static(pc, in.RSSR, P.cam, pi, cv);
         vis = 1;
         uint32_t y0, y1, x0, x1;
@@ -267,10 +269,11 @@ __device__ __forceinline__ uint4 project_one(const StaticGaussian &in, int64_t p
     return out;
 }
 // S1 from the raw parameters: load_raw -> make_static (activations, R S S R^T) -> the camera half
+template <bool PP = false>
 __device__ __forceinline__ uint4 project_one(const RawGaussian &in, int64_t pid, const ProjectParams &P,
                                              float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched,
                                              uint4 *__restrict__ rects, uint32_t &vis, float2 &cxy) {
-    return project_one(make_static(in, P.scale_act, P.color_dim), pid, P, rec_geom, tiles_touched, rects, vis, cxy);
+    return project_one<PP>(make_static(in, P.scale_act, P.color_dim), pid, P, rec_geom, tiles_touched, rects, vis, cxy);
 }
 
 // One Gaussian per thread, grid-stride: both planes of the scene pack from the raw parameters (a stream: 56 B in, 80 B out).
@@ -290,9 +293,12 @@ __global__ void __launch_bounds__(256) scene_pack_build_kernel(
     }
 }
 
-__global__ void __launch_bounds__(256) frame_project_kernel(
+// (one body, two kernels, here and below: the kernel of a centred frame keeps its name, signature and code; *_pp_kernel is the
+// instantiation for frames with an off-centre principal point, GS_FRAME_PRINCIPAL_POINT)
+template <bool PP>
+__device__ __forceinline__ void project_body(
     const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
-    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, const ProjectParams &P,
     float4 *__restrict__ rec_geom,
     uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, uint32_t *__restrict__ block_sums,
     uint32_t *__restrict__ block_vis) {
@@ -300,7 +306,7 @@ __global__ void __launch_bounds__(256) frame_project_kernel(
     uint32_t cnt = 0, vis = 0;
     if (pid < n) {
         float2 cxy;
-        cnt = project_one(load_raw(pos, quat, scale, opa, rgb, pid, P.color_dim), pid, P, rec_geom, tiles_touched, rects,
+        cnt = project_one<PP>(load_raw(pos, quat, scale, opa, rgb, pid, P.color_dim), pid, P, rec_geom, tiles_touched, rects,
                           vis, cxy).w;
     }
     // block sums of cnt and of the visible flag -> two plain stores per block (a same-address
@@ -317,6 +323,22 @@ __global__ void __launch_bounds__(256) frame_project_kernel(
         block_sums[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
         block_vis[blockIdx.x] = s_vis[0] + s_vis[1] + s_vis[2] + s_vis[3];
     }
+}
+__global__ void __launch_bounds__(256) frame_project_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom,
+    uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, uint32_t *__restrict__ block_sums,
+    uint32_t *__restrict__ block_vis) {
+    project_body<false>(pos, quat, scale, opa, rgb, n, P, rec_geom, tiles_touched, rects, block_sums, block_vis);
+}
+__global__ void __launch_bounds__(256) frame_project_pp_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom,
+    uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, uint32_t *__restrict__ block_sums,
+    uint32_t *__restrict__ block_vis) {
+    project_body<true>(pos, quat, scale, opa, rgb, n, P, rec_geom, tiles_touched, rects, block_sums, block_vis);
 }
 
 // ---------------------------------------------------------------- S1 + L1a fused (strip variant of sort_mode 2)
@@ -336,7 +358,7 @@ __global__ void __launch_bounds__(256) frame_project_kernel(
 // from five arrays) and runs the camera half alone.
 // (One body, two kernels: frame_project_count_kernel<DIST> reads the raw arrays and keeps its name and signature,
 // frame_packed_project_count_kernel<DIST> is the PACKED instantiation.)
-template <bool DIST, bool PACKED>
+template <bool DIST, bool PACKED, bool PP>
 __device__ __forceinline__ void project_count_body(
     const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
     const float *__restrict__ opa, const float *__restrict__ rgb, const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
@@ -375,7 +397,7 @@ __device__ __forceinline__ void project_count_body(
         uint4 rc = make_uint4(0, 0, 0, 0);
         uint32_t vis = 0;
         float2 cxy = make_float2(0.f, 0.f);
-        if (in_range(i)) rc = project_one(cur, g0 + i, P, rec_geom, tiles_touched, rects, vis, cxy);
+        if (in_range(i)) rc = project_one<PP>(cur, g0 + i, P, rec_geom, tiles_touched, rects, vis, cxy);
         acc_cnt += rc.w;
         acc_vis += vis;
         walk_strips<DIST>(rc, g0 + i, SG, cxy, D,
@@ -406,7 +428,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_kernel(
     uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
     uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
     uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
-    project_count_body<DIST, false>(pos, quat, scale, opa, rgb, nullptr, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+    project_count_body<DIST, false, false>(pos, quat, scale, opa, rgb, nullptr, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
                                     tile_cost, n_tiles, tile_order, gate);
 }
 template <bool DIST>
@@ -416,8 +438,29 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_count_kern
     uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
     uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
     uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
-    project_count_body<DIST, true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_b, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+    project_count_body<DIST, true, false>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_b, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
                                     tile_cost, n_tiles, tile_order, gate);
+}
+template <bool DIST>
+__global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_pp_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
+    uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
+    uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
+    uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
+    project_count_body<DIST, false, true>(pos, quat, scale, opa, rgb, nullptr, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+                                          tile_cost, n_tiles, tile_order, gate);
+}
+template <bool DIST>
+__global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_count_pp_kernel(
+    const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
+    uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
+    uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
+    uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
+    project_count_body<DIST, true, true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_b, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+                                         tile_cost, n_tiles, tile_order, gate);
 }
 
 // ---------------------------------------------------------------- S1 + L1a of an occlusion-culled frame (first pass)
@@ -450,11 +493,15 @@ struct OccPyramid {
 // carries W's largest singular value, sqrt(tlog) and 2 % for the roundings -- fp32's are 1e-6), likewise S11; the tile
 // range follows tile_rect's "prob2" arithmetic, monotone in the extents, with 1e-3 tile of slack.  Anything not finite,
 // larger than 16 tiles, or another listing method: not tested (false).
+template <bool PP>
 __device__ __forceinline__ bool occluded_everywhere(const float pi[3], float z, float smax, uint32_t dbits,
                                                     const ProjectParams &P, const OccPyramid &Y) {
     if (P.cull_method != 2) return false;
     const float k = P.occ_k * smax * gs_rcp(z);
-    const float ax = 1.0f + pi[0] * pi[0], ay = 1.0f + pi[1] * pi[1];
+    // (GS_FRAME_PRINCIPAL_POINT: pi is the SHIFTED centre, which is what the tile arithmetic below wants; the bound on the
+    // extent is a function of x / z itself, pi - s up to a rounding the 1.0001 covers)
+    const float ux = PP ? pi[0] - P.sx : pi[0], uy = PP ? pi[1] - P.sy : pi[1];
+    const float ax = 1.0f + ux * ux, ay = 1.0f + uy * uy;
     const float rx = k * (ax * gs_rsq(ax)) * 1.0001f, ry = k * (ay * gs_rsq(ay)) * 1.0001f;
     const float fx0 = (pi[0] - rx - P.leftmost) * P.inv_tlx - 1e-3f, fx1 = (pi[0] + rx - P.leftmost) * P.inv_tlx + 1e-3f;
     const float fy0 = (pi[1] - ry - P.topmost) * P.inv_tly - 1e-3f, fy1 = (pi[1] + ry - P.topmost) * P.inv_tly + 1e-3f;
@@ -498,7 +545,7 @@ __device__ __forceinline__ bool occluded_everywhere(const float pi[3], float z, 
 // runs the camera half alone.  The ring carries indices only: nothing phase A read is needed again.  Pyramid, strip walk,
 // staging and every output are those of the raw variant.
 // (One body, two kernels, as above: frame_project_cull_count_kernel and frame_packed_project_cull_count_kernel.)
-template <bool PACKED>
+template <bool PACKED, bool PP>
 __device__ __forceinline__ void project_cull_count_body(
     const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
     const float *__restrict__ opa, const float *__restrict__ rgb, const float4 *__restrict__ pack_a,
@@ -601,7 +648,7 @@ __device__ __forceinline__ void project_cull_count_body(
         bool surv = false;
         if (in_slice(i)) {
             float pc[3], pi[3];
-            if (project_cull(pp, P.cam, P.near_plane, P.half_w, P.half_h, pc, pi)) {
+            if (project_cull<PP>(pp, P, pc, pi)) {
                 const float dep = sqrtf(pc[0] * pc[0] + pc[1] * pc[1] + pc[2] * pc[2]);  // == project_cov's pos_i[2]
                 float smax;
                 bool finite;
@@ -616,7 +663,7 @@ __device__ __forceinline__ void project_cull_count_body(
                     // (a NaN scale slips through fmaxf: s0 + s1 + s2 is NaN then, and the Gaussian is projected)
                     finite = s[0] + s[1] + s[2] < 3.0e38f;
                 }
-                if (finite && occluded_everywhere(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
+                if (finite && occluded_everywhere<PP>(pi, pc[2], smax, __float_as_uint(dep), P, Y)) {
                     // behind every cut it can reach, or beside the grid: visible, no tile.  NOTHING is written for it (nor
                     // for a Gaussian outside the frustum): this pass places the entries the drain stages, the second
                     // pass re-projects everything -- rects[] of a culled frame is only fresh for the survivors
@@ -677,7 +724,7 @@ __device__ __forceinline__ void project_cull_count_body(
         uint32_t vis = 0;
         float2 cxy = make_float2(0.f, 0.f);
         const int64_t pid = g0 + q;
-        if (active) rc = project_one(g, pid, P, rec_geom, nullptr, rects, vis, cxy);
+        if (active) rc = project_one<PP>(g, pid, P, rec_geom, nullptr, rects, vis, cxy);
         acc_cnt += rc.w;
         acc_vis += vis;
         // Every entry is counted AND kept: the LDS add returns the entry's rank inside this slice's run of its strip,
@@ -805,7 +852,7 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_kernel
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
     const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
     uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
-    project_cull_count_body<false>(pos, quat, scale, opa, rgb, nullptr, nullptr, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
+    project_cull_count_body<false, false>(pos, quat, scale, opa, rgb, nullptr, nullptr, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
                                    par_slots, stage_ent, stage_tag, ecap, slice_entries);
 }
 __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_cull_count_kernel(
@@ -815,8 +862,29 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_cull_count
     const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
     const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
     uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
-    project_cull_count_body<true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_a, pack_b, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
+    project_cull_count_body<true, false>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_a, pack_b, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
                                    par_slots, stage_ent, stage_tag, ecap, slice_entries);
+}
+__global__ void __launch_bounds__(STRIP_THREADS) frame_project_cull_count_pp_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
+    unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
+    const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
+    const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
+    uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
+    project_cull_count_body<false, true>(pos, quat, scale, opa, rgb, nullptr, nullptr, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
+                                         par_slots, stage_ent, stage_tag, ecap, slice_entries);
+}
+__global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_cull_count_pp_kernel(
+    const float4 *__restrict__ pack_a, const float4 *__restrict__ pack_b, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, uint32_t per_slice, gs_strip_geom SG, uint32_t S,
+    unsigned long long *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis,
+    const uint32_t *__restrict__ tile_cost, uint32_t n_tiles, uint32_t *__restrict__ tile_order,
+    const uint32_t *__restrict__ cut, uint32_t par_slots, unsigned long long *__restrict__ stage_ent,
+    uint32_t *__restrict__ stage_tag, uint32_t ecap, uint32_t *__restrict__ slice_entries) {
+    project_cull_count_body<true, true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_a, pack_b, n, P, rec_geom, rects, per_slice, SG, S, table, slice_pairs, slice_vis, tile_cost, n_tiles, tile_order, cut,
+                                        par_slots, stage_ent, stage_tag, ecap, slice_entries);
 }
 
 // ---------------------------------------------------------------- S1 + B1 fused (table variant of sort_mode 2: small scenes)
@@ -824,11 +892,11 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_cull_count
 // of ~7 us each, so the launch that re-reads the rectangles to histogram them per (slice, tile) is worth removing for
 // its latency alone.  One workgroup per slice (tile_bin.hip's slices: a multiple of 256 Gaussians), one LDS counter per
 // tile; same outputs as frame_project_kernel + bin_count_kernel.
-template <bool DIST>
-__global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_kernel(
+template <bool DIST, bool PP>
+__device__ __forceinline__ void project_bin_count_body(
     const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
-    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
-    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, GsDistCull D, uint32_t per_block, uint32_t T,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, const ProjectParams &P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, const GsDistCull &D, uint32_t per_block, uint32_t T,
     uint32_t *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis) {
     extern __shared__ uint32_t s_tile_hist[];  // [T]
     __shared__ uint32_t s_acc[2];
@@ -848,7 +916,7 @@ __global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_kernel(
         uint4 rc = make_uint4(0, 0, 0, 0);
         uint32_t vis = 0;
         float2 cxy = make_float2(0.f, 0.f);
-        if (in_range(i)) rc = project_one(cur, g0 + i, P, rec_geom, nullptr, rects, vis, cxy);
+        if (in_range(i)) rc = project_one<PP>(cur, g0 + i, P, rec_geom, nullptr, rects, vis, cxy);
         acc_cnt += rc.w;
         acc_vis += vis;
         walk_rect<DIST>(rc, g0 + i, P.ntx, cxy, D, [&](uint32_t tile, uint32_t, uint32_t) { atomicAdd(&s_tile_hist[tile], 1u); });
@@ -867,6 +935,22 @@ __global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_kernel(
         slice_pairs[slice] = s_acc[0];
         slice_vis[slice] = s_acc[1];
     }
+}
+template <bool DIST>
+__global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, GsDistCull D, uint32_t per_block, uint32_t T,
+    uint32_t *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis) {
+    project_bin_count_body<DIST, false>(pos, quat, scale, opa, rgb, n, P, rec_geom, rects, D, per_block, T, table, slice_pairs, slice_vis);
+}
+template <bool DIST>
+__global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_pp_kernel(
+    const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, GsDistCull D, uint32_t per_block, uint32_t T,
+    uint32_t *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis) {
+    project_bin_count_body<DIST, true>(pos, quat, scale, opa, rgb, n, P, rec_geom, rects, D, per_block, T, table, slice_pairs, slice_vis);
 }
 
 }  // namespace
@@ -968,7 +1052,12 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
             std::lock_guard<std::mutex> lock(attr_mu);
             for (const void *fn : {(const void *)frame_project_count_kernel<false>, (const void *)frame_project_count_kernel<true>,
                                    (const void *)frame_packed_project_count_kernel<false>, (const void *)frame_packed_project_count_kernel<true>,
-                                   (const void *)frame_project_cull_count_kernel, (const void *)frame_packed_project_cull_count_kernel})
+                                   (const void *)frame_project_cull_count_kernel, (const void *)frame_packed_project_cull_count_kernel,
+                                   (const void *)frame_project_count_pp_kernel<false>, (const void *)frame_project_count_pp_kernel<true>,
+                                   (const void *)frame_packed_project_count_pp_kernel<false>,
+                                   (const void *)frame_packed_project_count_pp_kernel<true>,
+                                   (const void *)frame_project_cull_count_pp_kernel,
+                                   (const void *)frame_packed_project_cull_count_pp_kernel})
                 // (the kernels also hold ~17 KiB of static LDS -- the tile-order workgroup's bins --: the strip histogram, and the
                 // cut pyramid + survivor queue behind it in a culled frame, get what gs_frame_occlusion_cull's room rule allows)
                 GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_BIN_LDS_BYTES - 8 * 4096));
@@ -1007,9 +1096,15 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
     f->N, P, ws.rec_geom, ws.rects, plan.per_slice, SG, nsl, table, ws.slice_pairs, ws.slice_vis, ws.tile_cost,        \
         (uint32_t)G.n_tiles, ws.tile_order, gs_frame_cut_table(f, ws), par_slots, (unsigned long long *)ws.keys_b,       \
         ws.vals_b, gs_cull_stage_cap(f->max_pairs, plan.slices), ws.slice_entries
-            if (packed)
+            if (packed && P.pp)
+                hipLaunchKernelGGL(frame_packed_project_cull_count_pp_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream,
+                                   pack_a, pack_b, GS_CULL_TAIL);
+            else if (packed)
                 hipLaunchKernelGGL(frame_packed_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, pack_a,
                                    pack_b, GS_CULL_TAIL);
+            else if (P.pp)
+                hipLaunchKernelGGL(frame_project_cull_count_pp_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, f->pos,
+                                   (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_CULL_TAIL);
             else
                 hipLaunchKernelGGL(frame_project_cull_count_kernel, dim3(nsl + 1), dim3(STRIP_THREADS), lds, stream, f->pos,
                                    (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_CULL_TAIL);
@@ -1025,9 +1120,15 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         ws.slice_vis, ws.tile_cost, (uint32_t)G.n_tiles, ws.tile_order, gate
 #define GS_LAUNCH_PROJECT_COUNT(DIST)                                                                                  \
     do {                                                                                                               \
-        if (packed)                                                                                                    \
+        if (packed && P.pp)                                                                                            \
+            hipLaunchKernelGGL(frame_packed_project_count_pp_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, \
+                               stream, pack_b, GS_COUNT_TAIL);                                                         \
+        else if (packed)                                                                                               \
             hipLaunchKernelGGL(frame_packed_project_count_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds,   \
                                stream, pack_b, GS_COUNT_TAIL);                                                         \
+        else if (P.pp)                                                                                                 \
+            hipLaunchKernelGGL(frame_project_count_pp_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, stream, \
+                               f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_COUNT_TAIL);              \
         else                                                                                                           \
             hipLaunchKernelGGL(frame_project_count_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, stream,  \
                                f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_COUNT_TAIL);              \
@@ -1052,28 +1153,43 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         GS_HIP(hipGetDevice(&dev));
         if (dev < 64 && !((attr_done2.load(std::memory_order_acquire) >> dev) & 1)) {
             std::lock_guard<std::mutex> lock(attr_mu2);
-            for (const void *fn : {(const void *)frame_project_bin_count_kernel<false>, (const void *)frame_project_bin_count_kernel<true>})
+            for (const void *fn : {(const void *)frame_project_bin_count_kernel<false>, (const void *)frame_project_bin_count_kernel<true>,
+                                   (const void *)frame_project_bin_count_pp_kernel<false>,
+                                   (const void *)frame_project_bin_count_pp_kernel<true>})
                 GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_BIN_MAX_TILES * 4));
             attr_done2.fetch_or(1ull << dev, std::memory_order_release);
         }
         const uint32_t per_block = bin_per_block(f->N), B = (uint32_t)gs_div_up(f->N, per_block);
         const uint32_t T = (uint32_t)G.n_tiles;
-#define GS_LAUNCH_PROJECT_BIN(DIST)                                                                                    \
-    hipLaunchKernelGGL(frame_project_bin_count_kernel<DIST>, dim3(B), dim3(BIN_THREADS), sizeof(uint32_t) * T, stream, \
+#define GS_LAUNCH_PROJECT_BIN_K(KERNEL)                                                                                \
+    hipLaunchKernelGGL(KERNEL, dim3(B), dim3(BIN_THREADS), sizeof(uint32_t) * T, stream,                               \
                        f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, ws.rects, D,   \
                        per_block, T, ws.bin_table, ws.slice_pairs, ws.slice_vis)
+#define GS_LAUNCH_PROJECT_BIN(DIST)                                                                                    \
+    do {                                                                                                               \
+        if (P.pp)                                                                                                      \
+            GS_LAUNCH_PROJECT_BIN_K(frame_project_bin_count_pp_kernel<DIST>);                                          \
+        else                                                                                                           \
+            GS_LAUNCH_PROJECT_BIN_K(frame_project_bin_count_kernel<DIST>);                                             \
+    } while (0)
         if (f->tile_culling_method == 0)
             GS_LAUNCH_PROJECT_BIN(true);
         else
             GS_LAUNCH_PROJECT_BIN(false);
 #undef GS_LAUNCH_PROJECT_BIN
+#undef GS_LAUNCH_PROJECT_BIN_K
         GS_CHECK_LAUNCH();
         return 0;
     }
     int nblk = (int)gs_div_up(f->N, 256);
-    hipLaunchKernelGGL(frame_project_kernel, dim3(nblk), dim3(256), 0, stream, f->pos, (const float4 *)f->quat,
-                       f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom,
-                       touched, ws.rects, ws.block_sums, ws.block_vis);
+    if (P.pp)
+        hipLaunchKernelGGL(frame_project_pp_kernel, dim3(nblk), dim3(256), 0, stream, f->pos, (const float4 *)f->quat,
+                           f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom,
+                           touched, ws.rects, ws.block_sums, ws.block_vis);
+    else
+        hipLaunchKernelGGL(frame_project_kernel, dim3(nblk), dim3(256), 0, stream, f->pos, (const float4 *)f->quat,
+                           f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom,
+                           touched, ws.rects, ws.block_sums, ws.block_vis);
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -12,6 +12,7 @@
 // The number of (tile, Gaussian) pairs M lives in device memory only; every later stage is
 // launched with a capacity-sized grid (or reads the tile ranges) and idles past M.  The reference
 // needs >= 8 blocking host syncs for the same work.
+#include <math.h>
 #include <stdarg.h>
 #include <string.h>
 
@@ -64,7 +65,7 @@ static int validate(const gs_frame *f) {
     GS_CHECK_ARG((f->flags & ~(GS_FRAME_EMIT_SORTED_KEYS | GS_FRAME_SLICE_SORT | GS_FRAME_TABLE_BIN |
                                GS_FRAME_SERIAL_LONG_LISTS | GS_FRAME_LONG_LISTS | GS_FRAME_STRIP_BIN |
                                GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR |
-                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD | GS_FRAME_SCENE_PACK)) == 0,
+                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD | GS_FRAME_SCENE_PACK | GS_FRAME_PRINCIPAL_POINT)) == 0,
                  "unknown flag bits");
     GS_CHECK_ARG(f->sort_mode >= 0 && f->sort_mode <= 2,
                  "sort_mode must be 0 (full LSD radix), 1 (tile-bit radix + per-tile LDS sort) or 2 (LDS counting sort "
@@ -106,6 +107,11 @@ static int validate(const gs_frame *f) {
                          sp->scene_pack_a_bytes, need_a, sp->scene_pack_b_bytes, need_b);
             return GS_E_INVALID;
         }
+    }
+    if (f->flags & GS_FRAME_PRINCIPAL_POINT) {  // (trailing fields behind the scene-pack fields, as above)
+        const gs_frame_pp *e = gs_frame_pp_fields(f);
+        GS_CHECK_ARG(f->focal_x > 0.f && f->focal_y > 0.f, "GS_FRAME_PRINCIPAL_POINT: focal lengths must be positive");
+        GS_CHECK_ARG(fabs(e->pp_dx) <= 1.0e6 && fabs(e->pp_dy) <= 1.0e6, "GS_FRAME_PRINCIPAL_POINT: pp_dx / pp_dy must be finite pixel offsets");
     }
     const size_t need = gs_frame_workspace_bytes(f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
     if (f->workspace_bytes < need) {

@@ -207,6 +207,8 @@ static inline bool gs_frame_occlusion_cull(const gs_frame *f) {
 static inline const gs_frame_scene *gs_frame_scene_fields(const gs_frame *f) {
     return reinterpret_cast<const gs_frame_scene *>(f);
 }
+// GS_FRAME_PRINCIPAL_POINT: the two offsets behind the scene-pack fields of a flagged frame (include/gs_abi.h, gs_frame_pp)
+static inline const gs_frame_pp *gs_frame_pp_fields(const gs_frame *f) { return reinterpret_cast<const gs_frame_pp *>(f); }
 static inline bool gs_frame_scene_pack(const gs_frame *f) {
     return (f->flags & GS_FRAME_SCENE_PACK) && !f->training && f->N > 0 && gs_frame_uses_strips(f);
 }

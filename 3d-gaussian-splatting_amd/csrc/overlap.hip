@@ -53,58 +53,27 @@ inline OverlapPlan overlap_plan(int32_t H, int32_t W, int32_t stride) {
     return P;
 }
 
+// (one body, two kernels: overlap_count_body.inc.  PP: the frame's camera and the views carry principal-point offsets -- the
+// frame's by value, view k's in row k of view_pp (two floats, uniform loads beside the view's 64-byte row; nullptr: no view
+// has one) -- and the *_pp decisions of overlap_point.h are taken.)
 __global__ void __launch_bounds__(OVL_BLOCK) __attribute__((amdgpu_num_sgpr(72))) overlap_count_kernel(const float *__restrict__ range, OverlapLattice G,
                                                                   gs_seed_camera cam,
                                                                   const gs_seed_camera *__restrict__ views, int32_t n_views,
                                                                   float near, int32_t border, uint32_t *__restrict__ rows) {
-    __shared__ uint32_t s_cnt[OVL_WAVES][GS_OVERLAP_MAX_VIEWS + 2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t acc[OVL_GROUPS] = {0, 0, 0, 0};
-    uint32_t n_meas = 0, n_none = 0;  // (the same in every lane of the wave)
-    const int64_t chunk0 = (int64_t)blockIdx.x * G.chunks_per_block;
-    for (int32_t c = 0; c < G.chunks_per_block; ++c) {
-        const int64_t base = (chunk0 + c) * OVL_BLOCK;
-        if (base >= G.L) break;
-        const int64_t j = base + threadIdx.x;
-        bool meas = false;
-        float p[3] = {0.f, 0.f, 0.f};
-        if (j < G.L) {
-            const int32_t ly = (int32_t)(j / G.Lw), lx = (int32_t)(j - (int64_t)ly * G.Lw);
-            const int32_t x = lx * G.stride + G.off, y = ly * G.stride + G.off;
-            const float z = range[(int64_t)y * G.W + x];
-            meas = gs_overlap_measured(z);
-            if (meas) gs_overlap_point(cam, x, y, z, p);
-        }
-        const unsigned long long mm = __ballot(meas);
-        if (mm == 0ull) continue;  // (the whole wave alike)
-        bool any = false;
-#pragma unroll
-        for (int g = 0; g < OVL_GROUPS; ++g) {
-            const int kend = min(64, n_views - 64 * g);
-            uint32_t a = acc[g];
-            for (int kk = 0; kk < kend; ++kk) {
-                const bool seen = meas & gs_overlap_seen(p, views[64 * g + kk], near, border);
-                const uint32_t cnt = (uint32_t)__popcll(__ballot(seen));
-                any = any || seen;
-                a += lane == kk ? cnt : 0u;
-            }
-            acc[g] = a;
-        }
-        n_meas += (uint32_t)__popcll(mm);
-        n_none += (uint32_t)__popcll(__ballot(meas && !any));
-    }
-#pragma unroll
-    for (int g = 0; g < OVL_GROUPS; ++g) s_cnt[wave][64 * g + lane] = acc[g];
-    if (lane == 0) {
-        s_cnt[wave][GS_OVERLAP_MAX_VIEWS] = n_meas;
-        s_cnt[wave][GS_OVERLAP_MAX_VIEWS + 1] = n_none;
-    }
-    __syncthreads();
-    uint32_t *row = rows + (size_t)blockIdx.x * (size_t)(n_views + 2);
-    for (int e = threadIdx.x; e < n_views + 2; e += OVL_BLOCK) {
-        const int s = e < n_views ? e : GS_OVERLAP_MAX_VIEWS + (e - n_views);
-        row[e] = s_cnt[0][s] + s_cnt[1][s] + s_cnt[2][s] + s_cnt[3][s];
-    }
+    constexpr bool PP = false;
+    constexpr float cam_dx = 0.f, cam_dy = 0.f;
+    constexpr const float2 *view_pp = nullptr;
+#include "overlap_count_body.inc"
+}
+__global__ void __launch_bounds__(OVL_BLOCK) overlap_count_pp_kernel(const float *__restrict__ range, OverlapLattice G,
+                                                                     gs_seed_camera_pp cam_pp,
+                                                                     const gs_seed_camera *__restrict__ views,
+                                                                     const float2 *__restrict__ view_pp, int32_t n_views,
+                                                                     float near, int32_t border, uint32_t *__restrict__ rows) {
+    constexpr bool PP = true;
+    const gs_seed_camera &cam = cam_pp.cam;
+    const float cam_dx = cam_pp.pp_dx, cam_dy = cam_pp.pp_dy;
+#include "overlap_count_body.inc"
 }
 
 __global__ void __launch_bounds__(OVL_BLOCK) overlap_finalize_kernel(const uint32_t *__restrict__ rows, int32_t nblk,
@@ -153,13 +122,16 @@ extern "C" int gs_view_overlap_check_view(const gs_seed_camera *view, int32_t bo
     return 0;
 }
 
-extern "C" int gs_view_overlap(const float *range, const gs_seed_camera *cam, const gs_seed_camera *views_dev,
-                               int32_t n_views, const gs_overlap_opts *opts, int64_t *counts_dev, void *workspace,
-                               size_t workspace_bytes, gs_stream_t stream) {
+// gs_view_overlap (pp = nullptr) and gs_view_overlap_pp (pp = the frame's offsets, view_pp_dev = the views'; no offset anywhere
+// runs gs_view_overlap's kernel)
+static int gs_view_overlap_impl(const float *range, const gs_seed_camera *cam, const float *pp, const gs_seed_camera *views_dev,
+                             const float *view_pp_dev, int32_t n_views, const gs_overlap_opts *opts, int64_t *counts_dev,
+                             void *workspace, size_t workspace_bytes, gs_stream_t stream) {
     int rc = overlap_check_opts(opts);
     if (rc) return rc;
     rc = overlap_check_camera(cam, "camera is null");
     if (rc) return rc;
+    GS_CHECK_ARG(((uintptr_t)view_pp_dev & 7) == 0, "view_pp_dev must be 8-byte aligned");
     GS_CHECK_ARG(range != nullptr, "range is null");
     GS_CHECK_ARG(n_views >= 1 && n_views <= GS_OVERLAP_MAX_VIEWS, "n_views must lie in [1, GS_OVERLAP_MAX_VIEWS]");
     GS_CHECK_ARG(views_dev != nullptr, "views_dev is null");
@@ -171,7 +143,16 @@ extern "C" int gs_view_overlap(const float *range, const gs_seed_camera *cam, co
     hipStream_t s = (hipStream_t)stream;
     const OverlapPlan P = overlap_plan(cam->height, cam->width, opts->stride);
     uint32_t *rows = (uint32_t *)workspace;
-    if (P.nblk > 0) {
+    const bool off_centre = (pp && (pp[0] != 0.f || pp[1] != 0.f)) || view_pp_dev;
+    if (P.nblk > 0 && off_centre) {
+        gs_seed_camera_pp c;
+        c.cam = *cam;
+        c.pp_dx = pp ? pp[0] : 0.f;
+        c.pp_dy = pp ? pp[1] : 0.f;
+        hipLaunchKernelGGL(overlap_count_pp_kernel, dim3(P.nblk), dim3(OVL_BLOCK), 0, s, range, P.G, c, views_dev,
+                           (const float2 *)view_pp_dev, n_views, opts->near, opts->border, rows);
+        GS_CHECK_LAUNCH();
+    } else if (P.nblk > 0) {
         hipLaunchKernelGGL(overlap_count_kernel, dim3(P.nblk), dim3(OVL_BLOCK), 0, s, range, P.G, *cam, views_dev, n_views,
                            opts->near, opts->border, rows);
         GS_CHECK_LAUNCH();
@@ -180,4 +161,21 @@ extern "C" int gs_view_overlap(const float *range, const gs_seed_camera *cam, co
                        (long long *)counts_dev);
     GS_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int gs_view_overlap(const float *range, const gs_seed_camera *cam, const gs_seed_camera *views_dev,
+                               int32_t n_views, const gs_overlap_opts *opts, int64_t *counts_dev, void *workspace,
+                               size_t workspace_bytes, gs_stream_t stream) {
+    return gs_view_overlap_impl(range, cam, nullptr, views_dev, nullptr, n_views, opts, counts_dev, workspace, workspace_bytes,
+                             stream);
+}
+
+extern "C" int gs_view_overlap_pp(const float *range, const gs_seed_camera_pp *cam, const gs_seed_camera *views_dev,
+                                  const float *view_pp_dev, int32_t n_views, const gs_overlap_opts *opts, int64_t *counts_dev,
+                                  void *workspace, size_t workspace_bytes, gs_stream_t stream) {
+    GS_CHECK_ARG(cam != nullptr, "camera is null");
+    GS_CHECK_ARG(std::isfinite(cam->pp_dx) && std::isfinite(cam->pp_dy), "the principal point's offset must be finite");
+    const float pp[2] = {cam->pp_dx, cam->pp_dy};
+    return gs_view_overlap_impl(range, &cam->cam, pp, views_dev, view_pp_dev, n_views, opts, counts_dev, workspace, workspace_bytes,
+                             stream);
 }

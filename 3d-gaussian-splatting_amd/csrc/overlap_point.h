@@ -13,6 +13,11 @@
 //              seen  <=>  q.z > near  and  fl(fx_k q.x) >= fl((border - cx) q.z)  and  fl(fx_k q.x) < fl((W_k - border - cx) q.z)
 //                         and the same two for y
 // -- the inverse of the renderer's pixel coordinate (raster_pixel_coord), cross-multiplied: no division in the test.
+// Cameras whose principal point is off the renderer's centre by (dx, dy) pixels (gs_view_overlap_pp; the *_pp functions below):
+//   point:     u = fl(fl(fl((float)(x + left - padW / 2) + 0.5f) - dx) / fx),  v likewise  (the ray of gs_seed_apply_pp)
+//   view k:    every bound moves by the view's own offset before it is multiplied:
+//              fl(fx_k q.x) >= fl(fl((float)(border - cx) - dx_k) q.z)  and  fl(fx_k q.x) < fl(fl((float)(W_k - border - cx) - dx_k) q.z)
+// The functions without the suffix are what they were: a call without offsets runs them.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -56,4 +61,27 @@ GS_OVERLAP_HD inline bool gs_overlap_seen(const float p[3], const gs_seed_camera
     // (`&` on purpose: five compares and four ANDs, no branch per condition)
     return (qz > near) & (fx >= (float)(border + ox) * qz) & (fx < (float)(w.width - border + ox) * qz)
            & (fy >= (float)(border + oy) * qz) & (fy < (float)(w.height - border + oy) * qz);
+}
+
+// ---- cameras with an off-centre principal point ((dx, dy) = c's offset in pixels)
+GS_OVERLAP_HD inline void gs_overlap_point_pp(const gs_seed_camera &c, float dx, float dy, int32_t x, int32_t y, float z,
+                                              float p[3]) {
+    const float un = ((float)(x + gs_overlap_origin(c.width)) + 0.5f) - dx;
+    const float vn = ((float)(y + gs_overlap_origin(c.height)) + 0.5f) - dy;
+    const float u = un / c.focal_x, v = vn / c.focal_y;
+    const float zc = z / sqrtf(u * u + v * v + 1.0f);
+    const float q0 = u * zc - c.tran[0], q1 = v * zc - c.tran[1], q2 = zc - c.tran[2];
+    for (int k = 0; k < 3; ++k) p[k] = c.rot[k] * q0 + c.rot[3 + k] * q1 + c.rot[6 + k] * q2;
+}
+
+GS_OVERLAP_HD inline bool gs_overlap_seen_pp(const float p[3], const gs_seed_camera &w, float dx, float dy, float near,
+                                             int32_t border) {
+    const float qx = w.rot[0] * p[0] + w.rot[1] * p[1] + w.rot[2] * p[2] + w.tran[0];
+    const float qy = w.rot[3] * p[0] + w.rot[4] * p[1] + w.rot[5] * p[2] + w.tran[1];
+    const float qz = w.rot[6] * p[0] + w.rot[7] * p[1] + w.rot[8] * p[2] + w.tran[2];
+    const int32_t ox = gs_overlap_origin(w.width), oy = gs_overlap_origin(w.height);  // -cx, -cy
+    const float fx = w.focal_x * qx, fy = w.focal_y * qy;
+    const float x_lo = (float)(border + ox) - dx, x_hi = (float)(w.width - border + ox) - dx;
+    const float y_lo = (float)(border + oy) - dy, y_hi = (float)(w.height - border + oy) - dy;
+    return (qz > near) & (fx >= x_lo * qz) & (fx < x_hi * qz) & (fy >= y_lo * qz) & (fy < y_hi * qz);
 }

@@ -145,7 +145,30 @@ struct ProjectParams {
     // occlusion test of frame_project_cull_count_kernel (conservative, never compared bit for bit): 1 / tlx, 1 / tly and
     // 1.02 x sqrt(tlog) x the largest singular value of the camera rotation (1 for a rotation; the caller's matrix is not trusted)
     float inv_tlx, inv_tly, occ_k;
+    // GS_FRAME_PRINCIPAL_POINT: the principal point's offset from the renderer's centre, over the focal lengths (make_params,
+    // in double, rounded once); pp = 0: a centred frame, which runs the kernels without the addition -- the PP = false
+    // instantiations below, the kernels from before the flag existed (an unconditional + 0.0f would turn a stored -0 into +0)
+    float sx, sy;
+    int32_t pp;
 };
+
+// project_cull of the frame path: the same camera transform, near plane and frustum test; PP: the principal point's offset is
+// added to the projected centre -- pos_i = (fl(fl(x / z) + sx), fl(fl(y / z) + sy)) -- BEFORE the frustum test (the guard band
+// stays centred on the image).  Everything downstream reads this centre; J, the covariance and every backward are functions
+// of p_c alone and do not see the offset (a constant added to pos_i has derivative 1).  A compile-time variant: the project
+// kernels of a flagged frame are instantiations of their own (cull_project.hip, *_pp_kernel).
+template <bool PP>
+__device__ __forceinline__ bool project_cull(const float p[3], const ProjectParams &P, float pc[3], float pos_i[3]) {
+    world_to_camera(p, P.cam, pc);
+    if (pc[2] <= P.near_plane) return false;
+    pos_i[0] = pc[0] / pc[2];
+    pos_i[1] = pc[1] / pc[2];
+    if (PP) {
+        pos_i[0] = pos_i[0] + P.sx;
+        pos_i[1] = pos_i[1] + P.sy;
+    }
+    return !(fabsf(pos_i[0]) >= P.half_w || fabsf(pos_i[1]) >= P.half_h);
+}
 
 // sigmoid on the transcendental unit (v_exp_f32 + v_rcp_f32, ~2 ulp): the opacity / colour activations feed the
 // compositing only (image tolerance 5e-5), not the integer side of the pipeline; expf + an IEEE division cost
@@ -224,6 +247,14 @@ inline ProjectParams make_params(const gs_frame *f) {
     P.half_padh = (float)(G.padH / 2);
     P.fx = f->focal_x;
     P.fy = f->focal_y;
+    P.sx = P.sy = 0.f;
+    P.pp = 0;
+    if (f->flags & GS_FRAME_PRINCIPAL_POINT) {
+        const gs_frame_pp *e = gs_frame_pp_fields(f);
+        P.sx = (float)(e->pp_dx / (double)f->focal_x);
+        P.sy = (float)(e->pp_dy / (double)f->focal_y);
+        P.pp = (e->pp_dx != 0.0 || e->pp_dy != 0.0) ? 1 : 0;  // a zero offset is no offset
+    }
     P.inv_tlx = 1.0f / G.tlx;
     P.inv_tly = 1.0f / G.tly;
     {   // largest singular value of the camera rotation as given (power iteration on W^T W; 1 for a rotation)

@@ -17,6 +17,10 @@
 // A selected pixel (x, y), in fp32, one rounding per operation (the file is compiled with -ffp-contract=off):
 //   u = (x + left - padW / 2 + 0.5) / fx,  v = (y + top - padH / 2 + 0.5) / fy     the renderer's own ray through the centre of
 //                                                                   the pixel (raster_pixel_coord; gs_geometry.RayBasis)
+//   gs_seed_apply_pp (a camera whose principal point is off the renderer's centre by (dx, dy) pixels, gs_seed_camera_pp): the
+//   ray moves with it, u = fl(fl(fl((float)(x + left - padW / 2) + 0.5f) - dx) / fx), v likewise -- the pixel's ray of a
+//   GS_FRAME_PRINCIPAL_POINT frame of that camera, so the Gaussian still projects onto the centre of its pixel.  A kernel of
+//   its own (seed_apply_pp_kernel); gs_seed_apply's runs what it ran before.
 //   z_cam = z / sqrt(u u + v v + 1),  p_c = (u z_cam, v z_cam, z_cam),  pos = rot^T (p_c - tran)
 //   sigma = scale_factor stride z_cam / ((fx + fy) / 2): `scale_factor` lattice steps at that depth; stored as the inverse of
 //           the renderer's activation (project_common.h `activate`): max(sigma - 1e-4, 0) for abs, log sigma for exp
@@ -143,6 +147,7 @@ struct SeedOut {
     float *pos, *quat, *scale, *opa, *rgb;
 };
 
+// (one body, two kernels: seed_apply_body.inc)
 template <int CD>
 __global__ void __launch_bounds__(SEED_BLOCK) seed_apply_kernel(const float *__restrict__ image,
                                                                const float *__restrict__ range, SeedLattice G,
@@ -150,58 +155,21 @@ __global__ void __launch_bounds__(SEED_BLOCK) seed_apply_kernel(const float *__r
                                                                const unsigned long long *__restrict__ masks,
                                                                const uint2 *__restrict__ block_offsets,
                                                                const long long *__restrict__ counts) {
-    __shared__ float s_dc[CD == 3 ? 1 : SEED_WAVES][CD == 3 ? 1 : 64][3];
-    const int64_t need = counts[0];
-    if (offset + need > capacity) return;  // (the whole grid alike; the host reads the same count)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long *m = masks + (size_t)blockIdx.x * SEED_WAVES;
-    int64_t wave_base = block_offsets[blockIdx.x].x;
-#pragma unroll
-    for (int w = 0; w < SEED_WAVES - 1; ++w) wave_base += w < wave ? __popcll(m[w]) : 0;
-    const unsigned long long mine = m[wave];
-    const int rank_in_wave = __popcll(mine & ((1ull << lane) - 1ull));
-    const int64_t rank = wave_base + rank_in_wave;
-    // (rank < need always holds for the workspace and counts of ONE classify call; the test keeps a mismatched pair in bounds)
-    const bool sel = ((mine >> lane) & 1ull) != 0 && rank < need;
-    if (sel) {
-        const int64_t j = (int64_t)blockIdx.x * SEED_BLOCK + threadIdx.x;
-        int32_t x, y;
-        const int64_t p = seed_pixel(G, j, x, y);
-        const float z = range[p];
-        const float u = ((float)(x + P.x0) + 0.5f) / P.fx, v = ((float)(y + P.y0) + 0.5f) / P.fy;
-        const float zc = z / sqrtf(u * u + v * v + 1.0f);
-        const float q0 = u * zc - P.tran[0], q1 = v * zc - P.tran[1], q2 = zc - P.tran[2];
-        const int64_t dst = offset + rank;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) O.pos[dst * 3 + k] = P.rot[k] * q0 + P.rot[3 + k] * q1 + P.rot[6 + k] * q2;
-        const float sigma = P.k_sigma * zc / P.f_mean;
-        const float s = P.scale_act == 0 ? fmaxf(sigma - 1e-4f, 0.f) : logf(sigma);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) O.scale[dst * 3 + k] = s;
-        *reinterpret_cast<float4 *>(O.quat + dst * 4) = make_float4(1.f, 0.f, 0.f, 0.f);
-        O.opa[dst] = P.opa_logit;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float c = fminf(fmaxf(image[p * 3 + k], SEED_COLOR_MIN), 1.0f - SEED_COLOR_MIN);
-            const float lg = logf(c / (1.0f - c));
-            if (CD == 3)
-                O.rgb[dst * 3 + k] = lg;
-            else
-                s_dc[wave][rank_in_wave][k] = lg / SEED_SH_C0;
-        }
-    }
-    if (CD != 3) {
-        constexpr int NB = CD / 3;
-        __syncthreads();
-        // the wave's selected pixels are the consecutive rows [wave_base, wave_base + cnt): cnt * CD consecutive floats
-        const int64_t cnt = min((int64_t)__popcll(mine), need - wave_base);
-        float *row0 = O.rgb + (offset + wave_base) * CD;
-        for (int64_t e = lane; e < cnt * CD; e += 64) {
-            const int r = (int)(e / CD), k = (int)(e - (int64_t)r * CD);
-            const int c = k / NB;
-            row0[e] = k == c * NB ? s_dc[wave][r][c] : 0.f;
-        }
-    }
+    constexpr bool PP = false;
+    constexpr float pp_dx = 0.f, pp_dy = 0.f;
+#include "seed_apply_body.inc"
+}
+// gs_seed_apply_pp: the camera's principal point is off the renderer's centre by (pp_dx, pp_dy) pixels; the ray moves with it
+template <int CD>
+__global__ void __launch_bounds__(SEED_BLOCK) seed_apply_pp_kernel(const float *__restrict__ image,
+                                                                  const float *__restrict__ range, SeedLattice G,
+                                                                  SeedApplyParams P, float pp_dx, float pp_dy, SeedOut O,
+                                                                  int64_t offset, int64_t capacity,
+                                                                  const unsigned long long *__restrict__ masks,
+                                                                  const uint2 *__restrict__ block_offsets,
+                                                                  const long long *__restrict__ counts) {
+    constexpr bool PP = true;
+#include "seed_apply_body.inc"
 }
 
 struct SeedWs {
@@ -262,10 +230,11 @@ extern "C" int gs_seed_classify(const float *range, const float *depth, const fl
     return 0;
 }
 
-extern "C" int gs_seed_apply(const float *image, const float *range, const gs_seed_camera *cam, const gs_seed_opts *opts,
-                             float *pos, float *quat, float *scale, float *opa, float *rgb, int64_t offset,
-                             int64_t capacity, const int64_t *counts_dev, const void *workspace, size_t workspace_bytes,
-                             gs_stream_t stream) {
+// gs_seed_apply (pp = nullptr) and gs_seed_apply_pp (pp = the two offsets; (0, 0) runs gs_seed_apply's kernel)
+static int gs_seed_apply_impl(const float *image, const float *range, const gs_seed_camera *cam, const float *pp,
+                           const gs_seed_opts *opts, float *pos, float *quat, float *scale, float *opa, float *rgb,
+                           int64_t offset, int64_t capacity, const int64_t *counts_dev, const void *workspace,
+                           size_t workspace_bytes, gs_stream_t stream) {
     int rc = seed_check_opts(opts);
     if (rc) return rc;
     GS_CHECK_ARG(cam != nullptr, "camera is null");
@@ -300,10 +269,34 @@ extern "C" int gs_seed_apply(const float *image, const float *range, const gs_se
     const SeedOut O = {pos, quat, scale, opa, rgb};
     hipStream_t s = (hipStream_t)stream;
     const long long *cnt = (const long long *)counts_dev;
+    const bool off_centre = pp && (pp[0] != 0.f || pp[1] != 0.f);
     gs_for_color_dim(opts->color_dim, [&](auto cd) {
-        hipLaunchKernelGGL(seed_apply_kernel<decltype(cd)::value>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P, O,
-                           offset, capacity, w.masks, w.block_counts, cnt);
+        if (off_centre)
+            hipLaunchKernelGGL(seed_apply_pp_kernel<decltype(cd)::value>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P,
+                               pp[0], pp[1], O, offset, capacity, w.masks, w.block_counts, cnt);
+        else
+            hipLaunchKernelGGL(seed_apply_kernel<decltype(cd)::value>, dim3(nblk), dim3(SEED_BLOCK), 0, s, image, range, G, P, O,
+                               offset, capacity, w.masks, w.block_counts, cnt);
     });
     GS_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int gs_seed_apply(const float *image, const float *range, const gs_seed_camera *cam, const gs_seed_opts *opts,
+                             float *pos, float *quat, float *scale, float *opa, float *rgb, int64_t offset,
+                             int64_t capacity, const int64_t *counts_dev, const void *workspace, size_t workspace_bytes,
+                             gs_stream_t stream) {
+    return gs_seed_apply_impl(image, range, cam, nullptr, opts, pos, quat, scale, opa, rgb, offset, capacity, counts_dev, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int gs_seed_apply_pp(const float *image, const float *range, const gs_seed_camera_pp *cam, const gs_seed_opts *opts,
+                                float *pos, float *quat, float *scale, float *opa, float *rgb, int64_t offset,
+                                int64_t capacity, const int64_t *counts_dev, const void *workspace, size_t workspace_bytes,
+                                gs_stream_t stream) {
+    GS_CHECK_ARG(cam != nullptr, "camera is null");
+    GS_CHECK_ARG(std::isfinite(cam->pp_dx) && std::isfinite(cam->pp_dy), "the principal point's offset must be finite");
+    const float pp[2] = {cam->pp_dx, cam->pp_dy};
+    return gs_seed_apply_impl(image, range, &cam->cam, pp, opts, pos, quat, scale, opa, rgb, offset, capacity, counts_dev,
+                           workspace, workspace_bytes, stream);
 }

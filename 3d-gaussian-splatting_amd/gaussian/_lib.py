@@ -56,6 +56,13 @@ class GsFrameScene(GsFrame):
     _fields_ = [("scene_pack_a", vp), ("scene_pack_b", vp), ("scene_pack_a_bytes", sz), ("scene_pack_b_bytes", sz)]
 
 
+class GsFramePP(GsFrameScene):
+    """Mirror of ``struct gs_frame_pp``: a ``gs_frame_scene`` followed by the GS_FRAME_PRINCIPAL_POINT fields (read by the
+    library only when the flag is set).  An instance is accepted wherever a ``GsFrame`` is."""
+
+    _fields_ = [("pp_dx", C.c_double), ("pp_dy", C.c_double)]
+
+
 GS_FRAME_EMIT_SORTED_KEYS = 1
 GS_FRAME_SLICE_SORT = 2
 GS_FRAME_TABLE_BIN = 4
@@ -70,6 +77,7 @@ GS_FRAME_CULL_DILATE_NEAR = 1024
 GS_FRAME_AUX = 2048
 GS_FRAME_POSE_GRAD = 4096
 GS_FRAME_SCENE_PACK = 8192
+GS_FRAME_PRINCIPAL_POINT = 16384
 
 
 def _sig(name, restype, *argtypes):
@@ -192,10 +200,18 @@ class GsSeedCamera(C.Structure):
     _fields_ = [("rot", f32 * 9), ("tran", f32 * 3), ("focal_x", f32), ("focal_y", f32), ("width", i32), ("height", i32)]
 
 
+class GsSeedCameraPP(C.Structure):
+    """Mirror of ``struct gs_seed_camera_pp``: a ``gs_seed_camera`` and the principal point's offset in pixels."""
+
+    _fields_ = [("cam", GsSeedCamera), ("pp_dx", f32), ("pp_dy", f32)]
+
+
 gs_seed_workspace_bytes = _sig("gs_seed_workspace_bytes", sz, i32, i32)
 gs_seed_classify = _sig("gs_seed_classify", ci, vp, vp, vp, i32, i32, C.POINTER(GsSeedOpts), vp, vp, sz, vp)
 gs_seed_apply = _sig("gs_seed_apply", ci, vp, vp, C.POINTER(GsSeedCamera), C.POINTER(GsSeedOpts), vp, vp, vp, vp, vp, i64,
                      i64, vp, vp, sz, vp)
+gs_seed_apply_pp = _sig("gs_seed_apply_pp", ci, vp, vp, C.POINTER(GsSeedCameraPP), C.POINTER(GsSeedOpts), vp, vp, vp, vp, vp,
+                        i64, i64, vp, vp, sz, vp)
 
 GS_OVERLAP_MAX_VIEWS = 256
 
@@ -209,6 +225,8 @@ class GsOverlapOpts(C.Structure):
 gs_view_overlap_workspace_bytes = _sig("gs_view_overlap_workspace_bytes", sz, i32, i32, i32, i32)
 gs_view_overlap_check_view = _sig("gs_view_overlap_check_view", ci, C.POINTER(GsSeedCamera), i32)
 gs_view_overlap = _sig("gs_view_overlap", ci, vp, C.POINTER(GsSeedCamera), vp, i32, C.POINTER(GsOverlapOpts), vp, vp, sz, vp)
+gs_view_overlap_pp = _sig("gs_view_overlap_pp", ci, vp, C.POINTER(GsSeedCameraPP), vp, vp, i32, C.POINTER(GsOverlapOpts), vp,
+                          vp, sz, vp)
 
 GS_PRUNE_MAX_ARRAYS = 16
 
@@ -249,6 +267,7 @@ EXPORTS = [
     "gs_view_overlap_workspace_bytes", "gs_view_overlap_check_view", "gs_view_overlap",
     "gs_scene_pack_bytes", "gs_scene_pack_build", "gs_frame_reads_scene_pack",
     "gs_prune_workspace_bytes", "gs_prune_classify", "gs_prune_apply",
+    "gs_seed_apply_pp", "gs_view_overlap_pp",
 ]
 
 

@@ -205,7 +205,7 @@ class ColmapScene:
 
 
 def load_scene(data_dir: str, render_downsample: int = 4, device="cpu", near: float = 0.3,
-               image_dir: str = None) -> ColmapScene:
+               image_dir: str = None, principal_point: bool = False) -> ColmapScene:
     """``<data_dir>/sparse/0/*.bin`` + ``<data_dir>/images_<render_downsample>/`` (train.py:368-369), as the
     reference reads them:
 
@@ -215,6 +215,11 @@ def load_scene(data_dir: str, render_downsample: int = 4, device="cpu", near: fl
       (splatter.py:497-501) -- the pre-downsampled ``images_<k>`` folders of the usual capture layout;
     * ground truth: uint8 -> float16 / 255 (splatter.py:443, 494), kept as float32 here because the loss runs in
       fp32 (the fp16 rounding of the reference's targets is applied, so the values are the same).
+
+    ``principal_point=True`` reads the intrinsics by camera model instead -- SIMPLE_PINHOLE ``f, cx, cy``, PINHOLE ``fx, fy, cx,
+    cy``, all divided by ``render_downsample`` -- and gives every camera its ``cx`` / ``cy``; any other model (one with
+    distortion terms) raises.  The default drops ``cx, cy`` and takes ``params[0:2]`` whatever the model, as the reference
+    does (for SIMPLE_PINHOLE that makes ``params[1]``, which is cx, the second focal length).
 
     The reference decodes with cv2.imread (absent in this image); Pillow decodes here -- PNG is lossless and both
     use libjpeg-turbo for JPEG."""
@@ -242,9 +247,19 @@ def load_scene(data_dir: str, render_downsample: int = 4, device="cpu", near: fl
         if len(cam.params) < 2:
             raise RuntimeError(f"camera model {cam.model} has no focal parameters")
         fx, fy = float(cam.params[0]) / render_downsample, float(cam.params[1]) / render_downsample
+        cx = cy = None
+        if principal_point:
+            if cam.model == "SIMPLE_PINHOLE":
+                f, cx, cy = (float(v) / render_downsample for v in cam.params)
+                fx = fy = f
+            elif cam.model == "PINHOLE":
+                fx, fy, cx, cy = (float(v) / render_downsample for v in cam.params)
+            else:
+                raise RuntimeError(f"principal_point=True reads SIMPLE_PINHOLE and PINHOLE cameras; camera {cam.id} is "
+                                   f"{cam.model} (lens distortion is not modelled)")
         out.cameras.append(Camera(int(rgb.shape[1]), int(rgb.shape[0]), fx, fy,
                                   qvec2rotmat(info.qvec).astype(np.float32), np.asarray(info.tvec, np.float32),
-                                  near=near))
+                                  near=near, cx=cx, cy=cy))
         out.targets.append(target)
         out.names.append(info.name)
     if not out.cameras:

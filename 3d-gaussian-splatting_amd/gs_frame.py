@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from gaussian import _lib
-from gs_geometry import RayBasis, TileGrid
+from gs_geometry import RayBasis, TileGrid, principal_point_offset
 
 SCALE_ACT = {"abs": 0, "exp": 1}
 TILE_CULLING = {"dist": 0, "prob": 1, "prob2": 2}  # the reference's `_method_config` (splatter.py:571)
@@ -136,7 +136,7 @@ class FrameRenderer:
         self._aux_keep = None  # (depth, alpha, aux_padded) of the last forward, kept for its backward
         self._pose_ws: Optional[torch.Tensor] = None  # GS_FRAME_POSE_GRAD backwards: the per-workgroup partial sums
         self._stats_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
-        self._frame: Optional[_lib.GsFrameScene] = None
+        self._frame: Optional[_lib.GsFramePP] = None
         self._frame_serial = 0  # counts forwards: autograd checks that backward() belongs to the latest one
         self._cam_cache = {}
         self._keep = None
@@ -148,15 +148,21 @@ class FrameRenderer:
         self.overflowed_frames = 0  # frames that were rendered empty / truncated and could not be redone (see forward)
 
     # ------------------------------------------------------------------ frame descriptor
-    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameScene:
+    @staticmethod
+    def _camera_key(camera):
+        """The camera by value: what the descriptor cache, the per-camera constants and the occlusion cull's recorded view are
+        keyed on.  [7]: the principal point's offset -- two cameras that differ only in ``cx`` share nothing."""
+        return (int(camera.width), int(camera.height), float(camera.focal_x), float(camera.focal_y),
+                float(camera.near), np.asarray(camera.rot, np.float32).tobytes(),
+                np.asarray(camera.tran, np.float32).tobytes(), principal_point_offset(camera))
+
+    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFramePP:
         # A viewer or a benchmark renders the same tensors from the same camera object again and again: the descriptor
         # of the previous call is reused as long as nothing it was built from has changed (tensor identities and
         # storage, camera object, renderer settings) -- the validation below, ~40 ctypes stores and a library call cost
         # ~15 us of host time per frame otherwise, which is what bounds small scenes with several frames in flight.
         # (the camera enters by VALUE: a viewer may move one Camera object in place)
-        ck = (int(camera.width), int(camera.height), float(camera.focal_x), float(camera.focal_y),
-              float(camera.near), np.asarray(camera.rot, np.float32).tobytes(),
-              np.asarray(camera.tran, np.float32).tobytes())
+        ck = self._camera_key(camera)
         # what a cache hit must not skip (ADVICE round 3): a different tensor may reuse an address -- a freed fp32 tensor
         # replaced by an fp16 one, a strided view that shares its base's data_ptr.  dtype / contiguity are checked on every
         # call (~1 us), the shapes are part of the key.
@@ -176,19 +182,19 @@ class FrameRenderer:
                self._ws.data_ptr() if self._ws is not None else 0)
         cached = getattr(self, "_desc_cache", None)
         if cached is not None and cached[0] == key:
-            f = _lib.GsFrameScene()
-            C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFrameScene))
+            f = _lib.GsFramePP()
+            C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFramePP))
             self._grid = cached[3]
             return f
         f = self._describe_uncached(pos, quat, scale, opa, rgb, camera, training, aux)
         # (the key is taken again: building the descriptor may have (re)allocated the workspaces)
         key = key[:-2] + (self._aux_ws.data_ptr() if aux else 0, self._ws.data_ptr())
-        keep = _lib.GsFrameScene()
-        C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFrameScene))
+        keep = _lib.GsFramePP()
+        C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFramePP))
         self._desc_cache = (key, keep, None, self._grid)
         return f
 
-    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameScene:
+    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFramePP:
         n = int(pos.shape[0])
         color_dim = int(rgb.shape[1]) if rgb.dim() == 2 else 1
         if color_dim not in (3, 27, 48):  # rgb logits, SH degree 2 (the reference's), SH degree 3 (extension)
@@ -202,9 +208,7 @@ class FrameRenderer:
         # per-camera constants (tile grid, frustum guard band, ray basis) are cached: a viewer or a
         # trainer cycles through a fixed set of cameras, and this host work (a 3x3 inverse, ~40
         # ctypes stores) would otherwise cost more than the launches themselves
-        ck = (int(camera.width), int(camera.height), float(camera.focal_x), float(camera.focal_y),
-              float(camera.near), np.asarray(camera.rot, np.float32).tobytes(),
-              np.asarray(camera.tran, np.float32).tobytes())
+        ck = self._camera_key(camera)
         # (the ray basis -- a 3x3 inverse and four small matrix products in NumPy, ~100 us of host time -- only feeds the
         # SH colours: a moving camera over an rgb scene, where a frame is 0.14 - 0.3 ms of GPU time, does not pay for it)
         need_rays = color_dim != 3
@@ -213,13 +217,14 @@ class FrameRenderer:
         if cached is None:
             grid = TileGrid(int(camera.width), int(camera.height), float(camera.focal_x), float(camera.focal_y))
             half_w, half_h = grid.frustum_half_extents()
+            pp = ck[7]
             if need_rays:
                 rays = RayBasis.from_camera(camera.rot, camera.tran, grid.padded_height, grid.padded_width,
-                                            grid.focal_x, grid.focal_y)
+                                            grid.focal_x, grid.focal_y, pp_offset=pp)
             else:
                 zero3 = np.zeros(3, np.float32)
                 rays = RayBasis(zero3, zero3, zero3, zero3)
-            c = _lib.GsFrameScene()
+            c = _lib.GsFramePP()
             c.rot = (C.c_float * 9)(*np.asarray(camera.rot, np.float32).reshape(9))
             c.tran = (C.c_float * 3)(*np.asarray(camera.tran, np.float32).reshape(3))
             c.near_plane, c.half_width, c.half_height = float(camera.near), half_w, half_h
@@ -231,12 +236,13 @@ class FrameRenderer:
             c.lefttop = (C.c_float * 3)(*rays.lefttop)
             c.vec_dx = (C.c_float * 3)(*rays.dx)
             c.vec_dy = (C.c_float * 3)(*rays.dy)
+            c.pp_dx, c.pp_dy = pp  # (read by the library only with GS_FRAME_PRINCIPAL_POINT, set below for a non-zero offset)
             if len(self._cam_cache) > 64:
                 self._cam_cache.clear()
             cached = self._cam_cache[ck] = (c, grid)
         proto, grid = cached
-        f = _lib.GsFrameScene()
-        C.memmove(C.byref(f), C.byref(proto), C.sizeof(_lib.GsFrameScene))
+        f = _lib.GsFramePP()
+        C.memmove(C.byref(f), C.byref(proto), C.sizeof(_lib.GsFramePP))
         f.N, f.color_dim, f.scale_activation = n, color_dim, self.scale_activation
         f.pos, f.quat, f.scale, f.opa, f.rgb = (t.data_ptr() for t in (pos, quat, scale, opa, rgb))
         # "dist": the squared distance threshold of splatter.py:577
@@ -250,7 +256,8 @@ class FrameRenderer:
             (_lib.GS_FRAME_SERIAL_LONG_LISTS if self.serial_long_lists else 0) | \
             (_lib.GS_FRAME_LONG_LISTS if (self.long_lists or (self.long_lists is None and self._long_lists_seen)) else 0) | \
             (_lib.GS_FRAME_LONG_SORT if (self.long_lists is None and self._long_sort_seen) else 0) | \
-            (_lib.GS_FRAME_BWD_ROWS if (self.bwd_rows or (self.bwd_rows is None and self._bwd_rows_seen)) else 0)
+            (_lib.GS_FRAME_BWD_ROWS if (self.bwd_rows or (self.bwd_rows is None and self._bwd_rows_seen)) else 0) | \
+            (_lib.GS_FRAME_PRINCIPAL_POINT if ck[7] != (0.0, 0.0) else 0)  # a zero offset is no offset: today's frame
         if _LOG_FLAGS and (f.flags, self.max_pairs) != getattr(self, "_logged_flags", None):
             # GS_LOG_FLAGS=1: every change of the latched flags / the capacity, with the frame it happens at (diagnostic)
             print(f"[gs_frame {id(self) & 0xffff:04x}] frame {self._frame_serial} N={n} training={int(training)} "
@@ -461,7 +468,7 @@ class FrameRenderer:
         """Upper estimate of how far image content moved, in pixels, between the camera the cut table was recorded under
         and ``camera``: rotation angle x focal length + focal length x camera-centre displacement / 1 (unit depth)."""
         prev, cur = getattr(self, "_cut_ck", None), getattr(self, "_cur_ck", None)
-        if prev is None or cur is None or prev[:4] != cur[:4]:  # (width, height, focal lengths)
+        if prev is None or cur is None or prev[:4] != cur[:4] or prev[7:] != cur[7:]:  # (width, height, focal lengths; the principal point)
             return float("inf")
         if prev[5] == cur[5] and prev[6] == cur[6]:  # the same pose, byte for byte (the common case: no arithmetic)
             return 0.0
@@ -871,8 +878,8 @@ class FrameRenderer:
         need = _lib.gs_frame_pose_workspace_bytes(int(f.N))
         if self._pose_ws is None or self._pose_ws.numel() < need + 256:
             self._pose_ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
-        g = _lib.GsFrameScene()
-        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFrameScene))
+        g = _lib.GsFramePP()
+        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFramePP))
         base = self._pose_ws.data_ptr()
         g.pose_workspace = (base + 255) // 256 * 256
         g.pose_workspace_bytes = self._pose_ws.numel() - (g.pose_workspace - base)
@@ -1001,10 +1008,19 @@ class FrameRenderer:
             rot = torch.tensor(list(f.rot), dtype=torch.float32, device=self.device).reshape(3, 3)
             tran = torch.tensor(list(f.tran), dtype=torch.float32, device=self.device)
             mask = torch.zeros(n, dtype=torch.int64, device=self.device)
+            pos_i = torch.empty_like(pos)
+            pp = bool(f.flags & _lib.GS_FRAME_PRINCIPAL_POINT)
+            # (an off-centre principal point: the operator knows no offset.  It is run with half extents that cull nothing --
+            # its mask is then the near-plane test -- and the frame's own two operations and comparisons follow in fp32.)
+            half = (float("inf"), float("inf")) if pp else (float(f.half_width), float(f.half_height))
             with torch.cuda.device(self.device):
-                gaussian.global_culling(pos, quat, scale, rot, tran, torch.empty_like(pos),
+                gaussian.global_culling(pos, quat, scale, rot, tran, pos_i,
                                         torch.empty((n, 2, 2), dtype=torch.float32, device=self.device), mask,
-                                        float(f.near_plane), float(f.half_width), float(f.half_height))
+                                        float(f.near_plane), *half)
+            if pp:
+                sx = float(np.float32(float(f.pp_dx) / float(f.focal_x))), float(np.float32(float(f.pp_dy) / float(f.focal_y)))
+                inside = ((pos_i[:, 0] + sx[0]).abs() < float(f.half_width)) & ((pos_i[:, 1] + sx[1]).abs() < float(f.half_height))
+                return (mask != 0) & inside
             return mask != 0
         return self._rects()[:, 2] != 0  # depth bits: |p_c| > near > 0 for visible Gaussians, 0 for culled ones
 

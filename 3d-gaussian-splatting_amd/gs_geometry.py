@@ -15,6 +15,33 @@ import numpy as np
 TILE = 16
 
 
+def principal_point_default(width: int, height: int):
+    """(cx0, cy0): where the optical axis of a camera without ``cx`` / ``cy`` meets the image, in pixels (pixel (i, j) covers
+    [i, i+1) x [j, j+1)): the middle of the PADDED image seen through the centred crop, cx0 = padW / 2 - (padW - W) // 2 --
+    W / 2 for an even width, (W + 1) / 2 for an odd one; cy0 likewise."""
+    def one(size):
+        size = int(size)
+        pad = -(-size // TILE) * TILE
+        return pad / 2 - (pad - size) // 2
+    return one(width), one(height)
+
+
+def principal_point_offset(camera):
+    """(dx, dy) = (cx - cx0, cy - cy0) in pixels, in double: how far the camera's principal point lies from the renderer's
+    centre.  (0.0, 0.0) for a camera without ``cx`` / ``cy`` (or with None) and for one that spells the default out.  The ONE
+    place the offset is computed: the frame descriptor, the ray basis, seeding, the overlap count and the z-depth conversion
+    all take it from here."""
+    cx, cy = getattr(camera, "cx", None), getattr(camera, "cy", None)
+    if cx is None and cy is None:
+        return 0.0, 0.0
+    cx0, cy0 = principal_point_default(camera.width, camera.height)
+    dx = 0.0 if cx is None else float(cx) - cx0
+    dy = 0.0 if cy is None else float(cy) - cy0
+    if not (math.isfinite(dx) and math.isfinite(dy)):
+        raise ValueError(f"the principal point ({cx}, {cy}) is not finite")
+    return dx + 0.0, dy + 0.0  # (-0.0 -> 0.0)
+
+
 @dataclass
 class TileGrid:
     width: int
@@ -82,12 +109,15 @@ class RayBasis:
     dy: np.ndarray
 
     @staticmethod
-    def from_camera(rot, tran, padded_h: int, padded_w: int, focal_x: float, focal_y: float) -> "RayBasis":
+    def from_camera(rot, tran, padded_h: int, padded_w: int, focal_x: float, focal_y: float,
+                    pp_offset=(0.0, 0.0)) -> "RayBasis":
+        """``pp_offset`` = ``principal_point_offset(camera)``: the pixel grid stays, the rays move with the principal point."""
         w2c = np.asarray(rot, dtype=np.float32)
         t = np.asarray(tran, dtype=np.float32)
         c2w = np.linalg.inv(w2c).astype(np.float32)  # splatter.py:308
         rays_o = -(c2w @ t)  # :314
-        lefttop_cam = np.array([(-padded_w / 2 + 0.5) / focal_x, (-padded_h / 2 + 0.5) / focal_y, 1.0],
+        lefttop_cam = np.array([(-padded_w / 2 + 0.5 - pp_offset[0]) / focal_x,
+                                (-padded_h / 2 + 0.5 - pp_offset[1]) / focal_y, 1.0],
                                dtype=np.float32)  # :316
         dx_cam = np.array([1.0 / focal_x, 0, 0], dtype=np.float32)
         dy_cam = np.array([0, 1.0 / focal_y, 0], dtype=np.float32)

@@ -28,6 +28,10 @@ class Camera:
     rot: np.ndarray  # [3,3] world->camera rotation (current_w2c_rot)
     tran: np.ndarray  # [3]   world->camera translation (current_w2c_tran)
     near: float = 0.3  # splatter.py:327
+    # principal point in pixels, COLMAP's convention (pixel (i, j) covers [i, i+1) x [j, j+1), its centre is (i + 0.5, j + 0.5));
+    # None: the renderer's centre (gs_geometry.principal_point_default: W / 2 for an even width, (W + 1) / 2 for an odd one)
+    cx: float = None
+    cy: float = None
 
 
 @dataclass

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from gaussian import _lib
+from gs_geometry import principal_point_offset
 
 SCALE_ACT = {"abs": 0, "exp": 1}
 # opa_init > alpha_thresh: a pixel that was seeded has A >= opa_init at its centre from its own Gaussian alone, so the
@@ -53,6 +54,12 @@ def seed_camera(camera) -> "_lib.GsSeedCamera":
     return c
 
 
+def seed_camera_pp(camera) -> "_lib.GsSeedCameraPP":
+    """``camera`` with its principal point's offset (``struct gs_seed_camera_pp``; (0, 0) for a centred camera)."""
+    dx, dy = principal_point_offset(camera)
+    return _lib.GsSeedCameraPP(seed_camera(camera), dx, dy)
+
+
 def seed_classify(rng: torch.Tensor, rendered: Optional[Tuple[torch.Tensor, torch.Tensor]], opts):
     """The decision pass: -> (counts [2] int64 on the device = (selected, measured lattice pixels), workspace)."""
     if rng.device.type != "cuda":
@@ -83,9 +90,13 @@ def seed_apply(image: torch.Tensor, rng: torch.Tensor, camera, opts, out: Sequen
     cam = seed_camera(camera)
     if (cam.height, cam.width) != (H, W):
         raise RuntimeError(f"the maps are {H} x {W}, the camera is {cam.height} x {cam.width}")
-    _lib.check(_lib.gs_seed_apply(image.data_ptr(), rng.data_ptr(), C.byref(cam), C.byref(opts),
-                                  *(t.data_ptr() for t in out), int(offset), cap, counts.data_ptr(), ws.data_ptr(),
-                                  ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_seed_apply")
+    tail = (*(t.data_ptr() for t in out), int(offset), cap, counts.data_ptr(), ws.data_ptr(), ws.numel(),
+            torch.cuda.current_stream().cuda_stream)
+    if principal_point_offset(camera) != (0.0, 0.0):  # the rays move with the principal point (gs_seed_apply_pp)
+        cpp = seed_camera_pp(camera)
+        _lib.check(_lib.gs_seed_apply_pp(image.data_ptr(), rng.data_ptr(), C.byref(cpp), C.byref(opts), *tail), "gs_seed_apply_pp")
+    else:
+        _lib.check(_lib.gs_seed_apply(image.data_ptr(), rng.data_ptr(), C.byref(cam), C.byref(opts), *tail), "gs_seed_apply")
     # rows written through raw pointers into tensors the caller may already have rendered from (a set with spare capacity):
     # advance their version counters, which a renderer's scene pack is keyed on
     torch.autograd.graph.increment_version(tuple(out))

@@ -36,6 +36,7 @@ import torch
 
 import gs_seed
 from gaussian import _lib
+from gs_geometry import principal_point_offset
 from gs_track import _SH_REFUSAL, TrackOptions, TrackResult, Tracker
 from gs_train import TrainOptions, Trainer
 
@@ -43,13 +44,17 @@ GS_OVERLAP_MAX_VIEWS = _lib.GS_OVERLAP_MAX_VIEWS
 
 
 def view_overlap(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: int, stride: int = 1, near: float = 0.3,
-                 border: int = 0) -> torch.Tensor:
+                 border: int = 0, table_pp: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``gs_view_overlap`` (include/gs_abi.h) -> counts [n_views + 2] int64 on the device: per view the measured lattice pixels
     of ``range_map`` whose surface point the view sees, then the measured lattice pixels, then those no view sees.  ``table``
     is the device array of view rows [>= n_views, 16] float32 (``KeyframeSet.table``); ``camera`` the frame's posed camera.
     No host synchronisation.  The rows of ``table`` are not validated here (``view_row`` does that when a row is made), and
     a ``border`` that leaves nothing of a view -- 2 border >= its width or height -- is NOT refused by this call: the sizes are
-    in device memory.  ``KeyframeSet.overlap`` holds the border against its smallest view."""
+    in device memory.  ``KeyframeSet.overlap`` holds the border against its smallest view.
+
+    Off-centre principal points: ``camera``'s own offset is honoured (``gs_geometry.principal_point_offset``); the views'
+    offsets come as ``table_pp`` [>= n_views, 2] float32 on the device, row k = (dx_k, dy_k) in pixels
+    (``KeyframeSet.table_pp``; None: no view has one).  With no offset anywhere the call is ``gs_view_overlap`` itself."""
     if range_map.device.type != "cuda":
         raise RuntimeError("the overlap count needs a HIP device; there is no CPU fallback")
     cam = gs_seed.seed_camera(camera)
@@ -62,6 +67,17 @@ def view_overlap(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: 
                                                               min(max(int(n_views), 1), GS_OVERLAP_MAX_VIEWS))),
                      dtype=torch.uint8, device=range_map.device)
     counts = torch.empty(max(int(n_views), 0) + 2, dtype=torch.int64, device=range_map.device)
+    if table_pp is not None or principal_point_offset(camera) != (0.0, 0.0):
+        if table_pp is not None and (table_pp.dtype != torch.float32 or not table_pp.is_cuda or not table_pp.is_contiguous()
+                                     or table_pp.dim() != 2 or table_pp.shape[1] != 2 or table_pp.shape[0] < n_views
+                                     or table_pp.device != table.device):
+            raise RuntimeError(f"table_pp must be a contiguous float32 HIP tensor of shape [>= {n_views}, 2] beside table")
+        cpp = gs_seed.seed_camera_pp(camera)
+        _lib.check(_lib.gs_view_overlap_pp(range_map.data_ptr(), C.byref(cpp), table.data_ptr(),
+                                           table_pp.data_ptr() if table_pp is not None else None, int(n_views),
+                                           C.byref(opts), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           torch.cuda.current_stream().cuda_stream), "gs_view_overlap_pp")
+        return counts
     _lib.check(_lib.gs_view_overlap(range_map.data_ptr(), C.byref(cam), table.data_ptr(), int(n_views), C.byref(opts),
                                     counts.data_ptr(), ws.data_ptr(), ws.numel(),
                                     torch.cuda.current_stream().cuda_stream), "gs_view_overlap")
@@ -87,6 +103,10 @@ class KeyframeSet:
         self.capacity = int(capacity)
         self.cameras, self.images, self.ranges = [], [], []
         self.table = torch.zeros((self.capacity, 16), dtype=torch.float32, device=device)
+        # the views' principal-point offsets (dx_k, dy_k), a table beside the 64-byte rows; handed to the count only once a
+        # keyframe has one (a set of centred cameras runs the kernel it always ran, on the rows it always read)
+        self.table_pp = torch.zeros((self.capacity, 2), dtype=torch.float32, device=device)
+        self._offsets = []
         self._min_size = None
 
     def __len__(self) -> int:
@@ -98,7 +118,10 @@ class KeyframeSet:
         if n >= self.capacity:
             raise RuntimeError(f"the keyframe set is full ({self.capacity} views); there is no eviction")
         row = view_row(camera)
+        off = principal_point_offset(camera)
         self.table[n].copy_(torch.from_numpy(row))
+        self.table_pp[n].copy_(torch.tensor(off, dtype=torch.float32))
+        self._offsets.append(off)
         self.cameras.append(copy.copy(camera))
         self.images.append(image)
         self.ranges.append(range_map)
@@ -124,7 +147,8 @@ class KeyframeSet:
             raise RuntimeError("the keyframe set is empty")
         if 2 * int(border) >= self._min_size:
             raise RuntimeError(f"border {border} leaves nothing of a {self._min_size}-pixel keyframe")
-        return view_overlap(range_map, camera, self.table, len(self.cameras), stride, near, border).cpu().numpy()
+        table_pp = self.table_pp if any(o != (0.0, 0.0) for o in self._offsets) else None
+        return view_overlap(range_map, camera, self.table, len(self.cameras), stride, near, border, table_pp).cpu().numpy()
 
 
 def select_keyframes(counts: Sequence[int], measured: int, k: int, min_share: float) -> List[int]:

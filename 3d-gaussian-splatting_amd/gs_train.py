@@ -30,7 +30,7 @@ import torch
 from gaussian import _lib
 from gs_dp import ORDER, FlatGaussianParams, ViewParallelGradStat
 from gs_frame import FrameRenderer
-from gs_geometry import RayBasis, TileGrid
+from gs_geometry import RayBasis, TileGrid, principal_point_offset
 
 GROUPS = ("opa", "rgb", "pos", "scale", "quat")  # the reference's param-group order (train.py:59-65)
 
@@ -342,7 +342,8 @@ def z_to_range(z: torch.Tensor, camera) -> torch.Tensor:
     centres of the padded image, cropped like the image), so the conversion and the rendered map agree on where a pixel
     looks.  Pixels without a measurement (<= 0, inf, NaN) stay what they are."""
     grid = TileGrid(int(camera.width), int(camera.height), float(camera.focal_x), float(camera.focal_y))
-    rays = RayBasis.from_camera(camera.rot, camera.tran, grid.padded_height, grid.padded_width, grid.focal_x, grid.focal_y)
+    rays = RayBasis.from_camera(camera.rot, camera.tran, grid.padded_height, grid.padded_width, grid.focal_x, grid.focal_y,
+                                pp_offset=principal_point_offset(camera))  # (the rays of the camera's own principal point)
     top, left = grid.crop_offsets()
     px = (np.arange(grid.width, dtype=np.float64) + left)[None, :, None]
     py = (np.arange(grid.height, dtype=np.float64) + top)[:, None, None]
@@ -956,7 +957,7 @@ class Trainer:
     def test(self, camera_id, extrinsics=None, intrinsics=None) -> dict:
         """``Trainer.test`` of the reference (train.py:256-281), which is also what its viser GUI calls per
         frame (visergui.py:137-149): ``test(None, extrinsics={"rot", "tran"}, intrinsics={"width", "height",
-        "focal_x", "focal_y"})`` renders an arbitrary world->camera pose at an arbitrary resolution (the tile
+        "focal_x", "focal_y"[, "cx", "cy"]})`` renders an arbitrary world->camera pose at an arbitrary resolution (the tile
         grid is rebuilt, sizes need not be multiples of 16); ``test(camera_id)`` renders a training / test
         camera and adds ``psnr``, ``ssim`` and ``render_time`` (seconds, device time) against its target."""
         import numpy as np
@@ -968,7 +969,8 @@ class Trainer:
             to_np = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float32)  # noqa: E731
             cam = Camera(int(intrinsics["width"]), int(intrinsics["height"]), float(intrinsics["focal_x"]),
                          float(intrinsics["focal_y"]), to_np(extrinsics["rot"]).reshape(3, 3),
-                         to_np(extrinsics["tran"]).reshape(3), near=getattr(self.cameras[0], "near", 0.3) if self.cameras else 0.3)
+                         to_np(extrinsics["tran"]).reshape(3), near=getattr(self.cameras[0], "near", 0.3) if self.cameras else 0.3,
+                         cx=intrinsics.get("cx"), cy=intrinsics.get("cy"))  # (optional: the principal point in pixels)
         elif camera_id is not None:
             self._settle_pose(camera_id)
             cam = self.cameras[camera_id]

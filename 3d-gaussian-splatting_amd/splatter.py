@@ -148,6 +148,10 @@ class Splatter(nn.Module):
     def set_camera(self, idx, extrinsics=None, intrinsics=None):
         """splatter.py:467-511."""
         if idx is None:
+            if "cx" in intrinsics or "cy" in intrinsics:
+                raise RuntimeError("Splatter (the reference's class API) renders with the principal point at the image "
+                                   "centre: intrinsics with cx / cy are refused, not ignored -- use gs_frame.FrameRenderer "
+                                   "with a gs_scene.Camera(cx=..., cy=...)")
             to = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))).to(torch.float32).to(self.device)  # noqa: E731
             host = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float32)  # noqa: E731
             self.current_w2c_rot, self.current_w2c_tran = to(extrinsics["rot"]), to(extrinsics["tran"])

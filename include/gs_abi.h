@@ -34,7 +34,12 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_prune_workspace_bytes,
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_PRINCIPAL_POINT with
+ *   gs_frame_pp -- a gs_frame_scene followed by pp_dx / pp_dy, the principal point's offset in pixels from the renderer's centre,
+ *   read only when the flag is set; gs_frame and gs_frame_scene are unchanged --, honoured by every gs_frame_* entry point;
+ *   gs_seed_camera_pp (a gs_seed_camera followed by the same two offsets; gs_seed_camera stays 64 bytes) with gs_seed_apply_pp
+ *   and gs_view_overlap_pp, the variants of gs_seed_apply and gs_view_overlap for cameras with an off-centre principal point.
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_prune_workspace_bytes,
  *   gs_prune_classify and gs_prune_apply with gs_prune_opts / gs_prune_arrays / GS_PRUNE_MAX_ARRAYS (remove Gaussians by one
  *   per-row decision and move every array that shares the row index -- parameters, optimizer moments, the densification
  *   statistic -- in one stable compaction).
@@ -337,6 +342,29 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        training frames; gs_frame_reads_scene_pack tells.  Frames without the flag run
                                        exactly the kernels they ran before it existed. */
 
+#define GS_FRAME_PRINCIPAL_POINT 16384 /* the camera's principal point is NOT the renderer's centre (the descriptor is a gs_frame_pp,
+                                       below).  The centre: pixel (i, j) of the width x height image covers [i, i + 1) x [j, j + 1)
+                                       (COLMAP's convention) and the optical axis of an unflagged frame passes through
+                                       cx0 = padW / 2 - (padW - width) / 2 (integer division: width / 2 for an even width,
+                                       (width + 1) / 2 for an odd one), cy0 likewise.  pp_dx = cx - cx0, pp_dy = cy - cy0.
+                                       The tile grid, the padded image and the centred crop are those of the unflagged frame;
+                                       the offset enters at ONE place, the projected centre of a Gaussian, in fp32 with one
+                                       rounding per operation:
+                                         sx = (float)(pp_dx / focal_x), sy = (float)(pp_dy / focal_y)     (host, in double)
+                                         pos_i = (fl(fl(x / z) + sx), fl(fl(y / z) + sy), |p_c|)
+                                         culled <=> z <= near or |pos_i.x| >= half_width or |pos_i.y| >= half_height
+                                       -- the frustum test looks at the SHIFTED centre: the guard band stays centred on the
+                                       image.  Binning, sorting, compositing, the maps and every backward read that centre;
+                                       the Jacobian, the covariance, the projection backward and the pose gradient are
+                                       functions of p_c and are unchanged (a constant added to pos_i has derivative 1).  SH
+                                       colours: the caller's ray basis moves with the principal point, lefttop_cam =
+                                       ((-padW / 2 + 0.5 - pp_dx) / focal_x, (-padH / 2 + 0.5 - pp_dy) / focal_y, 1).
+                                       Every gs_frame_* entry point honours the flag, with or without a scene pack (the pack
+                                       is camera-independent).  An offset of exactly (0, 0) runs the unflagged frame's code
+                                       paths and gives its bits.  GS_E_INVALID, before anything is enqueued, for an offset
+                                       that is not finite (or beyond 1e6 pixels) or a non-positive focal length.  Frames
+                                       without the flag run exactly the code paths they ran before it existed. */
+
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
  * splatter.py does (Tiles, RayInfo, frustum guard band); rot/tran are passed by value. */
 typedef struct gs_frame {
@@ -421,6 +449,14 @@ typedef struct gs_frame_scene {
     const void *scene_pack_b; /* 64-byte aligned, >= b_bytes                                                                */
     size_t scene_pack_a_bytes, scene_pack_b_bytes;
 } gs_frame_scene;
+
+/* GS_FRAME_PRINCIPAL_POINT: the descriptor of a flagged frame continues behind gs_frame_scene with two more fields, by the
+ * rule of gs_frame_scene: read only when the flag is set; the pack fields in front of them are read only with
+ * GS_FRAME_SCENE_PACK and may be zero otherwise.  sizeof(gs_frame) and sizeof(gs_frame_scene) stay what they were. */
+typedef struct gs_frame_pp {
+    gs_frame_scene scene;     /* first member: (const gs_frame_pp *)f == f                                                  */
+    double pp_dx, pp_dy;      /* cx - cx0, cy - cy0 in pixels (see the flag)                                               */
+} gs_frame_pp;
 
 /* Bytes of workspace needed for N Gaussians, `max_pairs` pairs, a width x height image. */
 size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int32_t height,
@@ -849,6 +885,21 @@ int gs_seed_apply(const float *image, const float *range, const gs_seed_camera *
                   float *quat, float *scale, float *opa, float *rgb, int64_t offset, int64_t capacity,
                   const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
+/* A camera whose principal point is off the renderer's centre (GS_FRAME_PRINCIPAL_POINT: pp_dx = cx - cx0, pp_dy = cy - cy0 in
+ * pixels).  gs_seed_apply_pp is gs_seed_apply with the ray of pixel (x, y) moved accordingly, in fp32, one rounding per
+ * operation:
+ *   u = fl(fl(fl((float)(x + left - padW / 2) + 0.5f) - pp_dx) / focal_x),  v likewise
+ * -- the seeded Gaussian projects onto the centre of its pixel in a frame of the same camera.  Everything else, the workspace
+ * and gs_seed_classify (which sees no camera) are as above.  Refuses an offset that is not finite.  gs_seed_camera and
+ * gs_seed_apply keep their layout, signature and device code. */
+typedef struct gs_seed_camera_pp {
+    gs_seed_camera cam;
+    float pp_dx, pp_dy;
+} gs_seed_camera_pp;
+int gs_seed_apply_pp(const float *image, const float *range, const gs_seed_camera_pp *cam, const gs_seed_opts *opts, float *pos,
+                     float *quat, float *scale, float *opa, float *rgb, int64_t offset, int64_t capacity,
+                     const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
 /* ---- covisibility: of the surface points a frame measured, how many does each keyframe see? ----
  * range [H,W] (H, W = cam->height, cam->width): the incoming frame's measured range, "no measurement" where it is <= 0,
  * infinite or NaN (the rule of gs_seed and gs_loss_depth).  cam: the frame's posed camera, by value, on the host.
@@ -887,6 +938,17 @@ int gs_view_overlap(const float *range, const gs_seed_camera *cam,        /* the
                     const gs_seed_camera *views_dev, int32_t n_views,     /* DEVICE array, 64 bytes per view     */
                     const gs_overlap_opts *opts, int64_t *counts_dev,     /* [n_views + 2]                       */
                     void *workspace, size_t workspace_bytes, gs_stream_t stream);
+/* gs_view_overlap with off-centre principal points.  cam: the incoming frame's camera with its offset (its points are those
+ * gs_seed_apply_pp writes).  views_dev: the same table of 64-byte rows; view_pp_dev: a DEVICE array of n_views rows of two floats
+ * (pp_dx_k, pp_dy_k), 8-byte aligned, or NULL when no view has an offset.  View k's test moves its four bounds by its own
+ * offset, in fp32 with one rounding per operation (csrc/overlap_point.h is the text):
+ *   fl(fx_k q.x) >= fl(fl((float)(border - cx0_k) - pp_dx_k) q.z)  and  fl(fx_k q.x) < fl(fl((float)(W_k - border - cx0_k) - pp_dx_k) q.z)
+ * and the same two for y.  A call in which no camera has an offset -- cam's is (0, 0) and view_pp_dev is NULL -- IS
+ * gs_view_overlap: the same kernel on the same rows.  Workspace, counts and refusals as gs_view_overlap; also refused: an
+ * offset of `cam` that is not finite, a misaligned view_pp_dev.  (The rows of view_pp_dev are validated by the table's owner.) */
+int gs_view_overlap_pp(const float *range, const gs_seed_camera_pp *cam, const gs_seed_camera *views_dev,
+                       const float *view_pp_dev, int32_t n_views, const gs_overlap_opts *opts, int64_t *counts_dev,
+                       void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 /* ---- editing the map: remove rows by one per-row decision, move everything that shares the row index ----
  * Two calls around one host read, because the caller sizes the destination arrays between them (as gs_densify_* and

@@ -23,27 +23,13 @@
 #include <cmath>
 
 #include "gs_common.h"
+#include "map_terms.h"  // map_measured, map_signed, map_expected_residual, map_expected_grads
 
 namespace {
 
 constexpr int ML_BLOCK = 256, ML_PER_BLOCK = ML_BLOCK * 4;
 
 inline int64_t map_loss_blocks(int64_t H, int64_t W) { return (H * W + ML_PER_BLOCK - 1) / ML_PER_BLOCK; }
-
-__device__ __forceinline__ bool map_measured(float z) { return z > 0.f && z <= 3.402823466e38f; }  // (false for NaN and +inf)
-
-__device__ __forceinline__ float map_signed(float d, float s) { return d > 0.f ? s : (d < 0.f ? -s : 0.f); }
-
-// the expected-depth term, in two steps (tracking gates on |r| between them): e = D / A and the residual r = e - z; then,
-// with sg = map_signed(r, .), the gradients sg dr/dD = sg (1 / A) and sg dr/dA = sg (-(e / A)).  A > 0.
-__device__ __forceinline__ float map_expected_residual(float D, float A, float z, float &e) {
-    e = D / A;
-    return e - z;
-}
-__device__ __forceinline__ void map_expected_grads(float sg, float e, float A, float &gD, float &gA) {
-    gD = sg * (1.f / A);
-    gA = sg * (-(e / A));
-}
 
 // one pixel: returns |r| (0 where the pixel does not count) and its two gradients; `cnt` counts the pixels that counted
 template <int MODE>

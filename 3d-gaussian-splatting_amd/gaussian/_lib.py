@@ -170,6 +170,9 @@ gs_loss_depth_workspace_bytes = _sig("gs_loss_depth_workspace_bytes", sz, i32, i
 gs_loss_depth = _sig("gs_loss_depth", ci, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, sz, vp)
 gs_loss_track_workspace_bytes = _sig("gs_loss_track_workspace_bytes", sz, i32, i32)
 gs_loss_track = _sig("gs_loss_track", ci, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, sz, vp)
+gs_loss_track_gated_workspace_bytes = _sig("gs_loss_track_gated_workspace_bytes", sz, i32, i32)
+gs_loss_track_gated = _sig("gs_loss_track_gated", ci, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, i32, f32,
+                           vp, vp, vp, vp, vp, vp, vp, sz, vp)
 
 
 
@@ -264,6 +267,7 @@ EXPORTS = [
     "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
     "gs_loss_track_workspace_bytes", "gs_loss_track",
+    "gs_loss_track_gated_workspace_bytes", "gs_loss_track_gated",
     "gs_view_overlap_workspace_bytes", "gs_view_overlap_check_view", "gs_view_overlap",
     "gs_scene_pack_bytes", "gs_scene_pack_build", "gs_frame_reads_scene_pack",
     "gs_prune_workspace_bytes", "gs_prune_classify", "gs_prune_apply",

@@ -42,6 +42,9 @@ SOURCES = {
     # r = D - A z, r = D / A - z and the gate as written: one rounding per operation, and gs_loss_track's depth term is
     # gs_loss_depth mode 1 bit for bit
     "map_loss.hip": ["-ffp-contract=off"],
+    # the per-pixel terms of map_loss.hip (map_terms.h) with the same roundings: where a term counts, gs_loss_track_gated's
+    # gradients are gs_loss_track's bit for bit, and the thresholds are fl(k m) as written
+    "track_gate.hip": ["-ffp-contract=off"],
     # the seen / not seen test as written: a float32 restatement decides identically; no SLP packing, as above
     "overlap.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # the keep test (opa > t and ||act(scale)|| < s) as written: densify.hip's delete rule, decided identically
@@ -52,7 +55,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
 HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
            "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
-           "seed_apply_body.inc", "overlap_count_body.inc",
+           "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h",
            os.path.join("..", "..", "include", "gs_abi.h")]
 
 

@@ -6,6 +6,10 @@ One iteration, without autograd:
     posed camera (host, by value) -> forward(training=True, aux=True) -> gs_loss_track (gs_train.TrackLoss)
       -> backward(part=GS_BWD_RASTER) -> backward(part=GS_BWD_GEOMETRY, grad_pose=...) -> one 64-byte read -> SE(3) step
 
+With ``TrackOptions.depth_gate_k`` or ``color_gate_k`` above zero the loss is gs_loss_track_gated (gs_train.GatedTrackLoss): a
+term counts where its residual is at most k x the frame's own median residual, selected on the device every iteration; the
+buffer then holds 20 floats and the read 80 bytes -- still one read per iteration.
+
 The colour part of the backward (GS_BWD_COLOR: opacity and colour gradients) is never run: nobody reads it.  dL/drot,
 dL/dtran and the four loss values are views of one 16-float device buffer that a single copy brings into pinned host memory.
 The pose step runs on the host in float64: rot = exp([w]x) R re-linearised at w = 0 every iteration, Adam on (w, tran),
@@ -23,7 +27,7 @@ import torch
 
 from gaussian import _lib
 from gs_frame import FrameRenderer
-from gs_train import TrackLoss
+from gs_train import GatedTrackLoss, TrackLoss
 
 
 @dataclass
@@ -41,6 +45,19 @@ class TrackOptions:
     depth_weight: float = 1.0       # x |D / A - z| / (H W)
     depth_gate: float = 0.0         # <= 0: off; else depth residuals beyond it do not count
     max_pairs: int = 1 << 20        # the renderer's initial pair capacity (it grows by itself)
+    # the median gate (gs_loss_track_gated): a k <= 0 leaves that term ungated; both <= 0 (the default) is gs_loss_track
+    depth_gate_k: float = 0.0       # depth counts where |r| <= max(k x median |r|, depth_gate_floor); excludes depth_gate
+    color_gate_k: float = 0.0       # colour counts where sum_c |I_c - T_c| <= max(k x its median, color_gate_floor)
+    depth_gate_floor: float = 0.0
+    color_gate_floor: float = 0.0
+    gate_couple: bool = True        # a pixel that fails the depth gate loses its colour term too
+
+    def gated(self) -> bool:
+        """Whether the median gate is on (-> GatedTrackLoss and the 20-float buffer); refuses the two depth gates together."""
+        if self.depth_gate > 0.0 and self.depth_gate_k > 0.0:
+            raise ValueError("depth_gate (a fixed threshold) and depth_gate_k (a multiple of the median residual) both gate "
+                             "the depth term: give one of them")
+        return self.depth_gate_k > 0.0 or self.color_gate_k > 0.0
 
 
 @dataclass
@@ -50,6 +67,9 @@ class TrackResult:
     loss: float          # the lowest loss seen: the loss of (rot, tran)
     iterations: int
     losses: List[float] = field(default_factory=list)  # per iteration, the loss of the pose that iteration rendered
+    # With the median gate on, from the iteration that rendered (rot, tran) -- plain attributes, None with the gate off:
+    inliers = None       # (depth pixels that counted, n_d = covered measured pixels, colour pixels that counted)
+    medians = None       # (m_d, m_c): the median residuals the thresholds were multiples of
 
 
 def so3_exp(w) -> np.ndarray:
@@ -168,16 +188,26 @@ class Tracker:
         self.renderer = FrameRenderer(self.device, max_pairs=int(self.opt.max_pairs), training=True, occlusion_cull=False,
                                       auto_grow=True)
         self.device = self.renderer.device
-        o = self.opt
-        self.loss = TrackLoss(self.H, self.W, o.alpha_min, o.color_weight, o.depth_weight, o.depth_gate, self.device)
-        # grad_rot [0:9], grad_tran [9:12], (loss, colour term, depth term, depth pixels) [12:16]: one read per iteration
-        self._dev = torch.zeros(16, dtype=torch.float32, device=self.device)
+        cls, args, nfloat = self.loss_plan(self.opt, self.H, self.W)
+        self.loss = cls(*args, self.device)
+        # grad_rot [0:9], grad_tran [9:12], (loss, colour term, depth term, depth pixels) [12:16] and, with the median gate,
+        # (colour pixels, m_d, m_c, n_d) [16:20]: one read per iteration
+        self._dev = torch.zeros(nfloat, dtype=torch.float32, device=self.device)
         self._grad_pose = (self._dev[0:9].view(3, 3), self._dev[9:12])
-        self._values = self._dev[12:16]
-        self._host = torch.zeros(16, dtype=torch.float32).pin_memory()
+        self._values = self._dev[12:nfloat]
+        self._host = torch.zeros(nfloat, dtype=torch.float32).pin_memory()
         self._scratch = None
         self.set_map(params)
         self.reset()
+
+    @staticmethod
+    def loss_plan(o: TrackOptions, height: int, width: int):
+        """(loss class, its arguments before the device, floats per iteration) for these options -- no device needed.  Gate
+        off: TrackLoss and 16 floats, exactly the calls of a tracker without the gate; on: GatedTrackLoss and 20."""
+        if not o.gated():
+            return TrackLoss, (height, width, o.alpha_min, o.color_weight, o.depth_weight, o.depth_gate), 16
+        return GatedTrackLoss, (height, width, o.alpha_min, o.color_weight, o.depth_weight, o.depth_gate_k, o.color_gate_k,
+                                o.depth_gate_floor, o.color_gate_floor, o.gate_couple), 20
 
     @staticmethod
     def _check_map(params):
@@ -223,7 +253,8 @@ class Tracker:
 
     def iteration(self, rot, tran, image, range_map=None):
         """One forward / loss / pose backward at the pose (rot, tran); the 16 floats land in ``self._host`` (pinned):
-        dL/drot [0:9], dL/dtran [9:12], (loss, colour term, depth term, depth pixels) [12:16].  Returns that buffer."""
+        dL/drot [0:9], dL/dtran [9:12], (loss, colour term, depth term, depth pixels) [12:16]; with the median gate 20 floats,
+        [16:20] = (colour pixels, m_d, m_c, n_d).  Returns that buffer."""
         cam = copy.copy(self.camera)
         cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
         cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
@@ -233,7 +264,7 @@ class Tracker:
             gi, gd, ga = self.loss(img, depth, alpha, image, range_map, 1.0 / (self.H * self.W), values=self._values)
         r.backward(gi, out=self._scratch, part=_lib.GS_BWD_RASTER, grad_depth=gd, grad_alpha=ga)
         r.backward(None, out=self._scratch, part=_lib.GS_BWD_GEOMETRY, grad_pose=self._grad_pose)
-        self._host.copy_(self._dev)  # (device -> pinned host: returns when the 64 bytes have landed)
+        self._host.copy_(self._dev)  # (device -> pinned host: returns when the 64 -- gated: 80 -- bytes have landed)
         return self._host
 
     def track(self, image, range_map=None, init=None) -> TrackResult:
@@ -242,15 +273,19 @@ class Tracker:
         o = self.opt
         R, t = self._start_pose(init)
         adam = PoseAdam(R, t, o.lr_rot, o.lr_tran, o.betas, o.eps)  # Adam's moments on (w, tran): kept across iterations, reset per call
-        best = (math.inf, R, t)
+        best = (math.inf, R, t, None)
         losses: List[float] = []
         for k in range(int(o.iterations)):
             h = self.iteration(R, t, image, range_map).numpy().astype(np.float64)
             loss = float(h[12])
             losses.append(loss)
             if loss < best[0]:
-                best = (loss, R, t)
+                best = (loss, R, t, h[15:20] if len(h) == 20 else None)
             R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / o.iterations))
-        loss, R, t = best
+        loss, R, t, gate = best
         self._history = (self._history + [(R, t)])[-2:]
-        return TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)
+        res = TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)
+        if gate is not None:  # (depth pixels, colour pixels, m_d, m_c, n_d) of the returned pose's iteration
+            res.inliers = (int(gate[0]), int(gate[4]), int(gate[1]))
+            res.medians = (float(gate[2]), float(gate[3]))
+        return res

@@ -336,6 +336,54 @@ class TrackLoss(_MapLoss):
         return self.grad_image, self.grad_depth, self.grad_alpha
 
 
+class GatedTrackLoss(_MapLoss):
+    """``TrackLoss`` with each term gated at a multiple of the frame's own median residual (gs_loss_track_gated,
+    include/gs_abi.h): depth counts where |D / A - z| <= max(``depth_gate_k`` x its lower median over the covered, measured
+    pixels, ``depth_gate_floor``), colour where sum_c |I_c - T_c| <= max(``color_gate_k`` x its lower median over the covered
+    pixels, ``color_gate_floor``); a k <= 0 switches that term's gate off; with ``couple`` a pixel that fails the depth gate
+    loses its colour term too.  The medians are selected on the device: no host synchronisation.  The call shape of
+    ``TrackLoss``; ``values`` = (loss, colour term, depth term, depth pixels that counted, colour pixels that counted, m_d,
+    m_c, n_d).  ``keep_residuals=True`` exposes the two residual maps the kernels store (``resid_depth`` = |D / A - z|,
+    ``resid_color`` = sum_c |I_c - T_c| at the pixels of their sets, NaN elsewhere); otherwise they live in the workspace."""
+
+    def __init__(self, height: int, width: int, alpha_min: float = 0.5, color_weight: float = 1.0, depth_weight: float = 1.0,
+                 depth_gate_k: float = 0.0, color_gate_k: float = 0.0, depth_gate_floor: float = 0.0,
+                 color_gate_floor: float = 0.0, couple: bool = True, device="cuda", keep_residuals: bool = False):
+        self.alpha_min = float(alpha_min)
+        self.color_weight, self.depth_weight = float(color_weight), float(depth_weight)
+        self.depth_gate_k, self.color_gate_k = float(depth_gate_k), float(color_gate_k)
+        self.depth_gate_floor, self.color_gate_floor = float(depth_gate_floor), float(color_gate_floor)
+        self.couple = bool(couple)
+        self._setup(height, width, device, _lib.gs_loss_track_gated_workspace_bytes)
+        self.grad_image = self._new(self.H, self.W, 3)
+        self.grad_depth, self.grad_alpha = self._new(self.H, self.W), self._new(self.H, self.W)
+        self.resid_depth = self._new(self.H, self.W) if keep_residuals else None
+        self.resid_color = self._new(self.H, self.W) if keep_residuals else None
+        self.values = torch.zeros(8, dtype=torch.float32, device=self.device)  # stays on the device
+
+    def __call__(self, image: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_image: torch.Tensor,
+                 target_range: Optional[torch.Tensor], scale: float, values: Optional[torch.Tensor] = None):
+        """As ``TrackLoss.__call__``; ``values``: eight contiguous float32 on the device to receive the values in place of
+        ``self.values``.  Returns (grad_image, grad_depth, grad_alpha)."""
+        maps = [("image", image, 3), ("depth", depth, 0), ("alpha", alpha, 0), ("target_image", target_image, 3)]
+        if target_range is not None:
+            maps.append(("target_range", target_range, 0))
+        for name, t, c in maps:
+            self._check_map(name, t, (self.H, self.W, 3) if c else (self.H, self.W), sep=", ")
+        values = self.values if values is None else values
+        if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous() or values.numel() != 8:
+            raise RuntimeError("values must be eight contiguous float32 on the device")
+        _lib.check(_lib.gs_loss_track_gated(
+            image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
+            target_range.data_ptr() if target_range is not None else None, self.H, self.W, self.alpha_min, self.color_weight,
+            self.depth_weight, self.depth_gate_k, self.color_gate_k, self.depth_gate_floor, self.color_gate_floor,
+            int(self.couple), float(scale), self.grad_image.data_ptr(), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
+            values.data_ptr(), self.resid_depth.data_ptr() if self.resid_depth is not None else None,
+            self.resid_color.data_ptr() if self.resid_color is not None else None, self._ws.data_ptr(), self._ws.numel(),
+            torch.cuda.current_stream().cuda_stream), "gs_loss_track_gated")
+        return self.grad_image, self.grad_depth, self.grad_alpha
+
+
 def z_to_range(z: torch.Tensor, camera) -> torch.Tensor:
     """Sensor z-depth [H,W] (distance along the optical axis) -> range from the camera centre, what the aux depth map
     measures (d_i = |p_c|): range = z |ray| / ray_z with the renderer's own per-pixel rays (gs_geometry.RayBasis: pixel

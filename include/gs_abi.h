@@ -48,6 +48,9 @@ extern "C" {
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_overlap,
  *   gs_view_overlap_workspace_bytes and gs_view_overlap_check_view with gs_overlap_opts / GS_OVERLAP_MAX_VIEWS (how many of the
  *   surface points an RGB-D frame measured does each keyframe see: the covisibility count of a mapping loop).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_track_gated +
+ *   gs_loss_track_gated_workspace_bytes (gs_loss_track with each term gated at a multiple of the frame's own median
+ *   residual: an exact device radix select, no host synchronisation).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_loss_track +
  *   gs_loss_track_workspace_bytes (the masked colour + depth loss of camera tracking against a frozen map, one pass).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_seed_workspace_bytes,
@@ -802,6 +805,38 @@ int gs_loss_track(const float *image, const float *depth, const float *alpha, co
                   const float *target_range, int32_t H, int32_t W, float alpha_min, float color_weight, float depth_weight,
                   float depth_gate, float scale, float *grad_image, float *grad_depth, float *grad_alpha, float *values_out,
                   void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* gs_loss_track with a median gate in place of the fixed depth_gate: a term counts where its residual is at most k x the
+ * LOWER MEDIAN of that residual over the frame (SplaTAM's outlier rule), decided on the device.  Every argument of
+ * gs_loss_track except depth_gate, with its meaning; per pixel, in fp32 with one rounding per operation and the expressions
+ * of gs_loss_track in their order:
+ *   covered = A >= alpha_min,   c = (|d_0| + |d_1|) + |d_2| with d = I - T,   e = D / A,  r = e - z,  a = |r|.
+ *   S_d = covered, measured (the rule of gs_loss_depth) and a <= FLT_MAX (false for NaN);  S_c = covered and c <= FLT_MAX;
+ *   n_d = |S_d|, n_c = |S_c|;  m_d = the element of rank floor((n_d - 1) / 2) of S_d's a values in ascending order -- an
+ *   element of the set, never an average --, 0 for an empty set;  m_c likewise over c.  Both are taken before any gating.
+ *   t_d = max(fl(depth_gate_k m_d), depth_gate_floor),   t_c = max(fl(color_gate_k m_c), color_gate_floor).
+ *   depth  counts iff covered, measured and (depth_gate_k <= 0 or (a <= FLT_MAX and a <= t_d));
+ *   with couple != 0 and depth_gate_k > 0 a pixel of S_d that fails its depth gate loses its colour term too (an occluder
+ *   has the wrong colour as well);
+ *   colour counts iff covered, not dropped by the coupling, and (color_gate_k <= 0 or (c <= FLT_MAX and c <= t_c)).
+ * Where a term counts its gradients are, bit for bit, those gs_loss_track writes with depth_gate <= 0 and the same scale and
+ * weights; everywhere else they are exact zeros.  With both k <= 0 the gradients and values_out[0..3] are gs_loss_track's.
+ * values_out (device, 4-byte aligned, 8 floats, may be NULL) receives (loss, colour term, depth term, depth pixels that
+ * counted, colour pixels that counted, m_d, m_c, n_d), the sums in gs_loss_track's fixed order in double.  resid_depth /
+ * resid_color ([H,W], 16-byte aligned, each may be NULL: the map then lives in the workspace) receive a and c at the pixels
+ * of S_d / S_c and a NaN at every other pixel.  Launches: one memset of the select's counters, a residual pass (reads the
+ * five inputs once, writes a and c), two digit passes over a and c, the gated loss pass, the one-workgroup sum -- see
+ * csrc/track_gate.hip.  No host synchronisation (the thresholds never leave the device), integer counting only, no float
+ * atomics: bitwise repeatable.
+ * GS_E_INVALID -- before anything is enqueued -- for everything gs_loss_track refuses, a NaN or negative floor, a NaN k, a
+ * misaligned residual map, and H W > 2^24 (the counts are returned as floats and must be exact). */
+size_t gs_loss_track_gated_workspace_bytes(int32_t H, int32_t W);
+int gs_loss_track_gated(const float *image, const float *depth, const float *alpha, const float *target_image,
+                        const float *target_range, int32_t H, int32_t W, float alpha_min, float color_weight,
+                        float depth_weight, float depth_gate_k, float color_gate_k, float depth_gate_floor,
+                        float color_gate_floor, int32_t couple, float scale, float *grad_image, float *grad_depth,
+                        float *grad_alpha, float *values_out, float *resid_depth, float *resid_color, void *workspace,
+                        size_t workspace_bytes, gs_stream_t stream);
 
 /* ---- densification: Gaussian3ds.adaptive_control (splatter.py:122-228) ----
  * Two calls because the number of split Gaussians decides how many standard-normal draws the split

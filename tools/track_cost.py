@@ -9,11 +9,16 @@ the 2.4 M scene (rgb colours), each against what the tree offered before:
              tests/test_gpu_pose.py::test_pose_recovery(with_depth=True) does it: autograd render_aux(pose=...), a masked
              torch loss, loss.backward() (the whole backward), torch.optim.Adam on (w, tran).
 
+  gate       the median gate (gs_loss_track_gated, TrackOptions.depth_gate_k = 10): us per call of its kernel chain (one
+             memset, residual pass, two digit passes, gated loss pass, finalize; through gs_train.GatedTrackLoss) against
+             the ungated pair, and ms per Tracker iteration with the gate on against the gate off -- the ungated side is the
+             code of the legs above, unchanged by the gate, and is the baseline.
+
 Protocol of tools/rgbd_step_cost.py: warm-up, then blocks of K calls, the two sides interleaved in rounds in one process;
 medians with the spread of the blocks.  The loss blocks are bracketed by device events; an iteration synchronises with the
 host on both sides, so those blocks are timed by the host clock around work that ends in a synchronise.
 
-    python tools/track_cost.py [--calls 200] [--iters 60] [--rounds 5]
+    python tools/track_cost.py [--calls 200] [--iters 60] [--rounds 5] [--legs loss,iteration,gate]
 """
 import argparse
 import json
@@ -32,7 +37,7 @@ import torch  # noqa: E402
 from gs_frame import FrameRenderer  # noqa: E402
 from gs_scene import make_camera, make_scene  # noqa: E402
 from gs_track import TrackOptions, Tracker, so3_exp  # noqa: E402
-from gs_train import TrackLoss  # noqa: E402
+from gs_train import GatedTrackLoss, TrackLoss  # noqa: E402
 
 CASES = [("vga_376k", 376_467, 640, 480), ("1080p_2.4M", 2_400_000, 1920, 1080)]
 
@@ -66,6 +71,54 @@ def report(case, what, unit, times):
                       "spread_fused": round(sa, 3), "spread_assembled": round(sb, 3)}), flush=True)
 
 
+def report_gate(case, what, unit, times):
+    for k, v in times.items():
+        print(json.dumps({"case": case, "what": what, "variant": k, f"{unit}_median": round(statistics.median(v), 3),
+                          f"{unit}_min": round(min(v), 3), f"{unit}_max": round(max(v), 3), "blocks": len(v)}), flush=True)
+    a, b = (statistics.median(times[k]) for k in ("gated", "ungated"))
+    print(json.dumps({"case": case, "what": what, "gated_over_ungated": round(a / b, 4),
+                      f"gated_minus_ungated_{unit}": round(a - b, 3),
+                      "spread_gated": round(max(times["gated"]) - min(times["gated"]), 3),
+                      "spread_ungated": round(max(times["ungated"]) - min(times["ungated"]), 3)}), flush=True)
+
+
+def gate_leg(args, name, dev, params, cam, maps, targets, start, H, W):
+    """Gate off and on, interleaved: the kernel chain on the maps of the frame rendered from the start pose, then Tracker
+    iterations.  k = 10 (SplaTAM's factor), coupled: the options of tests/test_gpu_track_gate.py."""
+    img, d, a = maps
+    tgt_img, tgt_rng = targets
+    R0, t0 = start
+    o = TrackOptions()
+    scale = 1.0 / (H * W)
+    tl = TrackLoss(H, W, o.alpha_min, o.color_weight, o.depth_weight, 0.0, dev)
+    gl = GatedTrackLoss(H, W, o.alpha_min, o.color_weight, o.depth_weight, 10.0, 0.0, 0.0, 0.0, True, dev)
+    sides = {"ungated": lambda: tl(img, d, a, tgt_img, tgt_rng, scale), "gated": lambda: gl(img, d, a, tgt_img, tgt_rng, scale)}
+    for f in sides.values():
+        for _ in range(args.warmup):
+            f()
+    v = gl.values.cpu().numpy()
+    print(json.dumps({"case": name, "what": "gate_frame", "n_d": int(v[7]), "depth_counted": int(v[3]),
+                      "colour_counted": int(v[4]), "m_d": float(v[5]), "m_c": float(v[6])}), flush=True)
+    times = {k: [] for k in sides}
+    for _ in range(args.rounds):
+        for k, f in sides.items():
+            times[k].append(events_us(f, args.calls))
+    report_gate(name, "gate_loss", "us", times)
+    trackers = {"ungated": Tracker(params, cam, TrackOptions(max_pairs=1 << 22, iterations=args.iters), dev),
+                "gated": Tracker(params, cam, TrackOptions(max_pairs=1 << 22, iterations=args.iters, depth_gate_k=10.0), dev)}
+    for tr in trackers.values():
+        tr.track(tgt_img, tgt_rng, init=(R0, t0))
+    times = {k: [] for k in trackers}
+    for _ in range(args.rounds):
+        for k, tr in trackers.items():
+            torch.cuda.synchronize()
+            t_ = time.perf_counter()
+            tr.track(tgt_img, tgt_rng, init=(R0, t0))
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t_) * 1e3 / args.iters)
+    report_gate(name, "gate_iteration", "ms", times)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
@@ -73,7 +126,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--cases", default=",".join(c[0] for c in CASES))
+    ap.add_argument("--legs", default="loss,iteration,gate")
     args = ap.parse_args()
+    legs = args.legs.split(",")
     dev = torch.device("cuda:0")
     for name, n, W, H in CASES:
         if name not in args.cases.split(","):
@@ -109,6 +164,13 @@ def main():
             colour = ((i_ - tgt_img).abs().sum(-1) * inside).sum() * (scale * o.color_weight)
             depth = ((d_ / a_.clamp_min(1e-6) - tgt_rng).abs() * (inside & measured)).sum() * (scale * o.depth_weight)
             return torch.autograd.grad(colour + depth, (i_, d_, a_))
+
+        if "gate" in legs:
+            gate_leg(args, name, dev, params, cam, (img, d, a), (tgt_img, tgt_rng), (R0, t0), H, W)
+        if "loss" not in legs and "iteration" not in legs:
+            del r, params, tl
+            torch.cuda.empty_cache()
+            continue
 
         got, want = tl(img, d, a, tgt_img, tgt_rng, scale), loss_torch()
         for g, w_ in zip(got, want):  # the two sides state the same loss

@@ -85,10 +85,16 @@ static inline bool gs_frame_long_lists(const gs_frame *f, int n_tiles) {
 // the depth of the last Gaussian it composited when ALL the tile's pixels had stopped before the end of its list (x (1 +
 // GS_CUT_MARGIN); GS_NO_CUT otherwise), and the NEXT frame of the same workspace -- when the caller allows it with
 // GS_FRAME_OCCLUSION_CULL -- trims every level-1 entry at the ends whose tiles' cut lies in front of the Gaussian
-// (strip_common.h, walk_strips): those pairs are never emitted.  Exactness: a tile's list ascends in depth, the dropped
-// pairs are deeper than every kept one, so a tile whose pixels all stop inside its kept prefix composites exactly what it
-// would have composited from the full list -- bit for bit.  A tile that reaches the end of a trimmed list with a live pixel
-// "ran past the cut" (the camera moved, something in front went away): it raises counters[GS_CNT_RANPAST], and the same
+// (strip_common.h, walk_strips): those pairs are never emitted.  What a trimmed list is: a run is trimmed at its two ends
+// only and strip_sort_kernel lists the Gaussian in every tile between them, so tile T's list is the complete prefix
+// {d <= cut[T]} plus SOME deeper pairs (the interior extras of runs that kept their ends), minus the other deeper pairs
+// (trimmed at a run end, or never projected: occluded_everywhere).  Past cut[T] it is NOT a depth prefix.  Exactness: the
+// list ascends in depth, so a tile whose pixels have all stopped and whose last composited Gaussian has d <= cut[T] walked
+// the prefix alone -- exactly what it would have composited from the full list, bit for bit.  Any other tile that has a cut
+// "ran past the cut" (the camera moved, something in front went away or faded): it reached the end of its trimmed list with
+// a live pixel, or it composited something behind its cut -- live or saturated; the compositing kernel's epilogue compares
+// the depth bits of the last composited record with the effective cut table, the bits and the table the trim compared.
+// Such a tile raises counters[GS_CNT_RANPAST], and the same
 // launch sequence that follows the compositing -- count (from the rectangles, untrimmed), column scan, scatter, per-tile
 // sort, compositing, each gated on that counter (a few microseconds of empty grids otherwise) -- renders the frame again
 // from the full lists.  No host synchronisation, the image is exact either way.  Not for training frames (the backward

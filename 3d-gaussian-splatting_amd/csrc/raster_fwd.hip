@@ -133,8 +133,8 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
     static_assert(!(EXACT && FRAME), "the exact-exp flavour belongs to the reference API (gs_draw, fast = 0)");
     // frame path, temporal occlusion cull (gs_frame_layout.h): `cut_out` [T] receives, per tile, the depth behind which this
     // launch composited nothing (all its pixels had stopped) or GS_NO_CUT; `cut_in` (the same table, set when this frame's
-    // lists were trimmed by it) makes a tile that reaches the end of its list with a live pixel raise *ranpast; `gate`: the
-    // untrimmed second pass, which only runs if some tile did
+    // lists were trimmed by it) makes a tile that reaches the end of its list with a live pixel, or that composited a Gaussian
+    // behind its cut, raise *ranpast; `gate`: the untrimmed second pass, which only runs if some tile did
     if (FRAME && gate && *gate == 0) return;
     using SM = FwdSmem<CDIM>;
     constexpr int CH = SM::CH;
@@ -501,12 +501,20 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
         // all pixels stopped inside the list (or exactly at its end): nothing behind the last composited Gaussian matters
         const bool sat = !continues && steps > 0 && (done || !any_live());
         if (lane == 0) {
-            uint32_t c = GS_NO_CUT;
+            uint32_t c = GS_NO_CUT, dlast = GS_NO_CUT;
             if (sat) {
                 const uint32_t last = S.ids[start + steps - 1];
-                c = __float_as_uint(S.geom[(size_t)last * GS_REC_STRIDE].z * (1.0f + GS_CUT_MARGIN));
+                const float zl = S.geom[(size_t)last * GS_REC_STRIDE].z;  // the depth bits the trim compared (rects[].z)
+                dlast = __float_as_uint(zl);
+                c = __float_as_uint(zl * (1.0f + GS_CUT_MARGIN));
             }
-            if (cut_in && !sat && cut_in[tile] != GS_NO_CUT) *ranpast = 1ull;  // this tile's list had been trimmed
+            // A trimmed list (this tile had a cut) is every pair up to the cut plus SOME of the deeper ones (gs_frame_layout.h):
+            // only a walk that ended inside {d <= cut} with every pixel stopped saw what the full list would have shown it.
+            // The list ascends in depth, so the last composited pair decides.  (cut_in may be cut_out: read before the store)
+            if (cut_in) {
+                const uint32_t ci = cut_in[tile];
+                if (ci != GS_NO_CUT && dlast > ci) *ranpast = 1ull;  // (!sat: dlast = GS_NO_CUT, the largest value there is)
+            }
             cut_out[tile] = c;
         }
     }

@@ -248,8 +248,10 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        pairs that lie behind the depth at which the PREVIOUS forward of this workspace saw all
                                        pixels of their tile stop -- 71 % of the pairs of the 2.4 M-Gaussian scene are emitted,
                                        scattered and sorted and never composited.  The image is exact (bit-identical to the
-                                       unculled frame): the dropped pairs are deeper than every kept one, and a tile that
-                                       reaches the end of a trimmed list with a live pixel makes the library render the frame
+                                       unculled frame) whatever the camera or the scene did since: a tile's trimmed list is
+                                       every pair up to its cut plus some of the deeper ones (runs are trimmed at their ends
+                                       only), and a tile that composites anything behind its cut -- or reaches the end of
+                                       its trimmed list with a live pixel -- makes the library render the frame
                                        again from the full lists, on the device, inside the same call (five gated launches:
                                        ~13 us when nothing ran past its cut; 0.6 of a frame when something did, which with thousands
                                        of tiles is nearly every frame of a MOVING camera: set the flag for a camera at rest).  The CALLER's promise: the previous

@@ -496,6 +496,49 @@ extern "C" int gs_frame_backward(const gs_frame *f, const float *grad_image, flo
                                (hipStream_t)stream, nullptr);
 }
 
+// ---- per-Gaussian contribution statistics of a rendered training frame (contrib.hip) ----
+// *prepared: the preparation of the handle's last forward is (being) done on the side stream and `s` now waits for it.  The
+// pending flag stays: the frame's backward still joins (a second wait on the same event costs nothing), and builds nothing.
+// A wait that cannot be enqueued is an error: building the lists on `s` then would write what the side stream may still write.
+static int peek_prepared(const gs_frame *f, hipStream_t s, bool *prepared) {
+    *prepared = false;
+    gs_frame_async *a = (gs_frame_async *)f->async;
+    if (!a) return 0;
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (!a->pending) return 0;
+    GS_HIP(hipStreamWaitEvent(s, a->done, 0));
+    *prepared = true;
+    return 0;
+}
+
+extern "C" size_t gs_frame_contrib_workspace_bytes(int64_t max_pairs) {
+    return max_pairs < 0 ? 0 : gs_contrib_workspace_bytes(max_pairs);
+}
+
+extern "C" int gs_frame_contrib(const gs_frame *f, const gs_contrib_opts *opts, gs_contrib_row *rows, void *workspace,
+                                size_t workspace_bytes, gs_stream_t stream) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_contrib needs a training forward (image_padded kept)");
+    GS_CHECK_ARG(opts != nullptr, "opts is null");
+    GS_CHECK_ARG(opts->w_min > 0.f && opts->w_min <= 1.f, "w_min must lie in (0, 1]");  // (false for NaN)
+    GS_CHECK_ARG(opts->accumulate == 0 || opts->accumulate == 1, "accumulate must be 0 or 1");
+    GS_CHECK_ARG(f->N == 0 || rows != nullptr, "rows is null");
+    GS_CHECK_ARG(((uintptr_t)rows & 15) == 0, "rows must be 16-byte aligned");
+    GS_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 &&
+                     workspace_bytes >= gs_frame_contrib_workspace_bytes(f->max_pairs),
+                 "workspace null, not 256-byte aligned or too small");
+    if (f->N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
+    uint64_t *skeys, *okeys;
+    uint32_t *sids;
+    sorted_buffers(f, ws, &skeys, &sids, &okeys);
+    bool prepared = false;
+    if ((rc = peek_prepared(f, s, &prepared))) return rc;
+    return gs_stage_contrib(f, ws, sids, prepared, opts->w_min, opts->accumulate, rows, workspace, s);
+}
+
 // An all-zero [bytes] device buffer for a NULL grad_image of gs_frame_backward_adam_aux: the raster backward reads dL/dimage
 // of every pixel, and its kernels are left as they are.  One buffer per device, owned by the library, allocated (and
 // cleared, once) at the first call that needs it and grown when a larger image arrives; only ever read afterwards.  Growing

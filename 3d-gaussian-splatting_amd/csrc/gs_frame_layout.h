@@ -557,6 +557,13 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
                             bool second_pass = false);
 int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids, hipStream_t stream);
 int gs_stage_sh_big_rows(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
+// gs_frame_contrib (contrib.hip): the stop keys and the bucket work list where the frame's own preparation left them out
+// (raster_bwd.hip), then the pair pass and the Gaussian pass
+int gs_stage_contrib_prepare(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids, bool prepared,
+                             unsigned long long *n_buckets_own, hipStream_t stream);
+int gs_stage_contrib(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids, bool prepared, float w_min,
+                     int accumulate, gs_contrib_row *rows, void *workspace, hipStream_t stream);
+size_t gs_contrib_workspace_bytes(int64_t max_pairs);
 int gs_stage_aux_depth_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, int64_t g_begin, int64_t g_end,
                                 hipStream_t stream);
 // GS_FRAME_POSE_GRAD (rgb colours, all Gaussians): the projection backward's pose variant (part 0 or 1), the aux depth

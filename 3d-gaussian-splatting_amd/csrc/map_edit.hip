@@ -59,6 +59,33 @@ __global__ void __launch_bounds__(PRUNE_BLOCK) prune_classify_kernel(const float
     if (threadIdx.x == 0) block_counts[blockIdx.x] = s_keep[0] + s_keep[1] + s_keep[2] + s_keep[3];
 }
 
+// prune_classify_kernel's decision with the contribution rule joined to it (gs_prune_classify_contrib): a kernel of its own
+// beside it, the same ballots and counts out.  rows[i] = (weight_sum, weight_max, pixels, views) of gs_frame_contrib; a NaN
+// weight_max fails its comparison: not kept.
+__global__ void __launch_bounds__(PRUNE_BLOCK) prune_classify_contrib_kernel(
+    const float *__restrict__ scale, const float *__restrict__ opa, const uint4 *__restrict__ rows, int64_t n,
+    float opa_logit_min, float scale_max, int scale_act, float weight_max_min, uint32_t pixels_min, uint32_t views_min,
+    unsigned long long *__restrict__ masks, uint32_t *__restrict__ block_counts) {
+    __shared__ uint32_t s_keep[PRUNE_WAVES];
+    const int64_t i = (int64_t)blockIdx.x * PRUNE_BLOCK + threadIdx.x;
+    bool keep = false;
+    if (i < n) {
+        const float s[3] = {scale[i * 3], scale[i * 3 + 1], scale[i * 3 + 2]};
+        const float norm = prune_act_norm(s, scale_act);
+        const uint4 r = rows[i];
+        keep = opa[i] > opa_logit_min && norm < scale_max && __uint_as_float(r.y) >= weight_max_min && r.z >= pixels_min &&
+               r.w >= views_min;
+    }
+    const unsigned long long m = __ballot(keep);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        masks[(size_t)blockIdx.x * PRUNE_WAVES + wave] = m;
+        s_keep[wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = s_keep[0] + s_keep[1] + s_keep[2] + s_keep[3];
+}
+
 // one workgroup, trips of 1,024 counts: block_counts[i] <- exclusive scan; counts = (kept, n - kept)
 __global__ void __launch_bounds__(1024) prune_scan_kernel(uint32_t *__restrict__ block_counts, int nblk, int64_t n,
                                                           long long *__restrict__ counts) {
@@ -200,6 +227,37 @@ extern "C" int gs_prune_classify(const float *scale, const float *opa, int64_t N
     if (nblk > 0) {
         hipLaunchKernelGGL(prune_classify_kernel, dim3(nblk), dim3(PRUNE_BLOCK), 0, s, scale, opa, N, opts->opa_logit_min,
                            opts->scale_max, opts->scale_activation, w.masks, w.block_counts);
+        GS_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, s, w.block_counts, nblk, N, (long long *)counts_dev);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gs_prune_classify_contrib(const float *scale, const float *opa, const gs_contrib_row *rows, int64_t N,
+                                         const gs_prune_opts *opts, const gs_prune_contrib_opts *copts, int64_t *counts_dev,
+                                         void *workspace, size_t workspace_bytes, gs_stream_t stream) {
+    GS_CHECK_ARG(opts != nullptr, "opts is null");
+    GS_CHECK_ARG(copts != nullptr, "copts is null");
+    GS_CHECK_ARG(std::isfinite(opts->opa_logit_min), "opa_logit_min must be finite");
+    GS_CHECK_ARG(!std::isnan(opts->scale_max), "scale_max must not be NaN (+inf switches the test off)");
+    GS_CHECK_ARG(opts->scale_activation == 0 || opts->scale_activation == 1, "scale_activation must be 0 (abs) or 1 (exp)");
+    GS_CHECK_ARG(copts->weight_max_min >= 0.f, "weight_max_min must not be NaN or negative");
+    GS_CHECK_ARG(N >= 0 && N < (1ll << 31), "N out of range");
+    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev is null");
+    GS_CHECK_ARG(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= gs_prune_workspace_bytes(N),
+                 "workspace null, misaligned or too small");
+    GS_CHECK_ARG(N == 0 || (scale && opa), "scale or opa is null");
+    GS_CHECK_ARG(N == 0 || rows != nullptr, "rows is null");
+    GS_CHECK_ARG(((uintptr_t)rows & 15) == 0, "rows must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const PruneWs w = prune_carve(workspace, N);
+    const int nblk = (int)gs_div_up(N, PRUNE_BLOCK);
+    if (nblk > 0) {
+        hipLaunchKernelGGL(prune_classify_contrib_kernel, dim3(nblk), dim3(PRUNE_BLOCK), 0, s, scale, opa,
+                           reinterpret_cast<const uint4 *>(rows), N, opts->opa_logit_min, opts->scale_max,
+                           opts->scale_activation, copts->weight_max_min, copts->pixels_min, copts->views_min, w.masks,
+                           w.block_counts);
         GS_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, s, w.block_counts, nblk, N, (long long *)counts_dev);

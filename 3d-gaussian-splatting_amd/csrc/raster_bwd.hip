@@ -996,65 +996,7 @@ static inline int gs_bwd_mfma_waves(int n_tiles) { return n_tiles >= 1024 ? 2 : 
 #define GS_BWD_MFMA_WPE 3
 #endif
 
-// The DPP row scans of the row-layout kernels, for the lane's four pixels at once and every step ONE instruction per pixel
-// (v_mul_f32_dpp v, v, v row_shr:n: lanes whose source falls outside the row are disabled by the DPP bound check and keep v --
-// the identity for free; through the builtin the compiler emits v_mov 1.0 + v_mov_dpp + v_mul for a product step).  The four
-// chains are interleaved so that the write of a register and its DPP read in the next step are three instructions apart (the
-// hardware wants two wait states there, and the compiler's hazard pass does not look into inline assembly: hence also the
-// s_nop in front of a block).
-//
-// Inclusive prefix sum over the 16 lanes of a DPP row for the lane's four pixels, OUT of place: the first step's
-// bound_ctrl:0 reads 0 where a lane has no source -- the sum's identity --, so `in` survives (round 5: the unscanned w gc
-// gives s = w gc - rho beta one instruction cheaper than dL/dalpha alpha).
-__device__ __forceinline__ void gs_row_scan_add4_oop(float out[4], const float in[4]) {
-    asm volatile("s_nop 1\n\t"
-                 "v_add_f32_dpp %0, %4, %4 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                 "v_add_f32_dpp %1, %5, %5 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                 "v_add_f32_dpp %2, %6, %6 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                 "v_add_f32_dpp %3, %7, %7 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                 "v_add_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %1, %1, %1 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %2, %2, %2 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %3, %3, %3 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %1, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %2, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %3, %3, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %1, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %2, %2, %2 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %3, %3, %3 row_shr:8 row_mask:0xf bank_mask:0xf"
-                 : "=&v"(out[0]), "=&v"(out[1]), "=&v"(out[2]), "=&v"(out[3])
-                 : "v"(in[0]), "v"(in[1]), "v"(in[2]), "v"(in[3]));
-    // (no s_nop behind the block: the hazard is VALU write -> DPP READ; what follows reads the results with plain VALU
-    // instructions, and the kernels that use this helper contain no compiler-generated DPP instruction)
-}
-// Both at once (one asm block, no s_nop between the two: a register written by the scan's last step is read four
-// instructions later): p <- inclusive product scan of p; t <- t x (scanned p of the lane to the left), lane 0 keeps t.
-__device__ __forceinline__ void gs_row_scan_mul4_excl(float p[4], float t[4]) {
-    asm volatile("s_nop 1\n\t"
-                 "v_mul_f32_dpp %4, %4, %4 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %5, %5, %5 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %6, %6, %6 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %7, %7, %7 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %4, %4, %4 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %5, %5, %5 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %6, %6, %6 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %7, %7, %7 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %4, %4, %4 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %5, %5, %5 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %6, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %7, %7, %7 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %4, %4, %4 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %5, %5, %5 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %6, %6, %6 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %7, %7, %7 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %0, %4, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %1, %5, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %2, %6, %2 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                 "v_mul_f32_dpp %3, %7, %3 row_shr:1 row_mask:0xf bank_mask:0xf"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
-}
+// (the DPP row scans of the row-layout kernels, gs_row_scan_add4_oop / gs_row_scan_mul4_excl: raster_common.h)
 // workgroups of the matrix-pipe launch: one per work item up to 2 T (the kernel walks the items with the grid as the stride;
 // the executed-row counters have GS_BWD_EXEC_SLOTS x T = 8 T slots for grid x waves)
 static_assert(4 <= GS_BWD_EXEC_SLOTS, "executed-row counters");
@@ -2015,6 +1957,27 @@ int gs_stage_backward_prepare(const gs_frame *f, const gs_frame_ws &ws, const ui
                            (gs_frame_uses_strips(f) && f->N > 0) ? ws.tile_order : nullptr,
                            (uint32_t)GS_MFMA_ITEM_BUCKETS, ws.mfma_items, ws.mfma_n_items);
     }
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+// What gs_frame_contrib (contrib.hip) needs of the preparation above: the stop keys and the bucket work list.  `prepared`: the
+// frame's own preparation has run or is queued in front of `stream`; then only SH frames without maps lack the list (they got
+// work items instead), and theirs is built with its count in `n_buckets_own` -- nothing the backward of such a frame reads.
+// Otherwise the same launches with the same arguments as above: the list the backward will build again, bit for bit.
+int gs_stage_contrib_prepare(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids, bool prepared,
+                             unsigned long long *n_buckets_own, hipStream_t stream) {
+    gs_frame_geom FG = gs_frame_geometry(f);
+    if (!prepared)
+        hipLaunchKernelGGL(stop_key_kernel, dim3((unsigned)gs_div_up(FG.n_tiles, 256)), dim3(256), 0, stream, ws.tile_nproc,
+                           FG.n_tiles, ws.tile_ranges, sorted_ids, ws.rects, (unsigned long long *)ws.stop_keys);
+    const bool mfma_frame = f->color_dim != 3 && !(f->flags & GS_FRAME_AUX);
+    if (mfma_frame)
+        gs_launch_bucket_list(ws.tile_nproc, FG.n_tiles, ws.bucket_offsets, n_buckets_own, ws.bucket_info, ws.tile_ranges, 1,
+                              stream);
+    else if (!prepared)
+        gs_launch_bucket_list(ws.tile_nproc, FG.n_tiles, ws.bucket_offsets, ws.counters + GS_CNT_BUCKETS, ws.bucket_info,
+                              ws.tile_ranges, 1, stream);
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -251,6 +251,24 @@ gs_prune_workspace_bytes = _sig("gs_prune_workspace_bytes", sz, i64)
 gs_prune_classify = _sig("gs_prune_classify", ci, vp, vp, i64, C.POINTER(GsPruneOpts), vp, vp, sz, vp)
 gs_prune_apply = _sig("gs_prune_apply", ci, C.POINTER(GsPruneArrays), i64, i64, i64, vp, vp, sz, vp)
 
+
+class GsContribOpts(C.Structure):
+    """Mirror of ``struct gs_contrib_opts``."""
+
+    _fields_ = [("w_min", f32), ("accumulate", i32)]
+
+
+class GsPruneContribOpts(C.Structure):
+    """Mirror of ``struct gs_prune_contrib_opts``."""
+
+    _fields_ = [("weight_max_min", f32), ("pixels_min", C.c_uint32), ("views_min", C.c_uint32)]
+
+
+gs_frame_contrib_workspace_bytes = _sig("gs_frame_contrib_workspace_bytes", sz, i64)
+gs_frame_contrib = _sig("gs_frame_contrib", ci, C.POINTER(GsFrame), C.POINTER(GsContribOpts), vp, vp, sz, vp)
+gs_prune_classify_contrib = _sig("gs_prune_classify_contrib", ci, vp, vp, vp, i64, C.POINTER(GsPruneOpts),
+                                 C.POINTER(GsPruneContribOpts), vp, vp, sz, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -272,6 +290,7 @@ EXPORTS = [
     "gs_scene_pack_bytes", "gs_scene_pack_build", "gs_frame_reads_scene_pack",
     "gs_prune_workspace_bytes", "gs_prune_classify", "gs_prune_apply",
     "gs_seed_apply_pp", "gs_view_overlap_pp",
+    "gs_frame_contrib_workspace_bytes", "gs_frame_contrib", "gs_prune_classify_contrib",
 ]
 
 

@@ -49,6 +49,8 @@ SOURCES = {
     "overlap.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # the keep test (opa > t and ||act(scale)|| < s) as written: densify.hip's delete rule, decided identically
     "map_edit.hip": ["-ffp-contract=off"],
+    # the row step of raster_bwd.hip's row-layout kernel, built like it (no SLP packing, as above)
+    "contrib.hip": ["-fno-slp-vectorize"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

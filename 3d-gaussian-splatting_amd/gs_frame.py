@@ -46,6 +46,41 @@ class FrameStats:
 
 _LOG_FLAGS = os.environ.get("GS_LOG_FLAGS", "") == "1"
 
+# Default of ``FrameRenderer.contributions``: a contribution below 1/255 moves no 8-bit colour channel by a whole level.  That
+# justifies it as a default and nothing more.
+CONTRIB_W_MIN = 1.0 / 255.0
+
+
+class Contributions:
+    """Per-Gaussian contribution statistics (include/gs_abi.h, gs_frame_contrib) over one [N,4] buffer of 16-byte rows:
+    ``weight_sum`` = sum over pixels of w = alpha T, ``weight_max`` = its maximum (float32 views), ``pixels`` = pixels with
+    w >= w_min, ``views`` = frames in which there was such a pixel (int32 views of the uint32 columns); ``rows`` is the raw
+    buffer (float32 [N,4]: what ``gs_prune.prune_rows`` takes, and an array that can travel with a prune)."""
+
+    def __init__(self, rows: torch.Tensor, w_min: float):
+        self.rows = rows
+        self.w_min = float(w_min)
+
+    @staticmethod
+    def empty(n: int, device, w_min: float = CONTRIB_W_MIN) -> "Contributions":
+        return Contributions(torch.zeros(int(n), 4, dtype=torch.float32, device=device), w_min)
+
+    @property
+    def weight_sum(self) -> torch.Tensor:
+        return self.rows[:, 0]
+
+    @property
+    def weight_max(self) -> torch.Tensor:
+        return self.rows[:, 1]
+
+    @property
+    def pixels(self) -> torch.Tensor:
+        return self.rows.view(torch.int32)[:, 2]
+
+    @property
+    def views(self) -> torch.Tensor:
+        return self.rows.view(torch.int32)[:, 3]
+
 
 class FrameRenderer:
     default_force_strips = False  # see `force_strips`
@@ -135,6 +170,7 @@ class FrameRenderer:
         self._aux_ws: Optional[torch.Tensor] = None  # GS_FRAME_AUX frames: the library's second workspace (grown with the first)
         self._aux_keep = None  # (depth, alpha, aux_padded) of the last forward, kept for its backward
         self._pose_ws: Optional[torch.Tensor] = None  # GS_FRAME_POSE_GRAD backwards: the per-workgroup partial sums
+        self._contrib_ws: Optional[torch.Tensor] = None  # contributions(): the pair rows (regrown with max_pairs)
         self._stats_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
         self._frame: Optional[_lib.GsFramePP] = None
         self._frame_serial = 0  # counts forwards: autograd checks that backward() belongs to the latest one
@@ -1035,6 +1071,39 @@ class FrameRenderer:
         off = ptr.value - self._ws.data_ptr()
         T = self._grid.n_tiles
         return int(self._ws[off:off + 4 * T].view(torch.int32).to(torch.int64).sum().item())
+
+    def contributions(self, w_min: float = CONTRIB_W_MIN, out: Optional[Contributions] = None,
+                      accumulate: bool = False) -> Contributions:
+        """Each Gaussian's share of the last TRAINING forward (include/gs_abi.h, gs_frame_contrib): per Gaussian the sum and
+        the maximum over the image's pixels of its compositing weight w = alpha T, the number of pixels with w >= ``w_min``
+        and whether there was one.  ``out``: a ``Contributions`` of N rows to write into; with ``accumulate`` the frame is
+        combined with what it holds (+=, max, +=, +=: ``views`` then counts frames).  Two HIP launches on the current stream
+        behind the forward, no host synchronisation; a later ``backward`` of the same frame gives the bits it gives without
+        this call."""
+        f = self._frame
+        if f is None or not f.training:
+            raise RuntimeError("contributions() needs a preceding training forward")
+        n = int(f.N)
+        if out is None:
+            if accumulate:
+                raise RuntimeError("contributions(accumulate=True) needs `out`")
+            out = Contributions.empty(n, self.device, w_min)
+        elif accumulate and float(out.w_min) != float(w_min):  # pixels / views counted at two floors mean nothing
+            raise RuntimeError(f"contributions(accumulate=True): `out` was counted at w_min {out.w_min!r}, not {float(w_min)!r}")
+        rows = out.rows
+        if (rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous()
+                or tuple(rows.shape) != (n, 4)):
+            raise RuntimeError(f"contributions(): `out` must hold contiguous float32 rows [{n}, 4] on {self.device}")
+        need = int(_lib.gs_frame_contrib_workspace_bytes(int(f.max_pairs)))
+        if self._contrib_ws is None or self._contrib_ws.numel() < need + 256:
+            self._contrib_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        base = (self._contrib_ws.data_ptr() + 255) // 256 * 256
+        opts = _lib.GsContribOpts(float(w_min), 1 if accumulate else 0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.gs_frame_contrib(C.byref(f), C.byref(opts), rows.data_ptr() or None, base, need,
+                                             self._stream().cuda_stream), "gs_frame_contrib")
+        out.w_min = float(w_min)
+        return out
 
     def executed_row_steps(self) -> int:
         """SH frames: pixel-row steps (16 Gaussians x 16 pixels) the last backward's matrix-pipe kernel executed -- rows

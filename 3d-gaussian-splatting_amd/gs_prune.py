@@ -40,6 +40,22 @@ def prune_options(opa_min: float = DEFAULTS["opa_min"], scale_max: Optional[floa
                             SCALE_ACT[scale_activation])
 
 
+def contrib_options(weight_max_min: float = 0.0, pixels_min: int = 0, views_min: int = 0) -> "_lib.GsPruneContribOpts":
+    if not float(weight_max_min) >= 0.0:
+        raise ValueError(f"weight_max_min must not be NaN or negative, got {weight_max_min!r}")
+    if int(pixels_min) < 0 or int(views_min) < 0:
+        raise ValueError(f"pixels_min and views_min must not be negative, got {pixels_min!r} and {views_min!r}")
+    return _lib.GsPruneContribOpts(float(weight_max_min), int(pixels_min), int(views_min))
+
+
+def contrib_rows(contributions, n: int) -> torch.Tensor:
+    """The raw [N,4] float32 buffer of a ``gs_frame.Contributions`` (or the buffer itself), checked against N."""
+    rows = getattr(contributions, "rows", contributions)
+    if _rows("contributions", rows, n) != 4 or int(rows.shape[0]) != n:
+        raise RuntimeError(f"contributions must hold [{n},4] rows, got {list(rows.shape)}")
+    return rows
+
+
 def _rows(name: str, t: torch.Tensor, n: Optional[int] = None) -> int:
     """A contiguous float32 HIP tensor of rows -> floats per row."""
     if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() < 1 or (n is not None and t.shape[0] < n):
@@ -47,8 +63,11 @@ def _rows(name: str, t: torch.Tensor, n: Optional[int] = None) -> int:
     return int(math.prod(t.shape[1:]))
 
 
-def prune_classify(scale: torch.Tensor, opa: torch.Tensor, opts) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The decision pass: -> (counts [2] int64 on the device = (kept, removed), workspace)."""
+def prune_classify(scale: torch.Tensor, opa: torch.Tensor, opts, contributions=None,
+                   copts=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The decision pass: -> (counts [2] int64 on the device = (kept, removed), workspace).  With ``contributions`` (the rows of
+    ``FrameRenderer.contributions``) and ``copts`` (``contrib_options``) the contribution rule is joined to the decision
+    (gs_prune_classify_contrib); without them the call is gs_prune_classify."""
     if scale.device.type != "cuda":
         raise RuntimeError("pruning needs a HIP device; there is no CPU fallback")
     n = int(scale.shape[0])
@@ -56,6 +75,13 @@ def prune_classify(scale: torch.Tensor, opa: torch.Tensor, opts) -> Tuple[torch.
         raise RuntimeError(f"scale must be [N,3] and opa [N] of the same N, got {list(scale.shape)} and {list(opa.shape)}")
     ws = torch.empty(int(_lib.gs_prune_workspace_bytes(n)), dtype=torch.uint8, device=scale.device)
     counts = torch.zeros(2, dtype=torch.int64, device=scale.device)
+    if contributions is not None:
+        rows = contrib_rows(contributions, n)
+        _lib.check(_lib.gs_prune_classify_contrib(scale.data_ptr(), opa.data_ptr(), rows.data_ptr(), n, C.byref(opts),
+                                                  C.byref(copts if copts is not None else contrib_options()),
+                                                  counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                  torch.cuda.current_stream().cuda_stream), "gs_prune_classify_contrib")
+        return counts, ws
     _lib.check(_lib.gs_prune_classify(scale.data_ptr(), opa.data_ptr(), n, C.byref(opts), counts.data_ptr(), ws.data_ptr(),
                                       ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_prune_classify")
     return counts, ws
@@ -83,12 +109,21 @@ def prune_apply(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], n: int
 
 def prune_rows(scale: torch.Tensor, opa: torch.Tensor, arrays: Sequence[torch.Tensor], *,
                opa_min: float = DEFAULTS["opa_min"], scale_max: Optional[float] = DEFAULTS["scale_max"],
-               scale_activation: str = "abs") -> Tuple[List[torch.Tensor], int, int]:
+               scale_activation: str = "abs", contributions=None, weight_max_min: float = 0.0, pixels_min: int = 0,
+               views_min: int = 0) -> Tuple[List[torch.Tensor], int, int]:
     """-> (the arrays compacted to the kept rows, kept, removed).  ``scale`` [N,3] and ``opa`` [N] decide (raw parameters);
-    ``arrays``: up to sixteen float32 tensors of N rows each, ``scale`` and ``opa`` among them if they are to travel."""
+    ``arrays``: up to sixteen float32 tensors of N rows each, ``scale`` and ``opa`` among them if they are to travel.
+    ``contributions`` (``FrameRenderer.contributions`` / ``Trainer.contributions``, or their [N,4] buffer) joins the rule
+    weight_max >= ``weight_max_min`` and pixels >= ``pixels_min`` and views >= ``views_min`` to the decision; the buffer may
+    itself be one of ``arrays``.  Without it the calls are the ones issued before the rule existed."""
     opts = prune_options(opa_min, scale_max, scale_activation)
     n = int(scale.shape[0])
-    counts, ws = prune_classify(scale, opa, opts)
+    if contributions is None:
+        if weight_max_min or pixels_min or views_min:
+            raise ValueError("weight_max_min / pixels_min / views_min need contributions")
+        counts, ws = prune_classify(scale, opa, opts)
+    else:
+        counts, ws = prune_classify(scale, opa, opts, contributions, contrib_options(weight_max_min, pixels_min, views_min))
     kept, removed = (int(v) for v in counts.tolist())  # the one host synchronisation
     out = [torch.empty((kept,) + tuple(t.shape[1:]), dtype=torch.float32, device=scale.device) for t in arrays]
     if kept:

@@ -218,6 +218,13 @@ class SlamOptions:
     prune_every: int = 0            # prune behind the mapping steps of every k-th keyframe (0: never)
     prune_opa_min: float = 0.005    # ... the Gaussians with sigmoid(opa) <= this (no evidence: see above)
     prune_scale_max: Optional[float] = None  # ... or ||act(scale)|| >= this; None: no scale test
+    # Visibility pruning (off: the loop issues exactly the calls it issues without the option): behind the mapping steps of
+    # every k-th keyframe -- and behind prune_every's own prune -- the Gaussians that reach the weight prune_unseen_w_min at no
+    # pixel of any keyframe are removed (Trainer.contributions over all keyframes, Trainer.prune(views_min=1)), the optimizer
+    # state carried as carry_optimizer says.  1/255: below it no 8-bit colour channel moves by a whole level -- a reason for
+    # the default and nothing more; what the option did on the eight-frame arc is in profiles/contrib_prune.txt.
+    prune_unseen_every: int = 0
+    prune_unseen_w_min: float = 1.0 / 255.0
 
 
 @dataclass
@@ -236,6 +243,7 @@ class SlamFrame:
     # keyframe 0); rot / tran above then report this frame's own refined pose
     refined: Dict[int, Tuple[np.ndarray, np.ndarray]] = field(default_factory=dict)
     pruned: int = 0                  # Gaussians removed behind this keyframe's mapping steps (prune_every)
+    pruned_unseen: int = 0           # ... and those removed because no keyframe sees them (prune_unseen_every)
 
 
 class Slam:
@@ -309,6 +317,13 @@ class Slam:
             frame.pruned = tr.prune(self.i_iter, opa_min=o.prune_opa_min, scale_max=o.prune_scale_max,
                                     carry_state=bool(o.carry_optimizer))
             frame.seconds["prune"] = time.perf_counter() - t0
+        if o.prune_unseen_every > 0 and len(self.keyframes) % int(o.prune_unseen_every) == 0:
+            # what reaches w_min in no keyframe is constrained by no training view: seeds that ended up behind a surface,
+            # duplicates from several keyframes, whatever lies outside every frustum
+            t0 = time.perf_counter()
+            seen = tr.contributions(w_min=o.prune_unseen_w_min)
+            frame.pruned_unseen = tr.prune(self.i_iter, contributions=seen, views_min=1, carry_state=bool(o.carry_optimizer))
+            frame.seconds["prune_unseen"] = time.perf_counter() - t0
         # (also with no step taken: seeding gave the trainer new parameter tensors)
         if self.tracker is None:
             self.tracker = Tracker(self.trainer.flat.params, self.keyframes.cameras[0], self.opt.track, self.device)

@@ -29,7 +29,7 @@ import torch
 
 from gaussian import _lib
 from gs_dp import ORDER, FlatGaussianParams, ViewParallelGradStat
-from gs_frame import FrameRenderer
+from gs_frame import CONTRIB_W_MIN, Contributions, FrameRenderer
 from gs_geometry import RayBasis, TileGrid, principal_point_offset
 
 GROUPS = ("opa", "rgb", "pos", "scale", "quat")  # the reference's param-group order (train.py:59-65)
@@ -906,6 +906,36 @@ class Trainer:
             self._eval_renderer.tile_culling_dist_thresh = self.renderer.tile_culling_dist_thresh
         return self._eval_renderer
 
+    def _contrib_renderer_for_set(self) -> FrameRenderer:
+        """The second TRAINING renderer ``contributions`` renders its views with (created on first use, sized like the
+        evaluation renderer): the fit's own renderer, its workspace, a frame projected ahead in it and its asynchronous
+        counters are not touched."""
+        if getattr(self, "_contrib_renderer", None) is None:
+            self._contrib_renderer = FrameRenderer(self.flat.flat_param.device, max_pairs=self.renderer.max_pairs,
+                                                   training=True, scale_activation=self.scale_activation,
+                                                   thresh=self.renderer.thresh)
+            self._contrib_renderer.tile_culling_method = self.renderer.tile_culling_method
+            self._contrib_renderer.tile_culling_dist_thresh = self.renderer.tile_culling_dist_thresh
+        return self._contrib_renderer
+
+    @torch.no_grad()
+    def contributions(self, camera_ids: Optional[Sequence[int]] = None, w_min: float = CONTRIB_W_MIN) -> Contributions:
+        """Each Gaussian's share of the named views (default: all), accumulated into one buffer (``gs_frame.Contributions``:
+        weight_sum and pixels summed over the views, weight_max their maximum, ``views`` the number of views in which the
+        Gaussian reached ``w_min`` somewhere).  Every view is rendered with a training forward on a renderer of its own; no
+        loss, no backward, no optimizer step: a ``train_step`` after this call is the step without it, bit for bit."""
+        if self.world_size > 1:
+            raise RuntimeError("contributions() is not available under view parallelism (world_size > 1)")
+        self.flat.finish_gather()
+        ids = list(range(len(self.cameras))) if camera_ids is None else [int(k) for k in camera_ids]
+        renderer, params = self._contrib_renderer_for_set(), [t.detach() for t in self.flat.params]
+        out = Contributions.empty(self.n_gaussians, self.flat.flat_param.device, w_min)
+        for k in ids:
+            self._settle_pose(k)
+            renderer.forward(*params, self.cameras[k], training=True)
+            renderer.contributions(w_min, out=out, accumulate=True)
+        return out
+
     @torch.no_grad()
     def _refuse_carry(self, what: str):
         """The optimizer state can travel with the rows only where one rank holds all of it, addressed by row."""
@@ -915,23 +945,43 @@ class Trainer:
                                "counter): their moments are not row-addressable from one rank; pass carry_state=False")
 
     @torch.no_grad()
-    def prune(self, i_iter: int, *, opa_min: float, scale_max: Optional[float] = math.inf, carry_state: bool = True) -> int:
+    def prune(self, i_iter: int, *, opa_min: Optional[float] = None, scale_max: Optional[float] = math.inf,
+              contributions=None, weight_max_min: float = 0.0, pixels_min: int = 0, views_min: int = 0,
+              carry_state: bool = True) -> int:
         """Removes the Gaussians with sigmoid(opa) <= ``opa_min`` or ||act(scale)|| >= ``scale_max`` (``gs_prune``: the delete
         rule of ``adaptive_control`` with both thresholds as arguments; None / inf: no scale test) -> the number removed.
+        ``contributions`` (``Trainer.contributions()``) joins the contribution rule to it: a Gaussian also goes when its
+        weight_max < ``weight_max_min``, its pixels < ``pixels_min`` or its views < ``views_min`` (``views_min=1``: what reaches
+        w_min in no view).  ``opa_min`` may then be None: no opacity test.  Without ``contributions`` the method is what it was
+        before the rule existed, and ``opa_min`` is required.
         With ``carry_state`` the kept rows take their Adam moments and their densification statistic with them and the step
         count stays: ONE ``gs_prune_apply`` moves the five parameter arrays, the ten moment arrays and the statistic straight
         into the new flat buffer and the new optimizer's buffers.  ``carry_state=False``: the fresh optimizer of every other
         rebind.  When nothing is removed nothing changes -- no rebind; one host read either way.  A prune that would remove
         every Gaussian is refused.  The Trainer never calls this by itself."""
-        from gs_prune import prune_apply, prune_classify, prune_options
+        from gs_prune import SCALE_ACT, contrib_options, prune_apply, prune_classify, prune_options
 
         if carry_state:
             self._refuse_carry("prune(carry_state=True)")
-        opts = prune_options(opa_min, scale_max, self.scale_activation)
+        if contributions is None:
+            if opa_min is None:
+                raise TypeError("prune() needs opa_min (it may be None only with contributions)")
+            if weight_max_min or pixels_min or views_min:
+                raise ValueError("weight_max_min / pixels_min / views_min need contributions")
+            opts = prune_options(opa_min, scale_max, self.scale_activation)
+        elif opa_min is None:  # no opacity test: every finite logit lies above the most negative finite float
+            opts = _lib.GsPruneOpts(-torch.finfo(torch.float32).max, math.inf if scale_max is None else float(scale_max),
+                                    SCALE_ACT[self.scale_activation])
+        else:
+            opts = prune_options(opa_min, scale_max, self.scale_activation)
         self.flat.finish_gather()
         old_flat, old_opt = self.flat, self.optimizer
         params, n = old_flat.params, old_flat.n
-        counts, ws = prune_classify(params[2], params[3], opts)
+        if contributions is None:
+            counts, ws = prune_classify(params[2], params[3], opts)
+        else:
+            counts, ws = prune_classify(params[2], params[3], opts, contributions,
+                                        contrib_options(weight_max_min, pixels_min, views_min))
         kept, removed = (int(v) for v in counts.tolist())  # the one host synchronisation
         if removed == 0:
             return 0

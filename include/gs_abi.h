@@ -1028,6 +1028,45 @@ int gs_prune_classify(const float *scale, const float *opa, int64_t N, const gs_
 int gs_prune_apply(const gs_prune_arrays *arrays, int64_t N, int64_t dst_offset, int64_t capacity,
                    const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
+/* ---- per-Gaussian contributions: each Gaussian's share of a rendered frame ----
+ * For a TRAINING frame that gs_frame_forward has rendered (any colour model, with or without GS_FRAME_AUX,
+ * GS_FRAME_PRINCIPAL_POINT, GS_FRAME_LONG_SORT, GS_FRAME_LONG_LISTS, any listing method), a pixel p of the CROPPED height x width
+ * image (pixels of the padded border count for nothing) and a Gaussian g listed in the tile of p:
+ *   w_g(p) = alpha_g(p) T_g(p)
+ * with exactly the expressions of the compositing kernels: alpha = 2^-(q + nlop), nlop = -log2 sigmoid(opa), and the masked
+ * transmittance, which is exactly 0 once the pixel has reached the 1e-4 stop -- what the raster backward recomputes from a
+ * bucket's checkpoint.  For a list entry the forward did not process (its key lies behind the tile's stop key), w = 0.
+ * One 16-byte row per Gaussian:
+ *   weight_sum = sum_p w_g(p),  weight_max = max_p w_g(p),  pixels = #{p : w_g(p) >= w_min},  views = pixels > 0 ? 1 : 0.
+ * The row of a culled Gaussian is all zeros; so is every row of a frame that overflowed its pair capacity (it is rendered
+ * empty).  N = 0 is valid: nothing is written.  accumulate = 1 combines the row with what `rows` holds: +=, max, +=, += --
+ * `views` then counts the frames in which the Gaussian reached w_min somewhere.  Sums run in a fixed order and without
+ * atomics (a fixed tree over a tile's pixels, then the Gaussian's tiles in ascending row order): two calls give the same bytes,
+ * whatever the workspace held.
+ * Must follow a gs_frame_forward with training=1 on the same workspace, in the stream order a gs_frame_backward would: behind
+ * that forward, in front of the next forward of the workspace.  It writes nothing a later gs_frame_backward / _part / _adam*
+ * of the frame reads, except a bucket work list identical to the one that backward builds: their outputs are the bits they
+ * are without this call.
+ * workspace: 256-byte aligned, gs_frame_contrib_workspace_bytes(f->max_pairs) (16 bytes per pair; monotone in max_pairs).
+ * Refused before anything is enqueued (GS_E_INVALID, gs_last_error): a frame that is not a training frame, rows NULL with
+ * N > 0 or not 16-byte aligned, w_min NaN, <= 0 or > 1, accumulate outside {0, 1}, a NULL opts, a misaligned or too-small
+ * workspace; and whatever gs_frame_forward refuses of the description. */
+typedef struct gs_contrib_row { float weight_sum, weight_max; uint32_t pixels, views; } gs_contrib_row;
+typedef struct gs_contrib_opts { float w_min; int32_t accumulate; } gs_contrib_opts;
+size_t gs_frame_contrib_workspace_bytes(int64_t max_pairs);
+int gs_frame_contrib(const gs_frame *f, const gs_contrib_opts *opts, gs_contrib_row *rows /* [N] device */,
+                     void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* gs_prune_classify with the contribution rule joined to it: a row is kept iff gs_prune_classify would keep it AND
+ * rows[i].weight_max >= weight_max_min AND rows[i].pixels >= pixels_min AND rows[i].views >= views_min (a NaN weight_max: not
+ * kept).  The workspace and counts_dev are written in exactly gs_prune_classify's format: gs_prune_apply follows unchanged,
+ * and copts = {0.f, 0, 0} decides what gs_prune_classify decides.  Refusals: gs_prune_classify's, a NULL rows (with N > 0)
+ * or copts, a NaN or negative weight_max_min. */
+typedef struct gs_prune_contrib_opts { float weight_max_min; uint32_t pixels_min, views_min; } gs_prune_contrib_opts;
+int gs_prune_classify_contrib(const float *scale, const float *opa, const gs_contrib_row *rows, int64_t N,
+                              const gs_prune_opts *opts, const gs_prune_contrib_opts *copts, int64_t *counts_dev,
+                              void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

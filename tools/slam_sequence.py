@@ -5,7 +5,11 @@ colour loss on each keyframe, right after its seeding and at the end of the run,
 
     python tools/slam_sequence.py [--frames 12] [--width 320 --height 240] [--gaussians 40000] [--step-deg 0.5 --step 0.02]
                                   [--map-iterations 120] [--overlap-min 0.9] [--carry-optimizer] [--prune-every K]
-                                  [--prune-opa-min 0.005] [--prune-scale-max S]
+                                  [--prune-opa-min 0.005] [--prune-scale-max S] [--prune-unseen-every K]
+                                  [--prune-unseen-w-min 0.00392] [--count-unseen]
+
+``--count-unseen`` also reports, behind every keyframe's mapping steps (and prunes), how many Gaussians reach the weight
+``--prune-unseen-w-min`` in no keyframe (``Trainer.contributions``: it renders every keyframe and leaves the fit alone).
 """
 import argparse
 import copy
@@ -42,6 +46,9 @@ def parser():
     ap.add_argument("--prune-every", type=int, default=0)
     ap.add_argument("--prune-opa-min", type=float, default=SlamOptions().prune_opa_min)
     ap.add_argument("--prune-scale-max", type=float, default=None)
+    ap.add_argument("--prune-unseen-every", type=int, default=0)
+    ap.add_argument("--prune-unseen-w-min", type=float, default=SlamOptions().prune_unseen_w_min)
+    ap.add_argument("--count-unseen", action="store_true")
     return ap
 
 
@@ -75,12 +82,14 @@ def run(a):
 
     opts = SlamOptions(keyframe_every=a.keyframe_every, overlap_min=a.overlap_min, map_iterations=a.map_iterations,
                        carry_optimizer=a.carry_optimizer, prune_every=a.prune_every, prune_opa_min=a.prune_opa_min,
-                       prune_scale_max=a.prune_scale_max)
+                       prune_scale_max=a.prune_scale_max, prune_unseen_every=a.prune_unseen_every,
+                       prune_unseen_w_min=a.prune_unseen_w_min)
     slam = Slam(posed(*poses[0]), opts, dev)
     print(f"slam sequence: {a.gaussians} truth Gaussians, {W} x {H}, {a.frames} frames, {a.step_deg} degrees and {a.step} per "
           f"frame, keyframe_every {a.keyframe_every}, overlap_min {a.overlap_min}, map_iterations {a.map_iterations}, "
           f"carry_optimizer {a.carry_optimizer}, prune_every {a.prune_every} (opa_min {a.prune_opa_min}, scale_max "
-          f"{a.prune_scale_max}), defaults otherwise")
+          f"{a.prune_scale_max}), prune_unseen_every {a.prune_unseen_every} (w_min {a.prune_unseen_w_min:.5f}), defaults "
+          f"otherwise")
     ev = FrameRenderer(dev, max_pairs=1 << 21, training=False, auto_grow=True)
     probe = ImageLoss(H, W, slam.opt.train.ssim_weight, dev)
 
@@ -99,9 +108,15 @@ def run(a):
         fr = slam.map(fr)
         e = err(fr.rot, fr.tran, R, t)
         worst = [max(worst[0], e[0]), max(worst[1], e[1])]
-        ms = ", ".join(f"{k} {1e3 * fr.seconds[k]:.1f}" for k in ("track", "overlap", "seed", "map", "prune") if k in fr.seconds)
+        ms = ", ".join(f"{k} {1e3 * fr.seconds[k]:.1f}" for k in ("track", "overlap", "seed", "map", "prune", "prune_unseen")
+                       if k in fr.seconds)
+        unseen = ""
+        if a.count_unseen and fr.keyframe:
+            c = slam.trainer.contributions(w_min=a.prune_unseen_w_min)
+            unseen = f" unseen by every keyframe {int((c.views == 0).sum())}"
         print(f"  frame {f}: rotation error {e[0]:.3e} translation error {e[1]:.3e} keyframe {fr.keyframe} window {fr.window} "
-              f"added {fr.added} pruned {fr.pruned} Gaussians {slam.trainer.n_gaussians}; ms: {ms}")
+              f"added {fr.added} pruned {fr.pruned} pruned_unseen {fr.pruned_unseen} Gaussians {slam.trainer.n_gaussians}"
+              f"{unseen}; ms: {ms}")
     final = [colour_loss(k) for k in range(len(slam.keyframes))]
     for k, (s0, s1) in enumerate(zip(seeded, final)):
         print(f"  keyframe {k}: colour loss {s0:.5f} seeded -> {s1:.5f} at the end ({'below' if s1 < s0 else 'ABOVE'})")

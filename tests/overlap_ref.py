@@ -3,7 +3,9 @@
 ``counts_f32``: the contract in float32, operation by operation, one rounding each -- it must decide every point exactly as
 the kernel does.  ``counts_f64``: the same geometry in float64 from the same float32 inputs, with a per-view mask of the
 points float32 cannot be expected to decide: a border inequality within a relative 1e-5 of |q.z| W_k of flipping, or q.z
-within a relative 1e-5 of ``near``.  ``cases()`` builds the inputs: the smallest shapes at which the kernel can go wrong."""
+within a relative 1e-5 of ``near``.  ``cases()`` builds the inputs: the smallest shapes at which the kernel can go wrong.
+``plan`` restates the launch plan; ``LONG_CASES``, ``GROUP_EDGE_CASES`` and ``band_case`` are the inputs beyond its thresholds
+(tests/test_gpu_slam_regimes.py)."""
 import math
 from types import SimpleNamespace
 
@@ -146,14 +148,75 @@ def range_map(H, W, seed):
     return z
 
 
+BAND_ROWS = (51, 200, 201, 400, 401, 402, -1)  # lattice rows (-1: the last one, which the ragged last chunk ends)
+
+
+def range_map_bands(H, W, stride, seed):
+    """range_map with whole lattice rows unmeasured -- 0, NaN, -1 and inf cycling along the row -- in bands of one, two and
+    three rows and in the last row: runs of more than 256 lattice pixels in a row without a measurement, which the scattered
+    10 % of range_map never give.  (A row of every LONG_SHAPES lattice is at least 724 pixels long.)"""
+    z = range_map(H, W, seed)
+    off = stride // 2
+    rows = np.arange(off, H, stride)
+    blank = np.array([0.0, np.nan, -1.0, np.inf], F)[np.arange(W) % 4]
+    for ly in BAND_ROWS:
+        z[rows[ly]] = np.roll(blank, ly)
+    return z
+
+
+def skip_situations(z, stride):
+    """-> three arrays of workgroup numbers under plan(): first chunk blank and a later one measured; first chunk measured
+    and a later (existing) one blank; every chunk blank."""
+    _, chunks, per, nblk = plan(z.shape[0], z.shape[1], stride)
+    m = chunk_measured(z, stride)
+    assert len(m) == chunks
+    exists = (np.arange(nblk * per) < chunks).reshape(nblk, per)
+    m = np.concatenate([m, np.zeros(nblk * per - chunks, bool)]).reshape(nblk, per)
+    return (np.flatnonzero(~m[:, 0] & m[:, 1:].any(1)), np.flatnonzero(m[:, 0] & (~m[:, 1:] & exists[:, 1:]).any(1)),
+            np.flatnonzero(~m.any(1)))
+
+
+def chunk_measured(z, stride):
+    """bool [chunks]: does chunk c -- lattice pixels [256 c, 256 c + 256) in row-major order -- hold a measurement?"""
+    z = np.asarray(z, F)
+    ys, xs = lattice(z.shape[0], z.shape[1], stride)
+    r = z[ys, xs]
+    with np.errstate(invalid="ignore"):
+        m = (r > F(0)) & (r <= np.finfo(F).max)
+    pad = -len(m) % OVL_BLOCK
+    return np.concatenate([m, np.zeros(pad, bool)]).reshape(-1, OVL_BLOCK).any(1)
+
+
 SHAPES = ((37, 53, 1), (120, 160, 2), (64, 64, 3))  # (37, 53): padded 48 x 64, crop left = top = 5, 1,961 lattice pixels
 N_VIEWS = (1, 3, 65, 256)
 NEAR = 0.3
 SPECIAL = ("own", "behind", "other size and focal", "sideways", "yawed", "forward")
 # seeds of the random views, chosen on the CPU so that no view has more undecidable points than 0.1 % of the measured ones
 # (tests/test_overlap_host.py asserts it): with 394 measured points that means none at all
-VIEW_SEEDS = {(64, 65): 1, (64, 256): 80}
+VIEW_SEEDS = {(64, 65): 1, (64, 256): 80, (37, 128): 2, (37, 192): 1, (37, 193): 2}
 _CACHE = {}
+
+# csrc/overlap.hip: `constexpr int OVL_BLOCK = 256` lattice pixels to a chunk, `constexpr int OVL_MAX_BLOCKS = 2048` workgroups
+OVL_BLOCK, OVL_MAX_BLOCKS = 256, 2048
+# The smallest shapes whose workgroups run over more than one chunk (plan(); tests/test_gpu_slam_regimes.py):
+#   (725, 724, 1)  : 524,900 lattice pixels, 2,051 chunks, 2 per workgroup, 1,026 workgroups; the last one holds one ragged chunk
+#   (1449, 1450, 2): the same plan through a stride-2 lattice with offset 1
+#   (1025, 1024, 1): 4,100 chunks, 3 per workgroup, 1,367 workgroups; the last one holds two of its three
+LONG_SHAPES = ((725, 724, 1), (1449, 1450, 2), (1025, 1024, 1))
+LONG_CASES = tuple((H, W, s, 7) for H, W, s in LONG_SHAPES) + ((725, 724, 1, 65),)
+# the edges of the kernel's view groups (`kend = min(64, n_views - 64 * g)`), on the smallest shape
+GROUP_EDGE_CASES = tuple((37, 53, 1, n) for n in (64, 128, 129, 192, 193))
+
+
+def plan(H, W, stride):
+    """-> (L, chunks, chunks_per_block, nblk): overlap_plan of csrc/overlap.hip, restated."""
+    off = stride // 2
+    Lw = (W - off + stride - 1) // stride if W > off else 0
+    Lh = (H - off + stride - 1) // stride if H > off else 0
+    L = Lw * Lh
+    chunks = -(-L // OVL_BLOCK)
+    per = -(-chunks // OVL_MAX_BLOCKS) if chunks > OVL_MAX_BLOCKS else 1
+    return L, chunks, per, -(-chunks // per)
 
 
 def case(H, W, stride, n_views):
@@ -179,6 +242,29 @@ def case(H, W, stride, n_views):
 
 def cases():
     return [(H, W, s, n) for H, W, s in SHAPES for n in N_VIEWS]
+
+
+def band_case(H, W, stride, n_views):
+    """case() with the range map of range_map_bands (the same seed): computed once, never modified."""
+    key = (H, W, stride, n_views, "bands")
+    if key not in _CACHE:
+        _CACHE[key] = dict(case(H, W, stride, n_views), z=range_map_bands(H, W, stride, seed=H + W + stride))
+    return _CACHE[key]
+
+
+_REFERENCE = {}
+
+
+def reference(H, W, stride, n_views, border):
+    """-> dict(c32, c64, und_per_view, und_any) of case(H, W, stride, n_views): both restatements, evaluated once per process
+    (seconds each at LONG_SHAPES) and shared by the tests that need them."""
+    key = (H, W, stride, n_views, border)
+    if key not in _REFERENCE:
+        k = case(H, W, stride, n_views)
+        c64, und = counts_f64(k["z"], k["cam"], k["views"], stride, k["near"], border)
+        _REFERENCE[key] = dict(c32=counts_f32(k["z"], k["cam"], k["views"], stride, k["near"], border), c64=c64,
+                               und_per_view=und.sum(1), und_any=int(und.any(0).sum()))
+    return _REFERENCE[key]
 
 
 def table_rows(views):

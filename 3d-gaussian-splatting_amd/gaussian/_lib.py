@@ -269,6 +269,17 @@ gs_frame_contrib = _sig("gs_frame_contrib", ci, C.POINTER(GsFrame), C.POINTER(Gs
 gs_prune_classify_contrib = _sig("gs_prune_classify_contrib", ci, vp, vp, vp, i64, C.POINTER(GsPruneOpts),
                                  C.POINTER(GsPruneContribOpts), vp, vp, sz, vp)
 
+GS_PYRAMID_MAX_LEVELS = 4
+
+
+class GsPyramidOpts(C.Structure):
+    """Mirror of ``struct gs_pyramid_opts``."""
+
+    _fields_ = [("min_valid", i32), ("edge_rel", f32)]
+
+
+gs_pyramid_down = _sig("gs_pyramid_down", ci, vp, vp, i32, i32, C.POINTER(GsPyramidOpts), vp, vp, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -291,6 +302,7 @@ EXPORTS = [
     "gs_prune_workspace_bytes", "gs_prune_classify", "gs_prune_apply",
     "gs_seed_apply_pp", "gs_view_overlap_pp",
     "gs_frame_contrib_workspace_bytes", "gs_frame_contrib", "gs_prune_classify_contrib",
+    "gs_pyramid_down",
 ]
 
 

@@ -51,6 +51,9 @@ SOURCES = {
     "map_edit.hip": ["-ffp-contract=off"],
     # the row step of raster_bwd.hip's row-layout kernel, built like it (no SLP packing, as above)
     "contrib.hip": ["-fno-slp-vectorize"],
+    # the box sum, s / n and the edge test hi <= fl(fl(1 + edge_rel) lo) as written, one rounding per operation: the float32
+    # restatement (tests/pyramid_ref.py) gives the level targets bit for bit
+    "pyramid.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

@@ -14,6 +14,11 @@ The colour part of the backward (GS_BWD_COLOR: opacity and colour gradients) is 
 dL/dtran and the four loss values are views of one 16-float device buffer that a single copy brings into pinned host memory.
 The pose step runs on the host in float64: rot = exp([w]x) R re-linearised at w = 0 every iteration, Adam on (w, tran),
 R <- exp([dw]x) R -- rot stays on SO(3) by construction.  The map's parameters are never written.
+
+Coarse to fine: ``TrackOptions.pyramid`` = ((level, iterations), ...) walks pyramid levels in order (gs_pyramid: the targets of
+level l are gs_pyramid_down applied l times, its camera the frame's with size, focal lengths and principal point / 2^l), one
+renderer and one loss object per scheduled level, ONE PoseAdam for the whole call.  With the default () nothing of this exists
+and every call is the call described above.
 """
 from __future__ import annotations
 
@@ -27,6 +32,7 @@ import torch
 
 from gaussian import _lib
 from gs_frame import FrameRenderer
+from gs_pyramid import MAX_LEVELS, Pyramid, level_camera
 from gs_train import GatedTrackLoss, TrackLoss
 
 
@@ -45,6 +51,9 @@ class TrackOptions:
     depth_weight: float = 1.0       # x |D / A - z| / (H W)
     depth_gate: float = 0.0         # <= 0: off; else depth residuals beyond it do not count
     max_pairs: int = 1 << 20        # the renderer's initial pair capacity (it grows by itself)
+    # coarse to fine: stages (pyramid level, iterations) in order, levels strictly decreasing; () (the default): no pyramid,
+    # ``iterations`` full-resolution iterations.  With a schedule ``iterations`` is not read: the total is the stages' sum
+    pyramid: Tuple[Tuple[int, int], ...] = ()
     # the median gate (gs_loss_track_gated): a k <= 0 leaves that term ungated; both <= 0 (the default) is gs_loss_track
     depth_gate_k: float = 0.0       # depth counts where |r| <= max(k x median |r|, depth_gate_floor); excludes depth_gate
     color_gate_k: float = 0.0       # colour counts where sum_c |I_c - T_c| <= max(k x its median, color_gate_floor)
@@ -59,6 +68,23 @@ class TrackOptions:
                              "the depth term: give one of them")
         return self.depth_gate_k > 0.0 or self.color_gate_k > 0.0
 
+    def stages(self) -> Tuple[Tuple[int, int], ...]:
+        """``pyramid`` validated, as a tuple of (level, iterations) ints: levels within 0..GS_PYRAMID_MAX_LEVELS and strictly
+        decreasing, iterations >= 1.  () for no schedule."""
+        out = []
+        for stage in self.pyramid:
+            if len(stage) != 2 or any(int(x) != x for x in stage):
+                raise ValueError(f"pyramid holds pairs (level, iterations) of integers, got {stage!r}")
+            level, n = int(stage[0]), int(stage[1])
+            if not 0 <= level <= MAX_LEVELS:
+                raise ValueError(f"pyramid level {level} is outside 0..{MAX_LEVELS} (GS_PYRAMID_MAX_LEVELS)")
+            if out and level >= out[-1][0]:
+                raise ValueError(f"pyramid levels must be strictly decreasing (coarse to fine): {level} follows {out[-1][0]}")
+            if n < 1:
+                raise ValueError(f"pyramid level {level} is scheduled for {n} iterations: at least 1")
+            out.append((level, n))
+        return tuple(out)
+
 
 @dataclass
 class TrackResult:
@@ -70,6 +96,8 @@ class TrackResult:
     # With the median gate on, from the iteration that rendered (rot, tran) -- plain attributes, None with the gate off:
     inliers = None       # (depth pixels that counted, n_d = covered measured pixels, colour pixels that counted)
     medians = None       # (m_d, m_c): the median residuals the thresholds were multiples of
+    # With a schedule (TrackOptions.pyramid): [(level, index of its first iteration in ``losses``, count), ...]; else None
+    levels = None
 
 
 def so3_exp(w) -> np.ndarray:
@@ -185,17 +213,30 @@ class Tracker:
             raise RuntimeError("Tracker needs a HIP device; there is no CPU fallback")
         self.camera = camera
         self.H, self.W = int(camera.height), int(camera.width)
-        self.renderer = FrameRenderer(self.device, max_pairs=int(self.opt.max_pairs), training=True, occlusion_cull=False,
-                                      auto_grow=True)
+        plan = self.level_plan(self.opt, self.H, self.W)
+        self.renderer = self._new_renderer()
         self.device = self.renderer.device
         cls, args, nfloat = self.loss_plan(self.opt, self.H, self.W)
-        self.loss = cls(*args, self.device)
         # grad_rot [0:9], grad_tran [9:12], (loss, colour term, depth term, depth pixels) [12:16] and, with the median gate,
         # (colour pixels, m_d, m_c, n_d) [16:20]: one read per iteration
         self._dev = torch.zeros(nfloat, dtype=torch.float32, device=self.device)
         self._grad_pose = (self._dev[0:9].view(3, 3), self._dev[9:12])
         self._values = self._dev[12:nfloat]
         self._host = torch.zeros(nfloat, dtype=torch.float32).pin_memory()
+        if plan is None:  # no schedule: one renderer, one loss, no Pyramid
+            self.loss = cls(*args, self.device)
+            self._stages = self._levels = self._pyramid = None
+        else:
+            # per scheduled level (renderer, loss, camera, scale): a renderer and a loss object of its own, the level camera,
+            # scale = 1 / (H_l W_l) so that every level's loss is a mean; the two buffers above are shared
+            self._stages = self.opt.stages()
+            self._levels = {}
+            for level, h, w in plan:
+                r = self.renderer if not self._levels else self._new_renderer()
+                lcls, largs, _ = self.loss_plan(self.opt, h, w)
+                self._levels[level] = (r, lcls(*largs, self.device), level_camera(camera, level), 1.0 / (h * w))
+            self.renderer, self.loss = self._levels[plan[-1][0]][:2]  # the finest scheduled level's
+            self._pyramid = Pyramid(self.H, self.W, plan[0][0], self.device)
         self._scratch = None
         self.set_map(params)
         self.reset()
@@ -208,6 +249,23 @@ class Tracker:
             return TrackLoss, (height, width, o.alpha_min, o.color_weight, o.depth_weight, o.depth_gate), 16
         return GatedTrackLoss, (height, width, o.alpha_min, o.color_weight, o.depth_weight, o.depth_gate_k, o.color_gate_k,
                                 o.depth_gate_floor, o.color_gate_floor, o.gate_couple), 20
+
+    @staticmethod
+    def level_plan(o: TrackOptions, height: int, width: int):
+        """[(level, H_l, W_l)] of the stages of ``o.pyramid`` in order, None without a schedule -- no device needed.  Refuses
+        what ``TrackOptions.stages`` refuses and a frame size the deepest scheduled level does not divide."""
+        stages = o.stages()
+        if not stages:
+            return None
+        deepest = stages[0][0]
+        if height % (1 << deepest) or width % (1 << deepest):
+            raise ValueError(f"a {width} x {height} frame cannot be tracked at pyramid level {deepest}: 2^{deepest} = "
+                             f"{1 << deepest} does not divide its size")
+        return [(level, height >> level, width >> level) for level, _ in stages]
+
+    def _new_renderer(self):
+        return FrameRenderer(self.device, max_pairs=int(self.opt.max_pairs), training=True, occlusion_cull=False,
+                             auto_grow=True)
 
     @staticmethod
     def _check_map(params):
@@ -251,17 +309,26 @@ class Tracker:
         return (np.asarray(self.camera.rot, np.float64).reshape(3, 3).copy(),
                 np.asarray(self.camera.tran, np.float64).reshape(3).copy())
 
-    def iteration(self, rot, tran, image, range_map=None):
+    def iteration(self, rot, tran, image, range_map=None, level=0):
         """One forward / loss / pose backward at the pose (rot, tran); the 16 floats land in ``self._host`` (pinned):
         dL/drot [0:9], dL/dtran [9:12], (loss, colour term, depth term, depth pixels) [12:16]; with the median gate 20 floats,
-        [16:20] = (colour pixels, m_d, m_c, n_d).  Returns that buffer."""
-        cam = copy.copy(self.camera)
+        [16:20] = (colour pixels, m_d, m_c, n_d).  Returns that buffer.  ``level``: a scheduled level of ``TrackOptions.pyramid``
+        -- ``image`` / ``range_map`` are then that level's targets (gs_pyramid.Pyramid.build), rendered through the level camera;
+        without a schedule only level 0 exists."""
+        if self._levels is None:
+            if level != 0:
+                raise ValueError(f"level {level}: this Tracker has no schedule (TrackOptions.pyramid), only level 0")
+            r, loss, camera, scale = self.renderer, self.loss, self.camera, 1.0 / (self.H * self.W)
+        elif level in self._levels:
+            r, loss, camera, scale = self._levels[level]
+        else:
+            raise ValueError(f"level {level} is not in this Tracker's schedule {self._stages}")
+        cam = copy.copy(camera)
         cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
         cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
-        r = self.renderer
         img, _, depth, alpha = r.forward(*self.params, cam, training=True, aux=True)
         with torch.cuda.device(self.device):
-            gi, gd, ga = self.loss(img, depth, alpha, image, range_map, 1.0 / (self.H * self.W), values=self._values)
+            gi, gd, ga = loss(img, depth, alpha, image, range_map, scale, values=self._values)
         r.backward(gi, out=self._scratch, part=_lib.GS_BWD_RASTER, grad_depth=gd, grad_alpha=ga)
         r.backward(None, out=self._scratch, part=_lib.GS_BWD_GEOMETRY, grad_pose=self._grad_pose)
         self._host.copy_(self._dev)  # (device -> pinned host: returns when the 64 -- gated: 80 -- bytes have landed)
@@ -275,17 +342,38 @@ class Tracker:
         adam = PoseAdam(R, t, o.lr_rot, o.lr_tran, o.betas, o.eps)  # Adam's moments on (w, tran): kept across iterations, reset per call
         best = (math.inf, R, t, None)
         losses: List[float] = []
-        for k in range(int(o.iterations)):
-            h = self.iteration(R, t, image, range_map).numpy().astype(np.float64)
-            loss = float(h[12])
-            losses.append(loss)
-            if loss < best[0]:
-                best = (loss, R, t, h[15:20] if len(h) == 20 else None)
-            R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / o.iterations))
+        levels = None
+        if self._stages is None:
+            for k in range(int(o.iterations)):
+                h = self.iteration(R, t, image, range_map).numpy().astype(np.float64)
+                loss = float(h[12])
+                losses.append(loss)
+                if loss < best[0]:
+                    best = (loss, R, t, h[15:20] if len(h) == 20 else None)
+                R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / o.iterations))
+        else:
+            # coarse to fine: the targets once, then the stages in order under ONE PoseAdam (moments and step count carry
+            # across stages, the rate decays over the whole call); losses of different levels are not comparable, so the
+            # pose returned is the lowest-loss one of the LAST stage
+            images, ranges = self._pyramid.build(image, range_map)
+            total = sum(n for _, n in self._stages)
+            levels, k = [], 0
+            for level, n in self._stages:
+                levels.append((level, k, n))
+                last = level == self._stages[-1][0]
+                for _ in range(n):
+                    h = self.iteration(R, t, images[level], ranges[level], level).numpy().astype(np.float64)
+                    loss = float(h[12])
+                    losses.append(loss)
+                    if last and loss < best[0]:
+                        best = (loss, R, t, h[15:20] if len(h) == 20 else None)
+                    R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / total))
+                    k += 1
         loss, R, t, gate = best
         self._history = (self._history + [(R, t)])[-2:]
         res = TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)
         if gate is not None:  # (depth pixels, colour pixels, m_d, m_c, n_d) of the returned pose's iteration
             res.inliers = (int(gate[0]), int(gate[4]), int(gate[1]))
             res.medians = (float(gate[2]), float(gate[3]))
+        res.levels = levels
         return res

@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_PRINCIPAL_POINT with
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_pyramid_down with
+ *   gs_pyramid_opts / GS_PYRAMID_MAX_LEVELS (one level down of an image pyramid -- box-filtered colour and a measurement-aware
+ *   range map -- in one launch: the level targets of coarse-to-fine camera tracking).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_PRINCIPAL_POINT with
  *   gs_frame_pp -- a gs_frame_scene followed by pp_dx / pp_dy, the principal point's offset in pixels from the renderer's centre,
  *   read only when the flag is set; gs_frame and gs_frame_scene are unchanged --, honoured by every gs_frame_* entry point;
  *   gs_seed_camera_pp (a gs_seed_camera followed by the same two offsets; gs_seed_camera stays 64 bytes) with gs_seed_apply_pp
@@ -839,6 +842,35 @@ int gs_loss_track_gated(const float *image, const float *depth, const float *alp
                         float color_gate_floor, int32_t couple, float scale, float *grad_image, float *grad_depth,
                         float *grad_alpha, float *values_out, float *resid_depth, float *resid_color, void *workspace,
                         size_t workspace_bytes, gs_stream_t stream);
+
+/* One level down of an image pyramid: the targets of coarse-to-fine camera tracking (csrc/pyramid.hip).  image [H,W,3] and
+ * range [H,W] (NULL: RGB only; range_out must then be NULL too) give image_out [H/2,W/2,3] and range_out [H/2,W/2]; H and W
+ * are even.  Coarse pixel (i, j) covers the fine pixels (2i..2i+1, 2j..2j+1), named 00, 01, 10, 11 in row-major order.  Per
+ * coarse pixel, in fp32 with one rounding per operation:
+ *   colour, per channel: fl(fl(fl(fl(a00 + a01) + a10) + a11) 0.25f).  There is no rule for NaN: it propagates.
+ *   range : a fine pixel is measured iff it is > 0 and finite (the rule of gs_loss_depth and gs_loss_track).  n = the number of
+ *           measured pixels among the four, lo / hi = the minimum / maximum over them.  The coarse pixel is measured iff
+ *           n >= min_valid and (edge_rel < 0 or hi <= fl(fl(1 + edge_rel) lo)); its value is fl(s / (float)n) with
+ *           s = fl(fl(fl(v00 + v01) + v10) + v11), v = the range where measured and +0.0f where not.  An unmeasured coarse
+ *           pixel is written as exactly 0.0f.
+ * The edge test exists because a footprint that straddles a depth discontinuity has no range worth tracking against: dropping
+ * it is the conservative choice.  A coarse pixel's ray passes through the corner its four fine pixels share; the mean of four
+ * ranges along four slightly different rays is a SECOND-ORDER APPROXIMATION of the range along that ray: these targets are
+ * for tracking, not for seeding or mapping.  Level l of a pyramid is this call applied l times (at most
+ * GS_PYRAMID_MAX_LEVELS in gs_pyramid.Pyramid); there is no multi-level entry point.  The camera of level l: width, height,
+ * focal lengths and the principal point in pixels (pixel (i, j) covers [i, i+1) x [j, j+1)) all divided by 2^l -- exact.
+ * One launch: a lane makes four consecutive coarse pixels of one row, 256 lanes per workgroup, one item per lane (no grid
+ * cap); 16-byte accesses when W % 8 == 0, else 4-byte accesses.  No atomics: bitwise repeatable.  No host synchronisation.
+ * GS_E_INVALID -- before anything is enqueued -- for a NULL image, image_out or opts; range and range_out not both NULL or
+ * both given; H or W <= 0 or odd; any pointer not 16-byte aligned; min_valid outside 1..4; a NaN edge_rel; an output that
+ * overlaps an input; an image of 2^31 or more groups of four coarse pixels. */
+#define GS_PYRAMID_MAX_LEVELS 4
+typedef struct gs_pyramid_opts {
+    int32_t min_valid; /* 1..4: a coarse range pixel needs this many measured fine pixels */
+    float edge_rel;    /* < 0: off; else a footprint counts only where hi <= (1 + edge_rel) lo */
+} gs_pyramid_opts;
+int gs_pyramid_down(const float *image, const float *range, int32_t H, int32_t W, const gs_pyramid_opts *opts,
+                    float *image_out, float *range_out, gs_stream_t stream);
 
 /* ---- densification: Gaussian3ds.adaptive_control (splatter.py:122-228) ----
  * Two calls because the number of split Gaussians decides how many standard-normal draws the split

@@ -14,11 +14,17 @@ the 2.4 M scene (rgb colours), each against what the tree offered before:
              the ungated pair, and ms per Tracker iteration with the gate on against the gate off -- the ungated side is the
              code of the legs above, unchanged by the gate, and is the baseline.
 
+  pyramid    coarse to fine (gs_pyramid_down, TrackOptions.pyramid): us per gs_pyramid_down beside the bytes it moves; ms per
+             Tracker iteration at pyramid levels 0 / 1 / 2; ms per track() under the schedule ((2, 100), (1, 100), (0, 100))
+             against 300 level-0 iterations, interleaved in one process; and -- once, whatever --cases says -- on the
+             160 x 120 scene of tests/test_gpu_track.py the final pose errors from starts 0.5 deg / 0.02, 1 / 0.04, 2 / 0.08
+             and 4 / 0.16 off, with and without the schedule.
+
 Protocol of tools/rgbd_step_cost.py: warm-up, then blocks of K calls, the two sides interleaved in rounds in one process;
 medians with the spread of the blocks.  The loss blocks are bracketed by device events; an iteration synchronises with the
 host on both sides, so those blocks are timed by the host clock around work that ends in a synchronise.
 
-    python tools/track_cost.py [--calls 200] [--iters 60] [--rounds 5] [--legs loss,iteration,gate]
+    python tools/track_cost.py [--calls 200] [--iters 60] [--rounds 5] [--legs loss,iteration,gate,pyramid]
 """
 import argparse
 import json
@@ -119,6 +125,108 @@ def gate_leg(args, name, dev, params, cam, maps, targets, start, H, W):
     report_gate(name, "gate_iteration", "ms", times)
 
 
+PYRAMID_SCHEDULE = ((2, 100), (1, 100), (0, 100))
+
+
+def report_sides(case, what, unit, times, extra=None):
+    for k, v in times.items():
+        row = {"case": case, "what": what, "variant": k, f"{unit}_median": round(statistics.median(v), 3),
+               f"{unit}_min": round(min(v), 3), f"{unit}_max": round(max(v), 3), "blocks": len(v)}
+        row.update((extra or {}).get(k, {}))
+        print(json.dumps(row), flush=True)
+
+
+def pyramid_leg(args, name, dev, params, cam, targets, start, H, W):
+    """gs_pyramid_down alone (device events), one Tracker iteration per level and a whole track() with and without the
+    schedule (host clock around work that ends in a synchronise), the sides interleaved in rounds."""
+    from gs_pyramid import Pyramid
+
+    tgt_img, tgt_rng = targets
+    R0, t0 = start
+    pyr = Pyramid(H, W, 2, dev)
+    one = Pyramid(H, W, 1, dev)
+    images, ranges = pyr.build(tgt_img, tgt_rng)
+    rgb = Pyramid(H, W, 1, dev)
+    sides = {"rgbd": lambda: one.build(tgt_img, tgt_rng), "rgb_only": lambda: rgb.build(tgt_img)}
+    for f in sides.values():
+        for _ in range(args.warmup):
+            f()
+    times = {k: [] for k in sides}
+    for _ in range(args.rounds):
+        for k, f in sides.items():
+            times[k].append(events_us(f, args.calls))
+    report_sides(name, "pyramid_down", "us", times,  # 16 bytes in and 4 out per fine pixel; RGB only 12 and 3
+                 {"rgbd": {"bytes": H * W * 20}, "rgb_only": {"bytes": H * W * 15}})
+    tr = Tracker(params, cam, TrackOptions(max_pairs=1 << 22, pyramid=((2, 1), (1, 1), (0, 1))), dev)
+    its = {f"level{l}": (lambda l=l: tr.iteration(R0, t0, images[l], ranges[l], level=l)) for l in (0, 1, 2)}
+    for f in its.values():
+        for _ in range(args.warmup):
+            f()
+    times = {k: [] for k in its}
+    for _ in range(args.rounds):
+        for k, f in its.items():
+            torch.cuda.synchronize()
+            t_ = time.perf_counter()
+            for _ in range(args.iters):
+                f()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t_) * 1e3 / args.iters)
+    report_sides(name, "pyramid_iteration", "ms", times)
+    del tr
+    trackers = {"schedule": Tracker(params, cam, TrackOptions(max_pairs=1 << 22, pyramid=PYRAMID_SCHEDULE), dev),
+                "level0_x300": Tracker(params, cam, TrackOptions(max_pairs=1 << 22, iterations=300), dev)}
+    for tr in trackers.values():
+        tr.track(tgt_img, tgt_rng, init=(R0, t0))
+    times = {k: [] for k in trackers}
+    for _ in range(args.rounds):
+        for k, tr in trackers.items():
+            torch.cuda.synchronize()
+            t_ = time.perf_counter()
+            tr.track(tgt_img, tgt_rng, init=(R0, t0))
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t_) * 1e3)
+    report_sides(name, "pyramid_track", "ms", times)
+    a, b = (statistics.median(times[k]) for k in ("schedule", "level0_x300"))
+    print(json.dumps({"case": name, "what": "pyramid_track", "schedule": list(PYRAMID_SCHEDULE),
+                      "schedule_over_level0_x300": round(a / b, 4)}), flush=True)
+
+
+def pyramid_basin(dev):
+    """The 160 x 120 scene of tests/test_gpu_track.py (make_scene(20,000, seed 103), yaw 2 degrees, tran (0.03, -0.01, 0.2)),
+    targets rendered from the true pose, with depth: final pose errors from four starts, with and without the schedule."""
+    W, H = 160, 120
+    scene = make_scene(20_000, W, H, seed=103)
+    cam = make_camera(W, H, yaw_deg=2.0)
+    cam.tran = np.array([0.03, -0.01, 0.2], np.float32)
+    params = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (scene.pos, scene.quat, scene.scale, scene.opa,
+                                                                           scene.rgb)]
+    r = FrameRenderer(dev, max_pairs=1 << 19, training=False, occlusion_cull=False, auto_grow=True)
+    img, _, d, a = r.forward(*params, cam, training=False, aux=True)
+    rng_map = torch.where(a > 0.5, d / a.clamp_min(1e-3), torch.zeros_like(d)).contiguous()
+    img = img.contiguous()
+    R_true, t_true = np.asarray(cam.rot, np.float64), np.asarray(cam.tran, np.float64)
+    trackers = {"schedule": Tracker(params, cam, TrackOptions(pyramid=PYRAMID_SCHEDULE), dev),
+                "level0_x300": Tracker(params, cam, TrackOptions(), dev)}
+    g = np.random.default_rng(107)  # (the draws of tests/track_ref.py::perturbed_start)
+    axis = g.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    sh = g.normal(size=3)
+    sh /= np.linalg.norm(sh)
+    for deg, shift in ((0.5, 0.02), (1.0, 0.04), (2.0, 0.08), (4.0, 0.16)):
+        R0, t0 = so3_exp(axis * math.radians(deg)) @ R_true, t_true + sh * shift
+        for k, tr in trackers.items():
+            for depth in (True, False):
+                tr.reset()
+                res = tr.track(img, rng_map if depth else None, init=(R0, t0))
+                e_r = float(np.linalg.norm(res.rot - R_true) / math.sqrt(2.0))
+                e_t = float(np.linalg.norm(res.tran - t_true))
+                print(json.dumps({"case": "test_scene_160x120", "what": "pyramid_basin", "variant": k, "with_depth": depth,
+                                  "start_deg": deg, "start_shift": shift, "start_rot_err": round(math.radians(deg), 6),
+                                  "rot_err": float(f"{e_r:.3e}"), "tran_err": float(f"{e_t:.3e}"),
+                                  "to_a_tenth": bool(e_r <= 0.1 * math.radians(deg) and e_t <= 0.1 * shift),
+                                  "loss": float(f"{res.loss:.4e}")}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
@@ -130,6 +238,8 @@ def main():
     args = ap.parse_args()
     legs = args.legs.split(",")
     dev = torch.device("cuda:0")
+    if "pyramid" in legs:
+        pyramid_basin(dev)
     for name, n, W, H in CASES:
         if name not in args.cases.split(","):
             continue
@@ -167,6 +277,8 @@ def main():
 
         if "gate" in legs:
             gate_leg(args, name, dev, params, cam, (img, d, a), (tgt_img, tgt_rng), (R0, t0), H, W)
+        if "pyramid" in legs:
+            pyramid_leg(args, name, dev, params, cam, (tgt_img, tgt_rng), (R0, t0), H, W)
         if "loss" not in legs and "iteration" not in legs:
             del r, params, tl
             torch.cuda.empty_cache()

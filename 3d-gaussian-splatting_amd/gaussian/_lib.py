@@ -280,6 +280,36 @@ class GsPyramidOpts(C.Structure):
 
 gs_pyramid_down = _sig("gs_pyramid_down", ci, vp, vp, i32, i32, C.POINTER(GsPyramidOpts), vp, vp, vp)
 
+GS_ICP_LOG_DOUBLES = 40
+GS_ICP_OK, GS_ICP_TOO_FEW, GS_ICP_NOT_POSITIVE = 0, 1, 2
+
+
+class GsIcpModelOpts(C.Structure):
+    """Mirror of ``struct gs_icp_model_opts``."""
+
+    _fields_ = [("alpha_min", f32), ("edge_rel", f32), ("normal_step", i32)]
+
+
+class GsIcpOpts(C.Structure):
+    """Mirror of ``struct gs_icp_opts``."""
+
+    _fields_ = [("stride", i32), ("dist_max", f32), ("cos_min", f32), ("min_count", i32), ("damping", C.c_double)]
+
+
+class GsIcpState(C.Structure):
+    """Mirror of ``struct gs_icp_state`` (it lives in device memory)."""
+
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("iteration", i32), ("reserved", i32)]
+
+
+gs_icp_model_bytes = _sig("gs_icp_model_bytes", sz, i32, i32)
+gs_icp_workspace_bytes = _sig("gs_icp_workspace_bytes", sz, i32, i32, i32)
+gs_icp_log_bytes = _sig("gs_icp_log_bytes", sz, i32)
+gs_icp_model_maps = _sig("gs_icp_model_maps", ci, vp, vp, C.POINTER(GsSeedCameraPP), C.POINTER(GsIcpModelOpts), vp, vp, vp)
+gs_icp_reset = _sig("gs_icp_reset", ci, vp, vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp)
+gs_icp_step = _sig("gs_icp_step", ci, vp, C.POINTER(GsSeedCameraPP), vp, vp, C.POINTER(GsSeedCameraPP), C.POINTER(GsIcpOpts),
+                   vp, vp, i32, i32, vp, sz, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -303,6 +333,7 @@ EXPORTS = [
     "gs_seed_apply_pp", "gs_view_overlap_pp",
     "gs_frame_contrib_workspace_bytes", "gs_frame_contrib", "gs_prune_classify_contrib",
     "gs_pyramid_down",
+    "gs_icp_model_bytes", "gs_icp_workspace_bytes", "gs_icp_log_bytes", "gs_icp_model_maps", "gs_icp_reset", "gs_icp_step",
 ]
 
 

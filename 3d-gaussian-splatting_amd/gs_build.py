@@ -54,13 +54,16 @@ SOURCES = {
     # the box sum, s / n and the edge test hi <= fl(fl(1 + edge_rel) lo) as written, one rounding per operation: the float32
     # restatement (tests/pyramid_ref.py) gives the level targets bit for bit
     "pyramid.hip": ["-ffp-contract=off"],
+    # the vertices, the normals and the keep / drop tests of icp_point.h as written, one rounding per operation: the float32
+    # restatement (tests/icp_ref.py) gives the maps bit for bit and the counts exactly; no SLP packing, as above
+    "icp.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
 HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
            "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
-           "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h",
+           "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h", "icp_point.h",
            os.path.join("..", "..", "include", "gs_abi.h")]
 
 

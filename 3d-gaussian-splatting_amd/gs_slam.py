@@ -9,7 +9,9 @@ keyframe when the last keyframe sees too few of them or too many frames have pas
 together with the keyframes that share the most points with it.  A frame that is no keyframe leaves the map and the
 optimizer state untouched, bit for bit.
 
-rgb maps only.  By default a keyframe's pose is fixed once set.  With ``SlamOptions.refine_poses`` the mapping steps of a
+rgb maps only.  With ``SlamOptions.icp`` every frame after the first is first aligned to the map's rendered depth by
+point-to-plane ICP (``gs_icp.IcpAligner``) and the tracker starts from the aligned pose where the alignment is accepted.  By
+default a keyframe's pose is fixed once set.  With ``SlamOptions.refine_poses`` the mapping steps of a
 keyframe also refine the poses of its window (``Trainer.free_pose``: the fused step's pose variant,
 gs_frame_backward_adam_pose, delivers the pose gradient of every step, the Tracker's pose optimizer takes it) -- every view of
 the window except keyframe 0, which fixes the gauge; ``KeyframeSet.set_pose`` carries the result into the view table and the
@@ -37,6 +39,7 @@ import torch
 import gs_seed
 from gaussian import _lib
 from gs_geometry import principal_point_offset
+from gs_icp import IcpAligner, IcpOptions, IcpResult
 from gs_track import _SH_REFUSAL, TrackOptions, TrackResult, Tracker
 from gs_train import TrainOptions, Trainer
 
@@ -225,6 +228,12 @@ class SlamOptions:
     # the default and nothing more; what the option did on the eight-frame arc is in profiles/contrib_prune.txt.
     prune_unseen_every: int = 0
     prune_unseen_w_min: float = 1.0 / 255.0
+    # Depth alignment in front of the photometric tracker (None, the default: no aligner exists, no render is issued, the loop
+    # is bit for bit the one without the option).  With ``gs_icp.IcpOptions``: every frame after the first renders the frozen
+    # map's depth once at the pose the tracker would start from, aligns the frame's range map to it by point-to-plane ICP on
+    # the device (gs_icp.IcpAligner: one host read) and, where the result is accepted, starts the tracker from it.  The
+    # photometric iteration count stays ``track.iterations``.  What it did on the eight-frame arc: profiles/icp.txt.
+    icp: Optional[IcpOptions] = None
 
 
 @dataclass
@@ -244,6 +253,7 @@ class SlamFrame:
     refined: Dict[int, Tuple[np.ndarray, np.ndarray]] = field(default_factory=dict)
     pruned: int = 0                  # Gaussians removed behind this keyframe's mapping steps (prune_every)
     pruned_unseen: int = 0           # ... and those removed because no keyframe sees them (prune_unseen_every)
+    icp: Optional[IcpResult] = None  # SlamOptions.icp: the depth alignment in front of this frame's tracking, accepted or not
 
 
 class Slam:
@@ -268,6 +278,14 @@ class Slam:
         self.keyframes = KeyframeSet(device=self.device)
         self.trainer: Optional[Trainer] = None
         self.tracker: Optional[Tracker] = None
+        self.aligner: Optional[IcpAligner] = None
+        self._icp_renderer = None
+        if self.opt.icp is not None:  # (its own inference renderer: the tracker's workspace and counters stay untouched)
+            from gs_frame import FrameRenderer
+
+            self.aligner = IcpAligner(camera, self.opt.icp, self.device)
+            self._icp_renderer = FrameRenderer(self.device, max_pairs=int(self.opt.track.max_pairs), training=False,
+                                               occlusion_cull=False, auto_grow=True)
         self.i_iter = 0          # mapping steps taken so far, over the whole run
         self.n_frames = 0
         self._last_keyframe_at = 0
@@ -331,6 +349,16 @@ class Slam:
             self.tracker.set_map(self.trainer.flat.params)
         return frame
 
+    def _align(self, range_map, init) -> IcpResult:
+        """The depth alignment of ``SlamOptions.icp``: the frozen map's depth and alpha rendered once at the pose the tracker
+        would start from (its constant-velocity prediction, or ``init``), the frame's range map aligned to them.  The map's
+        tensors are read, never written."""
+        cam = self._posed(*self.tracker._start_pose(init))
+        _, _, depth, alpha = self._icp_renderer.forward(*self.tracker.params, cam, training=False, aux=True)
+        # (the model view is the float32 pose that was rendered; the frame starts from the same pose: the identity)
+        self.aligner.set_model(depth.contiguous(), alpha.contiguous(), cam.rot.astype(np.float64), cam.tran.astype(np.float64))
+        return self.aligner.align(range_map)
+
     def _first(self, image, range_map, init) -> SlamFrame:
         o = self.opt
         rot, tran = init if init is not None else (self.camera.rot, self.camera.tran)
@@ -359,6 +387,13 @@ class Slam:
             frame = self._first(image, range_map, init)
             self.n_frames, self._last_keyframe_at = 1, 0
             return frame
+        icp = None
+        if self.aligner is not None:
+            ti = time.perf_counter()
+            icp = self._align(range_map, init)
+            if icp.accepted:
+                init = (icp.rot, icp.tran)
+            ti = time.perf_counter() - ti
         t0 = time.perf_counter()
         res = self.tracker.track(image, range_map, init)
         t1 = time.perf_counter()
@@ -371,6 +406,9 @@ class Slam:
         frame = SlamFrame(rot=res.rot, tran=res.tran, tracked=res, overlap=counts,
                           keyframe=is_keyframe(int(counts[n - 1]), measured, frames_since, o.overlap_min, o.keyframe_every))
         frame.seconds.update(track=t1 - t0, overlap=t2 - t1)
+        if icp is not None:
+            frame.icp = icp
+            frame.seconds["icp"] = ti
         if frame.keyframe and n >= self.keyframes.capacity:  # before the trainer or the frame count is touched
             raise RuntimeError(f"the keyframe set is full ({self.keyframes.capacity} views); there is no eviction")
         index = self.n_frames

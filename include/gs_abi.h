@@ -34,7 +34,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_pyramid_down with
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_icp_model_maps, gs_icp_step and
+ *   gs_icp_reset with gs_icp_model_opts / gs_icp_opts / gs_icp_state and the size queries gs_icp_model_bytes,
+ *   gs_icp_workspace_bytes and gs_icp_log_bytes (frame-to-model point-to-plane ICP of a range map against the map's vertex and
+ *   normal maps: association, normal equations and the 6 x 6 solve on the device, no host read inside the loop).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_pyramid_down with
  *   gs_pyramid_opts / GS_PYRAMID_MAX_LEVELS (one level down of an image pyramid -- box-filtered colour and a measurement-aware
  *   range map -- in one launch: the level targets of coarse-to-fine camera tracking).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_PRINCIPAL_POINT with
@@ -1098,6 +1102,86 @@ typedef struct gs_prune_contrib_opts { float weight_max_min; uint32_t pixels_min
 int gs_prune_classify_contrib(const float *scale, const float *opa, const gs_contrib_row *rows, int64_t N,
                               const gs_prune_opts *opts, const gs_prune_contrib_opts *copts, int64_t *counts_dev,
                               void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- point-to-plane ICP: align an incoming range map to the map's depth, solved on the device ----
+ * The map is rendered ONCE, at the predicted pose (GS_FRAME_AUX: depth D and alpha A); gs_icp_model_maps turns those maps into
+ * a vertex map and a normal map in that camera's frame.  After that an iteration (gs_icp_step) is one pass over the incoming
+ * frame's range map and a 6 x 6 solve: no rendering, no backward, no host read.  The unknown is the rigid motion
+ * p_model = R p_frame + t between the two camera frames, kept in double in a small device state.
+ * Cameras are gs_seed_camera_pp; only the sizes, focal lengths and offsets are read (the maps live in their camera's own frame).
+ * "No measurement" is the rule of gs_view_overlap: a range counts where it is > 0 and finite.
+ * The per-pixel rule, in fp32 with one rounding per operation (division and square root correctly rounded; a float32
+ * restatement computes every vertex, normal and keep / drop decision alike; csrc/icp_point.h is the text, compilable for the
+ * host):
+ *   ray of pixel (x, y):  u = fl(fl(fl((float)(x + left - padW / 2) + 0.5f) - pp_dx) / focal_x),  v likewise  (the ray of
+ *                         gs_seed_apply_pp and gs_view_overlap_pp; offsets (0, 0) give the bits of the centred ray)
+ *   point at range z:     zc = z / sqrt(u u + v v + 1);  p = (u zc, v zc, zc)
+ *   model maps:           rho = D / A where A >= alpha_min, else no measurement (alpha == NULL: rho = D, a plain range map);
+ *                         vertex = point(rho) with w = 1 where rho is measured, else (0, 0, 0, 0);
+ *                         normal = normalize((v[x+s] - v[x-s]) x (v[y+s] - v[y-s])), s = normal_step, negated where n.v > 0,
+ *                         with w = 1 only where the pixel and its four neighbours are inside the image and measured, their
+ *                         largest range hi <= fl(fl(1 + edge_rel) lo) of their smallest (edge_rel < 0: no edge test; the edge
+ *                         rule of gs_pyramid_down: a stencil across a depth edge has no normal) and the cross product's length
+ *                         is > 0 and finite; else (0, 0, 0, 0)
+ *   step, per measured LATTICE pixel (x % stride == stride / 2, y likewise: the lattice of gs_seed):
+ *                         q = R p + t, each row summed left to right, the state rounded to fp32 once;
+ *                         model pixel: f = fl(fl(fl(fx_m fl(q.x / q.z)) + pp_dx_m) - (float)(left_m - padW_m / 2)), i = floor(f)
+ *                         (pixel i covers [i, i + 1): the inverse of the renderer's pixel coordinate), j likewise;
+ *                         kept  <=>  q.z > 0  and  0 <= f < W_m (and y)  and  the normal at (i, j) has w = 1
+ *                                    and  |q - v|^2 <= fl(dist_max dist_max)  and  -(n.v) >= fl(cos_min |v|)
+ *                         e = n.(q - v),  J = (q x n, n)
+ * gs_icp_step, two launches: the first accumulates, over the kept pixels, the 21 upper entries of J J^T (row-major), the 6 of
+ * J e and e e, and counts the kept and the measured lattice pixels -- per thread (one term per chunk of its workgroup's run),
+ * a butterfly per wave, the waves in index order, one 32-float row per workgroup in the workspace; no atomics.  The grid is
+ * capped at 1,024 workgroups of 256: a frame with more than 262,144 lattice pixels gives each workgroup a run of several
+ * chunks.  The second launch is one workgroup: it adds the rows in double in a fixed order, solves
+ *   (A + damping tr(A) / 6 I) x = -b,  A = sum J J^T,  b = sum J e,  x = (x_w, x_t)
+ * by Cholesky in double, applies R <- exp([x_w]x) R, t <- exp([x_w]x) t + x_t, adds one to state.iteration and writes row
+ * `log_row` of the log, GS_ICP_LOG_DOUBLES doubles:
+ *   [0] kept  [1] measured lattice pixels  [2] sum e e  [3..23] A (21 upper entries)  [24..29] b  [30..35] x  [36] status
+ *   [37] damping tr(A) / 6  [38] stride  [39] 0
+ * status GS_ICP_TOO_FEW (kept < min_count) or GS_ICP_NOT_POSITIVE (a pivot that is not positive and finite, or a solution
+ * that is not finite): R and t stay bit for bit, x is written as zeros.  The result is a pure function of the inputs,
+ * whatever the workspace held.  gs_icp_reset writes a state (iteration 0) and zeroes a log of `log_rows` rows, on the stream.
+ * vertex / normal: [H, W] float4 each, gs_icp_model_bytes(H, W) bytes each, 16-byte aligned.  workspace: 16-byte aligned,
+ * gs_icp_workspace_bytes(H, W, stride) of the FRAME's size (monotone in the image, falling with the stride).  log:
+ * gs_icp_log_bytes(rows).  The size queries return 0 for arguments the calls refuse.
+ * Refused before anything is enqueued (GS_E_INVALID, gs_last_error): a null pointer (alpha may be NULL), a non-positive size or
+ * focal length, an offset that is not finite, stride < 1, normal_step < 1, dist_max <= 0 or NaN, a NaN cos_min, alpha_min or
+ * edge_rel, a negative or non-finite damping, a negative min_count, misaligned maps, state or log, a misaligned or too-small
+ * workspace, log_row outside [0, log_rows) -- a full log --, a rot or tran of gs_icp_reset that is not finite. */
+#define GS_ICP_LOG_DOUBLES 40
+#define GS_ICP_OK 0
+#define GS_ICP_TOO_FEW 1
+#define GS_ICP_NOT_POSITIVE 2
+typedef struct gs_icp_model_opts {
+    float alpha_min;     /* the model has a surface where its alpha reaches this                        */
+    float edge_rel;      /* < 0: off; else a normal's stencil counts only where hi <= (1 + edge_rel) lo */
+    int32_t normal_step; /* >= 1: the central difference reaches this many pixels to each side          */
+} gs_icp_model_opts;
+typedef struct gs_icp_opts {
+    int32_t stride;      /* >= 1: the lattice of gs_seed over the incoming frame                        */
+    float dist_max;      /* > 0: a pair counts only within this distance                                */
+    float cos_min;       /* ... and where the model surface faces its own ray at least this much        */
+    int32_t min_count;   /* fewer kept pixels: no step, status GS_ICP_TOO_FEW                           */
+    double damping;      /* >= 0: x the mean diagonal of A, added to the diagonal                       */
+} gs_icp_opts;
+typedef struct gs_icp_state { /* on the DEVICE */
+    double R[9], t[3];   /* p_model = R p_frame + t (row-major)                                         */
+    int32_t iteration;   /* steps taken since gs_icp_reset                                              */
+    int32_t reserved;
+} gs_icp_state;
+size_t gs_icp_model_bytes(int32_t H, int32_t W);
+size_t gs_icp_workspace_bytes(int32_t H, int32_t W, int32_t stride);
+size_t gs_icp_log_bytes(int32_t rows);
+int gs_icp_model_maps(const float *depth, const float *alpha, const gs_seed_camera_pp *cam, const gs_icp_model_opts *opts,
+                      float *vertex, float *normal, gs_stream_t stream);
+int gs_icp_reset(gs_icp_state *state_dev, double *log_dev, int32_t log_rows, const double *rot /* [9] host */,
+                 const double *tran /* [3] host */, gs_stream_t stream);
+int gs_icp_step(const float *range, const gs_seed_camera_pp *cam,           /* the incoming frame            */
+                const float *vertex, const float *normal, const gs_seed_camera_pp *model_cam, /* gs_icp_model_maps' */
+                const gs_icp_opts *opts, gs_icp_state *state_dev, double *log_dev, int32_t log_rows, int32_t log_row,
+                void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -342,3 +342,8 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = gs_last_error()
         raise RuntimeError(f"{what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+
+def call(name: str, *args):
+    """``check`` of the int-returning symbol ``name``, looked up when called: the error names what was called."""
+    check(globals()[name](*args), name)

@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from gaussian import _lib
+from gs_call import check_tensor, require_hip, stream, workspace
 
 SCALE_ACT = {"abs": 0, "exp": 1}
 AGG = {"max": 0, "mean": 1}
@@ -38,22 +39,19 @@ def adaptive_control(params: Sequence[torch.Tensor], grad: torch.Tensor, taus: f
     ``torch.randn`` (tests replay the reference's draws with it)."""
     pos, quat, scale, opa, rgb = params
     n = int(pos.shape[0])
-    dev = pos.device
-    if dev.type != "cuda":
-        raise RuntimeError("adaptive_control needs a HIP device; there is no CPU fallback")
+    dev = require_hip(pos.device, "adaptive_control")
     color_dim = int(rgb.shape[1])
     for name, t, shape in (("pos", pos, (n, 3)), ("quat", quat, (n, 4)), ("scale", scale, (n, 3)), ("opa", opa, (n,)),
                            ("rgb", rgb, (n, color_dim)), ("grad", grad, (n, 3))):
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
-            raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape {shape}")
+        check_tensor(name, t, shape)
     opts = _lib.GsDensifyOpts(float(taus), float(delete_thresh), float(grad_thresh), float(clone_dt),
                               SCALE_ACT[scale_activation], AGG[grad_aggregation], int(bool(use_clone)),
                               int(bool(use_split)), color_dim)
-    stream = torch.cuda.current_stream().cuda_stream
-    ws = torch.empty(int(_lib.gs_densify_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    s = stream()
+    ws = workspace(_lib.gs_densify_workspace_bytes(n), dev)
     counts = torch.zeros(4, dtype=torch.int64, device=dev)
-    _lib.check(_lib.gs_densify_classify(scale.data_ptr(), opa.data_ptr(), grad.data_ptr(), n, C.byref(opts),
-                                        counts.data_ptr(), ws.data_ptr(), ws.numel(), stream), "gs_densify_classify")
+    _lib.call("gs_densify_classify", scale.data_ptr(), opa.data_ptr(), grad.data_ptr(), n, C.byref(opts), counts.data_ptr(),
+              ws.data_ptr(), ws.numel(), s)
     kept, cloned, split, total = (int(v) for v in counts.cpu())  # the one host synchronisation
     if draws is None:  # MultivariateNormal.sample() twice (utils.py:396-401): two [n_split, 3] normal blocks
         draws = tuple(torch.randn(split, 3, device=dev, generator=generator) for _ in range(2))
@@ -61,10 +59,9 @@ def adaptive_control(params: Sequence[torch.Tensor], grad: torch.Tensor, taus: f
     if eps1.shape[0] < split or eps2.shape[0] < split:
         raise RuntimeError(f"need {split} normal draws per block, got {eps1.shape[0]}, {eps2.shape[0]}")
     out = [torch.empty((total,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in params]
-    _lib.check(_lib.gs_densify_apply(pos.data_ptr(), quat.data_ptr(), scale.data_ptr(), opa.data_ptr(), rgb.data_ptr(),
-                                     grad.data_ptr(), n, C.byref(opts), eps1.data_ptr(), eps2.data_ptr(),
-                                     min(int(eps1.shape[0]), int(eps2.shape[0])), *(t.data_ptr() for t in out), total,
-                                     counts.data_ptr(), ws.data_ptr(), ws.numel(), stream), "gs_densify_apply")
+    _lib.call("gs_densify_apply", pos.data_ptr(), quat.data_ptr(), scale.data_ptr(), opa.data_ptr(), rgb.data_ptr(),
+              grad.data_ptr(), n, C.byref(opts), eps1.data_ptr(), eps2.data_ptr(), min(int(eps1.shape[0]), int(eps2.shape[0])),
+              *(t.data_ptr() for t in out), total, counts.data_ptr(), ws.data_ptr(), ws.numel(), s)
     return out, (kept, cloned, split)
 
 

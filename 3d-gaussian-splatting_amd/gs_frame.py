@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from gaussian import _lib
-from gs_geometry import RayBasis, TileGrid, principal_point_offset
+from gs_call import check_tensor, require_hip
+from gs_geometry import RayBasis, TileGrid, pose_ctypes, principal_point_offset
 
 SCALE_ACT = {"abs": 0, "exp": 1}
 TILE_CULLING = {"dist": 0, "prob": 1, "prob2": 2}  # the reference's `_method_config` (splatter.py:571)
@@ -92,9 +93,7 @@ class FrameRenderer:
                  serial_long_lists: bool = False, long_lists: Optional[bool] = None, bwd_rows: Optional[bool] = None,
                  force_strips: Optional[bool] = None, occlusion_cull: Optional[bool] = None,
                  scene_pack: Optional[bool] = None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("FrameRenderer needs a HIP device; there is no CPU fallback")
+        self.device = require_hip(device, "FrameRenderer")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if tile_culling_method not in TILE_CULLING:
@@ -179,7 +178,7 @@ class FrameRenderer:
         # opt-in side stream of the library (include/gs_abi.h, gs_frame_async_*): owned by this renderer
         self._async = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.gs_frame_async_create(C.byref(self._async)), "gs_frame_async_create")
+            _lib.call("gs_frame_async_create", C.byref(self._async))
         self._checked_once = False  # auto_grow="async": the first frame is checked synchronously
         self.overflowed_frames = 0  # frames that were rendered empty / truncated and could not be redone (see forward)
 
@@ -237,8 +236,7 @@ class FrameRenderer:
             raise RuntimeError(f"rgb must be [N,3], [N,27] or [N,48], got {tuple(rgb.shape)}")
         for name, t, cols in (("pos", pos, 3), ("quat", quat, 4), ("scale", scale, 3), ("opa", opa, None),
                               ("rgb", rgb, color_dim)):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor")
+            check_tensor(name, t)
             if t.shape[0] != n or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
                 raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected [{n},{cols}]")
         # per-camera constants (tile grid, frustum guard band, ray basis) are cached: a viewer or a
@@ -261,8 +259,7 @@ class FrameRenderer:
                 zero3 = np.zeros(3, np.float32)
                 rays = RayBasis(zero3, zero3, zero3, zero3)
             c = _lib.GsFramePP()
-            c.rot = (C.c_float * 9)(*np.asarray(camera.rot, np.float32).reshape(9))
-            c.tran = (C.c_float * 3)(*np.asarray(camera.tran, np.float32).reshape(3))
+            c.rot, c.tran = pose_ctypes(camera)
             c.near_plane, c.half_width, c.half_height = float(camera.near), half_w, half_h
             c.width, c.height = grid.width, grid.height
             c.focal_x, c.focal_y = grid.focal_x, grid.focal_y
@@ -845,8 +842,8 @@ class FrameRenderer:
             f = self._pose_frame(f, grad_pose, 0)  # (refuses SH colours)
         name = "gs_frame_backward_adam" + ("_pose" if grad_pose is not None else "_aux" if aux else "")
         with torch.cuda.device(self.device):
-            _lib.check(getattr(_lib, name)(C.byref(f), grad_image.data_ptr() if grad_image is not None else None,
-                                           C.byref(adam), self._stream().cuda_stream), name)
+            _lib.call(name, C.byref(f), grad_image.data_ptr() if grad_image is not None else None, C.byref(adam),
+                      self._stream().cuda_stream)
         # the library stepped the parameters through raw pointers: tell torch, so that whoever keys on the tensors' version
         # counters (a renderer's scene pack) sees them change -- all three fused entry points pass through here
         torch.autograd.graph.increment_version(self._keep[:5])
@@ -909,8 +906,7 @@ class FrameRenderer:
                                "each pixel's ray direction, which the backward does not differentiate")
         grad_rot, grad_tran = grad_pose
         for name, t, shape in (("grad_rot", grad_rot, (3, 3)), ("grad_tran", grad_tran, (3,))):
-            if (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device):
-                raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {list(shape)} on {self.device}")
+            check_tensor(name, t, shape, device=self.device)
         need = _lib.gs_frame_pose_workspace_bytes(int(f.N))
         if self._pose_ws is None or self._pose_ws.numel() < need + 256:
             self._pose_ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
@@ -940,8 +936,7 @@ class FrameRenderer:
         self._aux_keep = self._aux_outputs(f, training) if aux else None
         ms = (C.c_float * 6)()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.gs_frame_forward_profile(C.byref(f), ms, self._stream().cuda_stream),
-                       "gs_frame_forward_profile")
+            _lib.call("gs_frame_forward_profile", C.byref(f), ms, self._stream().cuda_stream)
         self._frame = f
         self._frame_serial += 1
         self._note_cut_table(f)
@@ -956,9 +951,8 @@ class FrameRenderer:
         out = tuple(torch.empty_like(t) for t in (pos, quat, scale, opa, rgb))
         ms = (C.c_float * 3)()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.gs_frame_backward_profile(C.byref(f), grad_image.contiguous().data_ptr(),
-                                                      *(t.data_ptr() for t in out), ms, self._stream().cuda_stream),
-                       "gs_frame_backward_profile")
+            _lib.call("gs_frame_backward_profile", C.byref(f), grad_image.contiguous().data_ptr(),
+                      *(t.data_ptr() for t in out), ms, self._stream().cuda_stream)
         self._bwd_serial = self._frame_serial
         return dict(zip(("raster_bwd", "project_bwd", "total"), (float(x) for x in ms)))
 
@@ -968,8 +962,7 @@ class FrameRenderer:
             raise RuntimeError("no frame rendered yet")
         stream = self._stream()
         tag = self._frame_serial & 0xffffffff
-        _lib.check(_lib.gs_frame_stats_tagged_async(C.byref(self._frame), tag, self._stats_host.data_ptr(),
-                                                    stream.cuda_stream), "gs_frame_stats_tagged_async")
+        _lib.call("gs_frame_stats_tagged_async", C.byref(self._frame), tag, self._stats_host.data_ptr(), stream.cuda_stream)
         stream.synchronize()
         h = self._stats_host.tolist()
         v, m, o, b, longest, ran_past, walk, xwalk = (int(h[k]) for k in (0, 1, 2, 3, 9, 10, 13, 14))
@@ -1004,7 +997,7 @@ class FrameRenderer:
         if self._frame is None:
             return None
         ptr = C.c_void_p()
-        _lib.check(_lib.gs_frame_overflow_flag(C.byref(self._frame), C.byref(ptr)), "gs_frame_overflow_flag")
+        _lib.call("gs_frame_overflow_flag", C.byref(self._frame), C.byref(ptr))
         return ptr.value
 
     def _rects(self, allow_culled: bool = False) -> torch.Tensor:
@@ -1017,12 +1010,12 @@ class FrameRenderer:
         if f is None:
             raise RuntimeError("no frame rendered yet")
         culled = C.c_int32(0)
-        _lib.check(_lib.gs_frame_is_occlusion_culled(C.byref(f), C.byref(culled)), "gs_frame_is_occlusion_culled")
+        _lib.call("gs_frame_is_occlusion_culled", C.byref(f), C.byref(culled))
         if culled.value and not allow_culled:
             raise RuntimeError("the rectangle records of an occlusion-culled frame cover its projected Gaussians only: "
                                "render with FrameRenderer(occlusion_cull=False) for debug_views()")
         ptr = C.c_void_p()
-        _lib.check(_lib.gs_frame_debug_rects(C.byref(f), C.byref(ptr)), "gs_frame_debug_rects")
+        _lib.call("gs_frame_debug_rects", C.byref(f), C.byref(ptr))
         off = ptr.value - self._ws.data_ptr()
         return self._ws[off:off + 16 * f.N].view(torch.int32).reshape(f.N, 4)
 
@@ -1036,7 +1029,7 @@ class FrameRenderer:
         if f is None:
             raise RuntimeError("no frame rendered yet")
         culled = C.c_int32(0)
-        _lib.check(_lib.gs_frame_is_occlusion_culled(C.byref(f), C.byref(culled)), "gs_frame_is_occlusion_culled")
+        _lib.call("gs_frame_is_occlusion_culled", C.byref(f), C.byref(culled))
         if culled.value:
             import gaussian  # (the reference-API operators: gaussian/__init__.py)
             pos, quat, scale = self._keep[:3]
@@ -1067,7 +1060,7 @@ class FrameRenderer:
         if f is None or not f.training:
             raise RuntimeError("composited_steps() needs a preceding training forward")
         ptr = C.c_void_p()
-        _lib.check(_lib.gs_frame_debug_tile_nproc(C.byref(f), C.byref(ptr)), "gs_frame_debug_tile_nproc")
+        _lib.call("gs_frame_debug_tile_nproc", C.byref(f), C.byref(ptr))
         off = ptr.value - self._ws.data_ptr()
         T = self._grid.n_tiles
         return int(self._ws[off:off + 4 * T].view(torch.int32).to(torch.int64).sum().item())
@@ -1091,17 +1084,15 @@ class FrameRenderer:
         elif accumulate and float(out.w_min) != float(w_min):  # pixels / views counted at two floors mean nothing
             raise RuntimeError(f"contributions(accumulate=True): `out` was counted at w_min {out.w_min!r}, not {float(w_min)!r}")
         rows = out.rows
-        if (rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous()
-                or tuple(rows.shape) != (n, 4)):
-            raise RuntimeError(f"contributions(): `out` must hold contiguous float32 rows [{n}, 4] on {self.device}")
+        check_tensor("contributions(): the rows of `out`", rows, (n, 4), device=self.device)
         need = int(_lib.gs_frame_contrib_workspace_bytes(int(f.max_pairs)))
         if self._contrib_ws is None or self._contrib_ws.numel() < need + 256:
             self._contrib_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
         base = (self._contrib_ws.data_ptr() + 255) // 256 * 256
         opts = _lib.GsContribOpts(float(w_min), 1 if accumulate else 0)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.gs_frame_contrib(C.byref(f), C.byref(opts), rows.data_ptr() or None, base, need,
-                                             self._stream().cuda_stream), "gs_frame_contrib")
+            _lib.call("gs_frame_contrib", C.byref(f), C.byref(opts), rows.data_ptr() or None, base, need,
+                      self._stream().cuda_stream)
         out.w_min = float(w_min)
         return out
 
@@ -1113,7 +1104,7 @@ class FrameRenderer:
         if f is None or not f.training:
             raise RuntimeError("executed_row_steps() needs a preceding training forward + backward")
         ptr, n = C.c_void_p(), C.c_int32()
-        _lib.check(_lib.gs_frame_debug_bwd_exec_rows(C.byref(f), C.byref(ptr), C.byref(n)), "gs_frame_debug_bwd_exec_rows")
+        _lib.call("gs_frame_debug_bwd_exec_rows", C.byref(f), C.byref(ptr), C.byref(n))
         if n.value == 0:
             return 0
         off = ptr.value - self._ws.data_ptr()
@@ -1123,7 +1114,7 @@ class FrameRenderer:
         """Device tensors aliasing the workspace of the last forward (parity tests)."""
         f = self._frame
         ptrs = [C.c_void_p() for _ in range(7)]
-        _lib.check(_lib.gs_frame_debug_views(C.byref(f), *[C.byref(p) for p in ptrs]), "gs_frame_debug_views")
+        _lib.call("gs_frame_debug_views", C.byref(f), *[C.byref(p) for p in ptrs])
         st = self.stats()
         n, m, T = f.N, st.pairs, self._grid.n_tiles
 

@@ -3,10 +3,13 @@
 ``TileGrid`` restates ``splatter.Tiles`` (splatter.py:255-300) and ``RayBasis`` restates
 ``splatter.RayInfo`` (splatter.py:305-321).  Pure Python/NumPy: all quantities are a handful
 of scalars that are computed once per camera in double precision (as the reference does in
-Python) and handed to the kernels as fp32.
+Python) and handed to the kernels as fp32.  Also the one statement of a pose on the host (``pose64``), of a camera's copy at
+a pose (``posed``) and of a pose as the ctypes arrays of a camera struct (``pose_ctypes``).
 """
 from __future__ import annotations
 
+import copy
+import ctypes as C
 import math
 from dataclasses import dataclass
 
@@ -40,6 +43,26 @@ def principal_point_offset(camera):
     if not (math.isfinite(dx) and math.isfinite(dy)):
         raise ValueError(f"the principal point ({cx}, {cy}) is not finite")
     return dx + 0.0, dy + 0.0  # (-0.0 -> 0.0)
+
+
+def pose64(rot, tran):
+    """(rot [3,3], tran [3]) in float64 from arrays, lists or torch tensors on any device; always fresh arrays."""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else a  # noqa: E731
+    return np.array(host(rot), np.float64).reshape(3, 3), np.array(host(tran), np.float64).reshape(3)
+
+
+def posed(camera, rot, tran):
+    """A copy of ``camera`` at the pose (rot, tran) in float32: fresh contiguous arrays, never views of the arguments."""
+    cam = copy.copy(camera)
+    cam.rot = np.array(rot, np.float32, order="C").reshape(3, 3)
+    cam.tran = np.array(tran, np.float32, order="C").reshape(3)
+    return cam
+
+
+def pose_ctypes(camera):
+    """(rot float[9], tran float[3]) of ``camera`` as the ctypes arrays of a camera struct (include/gs_abi.h)."""
+    return ((C.c_float * 9)(*np.asarray(camera.rot, np.float32).reshape(9)),
+            (C.c_float * 3)(*np.asarray(camera.tran, np.float32).reshape(3)))
 
 
 @dataclass

@@ -28,6 +28,8 @@ import torch
 
 import gs_seed
 from gaussian import _lib
+from gs_call import check_tensor, require_hip, stream, workspace
+from gs_geometry import pose64
 from gs_track import so3_exp
 
 LOG_DOUBLES = _lib.GS_ICP_LOG_DOUBLES
@@ -115,17 +117,16 @@ def _on_so3(R) -> np.ndarray:
 
 def relative_pose(rot_m, tran_m, rot_f, tran_f):
     """(R, t) with p_model = R p_frame + t for the world -> camera poses of the model view and of the frame, in float64."""
-    rot_m, rot_f = np.asarray(rot_m, np.float64).reshape(3, 3), np.asarray(rot_f, np.float64).reshape(3, 3)
+    (rot_m, tran_m), (rot_f, tran_f) = pose64(rot_m, tran_m), pose64(rot_f, tran_f)
     R = _on_so3(rot_m @ rot_f.T)
-    return R, np.asarray(tran_m, np.float64).reshape(3) - R @ np.asarray(tran_f, np.float64).reshape(3)
+    return R, tran_m - R @ tran_f
 
 
 def compose(rot_m, tran_m, R, t):
     """The frame's world -> camera pose from the model view's pose and (R, t): rot = R^T rot_m, tran = R^T (tran_m - t), in
     float64, rot re-orthonormalised through so3_exp."""
-    R = np.asarray(R, np.float64).reshape(3, 3)
-    rot = _on_so3(R.T @ np.asarray(rot_m, np.float64).reshape(3, 3))
-    return rot, R.T @ (np.asarray(tran_m, np.float64).reshape(3) - np.asarray(t, np.float64).reshape(3))
+    (rot_m, tran_m), (R, t) = pose64(rot_m, tran_m), pose64(R, t)
+    return _on_so3(R.T @ rot_m), R.T @ (tran_m - t)
 
 
 def decide(log: np.ndarray, min_inlier_share: float) -> bool:
@@ -156,9 +157,7 @@ class IcpAligner:
     def __init__(self, camera, options: Optional[IcpOptions] = None, device="cuda"):
         self.opt = options if options is not None else IcpOptions()
         self._stages = self.opt.validated()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("IcpAligner needs a HIP device; there is no CPU fallback")
+        self.device = require_hip(device, "IcpAligner")
         self.camera = camera
         self._cam = gs_seed.seed_camera_pp(camera)
         self._rows = sum(n for _, n in self._stages)
@@ -175,8 +174,7 @@ class IcpAligner:
     def _workspace(self, cam, stride: int) -> torch.Tensor:
         key = (cam.cam.height, cam.cam.width, stride)
         if key not in self._ws:
-            nbytes = int(_lib.gs_icp_workspace_bytes(cam.cam.height, cam.cam.width, stride))
-            self._ws[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            self._ws[key] = workspace(_lib.gs_icp_workspace_bytes(*key), self.device, floor=256)
         return self._ws[key]
 
     def set_model(self, depth: torch.Tensor, alpha: Optional[torch.Tensor], rot, tran, camera=None):
@@ -185,17 +183,16 @@ class IcpAligner:
         (vertex, normal) [H,W,4] -- overwritten by the next call of the same size."""
         cam = gs_seed.seed_camera_pp(camera if camera is not None else self.camera)
         H, W = cam.cam.height, cam.cam.width
-        gs_seed._map("depth", depth, (H, W))
+        check_tensor("depth", depth, (H, W))
         if alpha is not None:
-            gs_seed._map("alpha", alpha, (H, W))
+            check_tensor("alpha", alpha, (H, W))
         if (H, W) not in self._maps:
             self._maps[(H, W)] = tuple(torch.empty((H, W, 4), dtype=torch.float32, device=self.device) for _ in range(2))
         vertex, normal = self._maps[(H, W)]
         with torch.cuda.device(self.device):
-            _lib.check(_lib.gs_icp_model_maps(depth.data_ptr(), alpha.data_ptr() if alpha is not None else None, C.byref(cam),
-                                              C.byref(self._mopts), vertex.data_ptr(), normal.data_ptr(),
-                                              torch.cuda.current_stream().cuda_stream), "gs_icp_model_maps")
-        self._model = (vertex, normal, cam, np.array(rot, np.float64).reshape(3, 3), np.array(tran, np.float64).reshape(3))
+            _lib.call("gs_icp_model_maps", depth.data_ptr(), alpha.data_ptr() if alpha is not None else None, C.byref(cam),
+                      C.byref(self._mopts), vertex.data_ptr(), normal.data_ptr(), stream())
+        self._model = (vertex, normal, cam, *pose64(rot, tran))
         return vertex, normal
 
     def align(self, range_map: torch.Tensor, init=None, camera=None) -> IcpResult:
@@ -206,27 +203,27 @@ class IcpAligner:
             raise RuntimeError("align() needs a model: call set_model() first")
         vertex, normal, mcam, rot_m, tran_m = self._model
         cam = gs_seed.seed_camera_pp(camera) if camera is not None else self._cam
-        gs_seed._map("range_map", range_map, (cam.cam.height, cam.cam.width))
+        check_tensor("range_map", range_map, (cam.cam.height, cam.cam.width))
         if init is None:
             rot0, tran0 = rot_m, tran_m
             R0, t0 = np.eye(3), np.zeros(3)
         else:
-            rot0, tran0 = np.array(init[0], np.float64).reshape(3, 3), np.array(init[1], np.float64).reshape(3)
+            rot0, tran0 = pose64(*init)
             R0, t0 = relative_pose(rot_m, tran_m, rot0, tran0)
         o = self.opt
         state, log = self._dev[:_STATE_DOUBLES], self._dev[_STATE_DOUBLES:]
         R9, t3 = (C.c_double * 9)(*R0.reshape(9)), (C.c_double * 3)(*t0)
         with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            _lib.check(_lib.gs_icp_reset(state.data_ptr(), log.data_ptr(), self._rows, R9, t3, stream), "gs_icp_reset")
+            s = stream()
+            _lib.call("gs_icp_reset", state.data_ptr(), log.data_ptr(), self._rows, R9, t3, s)
             row = 0
             for stride, n in self._stages:
                 ws = self._workspace(cam, stride)
                 opts = _lib.GsIcpOpts(stride, float(o.dist_max), float(o.cos_min), int(o.min_count), float(o.damping))
                 for _ in range(n):
-                    _lib.check(_lib.gs_icp_step(range_map.data_ptr(), C.byref(cam), vertex.data_ptr(), normal.data_ptr(),
-                                                C.byref(mcam), C.byref(opts), state.data_ptr(), log.data_ptr(), self._rows, row,
-                                                ws.data_ptr(), ws.numel(), stream), "gs_icp_step")
+                    _lib.call("gs_icp_step", range_map.data_ptr(), C.byref(cam), vertex.data_ptr(), normal.data_ptr(),
+                              C.byref(mcam), C.byref(opts), state.data_ptr(), log.data_ptr(), self._rows, row, ws.data_ptr(),
+                              ws.numel(), s)
                     row += 1
             _read(self._host, self._dev)
         h = self._host.numpy()

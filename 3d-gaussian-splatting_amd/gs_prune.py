@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from gaussian import _lib
+from gs_call import check_tensor, require_hip, stream, workspace
 
 SCALE_ACT = {"abs": 0, "exp": 1}
 # opa_min 0.005: a quarter of the 0.02 the reference prunes below (gs_densify; utils.py:350-351), which it applies inside a
@@ -58,8 +59,7 @@ def contrib_rows(contributions, n: int) -> torch.Tensor:
 
 def _rows(name: str, t: torch.Tensor, n: Optional[int] = None) -> int:
     """A contiguous float32 HIP tensor of rows -> floats per row."""
-    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() < 1 or (n is not None and t.shape[0] < n):
-        raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor" + (f" of at least {n} rows" if n is not None else ""))
+    check_tensor(name, t, rows_min=0 if n is None else n)
     return int(math.prod(t.shape[1:]))
 
 
@@ -68,22 +68,19 @@ def prune_classify(scale: torch.Tensor, opa: torch.Tensor, opts, contributions=N
     """The decision pass: -> (counts [2] int64 on the device = (kept, removed), workspace).  With ``contributions`` (the rows of
     ``FrameRenderer.contributions``) and ``copts`` (``contrib_options``) the contribution rule is joined to the decision
     (gs_prune_classify_contrib); without them the call is gs_prune_classify."""
-    if scale.device.type != "cuda":
-        raise RuntimeError("pruning needs a HIP device; there is no CPU fallback")
+    require_hip(scale.device, "pruning")
     n = int(scale.shape[0])
     if _rows("scale", scale) != 3 or _rows("opa", opa) != 1 or int(opa.shape[0]) != n:
         raise RuntimeError(f"scale must be [N,3] and opa [N] of the same N, got {list(scale.shape)} and {list(opa.shape)}")
-    ws = torch.empty(int(_lib.gs_prune_workspace_bytes(n)), dtype=torch.uint8, device=scale.device)
+    ws = workspace(_lib.gs_prune_workspace_bytes(n), scale.device)
     counts = torch.zeros(2, dtype=torch.int64, device=scale.device)
+    tail = (counts.data_ptr(), ws.data_ptr(), ws.numel(), stream())
     if contributions is not None:
         rows = contrib_rows(contributions, n)
-        _lib.check(_lib.gs_prune_classify_contrib(scale.data_ptr(), opa.data_ptr(), rows.data_ptr(), n, C.byref(opts),
-                                                  C.byref(copts if copts is not None else contrib_options()),
-                                                  counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                  torch.cuda.current_stream().cuda_stream), "gs_prune_classify_contrib")
-        return counts, ws
-    _lib.check(_lib.gs_prune_classify(scale.data_ptr(), opa.data_ptr(), n, C.byref(opts), counts.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_prune_classify")
+        _lib.call("gs_prune_classify_contrib", scale.data_ptr(), opa.data_ptr(), rows.data_ptr(), n, C.byref(opts),
+                  C.byref(copts if copts is not None else contrib_options()), *tail)
+    else:
+        _lib.call("gs_prune_classify", scale.data_ptr(), opa.data_ptr(), n, C.byref(opts), *tail)
     return counts, ws
 
 
@@ -101,8 +98,7 @@ def prune_apply(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], n: int
         if _rows(f"dst[{k}]", d, cap) != w:
             raise RuntimeError(f"array {k}: src rows hold {w} floats, dst rows {_rows('dst', d)}")
         a.width[k], a.src[k], a.dst[k] = max(w, 0), s.data_ptr() or None, d.data_ptr() or None
-    _lib.check(_lib.gs_prune_apply(C.byref(a), int(n), int(dst_offset), cap, counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   torch.cuda.current_stream().cuda_stream), "gs_prune_apply")
+    _lib.call("gs_prune_apply", C.byref(a), int(n), int(dst_offset), cap, counts.data_ptr(), ws.data_ptr(), ws.numel(), stream())
     # rows written through raw pointers: advance the version counters (a renderer's scene pack is keyed on them)
     torch.autograd.graph.increment_version(tuple(dst))
 

@@ -16,6 +16,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from gaussian import _lib
+from gs_call import check_tensor, require_hip, stream
 from gs_geometry import principal_point_default
 
 MAX_LEVELS = _lib.GS_PYRAMID_MAX_LEVELS
@@ -73,32 +74,24 @@ class Pyramid:
             raise ValueError(f"min_valid must be 1..4, got {min_valid}")
         if edge_rel != edge_rel:
             raise ValueError("edge_rel must not be NaN (negative: the edge test is off)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("Pyramid needs a HIP device; there is no CPU fallback")
+        self.device = require_hip(device, "Pyramid")
         self._opts = _lib.GsPyramidOpts(int(min_valid), float(edge_rel))
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)  # noqa: E731
         self._images = [None] + [new(h, w, 3) for h, w in self.sizes[1:]]
         self._ranges = [None] + [new(h, w) for h, w in self.sizes[1:]]
 
-    def _check_map(self, name: str, t: torch.Tensor, shape):
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [{', '.join(map(str, shape))}]")
-
     def build(self, image: torch.Tensor, range_map: Optional[torch.Tensor] = None):
-        self._check_map("image", image, (self.H, self.W, 3))
+        check_tensor("image", image, (self.H, self.W, 3))
         if range_map is not None:
-            self._check_map("range_map", range_map, (self.H, self.W))
+            check_tensor("range_map", range_map, (self.H, self.W))
         images = [image] + self._images[1:]
         ranges = [range_map] + (self._ranges[1:] if range_map is not None else [None] * self.levels)
         if self.levels:
             with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream().cuda_stream
+                s = stream()
                 for l in range(self.levels):
                     h, w = self.sizes[l]
-                    _lib.check(_lib.gs_pyramid_down(images[l].data_ptr(),
-                                                    ranges[l].data_ptr() if range_map is not None else None, h, w,
-                                                    C.byref(self._opts), images[l + 1].data_ptr(),
-                                                    ranges[l + 1].data_ptr() if range_map is not None else None, stream),
-                               "gs_pyramid_down")
+                    _lib.call("gs_pyramid_down", images[l].data_ptr(), ranges[l].data_ptr() if range_map is not None else None,
+                              h, w, C.byref(self._opts), images[l + 1].data_ptr(),
+                              ranges[l + 1].data_ptr() if range_map is not None else None, s)
         return images, ranges

@@ -15,11 +15,11 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 
 from gaussian import _lib
-from gs_geometry import principal_point_offset
+from gs_call import check_tensor, require_hip, stream, workspace
+from gs_geometry import pose_ctypes, principal_point_offset
 
 SCALE_ACT = {"abs": 0, "exp": 1}
 # opa_init > alpha_thresh: a pixel that was seeded has A >= opa_init at its centre from its own Gaussian alone, so the
@@ -32,12 +32,6 @@ DEFAULTS = dict(stride=1, alpha_thresh=0.5, front_rel=0.2, scale_factor=0.7, opa
 ROW_SHAPES = ((3,), (4,), (3,), (), None)  # pos, quat, scale, opa, rgb (color_dim)
 
 
-def _map(name: str, t: torch.Tensor, shape) -> torch.Tensor:
-    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape {list(shape)}")
-    return t
-
-
 def seed_options(stride: int = DEFAULTS["stride"], alpha_thresh: float = DEFAULTS["alpha_thresh"],
                  front_rel: float = DEFAULTS["front_rel"], scale_factor: float = DEFAULTS["scale_factor"],
                  opa_init: float = DEFAULTS["opa_init"], color_dim: int = 3, scale_activation: str = "abs") -> "_lib.GsSeedOpts":
@@ -47,8 +41,7 @@ def seed_options(stride: int = DEFAULTS["stride"], alpha_thresh: float = DEFAULT
 
 def seed_camera(camera) -> "_lib.GsSeedCamera":
     c = _lib.GsSeedCamera()
-    c.rot = (C.c_float * 9)(*np.asarray(camera.rot, np.float32).reshape(9))
-    c.tran = (C.c_float * 3)(*np.asarray(camera.tran, np.float32).reshape(3))
+    c.rot, c.tran = pose_ctypes(camera)
     c.focal_x, c.focal_y = float(camera.focal_x), float(camera.focal_y)
     c.width, c.height = int(camera.width), int(camera.height)
     return c
@@ -62,17 +55,16 @@ def seed_camera_pp(camera) -> "_lib.GsSeedCameraPP":
 
 def seed_classify(rng: torch.Tensor, rendered: Optional[Tuple[torch.Tensor, torch.Tensor]], opts):
     """The decision pass: -> (counts [2] int64 on the device = (selected, measured lattice pixels), workspace)."""
-    if rng.device.type != "cuda":
-        raise RuntimeError("seeding needs a HIP device; there is no CPU fallback")
+    require_hip(rng.device, "seeding")
     H, W = (int(v) for v in rng.shape)
-    _map("depth", rng, (H, W))
+    check_tensor("depth", rng, (H, W))
     d_ptr = a_ptr = None
     if rendered is not None:
-        d_ptr, a_ptr = (_map(n, t, (H, W)).data_ptr() for n, t in zip(("rendered depth", "rendered alpha"), rendered))
-    ws = torch.empty(int(_lib.gs_seed_workspace_bytes(H, W)), dtype=torch.uint8, device=rng.device)
+        d_ptr, a_ptr = (check_tensor(n, t, (H, W)).data_ptr() for n, t in zip(("rendered depth", "rendered alpha"), rendered))
+    ws = workspace(_lib.gs_seed_workspace_bytes(H, W), rng.device)
     counts = torch.zeros(2, dtype=torch.int64, device=rng.device)
-    _lib.check(_lib.gs_seed_classify(rng.data_ptr(), d_ptr, a_ptr, H, W, C.byref(opts), counts.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_seed_classify")
+    _lib.call("gs_seed_classify", rng.data_ptr(), d_ptr, a_ptr, H, W, C.byref(opts), counts.data_ptr(), ws.data_ptr(),
+              ws.numel(), stream())
     return counts, ws
 
 
@@ -81,22 +73,18 @@ def seed_apply(image: torch.Tensor, rng: torch.Tensor, camera, opts, out: Sequen
     """The write pass into rows [offset, offset + selected) of ``out`` = (pos, quat, scale, opa, rgb), arrays of ``capacity``
     rows (default: their length); writes nothing if they do not fit."""
     H, W = (int(v) for v in rng.shape)
-    _map("image", image, (H, W, 3))
+    check_tensor("image", image, (H, W, 3))
     cap = int(out[0].shape[0]) if capacity is None else int(capacity)
     for name, t, tail in zip(("pos", "quat", "scale", "opa", "rgb"), out, ROW_SHAPES):
-        tail = (int(opts.color_dim),) if tail is None else tail
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape[1:]) != tail or t.shape[0] < cap:
-            raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [>= {cap}, {tail}]")
+        check_tensor(name, t, rows_min=cap, tail=(int(opts.color_dim),) if tail is None else tail)
     cam = seed_camera(camera)
     if (cam.height, cam.width) != (H, W):
         raise RuntimeError(f"the maps are {H} x {W}, the camera is {cam.height} x {cam.width}")
-    tail = (*(t.data_ptr() for t in out), int(offset), cap, counts.data_ptr(), ws.data_ptr(), ws.numel(),
-            torch.cuda.current_stream().cuda_stream)
-    if principal_point_offset(camera) != (0.0, 0.0):  # the rays move with the principal point (gs_seed_apply_pp)
-        cpp = seed_camera_pp(camera)
-        _lib.check(_lib.gs_seed_apply_pp(image.data_ptr(), rng.data_ptr(), C.byref(cpp), C.byref(opts), *tail), "gs_seed_apply_pp")
-    else:
-        _lib.check(_lib.gs_seed_apply(image.data_ptr(), rng.data_ptr(), C.byref(cam), C.byref(opts), *tail), "gs_seed_apply")
+    # the rays move with the principal point (gs_seed_apply_pp)
+    pp = principal_point_offset(camera) != (0.0, 0.0)
+    _lib.call("gs_seed_apply_pp" if pp else "gs_seed_apply", image.data_ptr(), rng.data_ptr(),
+              C.byref(seed_camera_pp(camera) if pp else cam), C.byref(opts), *(t.data_ptr() for t in out), int(offset), cap,
+              counts.data_ptr(), ws.data_ptr(), ws.numel(), stream())
     # rows written through raw pointers into tensors the caller may already have rendered from (a set with spare capacity):
     # advance their version counters, which a renderer's scene pack is keyed on
     torch.autograd.graph.increment_version(tuple(out))

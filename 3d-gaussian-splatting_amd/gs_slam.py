@@ -38,7 +38,8 @@ import torch
 
 import gs_seed
 from gaussian import _lib
-from gs_geometry import principal_point_offset
+from gs_call import check_tensor, require_hip, stream, workspace
+from gs_geometry import pose64, posed, principal_point_offset
 from gs_icp import IcpAligner, IcpOptions, IcpResult
 from gs_track import _SH_REFUSAL, TrackOptions, TrackResult, Tracker
 from gs_train import TrainOptions, Trainer
@@ -58,32 +59,22 @@ def view_overlap(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: 
     Off-centre principal points: ``camera``'s own offset is honoured (``gs_geometry.principal_point_offset``); the views'
     offsets come as ``table_pp`` [>= n_views, 2] float32 on the device, row k = (dx_k, dy_k) in pixels
     (``KeyframeSet.table_pp``; None: no view has one).  With no offset anywhere the call is ``gs_view_overlap`` itself."""
-    if range_map.device.type != "cuda":
-        raise RuntimeError("the overlap count needs a HIP device; there is no CPU fallback")
+    require_hip(range_map.device, "the overlap count")
     cam = gs_seed.seed_camera(camera)
-    gs_seed._map("range_map", range_map, (cam.height, cam.width))
-    if (table.dtype != torch.float32 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2
-            or table.shape[1] != 16 or table.shape[0] < n_views):
-        raise RuntimeError(f"table must be a contiguous float32 HIP tensor of shape [>= {n_views}, 16]")
+    check_tensor("range_map", range_map, (cam.height, cam.width))
+    check_tensor("table", table, rows_min=n_views, tail=(16,))
     opts = _lib.GsOverlapOpts(int(stride), float(near), int(border))
-    ws = torch.empty(int(_lib.gs_view_overlap_workspace_bytes(cam.height, cam.width, max(int(stride), 1),
-                                                              min(max(int(n_views), 1), GS_OVERLAP_MAX_VIEWS))),
-                     dtype=torch.uint8, device=range_map.device)
+    ws = workspace(_lib.gs_view_overlap_workspace_bytes(cam.height, cam.width, max(int(stride), 1),
+                                                        min(max(int(n_views), 1), GS_OVERLAP_MAX_VIEWS)), range_map.device)
     counts = torch.empty(max(int(n_views), 0) + 2, dtype=torch.int64, device=range_map.device)
+    tail = (int(n_views), C.byref(opts), counts.data_ptr(), ws.data_ptr(), ws.numel(), stream())
     if table_pp is not None or principal_point_offset(camera) != (0.0, 0.0):
-        if table_pp is not None and (table_pp.dtype != torch.float32 or not table_pp.is_cuda or not table_pp.is_contiguous()
-                                     or table_pp.dim() != 2 or table_pp.shape[1] != 2 or table_pp.shape[0] < n_views
-                                     or table_pp.device != table.device):
-            raise RuntimeError(f"table_pp must be a contiguous float32 HIP tensor of shape [>= {n_views}, 2] beside table")
-        cpp = gs_seed.seed_camera_pp(camera)
-        _lib.check(_lib.gs_view_overlap_pp(range_map.data_ptr(), C.byref(cpp), table.data_ptr(),
-                                           table_pp.data_ptr() if table_pp is not None else None, int(n_views),
-                                           C.byref(opts), counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           torch.cuda.current_stream().cuda_stream), "gs_view_overlap_pp")
-        return counts
-    _lib.check(_lib.gs_view_overlap(range_map.data_ptr(), C.byref(cam), table.data_ptr(), int(n_views), C.byref(opts),
-                                    counts.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    torch.cuda.current_stream().cuda_stream), "gs_view_overlap")
+        if table_pp is not None:
+            check_tensor("table_pp", table_pp, rows_min=n_views, tail=(2,), device=table.device)
+        _lib.call("gs_view_overlap_pp", range_map.data_ptr(), C.byref(gs_seed.seed_camera_pp(camera)), table.data_ptr(),
+                  table_pp.data_ptr() if table_pp is not None else None, *tail)
+    else:
+        _lib.call("gs_view_overlap", range_map.data_ptr(), C.byref(cam), table.data_ptr(), *tail)
     return counts
 
 
@@ -91,7 +82,7 @@ def view_row(camera) -> np.ndarray:
     """A camera as one 64-byte row of the view table (``struct gs_seed_camera``), validated: ``gs_view_overlap`` cannot
     check rows that live in device memory, so the owner of the table does when it appends one."""
     cam = gs_seed.seed_camera(camera)
-    _lib.check(_lib.gs_view_overlap_check_view(C.byref(cam), 0), "gs_view_overlap_check_view")
+    _lib.call("gs_view_overlap_check_view", C.byref(cam), 0)
     return np.frombuffer(bytes(cam), np.float32).copy()
 
 
@@ -137,9 +128,7 @@ class KeyframeSet:
         its 64-byte row of the device table by the validated row of that copy."""
         if not 0 <= int(index) < len(self.cameras):
             raise IndexError(f"no keyframe {index}")
-        cam = copy.copy(self.cameras[index])
-        cam.rot = np.array(rot, np.float32).reshape(3, 3)
-        cam.tran = np.array(tran, np.float32).reshape(3)
+        cam = posed(self.cameras[index], rot, tran)
         row = view_row(cam)  # (validated before anything is written)
         self.table[index].copy_(torch.from_numpy(row))
         self.cameras[index] = cam
@@ -270,9 +259,7 @@ class Slam:
         self._seed = {k: v for k, v in self.opt.seed.items() if k != "color_dim"}
         if int(self.opt.seed.get("color_dim", 3)) != 3:
             raise RuntimeError(_SH_REFUSAL)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("Slam needs a HIP device; there is no CPU fallback")
+        self.device = require_hip(device, "Slam")
         self.camera = camera
         self.near = float(self.opt.near if self.opt.near is not None else camera.near)
         self.keyframes = KeyframeSet(device=self.device)
@@ -295,10 +282,7 @@ class Slam:
         return self.trainer.flat.params if self.trainer is not None else None
 
     def _posed(self, rot, tran):
-        cam = copy.copy(self.camera)
-        cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
-        cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
-        return cam
+        return posed(self.camera, rot, tran)
 
     def map(self, frame: SlamFrame) -> SlamFrame:
         """The mapping steps of a keyframe that ``begin`` returned, round-robin over its window starting with the new view,
@@ -362,8 +346,7 @@ class Slam:
     def _first(self, image, range_map, init) -> SlamFrame:
         o = self.opt
         rot, tran = init if init is not None else (self.camera.rot, self.camera.tran)
-        to_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))  # noqa: E731
-        rot, tran = to_np(rot).astype(np.float64).reshape(3, 3), to_np(tran).astype(np.float64).reshape(3)
+        rot, tran = pose64(rot, tran)
         cam = self._posed(rot, tran)
         t0 = time.perf_counter()
         params = gs_seed.seed_from_depth(image, range_map, cam, color_dim=3, **self._seed)
@@ -420,10 +403,7 @@ class Slam:
         if added_as != new:
             raise RuntimeError(f"keyframe {new} became view {added_as} of the trainer: the two lists have diverged")
         self._last_keyframe_at = index
-        if o.carry_optimizer:
-            frame.added = self.trainer.seed_from_view(new, self.i_iter, carry_state=True, **self._seed)
-        else:
-            frame.added = self.trainer.seed_from_view(new, self.i_iter, **self._seed)
+        frame.added = self.trainer.seed_from_view(new, self.i_iter, carry_state=bool(o.carry_optimizer), **self._seed)
         frame.seconds["seed"] = time.perf_counter() - t2
         frame.window = [new] + select_keyframes(counts[:n], measured, o.window - 1, o.min_share)
         frame.pending = int(o.map_iterations)

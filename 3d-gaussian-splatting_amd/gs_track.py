@@ -22,7 +22,6 @@ and every call is the call described above.
 """
 from __future__ import annotations
 
-import copy
 import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -31,7 +30,9 @@ import numpy as np
 import torch
 
 from gaussian import _lib
+from gs_call import check_tensor, require_hip
 from gs_frame import FrameRenderer
+from gs_geometry import pose64, posed
 from gs_pyramid import MAX_LEVELS, Pyramid, level_camera
 from gs_train import GatedTrackLoss, TrackLoss
 
@@ -119,8 +120,7 @@ def rot_tangent_grad(grad_rot, rot) -> np.ndarray:
 def predict_constant_velocity(prev, last):
     """T_pred = T_last T_prev^-1 T_last in float64 for world -> camera poses (rot, tran): the motion between the last two
     frames, applied once more."""
-    Rp, tp = np.asarray(prev[0], np.float64).reshape(3, 3), np.asarray(prev[1], np.float64).reshape(3)
-    Rl, tl = np.asarray(last[0], np.float64).reshape(3, 3), np.asarray(last[1], np.float64).reshape(3)
+    (Rp, tp), (Rl, tl) = pose64(*prev), pose64(*last)
     dR = Rl @ Rp.T               # T_last T_prev^-1 = (dR, tl - dR tp)
     dt = tl - dR @ tp
     R = dR @ Rl
@@ -140,8 +140,7 @@ class PoseAdam:
 
     def __init__(self, rot, tran, lr_rot: float, lr_tran: float, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8):
-        self.rot = np.array(rot, np.float64).reshape(3, 3)
-        self.tran = np.array(tran, np.float64).reshape(3)
+        self.rot, self.tran = pose64(rot, tran)
         self.lr0 = np.array([lr_rot] * 3 + [lr_tran] * 3)
         self.betas = (betas[0], betas[1])
         self.eps = eps
@@ -208,9 +207,7 @@ class Tracker:
     def __init__(self, params, camera, options: Optional[TrackOptions] = None, device="cuda"):
         self.opt = options if options is not None else TrackOptions()
         self._check_map(params)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("Tracker needs a HIP device; there is no CPU fallback")
+        self.device = require_hip(device, "Tracker")
         self.camera = camera
         self.H, self.W = int(camera.height), int(camera.width)
         plan = self.level_plan(self.opt, self.H, self.W)
@@ -279,8 +276,7 @@ class Tracker:
         """Rebind the map (after the mapper changed or grew the Gaussian set).  The tensors are read, never written."""
         self._check_map(params)
         for name, t in zip(("pos", "quat", "scale", "opa", "rgb"), params):
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor")
+            check_tensor(name, t)
         self.params = tuple(t.detach() for t in params)
         if self._scratch is None or any(s.shape != p.shape for s, p in zip(self._scratch, self.params)):
             # the per-Gaussian gradient rows the backward writes on its way to the pose gradient: nobody reads them
@@ -295,19 +291,16 @@ class Tracker:
         constant-velocity prediction of the next ``track`` starts from it."""
         if not self._history:
             raise RuntimeError("set_last_pose() needs a tracked frame")
-        self._history[-1] = (np.array(rot, np.float64).reshape(3, 3), np.array(tran, np.float64).reshape(3))
+        self._history[-1] = pose64(rot, tran)
 
     def _start_pose(self, init):
         if init is not None:
-            rot, tran = init
-            to_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))  # noqa: E731
-            return to_np(rot).astype(np.float64).reshape(3, 3), to_np(tran).astype(np.float64).reshape(3)
+            return pose64(*init)
         if len(self._history) >= 2:
             return predict_constant_velocity(self._history[-2], self._history[-1])
         if self._history:
-            return self._history[-1][0].copy(), self._history[-1][1].copy()
-        return (np.asarray(self.camera.rot, np.float64).reshape(3, 3).copy(),
-                np.asarray(self.camera.tran, np.float64).reshape(3).copy())
+            return pose64(*self._history[-1])
+        return pose64(self.camera.rot, self.camera.tran)
 
     def iteration(self, rot, tran, image, range_map=None, level=0):
         """One forward / loss / pose backward at the pose (rot, tran); the 16 floats land in ``self._host`` (pinned):
@@ -323,9 +316,7 @@ class Tracker:
             r, loss, camera, scale = self._levels[level]
         else:
             raise ValueError(f"level {level} is not in this Tracker's schedule {self._stages}")
-        cam = copy.copy(camera)
-        cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
-        cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
+        cam = posed(camera, rot, tran)
         img, _, depth, alpha = r.forward(*self.params, cam, training=True, aux=True)
         with torch.cuda.device(self.device):
             gi, gd, ga = loss(img, depth, alpha, image, range_map, scale, values=self._values)
@@ -342,38 +333,32 @@ class Tracker:
         adam = PoseAdam(R, t, o.lr_rot, o.lr_tran, o.betas, o.eps)  # Adam's moments on (w, tran): kept across iterations, reset per call
         best = (math.inf, R, t, None)
         losses: List[float] = []
-        levels = None
+        # coarse to fine: the targets once, then the stages in order under ONE PoseAdam (moments and step count carry across
+        # stages, the rate decays over the whole call); losses of different levels are not comparable, so the pose returned
+        # is the lowest-loss one of the LAST stage.  Without a schedule: one stage at level 0 on the caller's tensors
         if self._stages is None:
-            for k in range(int(o.iterations)):
-                h = self.iteration(R, t, image, range_map).numpy().astype(np.float64)
+            stages, images, ranges = ((0, int(o.iterations)),), (image,), (range_map,)
+        else:
+            stages = self._stages
+            images, ranges = self._pyramid.build(image, range_map)
+        total = sum(n for _, n in stages)
+        levels, k = [], 0
+        for level, n in stages:
+            levels.append((level, k, n))
+            last = level == stages[-1][0]
+            for _ in range(n):
+                h = self.iteration(R, t, images[level], ranges[level], level).numpy().astype(np.float64)
                 loss = float(h[12])
                 losses.append(loss)
-                if loss < best[0]:
+                if last and loss < best[0]:
                     best = (loss, R, t, h[15:20] if len(h) == 20 else None)
-                R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / o.iterations))
-        else:
-            # coarse to fine: the targets once, then the stages in order under ONE PoseAdam (moments and step count carry
-            # across stages, the rate decays over the whole call); losses of different levels are not comparable, so the
-            # pose returned is the lowest-loss one of the LAST stage
-            images, ranges = self._pyramid.build(image, range_map)
-            total = sum(n for _, n in self._stages)
-            levels, k = [], 0
-            for level, n in self._stages:
-                levels.append((level, k, n))
-                last = level == self._stages[-1][0]
-                for _ in range(n):
-                    h = self.iteration(R, t, images[level], ranges[level], level).numpy().astype(np.float64)
-                    loss = float(h[12])
-                    losses.append(loss)
-                    if last and loss < best[0]:
-                        best = (loss, R, t, h[15:20] if len(h) == 20 else None)
-                    R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / total))
-                    k += 1
+                R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / total))
+                k += 1
         loss, R, t, gate = best
         self._history = (self._history + [(R, t)])[-2:]
         res = TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)
         if gate is not None:  # (depth pixels, colour pixels, m_d, m_c, n_d) of the returned pose's iteration
             res.inliers = (int(gate[0]), int(gate[4]), int(gate[1]))
             res.medians = (float(gate[2]), float(gate[3]))
-        res.levels = levels
+        res.levels = levels if self._stages is not None else None
         return res

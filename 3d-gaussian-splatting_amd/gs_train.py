@@ -17,7 +17,6 @@ schedule) is SURVEY 8f-2; data loading and the viewer stay out of scope (8f-3, 8
 """
 from __future__ import annotations
 
-import copy
 import ctypes as C
 import os
 import math
@@ -28,9 +27,10 @@ import numpy as np
 import torch
 
 from gaussian import _lib
+from gs_call import check_tensor, require_hip, stream, workspace
 from gs_dp import ORDER, FlatGaussianParams, ViewParallelGradStat
 from gs_frame import CONTRIB_W_MIN, Contributions, FrameRenderer
-from gs_geometry import RayBasis, TileGrid, principal_point_offset
+from gs_geometry import RayBasis, TileGrid, pose64, posed, principal_point_offset
 
 GROUPS = ("opa", "rgb", "pos", "scale", "quat")  # the reference's param-group order (train.py:59-65)
 
@@ -107,8 +107,7 @@ class FusedAdam:
 
     def __init__(self, flat: FlatGaussianParams, lrs: Sequence[float], betas=(0.9, 0.99), eps: float = 1e-8,
                  grad_stat: Optional[str] = None):
-        if flat.flat_param.device.type != "cuda":
-            raise RuntimeError("FusedAdam needs a HIP device; there is no CPU fallback")
+        require_hip(flat.flat_param.device, "FusedAdam")
         self.flat = flat
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.sharded = flat.exchange == "reduce_scatter"
@@ -187,11 +186,11 @@ class FusedAdam:
         f = self.flat
         b, e = self._stat_range
         n = f.flat_param.numel()
-        _lib.check(_lib.gs_adam_step_sharded(
-            f.flat_param.data_ptr(), f.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n, 0, n,
-            0, len(ORDER), self._ends, self._lr, self.betas[0], self.betas[1], self.eps, self.step_count,
-            self.accum_grad.data_ptr() if self.accum_grad is not None else None, b, e, self.stat_mode, self.skip_flag,
-            torch.cuda.current_stream().cuda_stream), "gs_adam_step")
+        _lib.call("gs_adam_step_sharded",
+                  f.flat_param.data_ptr(), f.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n, 0, n,
+                  0, len(ORDER), self._ends, self._lr, self.betas[0], self.betas[1], self.eps, self.step_count,
+                  self.accum_grad.data_ptr() if self.accum_grad is not None else None, b, e, self.stat_mode, self.skip_flag,
+                  stream())
         # the kernel wrote the flat buffer through a raw pointer: advance its version counter (shared by all its views, the
         # five parameter tensors among them), which a renderer's scene pack is keyed on
         torch.autograd.graph.increment_version(f.flat_param)
@@ -227,30 +226,24 @@ class FusedAdam:
             return
         f = self.flat
         b, e = self._stat_range
-        _lib.check(_lib.gs_adam_step_multi(
-            f.flat_param.data_ptr(), f.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            f.flat_param.numel(), n_r, lo, hi, off, len(ORDER), self._ends, self._lr, self.betas[0], self.betas[1],
-            self.eps, self.step_count, self.accum_grad.data_ptr() if self.accum_grad is not None else None, b, e,
-            self.stat_mode, self.skip_flag, float(grad_scale), torch.cuda.current_stream().cuda_stream),
-            "gs_adam_step_multi")
+        _lib.call("gs_adam_step_multi",
+                  f.flat_param.data_ptr(), f.flat_grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                  f.flat_param.numel(), n_r, lo, hi, off, len(ORDER), self._ends, self._lr, self.betas[0], self.betas[1],
+                  self.eps, self.step_count, self.accum_grad.data_ptr() if self.accum_grad is not None else None, b, e,
+                  self.stat_mode, self.skip_flag, float(grad_scale), stream())
         torch.autograd.graph.increment_version(f.flat_param)  # (as in `step`)
 
 
 class _MapLoss:
-    """What the three loss objects share: the refusal of a non-HIP device, the workspace, the check of an input map."""
+    """What the loss objects share: the refusal of a non-HIP device and the workspace."""
 
     def _setup(self, height: int, width: int, device, workspace_bytes):
-        self.H, self.W, self.device = int(height), int(width), torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} needs a HIP device; there is no CPU fallback")
-        self._ws = torch.empty(int(workspace_bytes(self.H, self.W)), dtype=torch.uint8, device=self.device)
+        self.H, self.W = int(height), int(width)
+        self.device = require_hip(device, type(self).__name__)
+        self._ws = workspace(workspace_bytes(self.H, self.W), self.device)
 
     def _new(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.device)
-
-    def _check_map(self, name: str, t: torch.Tensor, shape, sep=","):
-        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-            raise RuntimeError(f"{name} must be a contiguous float32 HIP tensor of shape [{sep.join(map(str, shape))}]")
 
 
 class ImageLoss(_MapLoss):
@@ -264,10 +257,9 @@ class ImageLoss(_MapLoss):
 
     def __call__(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         for name, t in (("pred", pred), ("target", target)):
-            self._check_map(name, t, (self.H, self.W, 3))
-        _lib.check(_lib.gs_loss_l1_ssim(pred.data_ptr(), target.data_ptr(), self.H, self.W, self.w,
-                                        self.grad.data_ptr(), self.values.data_ptr(), self._ws.data_ptr(),
-                                        self._ws.numel(), torch.cuda.current_stream().cuda_stream), "gs_loss_l1_ssim")
+            check_tensor(name, t, (self.H, self.W, 3))
+        _lib.call("gs_loss_l1_ssim", pred.data_ptr(), target.data_ptr(), self.H, self.W, self.w, self.grad.data_ptr(),
+                  self.values.data_ptr(), self._ws.data_ptr(), self._ws.numel(), stream())
         return self.grad
 
 
@@ -290,15 +282,37 @@ class DepthLoss(_MapLoss):
         """``target``: [H,W] range from the camera centre (<= 0, inf, NaN: no measurement); ``scale``: weight / number of
         measured pixels.  Returns (grad_depth, grad_alpha)."""
         for name, t in (("depth", depth), ("alpha", alpha), ("target", target)):
-            self._check_map(name, t, (self.H, self.W))
-        _lib.check(_lib.gs_loss_depth(depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), self.H, self.W, self.mode,
-                                      self.alpha_min, float(scale), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
-                                      self.values.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                      torch.cuda.current_stream().cuda_stream), "gs_loss_depth")
+            check_tensor(name, t, (self.H, self.W))
+        _lib.call("gs_loss_depth", depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), self.H, self.W, self.mode,
+                  self.alpha_min, float(scale), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(), self.values.data_ptr(),
+                  self._ws.data_ptr(), self._ws.numel(), stream())
         return self.grad_depth, self.grad_alpha
 
 
-class TrackLoss(_MapLoss):
+class _TrackMaps(_MapLoss):
+    """What the two tracking losses share: the three gradient maps, ``values``, and the check of a call's arguments."""
+
+    def _setup(self, height: int, width: int, device, workspace_bytes, n_values: int):
+        super()._setup(height, width, device, workspace_bytes)
+        self.grad_image = self._new(self.H, self.W, 3)
+        self.grad_depth, self.grad_alpha = self._new(self.H, self.W), self._new(self.H, self.W)
+        self.values = torch.zeros(n_values, dtype=torch.float32, device=self.device)  # stays on the device
+
+    def _checked(self, image, depth, alpha, target_image, target_range, values):
+        """The five input maps checked (``target_range`` may be None) -> the checked destination of the values."""
+        maps = [("image", image, (3,)), ("depth", depth, ()), ("alpha", alpha, ()), ("target_image", target_image, (3,))]
+        if target_range is not None:
+            maps.append(("target_range", target_range, ()))
+        for name, t, c in maps:
+            check_tensor(name, t, (self.H, self.W) + c)
+        if values is None:
+            return self.values
+        if check_tensor("values", values).numel() != self.values.numel():
+            raise RuntimeError(f"values must hold {self.values.numel()} floats, got {values.numel()}")
+        return values
+
+
+class TrackLoss(_TrackMaps):
     """The loss of camera tracking against a frozen map and its gradients w.r.t. the image, depth and alpha maps of an aux
     frame (gs_loss_track, include/gs_abi.h): ``scale * (color_weight * sum |I - T| + depth_weight * sum |D / A - z|)`` over
     the pixels the map covers (A >= ``alpha_min``), the depth term on those that are measured and pass ``depth_gate``
@@ -309,34 +323,23 @@ class TrackLoss(_MapLoss):
                  depth_gate: float = 0.0, device="cuda"):
         self.alpha_min = float(alpha_min)
         self.color_weight, self.depth_weight, self.depth_gate = float(color_weight), float(depth_weight), float(depth_gate)
-        self._setup(height, width, device, _lib.gs_loss_track_workspace_bytes)
-        self.grad_image = self._new(self.H, self.W, 3)
-        self.grad_depth, self.grad_alpha = self._new(self.H, self.W), self._new(self.H, self.W)
-        self.values = torch.zeros(4, dtype=torch.float32, device=self.device)  # stays on the device
+        self._setup(height, width, device, _lib.gs_loss_track_workspace_bytes, 4)
 
     def __call__(self, image: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_image: torch.Tensor,
                  target_range: Optional[torch.Tensor], scale: float, values: Optional[torch.Tensor] = None):
         """``target_range``: [H,W] range from the camera centre (<= 0, inf, NaN: no measurement) or None (RGB only);
         ``values``: four contiguous float32 on the device to receive the values in place of ``self.values``.  Returns
         (grad_image, grad_depth, grad_alpha)."""
-        maps = [("image", image, 3), ("depth", depth, 0), ("alpha", alpha, 0), ("target_image", target_image, 3)]
-        if target_range is not None:
-            maps.append(("target_range", target_range, 0))
-        for name, t, c in maps:
-            self._check_map(name, t, (self.H, self.W, 3) if c else (self.H, self.W), sep=", ")
-        values = self.values if values is None else values
-        if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous() or values.numel() != 4:
-            raise RuntimeError("values must be four contiguous float32 on the device")
-        _lib.check(_lib.gs_loss_track(image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
-                                      target_range.data_ptr() if target_range is not None else None, self.H, self.W,
-                                      self.alpha_min, self.color_weight, self.depth_weight, self.depth_gate, float(scale),
-                                      self.grad_image.data_ptr(), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
-                                      values.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                      torch.cuda.current_stream().cuda_stream), "gs_loss_track")
+        values = self._checked(image, depth, alpha, target_image, target_range, values)
+        _lib.call("gs_loss_track", image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
+                  target_range.data_ptr() if target_range is not None else None, self.H, self.W, self.alpha_min,
+                  self.color_weight, self.depth_weight, self.depth_gate, float(scale), self.grad_image.data_ptr(),
+                  self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(), values.data_ptr(), self._ws.data_ptr(),
+                  self._ws.numel(), stream())
         return self.grad_image, self.grad_depth, self.grad_alpha
 
 
-class GatedTrackLoss(_MapLoss):
+class GatedTrackLoss(_TrackMaps):
     """``TrackLoss`` with each term gated at a multiple of the frame's own median residual (gs_loss_track_gated,
     include/gs_abi.h): depth counts where |D / A - z| <= max(``depth_gate_k`` x its lower median over the covered, measured
     pixels, ``depth_gate_floor``), colour where sum_c |I_c - T_c| <= max(``color_gate_k`` x its lower median over the covered
@@ -354,33 +357,23 @@ class GatedTrackLoss(_MapLoss):
         self.depth_gate_k, self.color_gate_k = float(depth_gate_k), float(color_gate_k)
         self.depth_gate_floor, self.color_gate_floor = float(depth_gate_floor), float(color_gate_floor)
         self.couple = bool(couple)
-        self._setup(height, width, device, _lib.gs_loss_track_gated_workspace_bytes)
-        self.grad_image = self._new(self.H, self.W, 3)
-        self.grad_depth, self.grad_alpha = self._new(self.H, self.W), self._new(self.H, self.W)
+        self._setup(height, width, device, _lib.gs_loss_track_gated_workspace_bytes, 8)
         self.resid_depth = self._new(self.H, self.W) if keep_residuals else None
         self.resid_color = self._new(self.H, self.W) if keep_residuals else None
-        self.values = torch.zeros(8, dtype=torch.float32, device=self.device)  # stays on the device
 
     def __call__(self, image: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_image: torch.Tensor,
                  target_range: Optional[torch.Tensor], scale: float, values: Optional[torch.Tensor] = None):
         """As ``TrackLoss.__call__``; ``values``: eight contiguous float32 on the device to receive the values in place of
         ``self.values``.  Returns (grad_image, grad_depth, grad_alpha)."""
-        maps = [("image", image, 3), ("depth", depth, 0), ("alpha", alpha, 0), ("target_image", target_image, 3)]
-        if target_range is not None:
-            maps.append(("target_range", target_range, 0))
-        for name, t, c in maps:
-            self._check_map(name, t, (self.H, self.W, 3) if c else (self.H, self.W), sep=", ")
-        values = self.values if values is None else values
-        if values.dtype != torch.float32 or not values.is_cuda or not values.is_contiguous() or values.numel() != 8:
-            raise RuntimeError("values must be eight contiguous float32 on the device")
-        _lib.check(_lib.gs_loss_track_gated(
-            image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
-            target_range.data_ptr() if target_range is not None else None, self.H, self.W, self.alpha_min, self.color_weight,
-            self.depth_weight, self.depth_gate_k, self.color_gate_k, self.depth_gate_floor, self.color_gate_floor,
-            int(self.couple), float(scale), self.grad_image.data_ptr(), self.grad_depth.data_ptr(), self.grad_alpha.data_ptr(),
-            values.data_ptr(), self.resid_depth.data_ptr() if self.resid_depth is not None else None,
-            self.resid_color.data_ptr() if self.resid_color is not None else None, self._ws.data_ptr(), self._ws.numel(),
-            torch.cuda.current_stream().cuda_stream), "gs_loss_track_gated")
+        values = self._checked(image, depth, alpha, target_image, target_range, values)
+        _lib.call("gs_loss_track_gated", image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
+                  target_range.data_ptr() if target_range is not None else None, self.H, self.W, self.alpha_min,
+                  self.color_weight, self.depth_weight, self.depth_gate_k, self.color_gate_k, self.depth_gate_floor,
+                  self.color_gate_floor, int(self.couple), float(scale), self.grad_image.data_ptr(), self.grad_depth.data_ptr(),
+                  self.grad_alpha.data_ptr(), values.data_ptr(),
+                  self.resid_depth.data_ptr() if self.resid_depth is not None else None,
+                  self.resid_color.data_ptr() if self.resid_color is not None else None, self._ws.data_ptr(), self._ws.numel(),
+                  stream())
         return self.grad_image, self.grad_depth, self.grad_alpha
 
 
@@ -586,19 +579,14 @@ class Trainer:
         fp = self._free.get(camera_id)
         if fp is not None:
             return fp.adam.rot.copy(), fp.adam.tran.copy()
-        cam = self.cameras[camera_id]
-        return (np.array(cam.rot, np.float64).reshape(3, 3), np.array(cam.tran, np.float64).reshape(3))
+        return pose64(self.cameras[camera_id].rot, self.cameras[camera_id].tran)
 
     def _settle_pose(self, camera_id):
         """Apply the pose update a free view's last step left pending (waits for that step's 48-byte copy)."""
         fp = self._free.get(camera_id)
         if fp is None or not fp.settle():
             return
-        rot, tran = fp.adam.rot, fp.adam.tran
-        cam = copy.copy(self.cameras[camera_id])
-        cam.rot = np.ascontiguousarray(rot, np.float32).reshape(3, 3)
-        cam.tran = np.ascontiguousarray(tran, np.float32).reshape(3)
-        self.cameras[camera_id] = cam
+        self.cameras[camera_id] = posed(self.cameras[camera_id], fp.adam.rot, fp.adam.tran)
 
     @property
     def n_gaussians(self) -> int:
@@ -1064,10 +1052,10 @@ class Trainer:
 
         self.flat.finish_gather()
         if extrinsics is not None and intrinsics is not None:
-            to_np = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float32)  # noqa: E731
+            rot, tran = pose64(extrinsics["rot"], extrinsics["tran"])
             cam = Camera(int(intrinsics["width"]), int(intrinsics["height"]), float(intrinsics["focal_x"]),
-                         float(intrinsics["focal_y"]), to_np(extrinsics["rot"]).reshape(3, 3),
-                         to_np(extrinsics["tran"]).reshape(3), near=getattr(self.cameras[0], "near", 0.3) if self.cameras else 0.3,
+                         float(intrinsics["focal_y"]), rot.astype(np.float32), tran.astype(np.float32),
+                         near=getattr(self.cameras[0], "near", 0.3) if self.cameras else 0.3,
                          cx=intrinsics.get("cx"), cy=intrinsics.get("cy"))  # (optional: the principal point in pixels)
         elif camera_id is not None:
             self._settle_pose(camera_id)

@@ -8,6 +8,8 @@
     const uint4 rc = rects[pid];
     if (rc.z == 0) return;  // culled by the frustum test: zero gradient (written by the projection backward)
     const uint64_t off = pair_offsets[pid], cnt = rc.w;
+    constexpr bool gd_known = false;  // (the rows are walked here)
+    constexpr float gd_sum = 0.f;
 #include "aux_depth_term.inc"
 #pragma unroll
     for (int c = 0; c < 3; ++c) grad_pos[pid * 3 + c] += gpa[c];

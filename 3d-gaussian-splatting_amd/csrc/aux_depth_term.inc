@@ -4,11 +4,14 @@
 // in aux_depth_backward_body.inc (the kernels behind gs_frame_backward) and in the AUX variant of the fused optimizer step
 // (frame_project_backward_body.inc): ONE statement of the row walk, so both add the same rows in the same order.
 // Expects in scope: CDIM, P, D, pid, rc (the visible Gaussian's rectangle record), off, cnt, `const float *rows`, stop_keys,
-// rec_geom, max_pairs, pos, and GS_PB_SH_BIG (project_bwd.hip, in front of sh_big_rows_kernel).  Leaves gd, p, pc, gc and
-// gpa behind.
+// rec_geom, max_pairs, pos, GS_PB_SH_BIG (project_bwd.hip, in front of sh_big_rows_kernel), and `gd_known` / `gd_sum`: where
+// gd_known holds, the caller has already added these rows in this order and g_d is gd_sum (the pose-only kernel's own row
+// walk; everywhere else a constant false).  Leaves gd, p, pc, gc and gpa behind.
     constexpr int RWF = gs_row_floats(CDIM), SLOT = gs_row_aux_depth(CDIM);
     float gd = 0.f;
-    if (CDIM != 3 && cnt > (uint64_t)GS_PB_SH_BIG) {
+    if (gd_known) {
+        gd = gd_sum;
+    } else if (CDIM != 3 && cnt > (uint64_t)GS_PB_SH_BIG) {
         if (off < max_pairs) gd = rows[off * RWF + SLOT];
     } else {
         const uint32_t *stop_depth = reinterpret_cast<const uint32_t *>(stop_keys), *stop_id = stop_depth + P.ntx * P.nty;

@@ -1,13 +1,19 @@
 // frame_project_backward_body.inc -- the body of frame_project_backward_kernel, of its GS_FRAME_POSE_GRAD variant
-// frame_project_backward_pose_kernel and of the fused step's variants frame_project_backward_adam_aux_kernel and
-// frame_project_backward_adam_pose_kernel (project_bwd.hip), expanded in place in all of them.  Expects in scope: the kernel's
-// parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE`, `constexpr bool AUX`, `pose_part` and `pose_part_aux`.  (Included rather than called: an
+// frame_project_backward_pose_kernel, of the fused step's variants frame_project_backward_adam_aux_kernel and
+// frame_project_backward_adam_pose_kernel and of the pose-only frame_pose_backward_kernel (project_bwd.hip), expanded in place
+// in all of them.  Expects in scope: the kernel's parameters, CDIM / PART / BLOCK / ADAM, `constexpr bool POSE`,
+// `constexpr bool AUX`, `constexpr bool POSE_ONLY`, `pose_part` and `pose_part_aux`.  (Included rather than called: an
 // inlined device function leaves the kernel without the flag with other register assignments than before it existed;
 // expanded in place, it compiles to the same code.)
     static_assert(ADAM == 0 || PART == 0, "the fused optimizer step: everything in one kernel");
     static_assert(!POSE || (CDIM == 3 && (ADAM == 0 ? PART != 2 : PART == 0)),
                   "pose gradients: rgb colours; the geometry part, or everything in front of the fused step");
-    static_assert(!AUX || ADAM != 0, "the depth map's position term is added here only in front of the fused step");
+    static_assert(!AUX || ADAM != 0 || POSE_ONLY,
+                  "the depth map's term is formed here only in front of the fused step or in the pose-only kernel");
+    // POSE_ONLY (frame_pose_backward_kernel): the row sums and the pose terms alone -- no projection or activation backward,
+    // no colour part, nothing stored per Gaussian; AUX: the depth map's row as well, as in front of the fused step
+    static_assert(!POSE_ONLY || (POSE && CDIM == 3 && ADAM == 0 && PART == 1), "pose only: rgb colours, the geometry part's sums");
+    static_assert(gs_row_aux_depth(3) == 10, "POSE_ONLY: the depth float of an rgb row is r2.z of the row walk below");
     // rgb rows (round 4): only rows that EXIST are fetched.  71 % of the pairs of the 2.4 M scene lie behind their
     // tile's stop point and their rows are uninitialised memory; round 3 streamed all of them through LDS and looked at
     // the flags afterwards (PMC: 916 MB of traffic against 316 MB algorithmic).  Whether the row of pair (tile, g) was
@@ -222,6 +228,8 @@
                         d0.x += r0.x; d0.y += r0.y; d0.z += r0.z; d0.w += r0.w;
                         d1.x += r1.x; d1.y += r1.y; d1.z += r1.z; d1.w += r1.w;
                         d2.x += r2.x; d2.y += r2.y;
+                        // (the depth float: the rows aux_depth_term.inc walks, in its order, from zero -- the same bits)
+                        if constexpr (POSE_ONLY && AUX) d2.z += r2.z;
                         cm &= cm - 1;  // consumed
                         ++done;
                     }
@@ -444,7 +452,12 @@
         float4 q4 = quat[pid];
         float qraw[4] = {q4.x, q4.y, q4.z, q4.w};
         activate(qraw, sraw, P.scale_act, q, s);
-        float gi[3] = {d0.x, d0.y, 0.0f}, g2[4] = {d0.z, d0.w, d1.x, d1.y}, gq[4], gs[3];
+        float gi[3] = {d0.x, d0.y, 0.0f}, g2[4] = {d0.z, d0.w, d1.x, d1.y};
+        if constexpr (POSE_ONLY) {
+            // (AUX: U[a][0] stated explicitly, as in front of the fused step -- pose_terms, project_bwd.hip)
+            pose_terms<AUX>(p, q, s, P.cam, gi, g2, pose);
+        } else {
+        float gq[4], gs[3];
         project_backward(p, q, s, P.cam, gi, g2, gp, gq, gs);
         if constexpr (POSE) pose_terms<POSE && AUX>(p, q, s, P.cam, gi, g2, pose);
         // q_hat = q / |q|  ->  dq = (dq_hat - q_hat (q_hat . dq_hat)) / |q|
@@ -458,6 +471,7 @@
                 gsr[k] = sraw[k] > 0 ? gs[k] : (sraw[k] < 0 ? -gs[k] : 0.0f);
             else  // trunc_exp backward (renderer.py:97-100): g * exp(clamp(x, -1, 1))
                 gsr[k] = gs[k] * expf(fminf(fmaxf(sraw[k], -1.0f), 1.0f));
+        }
         }
     }
     if (vis && PART != 1) {
@@ -486,6 +500,10 @@
             float ga[3];
             {
                 const float *const rows = rows_f;
+                // (POSE_ONLY: a Gaussian its own thread summed has g_d from that walk; one the whole workgroup summed -- a
+                // tree, not this order -- walks its rows here)
+                [[maybe_unused]] const bool gd_known = POSE_ONLY && !big;
+                [[maybe_unused]] const float gd_sum = d2.z;
 #include "aux_depth_term.inc"
 #pragma unroll
                 for (int c = 0; c < 3; ++c) ga[c] = gpa[c];
@@ -508,6 +526,7 @@
             if (!valid) return;
         }  // (the fused step's LDS hand-over needs every lane of the wave: its invalid threads leave in the epilogue)
     }
+    if constexpr (POSE_ONLY) return;  // both rows are in: nothing is stored per Gaussian
     if constexpr (ADAM != 0) {
         // ---- the optimizer step of the wave's 64 x 14 parameters (gs_adam_one: torch's _single_tensor_adam); a culled
         // Gaussian takes its zero-gradient step (momentum), as gs_adam_step gives it.  Every global access is a whole

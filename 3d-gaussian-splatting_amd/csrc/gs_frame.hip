@@ -633,6 +633,31 @@ extern "C" int gs_frame_backward_adam_pose(const gs_frame *f, const float *grad_
     return frame_backward_adam_impl(__func__, f, grad_image, adam, (hipStream_t)stream);
 }
 
+// GS_FRAME_POSE_GRAD frames (rgb colours), the pose gradient alone: the raster backward (part 0) and ONE kernel for the
+// partial rows (gs_stage_pose_only_backward) in front of the reduction.  No per-Gaussian gradient exists afterwards.
+extern "C" int gs_frame_backward_pose(const gs_frame *f, const float *grad_image, int32_t part, gs_stream_t stream) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_backward_pose needs a training forward (image_padded kept)");
+    GS_CHECK_ARG(part == 0 || part == GS_BWD_GEOMETRY, "part must be 0 or GS_BWD_GEOMETRY");
+    GS_CHECK_ARG((f->flags & GS_FRAME_POSE_GRAD) != 0,
+                 "the frame is not flagged GS_FRAME_POSE_GRAD (there is no other gradient this entry point writes)");
+    if (f->color_dim != 3) return refuse_sh_pose(__func__);
+    GS_CHECK_ARG(part == GS_BWD_GEOMETRY || grad_image, "null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (f->N == 0) return zero_pose_grad(f, s);
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
+    if (part == 0) {
+        uint64_t *skeys, *okeys;
+        uint32_t *sids;
+        sorted_buffers(f, ws, &skeys, &sids, &okeys);
+        const bool prepared = join_prepared(f, s);
+        if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
+    }
+    if ((rc = gs_stage_pose_only_backward(f, ws, s))) return rc;
+    return gs_stage_pose_finalize(f, ws, s);
+}
+
 extern "C" int gs_frame_backward_part(const gs_frame *f, const float *grad_image, float *grad_pos, float *grad_quat,
                                       float *grad_scale, float *grad_opa, float *grad_rgb, int32_t part,
                                       gs_stream_t stream) {

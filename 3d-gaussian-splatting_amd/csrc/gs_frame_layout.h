@@ -571,6 +571,7 @@ int gs_stage_aux_depth_backward(const gs_frame *f, const gs_frame_ws &ws, float 
 int gs_stage_project_backward_pose(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, float *grad_quat,
                                    float *grad_scale, float *grad_opa, float *grad_rgb, int part, hipStream_t stream);
 int gs_stage_aux_depth_pose_backward(const gs_frame *f, const gs_frame_ws &ws, float *grad_pos, hipStream_t stream);
+int gs_stage_pose_only_backward(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
 int gs_stage_pose_finalize(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream);
 int gs_stage_raster_backward(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids,
                              const float *grad_image, hipStream_t stream, bool prepared);

@@ -115,12 +115,14 @@ __device__ __forceinline__ void project_backward(const float p[3], const float q
 // and folds into it).  With p_c = rot p + tran and cov2d = J rot C rot^T J^T, C = (R S)(R S)^T, J held fixed as above:
 //   dL/dtran = gc,   dL/drot = gc p^T + J^T (G + G^T) J rot C,   G = dL/dcov2d (g2: G00, G01, G10, G11).
 // J^T (G + G^T) J rot C = J^T K (RS)(RS)^T with K = (G + G^T) (J rot) [2x3]: ~80 FMAs.
-// U0_EXPLICIT (the fused step's AUX + POSE variant only): everything here contracts by pragma, and which product of a b + c d
-// the compiler fuses follows the operand order its optimizer leaves, which depends on the code around the call.  In every
-// other kernel that expands this function U[a][0] comes out as fma(K2, RS6, fma(K1, RS3, fl(K0 RS0))); with the depth map's
+// U0_EXPLICIT (the AUX variants of the fused step and of the pose-only kernel, no other): everything here contracts by pragma,
+// and which product of a b + c d the compiler fuses follows the operand order its optimizer leaves, which depends on the code
+// around the call.  In every other kernel that expands this function U[a][0] comes out as fma(K2, RS6, fma(K1, RS3, fl(K0 RS0))); with the depth map's
 // row walk in the same kernel the first two products change places -- the one sum of this function that moves, found by
 // comparing the kernels' machine code -- and the pose row loses its last bit against frame_project_backward_pose_kernel.
 // The flag states that sum the way the other kernels have it.  tests/test_gpu_pose_adam.py compares the rows bit for bit.
+// frame_pose_backward_kernel<true> met the same thing without project_backward around the call (one row entry of 24 lost its
+// last bit at N = 37; with the flag every row of tests/test_gpu_pose_only.py is equal); its plain variant needs no help.
 template <bool U0_EXPLICIT = false>
 __device__ __forceinline__ void pose_terms(const float p[3], const float q[4], const float s[3], const Cam &cam,
                                            const float gi[3], const float g2[4], float t[12]) {
@@ -485,7 +487,7 @@ __global__ void __launch_bounds__(BLOCK) frame_project_backward_kernel(
     float *__restrict__ grad_pos,
     float4 *__restrict__ grad_quat, float *__restrict__ grad_scale, float *__restrict__ grad_opa,
     float *__restrict__ grad_rgb, AdamFusedDev A = AdamFusedDev{}) {
-    constexpr bool POSE = false, AUX = false;
+    constexpr bool POSE = false, AUX = false, POSE_ONLY = false;
     [[maybe_unused]] float *const pose_part = nullptr, *const pose_part_aux = nullptr;
 #include "frame_project_backward_body.inc"
 }
@@ -503,7 +505,7 @@ __global__ void __launch_bounds__(BLOCK) frame_project_backward_adam_aux_kernel(
     const uint32_t *__restrict__ pair_offsets, const uint4 *__restrict__ rects, uint64_t max_pairs, AdamFusedDev A) {
     static_assert(ADAM != 0, "the fused step's variant");
     constexpr int PART = 0;
-    constexpr bool POSE = false, AUX = true;
+    constexpr bool POSE = false, AUX = true, POSE_ONLY = false;
     const int64_t g_first = 0;
     [[maybe_unused]] float *const pose_part = nullptr, *const pose_part_aux = nullptr;
     // (no gradient is stored: the names the body's unfused tail mentions)
@@ -526,7 +528,7 @@ __global__ void __launch_bounds__(256) frame_project_backward_pose_kernel(
     float4 *__restrict__ grad_quat, float *__restrict__ grad_scale, float *__restrict__ grad_opa,
     float *__restrict__ grad_rgb, float *__restrict__ pose_part) {
     constexpr int CDIM = 3, BLOCK = 256, ADAM = 0;
-    constexpr bool POSE = true, AUX = false;
+    constexpr bool POSE = true, AUX = false, POSE_ONLY = false;
     const int64_t g_first = 0;
     [[maybe_unused]] const AdamFusedDev A{};
     [[maybe_unused]] float *const pose_part_aux = nullptr;
@@ -551,8 +553,34 @@ __global__ void __launch_bounds__(256) frame_project_backward_adam_pose_kernel(
     float *__restrict__ pose_part, float *__restrict__ pose_part_aux) {
     static_assert(ADAM != 0, "the fused step's variant");
     constexpr int CDIM = 3, PART = 0, BLOCK = 256;
-    constexpr bool POSE = true;
+    constexpr bool POSE = true, POSE_ONLY = false;
     const int64_t g_first = 0;
+    // (no gradient is stored: the names the body's unfused tail mentions)
+    [[maybe_unused]] float *const grad_pos = nullptr, *const grad_scale = nullptr, *const grad_opa = nullptr, *const grad_rgb = nullptr;
+    [[maybe_unused]] float4 *const grad_quat = nullptr;
+#include "frame_project_backward_body.inc"
+}
+
+// GS_FRAME_POSE_GRAD frames whose per-Gaussian gradients nobody reads (gs_frame_backward_pose: camera tracking against a
+// frozen map), plain (AUX false) or GS_FRAME_AUX: the row sums of frame_project_backward_pose_kernel<1> and its pose terms --
+// and, AUX, those of frame_aux_depth_pose_backward_kernel, with g_d taken from the same row walk -- summed over the workgroup
+// into pose_part / pose_part_aux, the layout those two kernels leave, so pose_grad_finalize_kernel runs as it is.  No
+// projection backward, no activation backward, no colour part; nothing is stored per Gaussian and there is no gradient
+// destination.  Threads past N and culled Gaussians add zeros to both sums.  A kernel of its own name: the others keep
+// their code.  (rec_color, opa_raw and rgb_raw are the launch's common arguments; not read.)
+template <bool AUX>
+__global__ void __launch_bounds__(256) frame_pose_backward_kernel(
+    const float *pos, const float4 *quat, const float *scale,
+    int64_t n, ProjectParams P, const float4 *__restrict__ rec_geom,
+    const float4 *__restrict__ rec_color, const float4 *__restrict__ rows,
+    const unsigned long long *__restrict__ stop_keys, const float *opa_raw,
+    const float *rgb_raw, GsDistCull D,
+    const uint32_t *__restrict__ pair_offsets, const uint4 *__restrict__ rects, uint64_t max_pairs,
+    float *__restrict__ pose_part, float *__restrict__ pose_part_aux) {
+    constexpr int CDIM = 3, PART = 1, BLOCK = 256, ADAM = 0;
+    constexpr bool POSE = true, POSE_ONLY = true;
+    const int64_t g_first = 0;
+    [[maybe_unused]] const AdamFusedDev A{};
     // (no gradient is stored: the names the body's unfused tail mentions)
     [[maybe_unused]] float *const grad_pos = nullptr, *const grad_scale = nullptr, *const grad_opa = nullptr, *const grad_rgb = nullptr;
     [[maybe_unused]] float4 *const grad_quat = nullptr;
@@ -583,9 +611,9 @@ extern "C" int gs_global_culling_backward(const float *pos, const float *quat, c
 }
 
 // ================================================================= frame stages (internal)
-// One launch of frame_project_backward_kernel, frame_project_backward_adam_aux_kernel, frame_project_backward_pose_kernel or
-// frame_project_backward_adam_pose_kernel over the Gaussians below `n`: the arguments they have in common, then `tail` (what
-// each takes behind max_pairs).
+// One launch of frame_project_backward_kernel, frame_project_backward_adam_aux_kernel, frame_project_backward_pose_kernel,
+// frame_project_backward_adam_pose_kernel or frame_pose_backward_kernel over the Gaussians below `n`: the arguments they have in
+// common, then `tail` (what each takes behind max_pairs).
 template <class Kernel, class... Tail>
 static void launch_project_backward(Kernel kernel, unsigned grid, int block, hipStream_t stream, const gs_frame *f,
                                     const gs_frame_ws &ws, int64_t n, Tail... tail) {
@@ -649,6 +677,19 @@ int gs_stage_project_backward_pose(const gs_frame *f, const gs_frame_ws &ws, flo
         launch(gs_int<1>{});
     else
         launch(gs_int<0>{});
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+// The pose gradient's partial rows alone (frame_pose_backward_kernel): one row per workgroup into pw.proj, GS_FRAME_AUX a
+// second one into pw.aux -- what gs_stage_project_backward_pose(part 1) + gs_stage_aux_depth_pose_backward leave, bit for bit
+int gs_stage_pose_only_backward(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream) {
+    if (f->N <= 0) return 0;
+    const gs_frame_pose_ws pw = gs_frame_pose_carve(f->pose_workspace, f->N);
+    if (f->flags & GS_FRAME_AUX)
+        launch_project_backward(frame_pose_backward_kernel<true>, (unsigned)pw.rows, 256, stream, f, ws, f->N, pw.proj, pw.aux);
+    else
+        launch_project_backward(frame_pose_backward_kernel<false>, (unsigned)pw.rows, 256, stream, f, ws, f->N, pw.proj, pw.aux);
     GS_CHECK_LAUNCH();
     return 0;
 }

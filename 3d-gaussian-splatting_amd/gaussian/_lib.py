@@ -147,6 +147,7 @@ class GsAdamFused(C.Structure):
 gs_frame_backward_adam = _sig("gs_frame_backward_adam", ci, C.POINTER(GsFrame), vp, C.POINTER(GsAdamFused), vp)
 gs_frame_backward_adam_aux = _sig("gs_frame_backward_adam_aux", ci, C.POINTER(GsFrame), vp, C.POINTER(GsAdamFused), vp)
 gs_frame_backward_adam_pose = _sig("gs_frame_backward_adam_pose", ci, C.POINTER(GsFrame), vp, C.POINTER(GsAdamFused), vp)
+gs_frame_backward_pose = _sig("gs_frame_backward_pose", ci, C.POINTER(GsFrame), vp, i32, vp)
 gs_frame_debug_tile_nproc = _sig("gs_frame_debug_tile_nproc", ci, C.POINTER(GsFrame), C.POINTER(vp))
 gs_frame_debug_bwd_exec_rows = _sig("gs_frame_debug_bwd_exec_rows", ci, C.POINTER(GsFrame), C.POINTER(vp), C.POINTER(C.c_int32))
 
@@ -323,6 +324,7 @@ EXPORTS = [
     "gs_adam_step_multi",
     "gs_frame_backward_profile", "gs_adam_step", "gs_adam_step_range", "gs_adam_step_sharded", "gs_frame_overflow_flag", "gs_grad_stat_update", "gs_loss_workspace_bytes", "gs_loss_l1_ssim",
     "gs_loss_depth_workspace_bytes", "gs_loss_depth", "gs_frame_backward_adam_aux", "gs_frame_backward_adam_pose",
+    "gs_frame_backward_pose",
     "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
     "gs_loss_track_workspace_bytes", "gs_loss_track",

@@ -778,9 +778,7 @@ class FrameRenderer:
         """After ``backward(part=GS_BWD_RASTER)``: the per-Gaussian sums (projection + activation backward) of the
         Gaussians [g_begin, g_end) -- g_begin a multiple of 256 -- into ``out``; ``part`` = GS_BWD_GEOMETRY, GS_BWD_COLOR
         or (default) both in one kernel.  Any partition of the Gaussians gives exactly what ``backward`` writes."""
-        f = self._frame
-        if f is None or not f.training:
-            raise RuntimeError("backward_slice() needs a preceding forward(training=True)")
+        f = self._training_frame("backward_slice")
         if part is None:
             part = _lib.GS_BWD_GEOMETRY | _lib.GS_BWD_COLOR
         with torch.cuda.device(self.device):
@@ -824,9 +822,7 @@ class FrameRenderer:
         ``grad_pose`` = (grad_rot [3,3], grad_tran [3]) as in ``backward``: the step goes through
         gs_frame_backward_adam_pose, which also writes the gradient of the frame's pose -- that of the parameters the frame
         was rendered with, bit for bit what ``backward(..., grad_pose=...)`` writes.  rgb colours only."""
-        f = self._frame
-        if f is None or not f.training:
-            raise RuntimeError("backward_adam() needs a preceding forward(training=True)")
+        f = self._training_frame("backward_adam")
         aux = bool(f.flags & _lib.GS_FRAME_AUX)
         if not aux and (grad_depth is not None or grad_alpha is not None):
             raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
@@ -864,21 +860,11 @@ class FrameRenderer:
         raster backward (per-pair rows), then ``GS_BWD_GEOMETRY`` (pos / quat / scale) and ``GS_BWD_COLOR`` (opa /
         rgb) fill their share of ``out`` in either order, bit-identical to the one-call backward; ``grad_image``
         is only read by part 0 / GS_BWD_RASTER."""
-        f = self._frame
-        if f is None or not f.training:
-            raise RuntimeError("backward() needs a preceding forward(training=True)")
+        f = self._training_frame("backward")
         pos, quat, scale, opa, rgb = self._keep[:5]
         if out is None:
             out = tuple(torch.empty_like(t) for t in (pos, quat, scale, opa, rgb))
-        aux = bool(f.flags & _lib.GS_FRAME_AUX)
-        if not aux and (grad_depth is not None or grad_alpha is not None):
-            raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
-        if part in (0, _lib.GS_BWD_RASTER):
-            if aux:
-                grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
-            grad_image = self._checked_grad_image(f, grad_image, none_ok=aux)
-            if grad_image is None:
-                grad_image = torch.zeros(f.height, f.width, 3, device=self.device, dtype=torch.float32)
+        grad_image, grad_depth, grad_alpha = self._raster_inputs(f, part, grad_image, grad_depth, grad_alpha)
         for t, ref in zip(out, (pos, quat, scale, opa, rgb)):
             if t.shape != ref.shape or t.dtype != torch.float32 or not t.is_contiguous():
                 raise RuntimeError("gradient destinations must match the parameters")
@@ -895,6 +881,44 @@ class FrameRenderer:
         if part in (0, _lib.GS_BWD_RASTER):
             self._bwd_serial = self._frame_serial  # this frame's bucket counter is final once the stream gets here
         return out
+
+    def backward_pose(self, grad_image, grad_pose, part: int = 0, grad_depth=None, grad_alpha=None):
+        """dL/d(image) -> ``grad_pose`` = (grad_rot [3,3], grad_tran [3]) and nothing else (gs_frame_backward_pose, include/
+        gs_abi.h): the pose gradient ``backward(..., grad_pose=...)`` writes, bit for bit, for a caller that holds the map
+        fixed -- no per-Gaussian gradient is computed, and no per-Gaussian tensor is allocated or written.  rgb colours only.
+        ``part`` 0 = the raster backward and the pose gradient (``grad_depth`` / ``grad_alpha`` / a None ``grad_image`` as in
+        ``backward``); ``GS_BWD_GEOMETRY`` = the pose gradient from the rows a preceding ``backward(part=GS_BWD_RASTER)`` of
+        this frame left."""
+        f = self._training_frame("backward_pose")
+        grad_image, grad_depth, grad_alpha = self._raster_inputs(f, part, grad_image, grad_depth, grad_alpha)
+        f = self._pose_frame(f, grad_pose, part)
+        with torch.cuda.device(self.device):
+            _lib.call("gs_frame_backward_pose", C.byref(f), grad_image.data_ptr() if grad_image is not None else None,
+                      int(part), self._stream().cuda_stream)
+        if part == 0:
+            self._bwd_serial = self._frame_serial
+        return grad_pose
+
+    def _training_frame(self, who: str):
+        """The descriptor of the last forward, which ``who`` needs to have been a training forward."""
+        f = self._frame
+        if f is None or not f.training:
+            raise RuntimeError(f"{who}() needs a preceding forward(training=True)")
+        return f
+
+    def _raster_inputs(self, f, part, grad_image, grad_depth, grad_alpha):
+        """What the raster backward of ``backward`` / ``backward_pose`` reads, checked: the aux maps (wired into ``f``) and
+        dL/d(image), zeros for None on an aux frame -- for the parts that run it (0, GS_BWD_RASTER); the others read none."""
+        aux = bool(f.flags & _lib.GS_FRAME_AUX)
+        if not aux and (grad_depth is not None or grad_alpha is not None):
+            raise RuntimeError("grad_depth / grad_alpha need a preceding forward(..., aux=True)")
+        if part in (0, _lib.GS_BWD_RASTER):
+            if aux:
+                grad_depth, grad_alpha = self._aux_grad_maps(f, grad_depth, grad_alpha)
+            grad_image = self._checked_grad_image(f, grad_image, none_ok=aux)
+            if grad_image is None:
+                grad_image = torch.zeros(f.height, f.width, 3, device=self.device, dtype=torch.float32)
+        return grad_image, grad_depth, grad_alpha
 
     def _pose_frame(self, f, grad_pose, part):
         """A copy of the descriptor ``f`` flagged GS_FRAME_POSE_GRAD, with the destinations ``grad_pose`` and the

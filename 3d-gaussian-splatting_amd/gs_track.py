@@ -10,6 +10,11 @@ With ``TrackOptions.depth_gate_k`` or ``color_gate_k`` above zero the loss is gs
 term counts where its residual is at most k x the frame's own median residual, selected on the device every iteration; the
 buffer then holds 20 floats and the read 80 bytes -- still one read per iteration.
 
+With ``TrackOptions.pose_only`` the two backward calls are one ``backward_pose(part=0)`` (gs_frame_backward_pose): the raster
+backward, then ONE kernel that sums every Gaussian's rows and forms its pose terms -- the depth map's as well -- and the
+reduction.  The same pose gradient bit for bit, so the same track; no projection or activation backward runs, no
+per-Gaussian gradient is stored and the Tracker allocates no per-Gaussian scratch.  Off by default.
+
 The colour part of the backward (GS_BWD_COLOR: opacity and colour gradients) is never run: nobody reads it.  dL/drot,
 dL/dtran and the four loss values are views of one 16-float device buffer that a single copy brings into pinned host memory.
 The pose step runs on the host in float64: rot = exp([w]x) R re-linearised at w = 0 every iteration, Adam on (w, tran),
@@ -52,6 +57,9 @@ class TrackOptions:
     depth_weight: float = 1.0       # x |D / A - z| / (H W)
     depth_gate: float = 0.0         # <= 0: off; else depth residuals beyond it do not count
     max_pairs: int = 1 << 20        # the renderer's initial pair capacity (it grows by itself)
+    # the pose gradient through FrameRenderer.backward_pose: no per-Gaussian gradient is computed or stored (bit for bit the
+    # same pose gradient, so the same track)
+    pose_only: bool = False
     # coarse to fine: stages (pyramid level, iterations) in order, levels strictly decreasing; () (the default): no pyramid,
     # ``iterations`` full-resolution iterations.  With a schedule ``iterations`` is not read: the total is the stages' sum
     pyramid: Tuple[Tuple[int, int], ...] = ()
@@ -278,6 +286,8 @@ class Tracker:
         for name, t in zip(("pos", "quat", "scale", "opa", "rgb"), params):
             check_tensor(name, t)
         self.params = tuple(t.detach() for t in params)
+        if self.opt.pose_only:
+            return  # (backward_pose has no per-Gaussian destination)
         if self._scratch is None or any(s.shape != p.shape for s, p in zip(self._scratch, self.params)):
             # the per-Gaussian gradient rows the backward writes on its way to the pose gradient: nobody reads them
             self._scratch = tuple(torch.empty_like(p) for p in self.params)
@@ -320,8 +330,11 @@ class Tracker:
         img, _, depth, alpha = r.forward(*self.params, cam, training=True, aux=True)
         with torch.cuda.device(self.device):
             gi, gd, ga = loss(img, depth, alpha, image, range_map, scale, values=self._values)
-        r.backward(gi, out=self._scratch, part=_lib.GS_BWD_RASTER, grad_depth=gd, grad_alpha=ga)
-        r.backward(None, out=self._scratch, part=_lib.GS_BWD_GEOMETRY, grad_pose=self._grad_pose)
+        if self.opt.pose_only:
+            r.backward_pose(gi, self._grad_pose, 0, grad_depth=gd, grad_alpha=ga)
+        else:
+            r.backward(gi, out=self._scratch, part=_lib.GS_BWD_RASTER, grad_depth=gd, grad_alpha=ga)
+            r.backward(None, out=self._scratch, part=_lib.GS_BWD_GEOMETRY, grad_pose=self._grad_pose)
         self._host.copy_(self._dev)  # (device -> pinned host: returns when the 64 -- gated: 80 -- bytes have landed)
         return self._host
 

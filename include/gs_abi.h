@@ -50,6 +50,8 @@ extern "C" {
  *   gs_prune_classify and gs_prune_apply with gs_prune_opts / gs_prune_arrays / GS_PRUNE_MAX_ARRAYS (remove Gaussians by one
  *   per-row decision and move every array that shares the row index -- parameters, optimizer moments, the densification
  *   statistic -- in one stable compaction).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_backward_pose (the pose
+ *   gradient of a GS_FRAME_POSE_GRAD frame alone, without any per-Gaussian gradient: camera tracking against a frozen map).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_backward_adam_pose (the
  *   fused training step for GS_FRAME_POSE_GRAD frames, with or without GS_FRAME_AUX: the pose gradient of a mapping step).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_overlap,
@@ -331,6 +333,8 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        GS_E_UNSUPPORTED (a frame in slices has no point at which all partial sums are in)
                                        and so do gs_frame_backward_adam and gs_frame_backward_adam_aux: the fused training
                                        step of a flagged frame is gs_frame_backward_adam_pose, which writes both as well.
+                                       gs_frame_backward_pose writes both and nothing else: the same bits without the
+                                       per-Gaussian gradients, for a caller that holds the map fixed.
                                        All refusals come before anything is enqueued.
                                        Frames without the flag run exactly the kernels they ran before it existed. */
 
@@ -755,6 +759,22 @@ int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_image, const
  * NULL or invalid `adam`; GS_E_UNSUPPORTED with SH colours (color_dim 27 / 48: the image also depends on the pose through
  * the pixels' ray directions).  Everything is checked before anything is enqueued. */
 int gs_frame_backward_adam_pose(const gs_frame *f, const float *grad_image, const gs_adam_fused *adam, gs_stream_t stream);
+
+/* The pose gradient of a GS_FRAME_POSE_GRAD training frame (rgb colours; with or without GS_FRAME_AUX) and nothing else, for a
+ * caller that holds the map fixed (camera tracking): no per-Gaussian gradient is computed, stored or given a destination.
+ *   part 0               : the raster backward -- the stage gs_frame_backward_part(GS_BWD_RASTER) runs, with GS_FRAME_AUX
+ *                          reading f->grad_depth / f->grad_alpha as they are; grad_image must not be NULL --, then ONE kernel
+ *                          that sums every Gaussian's rows, forms its pose terms (with GS_FRAME_AUX the depth map's as well)
+ *                          and leaves the partial rows, then their reduction into f->grad_rot / f->grad_tran;
+ *   part GS_BWD_GEOMETRY : that kernel and the reduction, from the rows a preceding gs_frame_backward_part(GS_BWD_RASTER) of
+ *                          the same frame left; grad_image is not read.
+ * f->grad_rot / f->grad_tran and every partial row of the pose workspace are bit for bit what
+ * gs_frame_backward_part(GS_BWD_GEOMETRY) -- and so gs_frame_backward and gs_frame_backward_adam_pose -- leave for the same
+ * frame.  N = 0 and an overflowed frame get zeros.  Refusals, all before anything is enqueued, the first that applies: an
+ * invalid descriptor (the pose fields included); GS_E_INVALID for a frame that is not a training frame, a `part` other than 0
+ * or GS_BWD_GEOMETRY, a frame without GS_FRAME_POSE_GRAD; GS_E_UNSUPPORTED with SH colours; GS_E_INVALID for a NULL
+ * grad_image with part 0. */
+int gs_frame_backward_pose(const gs_frame *f, const float *grad_image, int32_t part, gs_stream_t stream);
 
 /* Device address of the frame's overflow counter (inside the caller's workspace; 64-bit, 0 = the last forward of this
  * frame description fitted its pair capacity, else the pair count it would have needed).  No launch, no copy. */

@@ -23,7 +23,7 @@
 // alpha = 0 once that T has reached the 1e-4 stop.  Pixels of the padded border count for nothing.
 #include <cmath>
 
-#include "raster_common.h"
+#include "raster_bwd_common.h"  // bwd_frame_grid
 
 namespace {
 
@@ -268,24 +268,12 @@ int gs_stage_contrib(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *s
     uint4 *pair_rows = (uint4 *)((char *)workspace + CONTRIB_HEADER);
     int rc = gs_stage_contrib_prepare(f, ws, sorted_ids, prepared, n_own, stream);
     if (rc) return rc;
-    RasterSrc S = {};
-    S.ids = sorted_ids;
-    S.geom = ws.rec_geom;
-    RasterGeom G = {};
-    G.padW = FG.padW;
-    G.padH = FG.padH;
-    G.ntx = FG.ntx;
-    G.nty = FG.nty;
-    G.width = f->width;
-    G.height = f->height;
-    G.crop_top = FG.crop_top;
-    G.crop_left = FG.crop_left;
-    G.focal_x = f->focal_x;
-    G.focal_y = f->focal_y;
+    RasterSrc S;
+    RasterGeom G;
+    gs_frame_raster_args(f, ws, sorted_ids, S, G);
     const ContribIn I = {ws.ckpt, ws.bucket_offsets, ws.bucket_info, ws.pair_offsets, ws.rects, (uint64_t)f->max_pairs};
     // the grid of the one-wave-per-bucket backward kernels: the list's capacity, capped (the kernel strides over the list)
-    const int64_t cap = ws.max_buckets > 0 ? ws.max_buckets : 1;
-    hipLaunchKernelGGL(contrib_pair_kernel, dim3((unsigned)(cap < 40960 ? cap : 40960)), dim3(64), 0, stream, S, G, I, w_min,
+    hipLaunchKernelGGL(contrib_pair_kernel, dim3(bwd_frame_grid(ws.max_buckets)), dim3(64), 0, stream, S, G, I, w_min,
                        pair_rows);
     GS_CHECK_LAUNCH();
     hipLaunchKernelGGL(contrib_gaussian_kernel, dim3((unsigned)gs_div_up(f->N, 256)), dim3(256), 0, stream, ws.rects,

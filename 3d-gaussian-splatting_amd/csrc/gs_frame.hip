@@ -21,6 +21,7 @@
 
 #include "gs_common.h"
 #include "gs_frame_layout.h"
+#include "raster_bwd_common.h"  // gs_bwd_mfma_slots
 
 static thread_local char g_err[512] = "";
 
@@ -285,6 +286,16 @@ static bool join_prepared(const gs_frame *f, hipStream_t s) {
     return hipStreamWaitEvent(s, a->done, 0) == hipSuccess;
 }
 
+// The raster backward of a carved training frame on `s`, behind every refusal of its entry point: the sorted ids, the
+// preparation joined from the side stream or issued inline, the kernels.
+static int raster_backward(const gs_frame *f, const gs_frame_ws &ws, const float *grad_image, hipStream_t s) {
+    uint64_t *skeys, *okeys;
+    uint32_t *sids;
+    sorted_buffers(f, ws, &skeys, &sids, &okeys);
+    const bool prepared = join_prepared(f, s);
+    return gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared);
+}
+
 // The forward in two phases: PROJECT (cull + project + activations + level-1 count; in the strip variant it may be
 // issued as several ranges of slices of the Gaussian array, in any order, slice 0's range first) and REST
 // (binning, per-tile sort, compositing).  gs_frame_forward = both; gs_frame_forward_project / _rest expose them to the
@@ -456,15 +467,11 @@ static int frame_backward_impl(const gs_frame *f, const float *grad_image, float
     const bool pose_out = pose && (part == 0 || part == GS_BWD_GEOMETRY);  // the parts that write grad_rot / grad_tran
     if (f->N == 0) return pose_out ? zero_pose_grad(f, s) : 0;
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
-    uint64_t *skeys, *okeys;
-    uint32_t *sids;
-    sorted_buffers(f, ws, &skeys, &sids, &okeys);
     StageTimer tm(stage_ms != nullptr, s);
     tm.mark();
     if (part == 0 || part == GS_BWD_RASTER) {
         GS_CHECK_ARG(g_begin == 0 && g_end == f->N, "the raster backward has no Gaussian range");
-        const bool prepared = join_prepared(f, s);
-        if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
+        if ((rc = raster_backward(f, ws, grad_image, s))) return rc;
     }
     tm.mark();
     if (pose_out) {
@@ -586,11 +593,7 @@ static int frame_backward_adam_impl(const char *entry, const gs_frame *f, const 
     if (f->N == 0) return pose ? zero_pose_grad(f, s) : 0;
     if (!grad_image && (rc = zero_image(sizeof(float) * 3 * (size_t)f->width * (size_t)f->height, &grad_image))) return rc;
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
-    uint64_t *skeys, *okeys;
-    uint32_t *sids;
-    sorted_buffers(f, ws, &skeys, &sids, &okeys);
-    const bool prepared = join_prepared(f, s);
-    if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
+    if ((rc = raster_backward(f, ws, grad_image, s))) return rc;
     if ((rc = gs_stage_project_backward_adam(f, ws, adam, s))) return rc;
     return pose ? gs_stage_pose_finalize(f, ws, s) : 0;
 }
@@ -647,13 +650,7 @@ extern "C" int gs_frame_backward_pose(const gs_frame *f, const float *grad_image
     hipStream_t s = (hipStream_t)stream;
     if (f->N == 0) return zero_pose_grad(f, s);
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, 1);
-    if (part == 0) {
-        uint64_t *skeys, *okeys;
-        uint32_t *sids;
-        sorted_buffers(f, ws, &skeys, &sids, &okeys);
-        const bool prepared = join_prepared(f, s);
-        if ((rc = gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared))) return rc;
-    }
+    if (part == 0 && (rc = raster_backward(f, ws, grad_image, s))) return rc;
     if ((rc = gs_stage_pose_only_backward(f, ws, s))) return rc;
     return gs_stage_pose_finalize(f, ws, s);
 }
@@ -774,8 +771,6 @@ extern "C" int gs_frame_debug_tile_nproc(const gs_frame *f, const uint32_t **til
     *tile_nproc = ws.tile_nproc;
     return 0;
 }
-
-int gs_bwd_mfma_slots(int color_dim, int n_tiles, int64_t max_buckets);  // raster_bwd.hip: (workgroup, wave) slots of the SH backward on the matrix pipe
 
 extern "C" int gs_frame_debug_bwd_exec_rows(const gs_frame *f, const uint32_t **exec_rows, int32_t *n_slots) {
     int rc = validate(f);

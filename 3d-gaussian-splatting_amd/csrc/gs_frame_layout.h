@@ -271,7 +271,7 @@ static constexpr int gs_row_compact(int color_dim, int f) {
 // executed pixel-row steps of the SH backward on the matrix pipe, one counter per (workgroup, wave): what its MFMA flops
 // are counted from (bench.py); [GS_BWD_EXEC_SLOTS x T] u32
 #define GS_BWD_EXEC_SLOTS 8
-// SH backward on the matrix pipe: buckets per work item (raster_bwd.hip: mfma_items_kernel); the item list holds at most
+// SH backward on the matrix pipe: buckets per work item (raster_bwd_mfma.hip: mfma_items_kernel); the item list holds at most
 // T + max_buckets / GS_MFMA_ITEM_BUCKETS items
 #define GS_MFMA_ITEM_BUCKETS 8
 
@@ -362,7 +362,7 @@ struct gs_frame_ws {
     float4 *ckpt;                  // [max_buckets][256] (T, Cr, Cg, Cb) at bucket starts
     float *rows;                   // [max_pairs][GS_ROW(C)] per-pair gradient rows in EMISSION order
     uint4 *mfma_items;             // SH frames: [T + max_buckets / 8 + 8] work items (tile, first bucket, buckets <= 8, -) of the SH
-    uint32_t *mfma_n_items;        //            backward on the matrix pipe, heavy tiles first, and their count (raster_bwd.hip)
+    uint32_t *mfma_n_items;        //            backward on the matrix pipe, heavy tiles first, and their count (raster_bwd_mfma.hip)
     uint32_t *bwd_exec_rows;       // [GS_BWD_EXEC_SLOTS x T] SH backward on the matrix pipe: pixel-row steps (16 Gaussians x 16
                                    // pixels) every wave executed in the last backward (rows whose pixels had all stopped are
                                    // left out); slot = workgroup x waves + wave.  Diagnostic (bench.py's MFMA flop count).

@@ -33,6 +33,47 @@ struct RasterGeom {
     const float *dev_rays_o, *dev_lefttop, *dev_vdx, *dev_vdy;
 };
 
+// The (S, G) of a frame-path launch, forward or backward: the frame's records under the sorted ids, its padded and cropped
+// geometry and its ray basis by value.
+static inline void gs_frame_raster_args(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids, RasterSrc &S,
+                                        RasterGeom &G) {
+    const gs_frame_geom FG = gs_frame_geometry(f);
+    S = {};
+    S.ids = sorted_ids;
+    S.geom = ws.rec_geom;
+    S.cov4 = ws.rec_cov;
+    S.color4 = ws.rec_color;
+    S.conic4 = ws.rec_conic;
+    S.sh = f->rgb;
+    G = {};
+    G.padW = FG.padW;
+    G.padH = FG.padH;
+    G.ntx = FG.ntx;
+    G.nty = FG.nty;
+    G.width = f->width;
+    G.height = f->height;
+    G.crop_top = FG.crop_top;
+    G.crop_left = FG.crop_left;
+    G.focal_x = f->focal_x;
+    G.focal_y = f->focal_y;
+    for (int i = 0; i < 3; ++i) {
+        G.rays_o[i] = f->rays_o[i];
+        G.lefttop[i] = f->lefttop[i];
+        G.vdx[i] = f->vec_dx[i];
+        G.vdy[i] = f->vec_dy[i];
+    }
+}
+// The (S, G) of a reference-API call (gs_draw / gs_draw_backward, raster_fwd.hip): attributes in sorted order, whole tiles,
+// and with SH colours the ray basis.  Nonzero: refused (SH without the basis), the error set under the name `entry`.
+int gs_ref_raster_args(const char *entry, const float *pos, const float *rgb, const float *opa, const float *cov, int32_t h,
+                       int32_t w, float focal_x, float focal_y, int use_sh_coeff, const float *rays_o,
+                       const float *lefttop_pos, const float *vec_dx, const float *vec_dy, RasterSrc &S, RasterGeom &G);
+// The reference API's forward (raster_fwd.hip); gs_draw_backward replays it for the checkpoints (`ckpt` != NULL).  `exact`:
+// the reference's `fast = 0` flavour of the exponential (double division + double exp per pixel, gaussian.cu:922-923).
+int gs_raster_forward_ref(const RasterSrc &S, const RasterGeom &G, const int32_t *accum, float *res, int use_sh,
+                          int sigmoid, int weight_normalize, float4 *ckpt, uint32_t *tile_nproc,
+                          hipStream_t stream, int exact);
+
 struct GaussianRec {
     float x, y, a, b, c, d, opa;
 };

@@ -991,6 +991,35 @@ int gs_raster_forward_ref(const RasterSrc &S, const RasterGeom &G, const int32_t
     return 0;
 }
 
+int gs_ref_raster_args(const char *entry, const float *pos, const float *rgb, const float *opa, const float *cov, int32_t h,
+                       int32_t w, float focal_x, float focal_y, int use_sh_coeff, const float *rays_o,
+                       const float *lefttop_pos, const float *vec_dx, const float *vec_dy, RasterSrc &S, RasterGeom &G) {
+    S = {};
+    S.pos = pos;
+    S.rgb = rgb;
+    S.opa = opa;
+    S.cov = cov;
+    G = {};
+    G.padW = w;
+    G.padH = h;
+    G.ntx = w / 16;
+    G.nty = h / 16;
+    G.focal_x = focal_x;
+    G.focal_y = focal_y;
+    if (use_sh_coeff) {
+        if (!(rays_o && lefttop_pos && vec_dx && vec_dy)) {
+            gs_set_error("%s: invalid argument: %s", entry, "SH needs the ray basis");
+            return GS_E_INVALID;
+        }
+        // the basis stays on the device: the kernels load it (raster_common.h), the call never synchronises
+        G.dev_rays_o = rays_o;
+        G.dev_lefttop = lefttop_pos;
+        G.dev_vdx = vec_dx;
+        G.dev_vdy = vec_dy;
+    }
+    return 0;
+}
+
 extern "C" int gs_draw(const float *pos, const float *rgb, const float *opa, const float *cov,
                        const int32_t *tile_n_point_accum, float *res, int32_t h, int32_t w, int64_t M,
                        float focal_x, float focal_y, int weight_normalize, int sigmoid, int fast,
@@ -1002,28 +1031,13 @@ extern "C" int gs_draw(const float *pos, const float *rgb, const float *opa, con
     GS_CHECK_ARG(tile_n_point_accum && res, "null pointer");
     GS_CHECK_ARG(M == 0 || (pos && rgb && opa && cov), "null pointer");
     GS_CHECK_ARG(((uintptr_t)cov & 15) == 0, "cov must be 16-byte aligned");
-    RasterSrc S = {};
-    S.pos = pos;
-    S.rgb = rgb;
-    S.opa = opa;
-    S.cov = cov;
-    RasterGeom G = {};
-    G.padW = w;
-    G.padH = h;
-    G.ntx = w / 16;
-    G.nty = h / 16;
-    G.focal_x = focal_x;
-    G.focal_y = focal_y;
-    if (use_sh_coeff) {
-        GS_CHECK_ARG(rays_o && lefttop_pos && vec_dx && vec_dy, "SH needs the ray basis");
-        // the basis stays on the device: the kernels load it (raster_common.h), the call never synchronises
-        G.dev_rays_o = rays_o;
-        G.dev_lefttop = lefttop_pos;
-        G.dev_vdx = vec_dx;
-        G.dev_vdy = vec_dy;
-    }
-    int rc = gs_raster_forward_ref(S, G, tile_n_point_accum, res, use_sh_coeff, sigmoid, weight_normalize, nullptr,
-                                   nullptr, (hipStream_t)stream, fast ? 0 : 1);
+    RasterSrc S;
+    RasterGeom G;
+    int rc = gs_ref_raster_args(__func__, pos, rgb, opa, cov, h, w, focal_x, focal_y, use_sh_coeff, rays_o, lefttop_pos, vec_dx,
+                                vec_dy, S, G);
+    if (rc) return rc;
+    rc = gs_raster_forward_ref(S, G, tile_n_point_accum, res, use_sh_coeff, sigmoid, weight_normalize, nullptr, nullptr,
+                               (hipStream_t)stream, fast ? 0 : 1);
     if (rc) {
         gs_set_error("gs_draw: unsupported flag combination");
         return rc;
@@ -1035,30 +1049,9 @@ extern "C" int gs_draw(const float *pos, const float *rgb, const float *opa, con
 int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint32_t *sorted_ids,
                             hipStream_t stream, bool second_pass) {
     gs_frame_geom FG = gs_frame_geometry(f);
-    RasterSrc S = {};
-    S.ids = sorted_ids;
-    S.geom = ws.rec_geom;
-    S.cov4 = ws.rec_cov;
-    S.color4 = ws.rec_color;
-    S.conic4 = ws.rec_conic;
-    S.sh = f->rgb;
-    RasterGeom G = {};
-    G.padW = FG.padW;
-    G.padH = FG.padH;
-    G.ntx = FG.ntx;
-    G.nty = FG.nty;
-    G.width = f->width;
-    G.height = f->height;
-    G.crop_top = FG.crop_top;
-    G.crop_left = FG.crop_left;
-    G.focal_x = f->focal_x;
-    G.focal_y = f->focal_y;
-    for (int i = 0; i < 3; ++i) {
-        G.rays_o[i] = f->rays_o[i];
-        G.lefttop[i] = f->lefttop[i];
-        G.vdx[i] = f->vec_dx[i];
-        G.vdy[i] = f->vec_dy[i];
-    }
+    RasterSrc S;
+    RasterGeom G;
+    gs_frame_raster_args(f, ws, sorted_ids, S, G);
     // dense frames: tiles still alive after GS_LONG_MIN Gaussians hand the rest of their list to the segment kernels
     // (GS_FRAME_AUX frames walk every list with one wave: the segment kernels carry no depth / alpha)
     const bool aux = (f->flags & GS_FRAME_AUX) != 0;

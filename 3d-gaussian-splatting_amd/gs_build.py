@@ -34,6 +34,10 @@ SOURCES = {
     # no SLP packing: v_pk_*_f32 has no rate advantage on gfx950 and costs extra v_mov shuffles
     "raster_fwd.hip": ["-fno-slp-vectorize"],
     "raster_bwd.hip": ["-fno-slp-vectorize"],
+    "raster_bwd_systolic.hip": ["-fno-slp-vectorize"],
+    "raster_bwd_pixel.hip": ["-fno-slp-vectorize"],
+    "raster_bwd_mfma.hip": ["-fno-slp-vectorize"],
+    "raster_bwd_rows.hip": ["-fno-slp-vectorize"],
     "gs_frame.hip": [],
     "adam.hip": ["-ffp-contract=off"],  # same roundings as torch's unfused elementwise kernels
     "loss.hip": ["-fno-slp-vectorize"],  # as above: the packer costs ~50 v_mov per row step of the fused kernel
@@ -49,7 +53,7 @@ SOURCES = {
     "overlap.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # the keep test (opa > t and ||act(scale)|| < s) as written: densify.hip's delete rule, decided identically
     "map_edit.hip": ["-ffp-contract=off"],
-    # the row step of raster_bwd.hip's row-layout kernel, built like it (no SLP packing, as above)
+    # the row step of raster_bwd_rows.hip's kernel, built like it (no SLP packing, as above)
     "contrib.hip": ["-fno-slp-vectorize"],
     # the box sum, s / n and the edge test hi <= fl(fl(1 + edge_rel) lo) as written, one rounding per operation: the float32
     # restatement (tests/pyramid_ref.py) gives the level targets bit for bit
@@ -61,7 +65,7 @@ SOURCES = {
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
-HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "strip_common.h", "tile_bin_common.h",
+HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "raster_bwd_common.h", "strip_common.h", "tile_bin_common.h",
            "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
            "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h", "icp_point.h",
            os.path.join("..", "..", "include", "gs_abi.h")]

@@ -605,7 +605,7 @@ def test_long_lists_sh_backward_hand_over_matches_oracle(gpu, sh_degree):
     """the SH backward of frames flagged GS_FRAME_LONG_LISTS was only compared with the serial walk
     of the same build, never with the oracle.  Round 4 had the matrix-pipe kernel take a tile's first 32 buckets and hand the
     rest to raster_backward_pixel_sh_kernel (one wave per bucket); since round 5 the matrix-pipe kernel takes work items of at
-    most 8 buckets, several workgroups per long tile, and there is no hand-over (raster_bwd.hip: mfma_items_kernel) -- either
+    most 8 buckets, several workgroups per long tile, and there is no hand-over (raster_bwd_mfma.hip: mfma_items_kernel) -- either
     way it is this test that puts the long-list backward against the oracle: every tile's list is 60 - 96 buckets deep (3,900 -
     6,150 Gaussians of opacity 0.0067: pixels stop at T <= 1e-4 around the 4,600th layer, i.e. deep inside the list, in
     another work item than the one that started the tile; the forward composites the lists in segments) and all five gradients
@@ -861,7 +861,7 @@ def test_frame_backward_parity(gpu, use_sh):
 
 @pytest.mark.parametrize("sh_degree", [2, 3])
 def test_frame_backward_sh_deep_saturating_tiles(gpu, sh_degree):
-    """The SH backward on the matrix pipe (raster_bwd.hip: raster_backward_mfma_sh_kernel) where its structure shows: tiles
+    """The SH backward on the matrix pipe (raster_bwd_mfma.hip: raster_backward_mfma_sh_kernel) where its structure shows: tiles
     several 64-Gaussian buckets deep (checkpoints, four waves sharing a tile), ragged last buckets and groups of 16,
     opaque Gaussians so that pixels -- and whole pixel rows, which the kernel then leaves out -- stop inside the list."""
     scene, cam = case(14_000, 96, 64, seed=5, use_sh=True, sh_degree=sh_degree)

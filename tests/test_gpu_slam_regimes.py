@@ -44,7 +44,7 @@ TG_PER_BLOCK = 1024
 TG_RESIDUAL_BLOCKS, TG_RESIDUAL_MAX_CHUNKS, TG_DIGIT_BLOCKS = 512, 8, 128
 TG_CLAMP_FROM = TG_PER_BLOCK * TG_RESIDUAL_BLOCKS * TG_RESIDUAL_MAX_CHUNKS  # 4,194,304 pixels: beyond it rchunks is clamped
 
-# contrib.hip, gs_stage_contrib: `dim3((unsigned)(cap < 40960 ? cap : 40960))` waves, `kb += gridDim.x` over the work list
+# contrib.hip, gs_stage_contrib: `bwd_frame_grid` (raster_bwd_common.h) waves, at most GS_BWD_GRID_CAP of them, `kb += gridDim.x` over the work list
 CONTRIB_GRID_CAP = 40960
 # raster_bwd.hip, bucket_scan_kernel: the work list is the exclusive scan over the tiles of ceil(nproc / 64) buckets
 GS_BUCKET = 64

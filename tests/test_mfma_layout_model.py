@@ -1,4 +1,4 @@
-"""CPU tier: the index algebra of the SH backward on the matrix pipe (raster_bwd.hip: raster_backward_mfma_sh_kernel), run as a
+"""CPU tier: the index algebra of the SH backward on the matrix pipe (raster_bwd_mfma.hip: raster_backward_mfma_sh_kernel), run as a
 NumPy model of the wave's 64 lanes against the plain per-pixel recursion it replaces.
 
 The kernel rests on three layout facts that no compiler checks: (1) with lane l = (Gaussian l & 15, pixel quad l >> 4) the
@@ -225,7 +225,7 @@ def test_row_store_permutation_writes_the_documented_layout():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Round 5: the rgb backward in the row layout (raster_bwd.hip: raster_backward_rows_kernel) -- the same lanes = (Gaussian,
+# Round 5: the rgb backward in the row layout (raster_bwd_rows.hip: raster_backward_rows_kernel) -- the same lanes = (Gaussian,
 # pixel quad) and DPP row scans as above, without the matrix products, plus three identities of its own:
 #   (a) the opacity rides in the exponent: alpha = 2^-(q - log2 sigma) and sum s q = sum s q' + log2 sigma sum s;
 #   (b) T in front of Gaussian g = T_in x (inclusive product scan of lane g - 1), lane 0 keeps T_in (one v_mul_f32_dpp

@@ -16,6 +16,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 OBJDUMP = os.environ.get("LLVM_OBJDUMP", "/opt/rocm/lib/llvm/bin/llvm-objdump")
+READELF = os.environ.get("LLVM_READELF", os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf"))
 
 _INSN = re.compile(r"^\s+(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):")
 _FUNC = re.compile(r"^[0-9a-f]+ <(\S+)>:$")
@@ -33,16 +34,24 @@ def disassemble_library(lib=None):
             fh.write(elf)
         try:
             txt = subprocess.run([OBJDUMP, "-d", path], check=True, capture_output=True, text=True).stdout
+            syms = subprocess.run([READELF, "-sW", path], check=True, capture_output=True, text=True).stdout
         finally:
             os.unlink(path)
-        cur = None
+        # a function ends at address + size of its symbol: behind it, up to the next label, the listing decodes the
+        # alignment padding, which depends on the function's neighbours in the code object and is not its code
+        end = {}
+        for line in syms.splitlines():
+            p = line.split()
+            if len(p) == 8 and p[3] == "FUNC":
+                end[p[7]] = int(p[1], 16) + int(p[2], 0)
+        cur, cur_end = None, None
         for line in txt.splitlines():
             m = _FUNC.match(line)
             if m:
-                cur = out.setdefault(m.group(1), [])
+                cur, cur_end = out.setdefault(m.group(1), []), end.get(m.group(1))
                 continue
             m = _INSN.match(line)
-            if m and cur is not None:
+            if m and cur is not None and (cur_end is None or int(m.group(3), 16) < cur_end):
                 cur.append((int(m.group(3), 16), m.group(1), m.group(2)))
     return out
 

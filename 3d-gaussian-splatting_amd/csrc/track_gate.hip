@@ -413,6 +413,142 @@ __global__ void __launch_bounds__(1024) track_gate_finalize_kernel(const float4 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// gs_track_gate_mask: the same sets, medians and thresholds, turned into the mapping inputs of a keyframe instead of a loss --
+// a range map without the measurements the depth gate rejects and a 0 / 1 colour weight.  The memset, the residual pass and
+// the two digit passes are the ones above; gate_mask_kernel takes the loss pass's place (it reads alpha, the range and the
+// two residual maps: 16 B / pixel, writes 8) and gate_mask_finalize_kernel adds the workgroups' counts.
+struct tg_counts {
+    uint32_t measured, kept, wsum, wint;
+};
+
+// one pixel: the decisions of track_gate_pixel, -> the range and the weight the pixel keeps
+template <bool RANGE>
+__device__ __forceinline__ void gate_mask_pixel(float A, float z, float ra, float rc, bool interior, const tg_gate &G, float &zo,
+                                                float &wo, tg_counts &acc) {
+    const bool covered = A >= G.alpha_min;  // (false for NaN)
+    const bool meas = RANGE && map_measured(z);
+    bool removed = false, dropped = false;
+    if (covered && meas) {
+        const bool in_set = ra <= TG_FLT_MAX;
+        const bool depth_in = !(G.kd > 0.f) || (in_set && ra <= G.td);
+        removed = !depth_in;
+        dropped = G.couple && in_set && !depth_in;
+    }
+    const bool colour_in = !dropped && (!(G.kc > 0.f) || (rc <= TG_FLT_MAX && rc <= G.tc));
+    zo = (meas && !removed) ? z : 0.f;
+    wo = (covered && !colour_in) ? 0.f : 1.f;
+    acc.measured += meas ? 1u : 0u;
+    acc.kept += (meas && !removed) ? 1u : 0u;
+    acc.wsum += wo != 0.f ? 1u : 0u;
+    acc.wint += (wo != 0.f && interior) ? 1u : 0u;
+}
+
+template <bool RANGE>
+__global__ void __launch_bounds__(TG_BLOCK)
+    gate_mask_kernel(const float *__restrict__ alpha, const float *__restrict__ target_range, const float *__restrict__ resid_a,
+                     const float *__restrict__ resid_c, int64_t n, int32_t H, int32_t W, float alpha_min, float kd, float kc,
+                     float floor_d, float floor_c, int couple, const uint32_t *__restrict__ hist, uint32_t *__restrict__ state,
+                     float *__restrict__ range_out, float *__restrict__ weight_out, uint4 *__restrict__ part) {
+    __shared__ uint32_t s_cnt[4][TG_BLOCK / 64];
+    // the last level's pick completes both medians' bit patterns (as in track_gate_loss_kernel)
+    const tg_pick p = track_gate_select<false>(hist + 2 * 2 * TG_BINS, state[TG_RANK2_D], state[TG_RANK2_C]);
+    const float m_d = __uint_as_float((state[TG_BIN0_D] << 21) | (state[TG_BIN1_D] << 10) | p.bin[0]);
+    const float m_c = __uint_as_float((state[TG_BIN0_C] << 21) | (state[TG_BIN1_C] << 10) | p.bin[1]);
+    tg_gate G;
+    G.alpha_min = alpha_min, G.cs = 0.f, G.ds = 0.f, G.kd = kd, G.kc = kc, G.couple = couple;
+    G.td = fmaxf(kd * m_d, floor_d);
+    G.tc = fmaxf(kc * m_c, floor_c);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {  // (for the finalize kernel; nobody reads them in this launch)
+        state[TG_M_D] = __float_as_uint(m_d), state[TG_M_C] = __float_as_uint(m_c);
+        state[TG_T_D] = __float_as_uint(G.td), state[TG_T_C] = __float_as_uint(G.tc);
+    }
+    const int64_t i0 = ((int64_t)blockIdx.x * TG_BLOCK + threadIdx.x) * 4;
+    tg_counts acc = {0u, 0u, 0u, 0u};
+    // the SSIM interior: rows 5 .. H - 6, columns 5 .. W - 6 (n <= 2^24: the pixel index fits an int)
+    auto interior = [&](int64_t i) {
+        const int r = (int)i / W, c = (int)i - r * W;
+        return r >= 5 && r < H - 5 && c >= 5 && c < W - 5;
+    };
+    if (i0 + 4 <= n) {
+        const float4 a = *reinterpret_cast<const float4 *>(alpha + i0);
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (RANGE) z = *reinterpret_cast<const float4 *>(target_range + i0);
+        const float4 ra = *reinterpret_cast<const float4 *>(resid_a + i0), rc = *reinterpret_cast<const float4 *>(resid_c + i0);
+        float4 zo, wo;
+        gate_mask_pixel<RANGE>(a.x, z.x, ra.x, rc.x, interior(i0), G, zo.x, wo.x, acc);
+        gate_mask_pixel<RANGE>(a.y, z.y, ra.y, rc.y, interior(i0 + 1), G, zo.y, wo.y, acc);
+        gate_mask_pixel<RANGE>(a.z, z.z, ra.z, rc.z, interior(i0 + 2), G, zo.z, wo.z, acc);
+        gate_mask_pixel<RANGE>(a.w, z.w, ra.w, rc.w, interior(i0 + 3), G, zo.w, wo.w, acc);
+        if (RANGE) *reinterpret_cast<float4 *>(range_out + i0) = zo;
+        *reinterpret_cast<float4 *>(weight_out + i0) = wo;
+    } else {
+        for (int64_t i = i0; i < n; ++i) {  // the up to three pixels an image whose size is no multiple of four ends with
+            float zo, wo;
+            gate_mask_pixel<RANGE>(alpha[i], RANGE ? target_range[i] : 0.f, resid_a[i], resid_c[i], interior(i), G, zo, wo, acc);
+            if (RANGE) range_out[i] = zo;
+            weight_out[i] = wo;
+        }
+    }
+    acc.measured = gs_wave_sum_u32(acc.measured);
+    acc.kept = gs_wave_sum_u32(acc.kept);
+    acc.wsum = gs_wave_sum_u32(acc.wsum);
+    acc.wint = gs_wave_sum_u32(acc.wint);
+    if ((threadIdx.x & 63) == 0) {
+        s_cnt[0][threadIdx.x >> 6] = acc.measured;
+        s_cnt[1][threadIdx.x >> 6] = acc.kept;
+        s_cnt[2][threadIdx.x >> 6] = acc.wsum;
+        s_cnt[3][threadIdx.x >> 6] = acc.wint;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        part[blockIdx.x] = make_uint4(((s_cnt[0][0] + s_cnt[0][1]) + s_cnt[0][2]) + s_cnt[0][3],
+                                      ((s_cnt[1][0] + s_cnt[1][1]) + s_cnt[1][2]) + s_cnt[1][3],
+                                      ((s_cnt[2][0] + s_cnt[2][1]) + s_cnt[2][2]) + s_cnt[2][3],
+                                      ((s_cnt[3][0] + s_cnt[3][1]) + s_cnt[3][2]) + s_cnt[3][3]);
+}
+
+// values_out = (measured pixels, range pixels kept, range pixels removed, sum of the weights, the same over the SSIM interior,
+// m_d, m_c, n_d): integer sums (at most H W <= 2^24: exact as floats) of the workgroups' rows, in the fixed order of gs_common.h
+__global__ void __launch_bounds__(1024) gate_mask_finalize_kernel(const uint4 *__restrict__ part, int64_t nrows,
+                                                                  const uint32_t *__restrict__ state,
+                                                                  float *__restrict__ values_out) {
+    __shared__ uint32_t s_w[16][4];
+    uint32_t c[4] = {0u, 0u, 0u, 0u};
+    for (int64_t r = threadIdx.x; r < nrows; r += 1024) {
+        const uint4 v = part[r];
+        c[0] += v.x, c[1] += v.y, c[2] += v.z, c[3] += v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        c[j] = gs_wave_sum_u32(c[j]);
+        if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6][j] = c[j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t[4];
+        for (int j = 0; j < 4; ++j) {
+            t[j] = s_w[0][j];
+            for (int w = 1; w < 16; ++w) t[j] += s_w[w][j];
+        }
+        values_out[0] = (float)t[0];
+        values_out[1] = (float)t[1];
+        values_out[2] = (float)(t[0] - t[1]);
+        values_out[3] = (float)t[2];
+        values_out[4] = (float)t[3];
+        values_out[5] = __uint_as_float(state[TG_M_D]);
+        values_out[6] = __uint_as_float(state[TG_M_C]);
+        values_out[7] = (float)state[TG_N_D];  // (at most 2^24: exact)
+    }
+}
+
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (a NULL pointer overlaps nothing)
+inline bool tg_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
 }  // namespace
 
 extern "C" size_t gs_loss_track_gated_workspace_bytes(int32_t H, int32_t W) {
@@ -486,6 +622,90 @@ extern "C" int gs_loss_track_gated(const float *image, const float *depth, const
     if (values_out) {
         hipLaunchKernelGGL(track_gate_finalize_kernel, dim3(1), dim3(1024), 0, s, (const float4 *)part, (int64_t)blocks, scale,
                            color_weight, depth_weight, (const uint32_t *)state, values_out);
+        GS_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" size_t gs_track_gate_mask_workspace_bytes(int32_t H, int32_t W) {
+    if (H <= 0 || W <= 0) return 0;
+    return tg_workspace((int64_t)H * W).total;
+}
+
+extern "C" int gs_track_gate_mask(const float *image, const float *depth, const float *alpha, const float *target_image,
+                                  const float *target_range, int32_t H, int32_t W, float alpha_min, float depth_gate_k,
+                                  float color_gate_k, float depth_gate_floor, float color_gate_floor, int32_t couple,
+                                  float *range_out, float *weight_out, float *values_out, float *resid_depth,
+                                  float *resid_color, void *workspace, size_t workspace_bytes, gs_stream_t stream) {
+    GS_CHECK_ARG(H > 0 && W > 0, "empty image");
+    const int64_t n = (int64_t)H * W;
+    GS_CHECK_ARG(n <= TG_MAX_PIXELS, "image size beyond 2^24 pixels (the counts are returned as floats and must be exact)");
+    GS_CHECK_ARG(image && depth && alpha && target_image && weight_out,
+                 "null pointer (only target_range with range_out, values_out, resid_depth and resid_color may be NULL)");
+    GS_CHECK_ARG((target_range != nullptr) == (range_out != nullptr),
+                 "target_range and range_out must both be given or both be NULL");
+    GS_CHECK_ARG(alpha_min > 0.f, "alpha_min must be positive (the expected depth divides by alpha)");
+    GS_CHECK_ARG(!std::isnan(depth_gate_k) && !std::isnan(color_gate_k), "depth_gate_k and color_gate_k must not be NaN");
+    GS_CHECK_ARG(depth_gate_floor >= 0.f && color_gate_floor >= 0.f, "the gate floors must not be negative or NaN");
+    {  // the kernels walk the maps float4 by float4
+        const void *al[] = {image, depth, alpha, target_image, target_range, range_out, weight_out, resid_depth, resid_color};
+        for (const void *q : al) GS_CHECK_ARG(((uintptr_t)q & 15) == 0, "the maps must be 16-byte aligned");
+    }
+    GS_CHECK_ARG(((uintptr_t)values_out & 3) == 0, "values_out must be 4-byte aligned");
+    {  // an output that shares a byte with an input (or with another output) would be read after it was written
+        const size_t b1 = sizeof(float) * (size_t)n, b3 = 3 * b1;
+        const struct {
+            const void *p;
+            size_t bytes;
+        } in[] = {{image, b3}, {depth, b1}, {alpha, b1}, {target_image, b3}, {target_range, b1}},
+          out[] = {{range_out, b1}, {weight_out, b1}, {values_out, 8 * sizeof(float)}, {resid_depth, b1}, {resid_color, b1}};
+        for (const auto &o : out)
+            for (const auto &i : in) GS_CHECK_ARG(!tg_overlap(o.p, o.bytes, i.p, i.bytes), "an output overlaps an input");
+        for (size_t u = 0; u < 5; ++u)
+            for (size_t v = u + 1; v < 5; ++v)
+                GS_CHECK_ARG(!tg_overlap(out[u].p, out[u].bytes, out[v].p, out[v].bytes), "two outputs overlap");
+    }
+    GS_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= gs_track_gate_mask_workspace_bytes(H, W),
+                 "workspace null, misaligned or too small");
+    hipStream_t s = (hipStream_t)stream;
+    const tg_layout L = tg_workspace(n);
+    char *ws = (char *)workspace;
+    uint4 *part = (uint4 *)(ws + L.part);
+    uint32_t *hist = (uint32_t *)(ws + L.hist), *state = (uint32_t *)(ws + L.state);
+    float *ra = resid_depth ? resid_depth : (float *)(ws + L.resid_a);
+    float *rc = resid_color ? resid_color : (float *)(ws + L.resid_c);
+    const int64_t nchunks = tg_blocks(n);  // (at most 2^14)
+    const unsigned blocks = (unsigned)nchunks;
+    int rchunks = (int)gs_div_up(nchunks, TG_RESIDUAL_BLOCKS);
+    if (rchunks > TG_RESIDUAL_MAX_CHUNKS) rchunks = TG_RESIDUAL_MAX_CHUNKS;
+    const int dchunks = (int)gs_div_up(nchunks, TG_DIGIT_BLOCKS);
+    const unsigned rblocks = (unsigned)gs_div_up(nchunks, rchunks), dblocks = (unsigned)gs_div_up(nchunks, dchunks);
+    GS_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * TG_LEVELS * 2 * TG_BINS, s));
+    if (target_range)
+        hipLaunchKernelGGL(track_gate_residual_kernel<true>, dim3(rblocks), dim3(TG_BLOCK), 0, s, image, depth, alpha, target_image,
+                           target_range, n, rchunks, alpha_min, ra, rc, hist);
+    else
+        hipLaunchKernelGGL(track_gate_residual_kernel<false>, dim3(rblocks), dim3(TG_BLOCK), 0, s, image, depth, alpha, target_image,
+                           target_range, n, rchunks, alpha_min, ra, rc, hist);
+    GS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(track_gate_digit_kernel<1>, dim3(dblocks), dim3(TG_BLOCK), 0, s, (const float *)ra, (const float *)rc, n, dchunks,
+                       hist, state);
+    GS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(track_gate_digit_kernel<2>, dim3(dblocks), dim3(TG_BLOCK), 0, s, (const float *)ra, (const float *)rc, n, dchunks,
+                       hist, state);
+    GS_CHECK_LAUNCH();
+    if (target_range)
+        hipLaunchKernelGGL(gate_mask_kernel<true>, dim3(blocks), dim3(TG_BLOCK), 0, s, alpha, target_range, (const float *)ra,
+                           (const float *)rc, n, H, W, alpha_min, depth_gate_k, color_gate_k, depth_gate_floor, color_gate_floor,
+                           couple != 0, (const uint32_t *)hist, state, range_out, weight_out, part);
+    else
+        hipLaunchKernelGGL(gate_mask_kernel<false>, dim3(blocks), dim3(TG_BLOCK), 0, s, alpha, target_range, (const float *)ra,
+                           (const float *)rc, n, H, W, alpha_min, depth_gate_k, color_gate_k, depth_gate_floor, color_gate_floor,
+                           couple != 0, (const uint32_t *)hist, state, range_out, weight_out, part);
+    GS_CHECK_LAUNCH();
+    if (values_out) {
+        hipLaunchKernelGGL(gate_mask_finalize_kernel, dim3(1), dim3(1024), 0, s, (const uint4 *)part, (int64_t)blocks,
+                           (const uint32_t *)state, values_out);
         GS_CHECK_LAUNCH();
     }
     return 0;

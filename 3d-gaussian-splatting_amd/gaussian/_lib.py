@@ -174,7 +174,11 @@ gs_loss_track = _sig("gs_loss_track", ci, vp, vp, vp, vp, vp, i32, i32, f32, f32
 gs_loss_track_gated_workspace_bytes = _sig("gs_loss_track_gated_workspace_bytes", sz, i32, i32)
 gs_loss_track_gated = _sig("gs_loss_track_gated", ci, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, f32, i32, f32,
                            vp, vp, vp, vp, vp, vp, vp, sz, vp)
-
+gs_track_gate_mask_workspace_bytes = _sig("gs_track_gate_mask_workspace_bytes", sz, i32, i32)
+gs_track_gate_mask = _sig("gs_track_gate_mask", ci, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, i32, vp, vp, vp, vp,
+                          vp, vp, sz, vp)
+gs_loss_l1_ssim_weighted = _sig("gs_loss_l1_ssim_weighted", ci, vp, vp, vp, i32, i32, f32, C.c_double, C.c_double, vp, vp, vp,
+                                sz, vp)
 
 
 class GsDensifyOpts(C.Structure):
@@ -329,6 +333,7 @@ EXPORTS = [
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
     "gs_loss_track_workspace_bytes", "gs_loss_track",
     "gs_loss_track_gated_workspace_bytes", "gs_loss_track_gated",
+    "gs_track_gate_mask_workspace_bytes", "gs_track_gate_mask", "gs_loss_l1_ssim_weighted",
     "gs_view_overlap_workspace_bytes", "gs_view_overlap_check_view", "gs_view_overlap",
     "gs_scene_pack_bytes", "gs_scene_pack_build", "gs_frame_reads_scene_pack",
     "gs_prune_workspace_bytes", "gs_prune_classify", "gs_prune_apply",

@@ -67,7 +67,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
 HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "raster_bwd_common.h", "strip_common.h", "tile_bin_common.h",
            "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
-           "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h", "icp_point.h",
+           "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h", "icp_point.h", "loss_fused_body.inc",
            os.path.join("..", "..", "include", "gs_abi.h")]
 
 

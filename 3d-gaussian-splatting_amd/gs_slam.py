@@ -18,6 +18,11 @@ the window except keyframe 0, which fixes the gauge; ``KeyframeSet.set_pose`` ca
 tracker's motion history starts from the refined pose.  The keyframe set only grows -- ``KeyframeSet.add`` raises when it is
 full; there is no loop closure and ``adaptive_control`` is never called.
 
+With ``SlamOptions.gate_map`` (off by default; it needs a gated tracker) a keyframe after the first reaches the trainer
+through the tracker's median gate: the frozen map rendered once at the tracked pose, ``gs_train.GateMask`` on it, the range map
+without the rejected measurements and the 0 / 1 colour weight into ``Trainer.add_view(..., weight=)`` -- what the tracker
+rejected is neither seeded nor fitted.
+
 Two options edit the map without resetting Adam, both off by default.  ``SlamOptions.carry_optimizer``: a keyframe's seeding
 keeps the old rows' moments and the step count (``Trainer.seed_from_view(carry_state=True)``) instead of starting a fresh
 optimizer for the whole map.  ``SlamOptions.prune_every`` = k: behind the mapping steps of every k-th keyframe the Gaussians
@@ -42,7 +47,7 @@ from gs_call import check_tensor, require_hip, stream, workspace
 from gs_geometry import pose64, posed, principal_point_offset
 from gs_icp import IcpAligner, IcpOptions, IcpResult
 from gs_track import _SH_REFUSAL, TrackOptions, TrackResult, Tracker
-from gs_train import TrainOptions, Trainer
+from gs_train import GateMask, TrainOptions, Trainer
 
 GS_OVERLAP_MAX_VIEWS = _lib.GS_OVERLAP_MAX_VIEWS
 
@@ -217,6 +222,13 @@ class SlamOptions:
     # the default and nothing more; what the option did on the eight-frame arc is in profiles/contrib_prune.txt.
     prune_unseen_every: int = 0
     prune_unseen_w_min: float = 1.0 / 255.0
+    # The tracker's median gate carried into seeding and mapping (off: no GateMask and no extra renderer exist, the loop issues
+    # exactly the calls it issues without the option).  Needs a gated tracker (``track.depth_gate_k`` or ``color_gate_k`` above
+    # zero).  Every keyframe after the first renders the frozen map once at its tracked pose, turns the tracker's gate into a
+    # range map without the rejected measurements and a 0 / 1 colour weight (gs_train.GateMask) and hands those to the trainer:
+    # seeding and the depth loss see the gated range, the colour loss the weight.  The keyframe set keeps the raw range.  A
+    # real new object in front of the map is rejected like an occluder while this is on.
+    gate_map: bool = False
     # Depth alignment in front of the photometric tracker (None, the default: no aligner exists, no render is issued, the loop
     # is bit for bit the one without the option).  With ``gs_icp.IcpOptions``: every frame after the first renders the frozen
     # map's depth once at the pose the tracker would start from, aligns the frame's range map to it by point-to-plane ICP on
@@ -242,6 +254,8 @@ class SlamFrame:
     refined: Dict[int, Tuple[np.ndarray, np.ndarray]] = field(default_factory=dict)
     pruned: int = 0                  # Gaussians removed behind this keyframe's mapping steps (prune_every)
     pruned_unseen: int = 0           # ... and those removed because no keyframe sees them (prune_unseen_every)
+    # SlamOptions.gate_map, a gated keyframe: (range pixels removed, pixels with colour weight 0); None otherwise
+    gated: Optional[Tuple[int, int]] = None
     icp: Optional[IcpResult] = None  # SlamOptions.icp: the depth alignment in front of this frame's tracking, accepted or not
 
 
@@ -255,6 +269,9 @@ class Slam:
 
     def __init__(self, camera, options: Optional[SlamOptions] = None, device="cuda"):
         self.opt = options if options is not None else SlamOptions()
+        if self.opt.gate_map and not self.opt.track.gated():  # (before any device work)
+            raise ValueError("SlamOptions.gate_map carries the tracker's median gate into seeding and mapping: it needs a gated "
+                             "tracker (TrackOptions.depth_gate_k or color_gate_k above zero)")
         # the map is seeded with rgb colours; a `seed` dict that asks for SH rows is refused with the tracker's sentence
         self._seed = {k: v for k, v in self.opt.seed.items() if k != "color_dim"}
         if int(self.opt.seed.get("color_dim", 3)) != 3:
@@ -266,13 +283,18 @@ class Slam:
         self.trainer: Optional[Trainer] = None
         self.tracker: Optional[Tracker] = None
         self.aligner: Optional[IcpAligner] = None
+        self.gate_mask: Optional[GateMask] = None
         self._icp_renderer = None
-        if self.opt.icp is not None:  # (its own inference renderer: the tracker's workspace and counters stay untouched)
+        if self.opt.icp is not None or self.opt.gate_map:
+            # an inference renderer of their own, shared: the tracker's workspace and counters stay untouched
             from gs_frame import FrameRenderer
 
-            self.aligner = IcpAligner(camera, self.opt.icp, self.device)
             self._icp_renderer = FrameRenderer(self.device, max_pairs=int(self.opt.track.max_pairs), training=False,
                                                occlusion_cull=False, auto_grow=True)
+        if self.opt.icp is not None:
+            self.aligner = IcpAligner(camera, self.opt.icp, self.device)
+        if self.opt.gate_map:
+            self.gate_mask = GateMask.from_track_options(int(camera.height), int(camera.width), self.opt.track, self.device)
         self.i_iter = 0          # mapping steps taken so far, over the whole run
         self.n_frames = 0
         self._last_keyframe_at = 0
@@ -398,8 +420,19 @@ class Slam:
         self.n_frames += 1
         if not frame.keyframe:
             return frame
-        new = self.keyframes.add(cam, image, range_map)
-        added_as = self.trainer.add_view(cam, image, range_map)
+        map_range, map_weight = range_map, None
+        if self.gate_mask is not None:
+            # the frozen map once more, at the tracked pose, with its aux maps; the tracker's gate on it gives what the
+            # trainer sees of this keyframe (clones: the GateMask's maps are rewritten by the next keyframe).  One host read.
+            tg = time.perf_counter()
+            rimg, _, rdepth, ralpha = self._icp_renderer.forward(*self.tracker.params, cam, training=False, aux=True)
+            g_range, g_weight = self.gate_mask(rimg.contiguous(), rdepth.contiguous(), ralpha.contiguous(), image, range_map)
+            map_range, map_weight = g_range.clone(), g_weight.clone()
+            v = self.gate_mask.values.tolist()
+            frame.gated = (int(v[2]), int(self.gate_mask.H * self.gate_mask.W - v[3]))
+            frame.seconds["gate"] = time.perf_counter() - tg
+        new = self.keyframes.add(cam, image, range_map)  # (the raw range: the overlap count reads what was measured)
+        added_as = self.trainer.add_view(cam, image, map_range, weight=map_weight)
         if added_as != new:
             raise RuntimeError(f"keyframe {new} became view {added_as} of the trainer: the two lists have diverged")
         self._last_keyframe_at = index

@@ -263,6 +263,40 @@ class ImageLoss(_MapLoss):
         return self.grad
 
 
+def weight_sums(weight: torch.Tensor) -> Tuple[float, float]:
+    """(sum of a weight map [H,W], its sum over the SSIM interior -- rows 5 .. H-6, columns 5 .. W-6; 0 when H <= 10 or
+    W <= 10), in double: the two host arguments of ``gs_loss_l1_ssim_weighted``.  One host read; a caller takes them once
+    per view."""
+    h, w = weight.shape
+    total = weight.sum(dtype=torch.float64)
+    inner = weight[5:h - 5, 5:w - 5].sum(dtype=torch.float64) if h > 10 and w > 10 else torch.zeros_like(total)
+    total, inner = torch.stack([total, inner]).tolist()
+    return float(total), float(inner)
+
+
+class WeightedImageLoss(_MapLoss):
+    """``ImageLoss`` with a per-pixel weight map [H,W] (finite, >= 0; gs_loss_l1_ssim_weighted, include/gs_abi.h): both terms
+    become weighted means.  The call takes the map and its two sums (``weight_sums``: the caller computes them once per view
+    and validates the map then -- the kernel checks neither); an all-ones map with sums H W and (H-10)(W-10) gives
+    ``ImageLoss``'s gradient and values bit for bit.  Same ``grad`` / ``values`` members as ``ImageLoss``."""
+
+    def __init__(self, height: int, width: int, ssim_weight: float = 0.1, device="cuda"):
+        self.w = float(ssim_weight)
+        self._setup(height, width, device, _lib.gs_loss_workspace_bytes)
+        self.grad = self._new(self.H, self.W, 3)
+        self.values = torch.zeros(3, dtype=torch.float32, device=self.device)  # (loss, l1, ssim), stays on device
+
+    def __call__(self, pred: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, weight_sum: float,
+                 weight_sum_interior: float) -> torch.Tensor:
+        for name, t in (("pred", pred), ("target", target)):
+            check_tensor(name, t, (self.H, self.W, 3))
+        check_tensor("weight", weight, (self.H, self.W))
+        _lib.call("gs_loss_l1_ssim_weighted", pred.data_ptr(), target.data_ptr(), weight.data_ptr(), self.H, self.W, self.w,
+                  float(weight_sum), float(weight_sum_interior), self.grad.data_ptr(), self.values.data_ptr(),
+                  self._ws.data_ptr(), self._ws.numel(), stream())
+        return self.grad
+
+
 class DepthLoss(_MapLoss):
     """``scale * sum |r|`` over the measured pixels of a range map and its gradients w.r.t. the depth / alpha maps of an aux
     frame (gs_loss_depth, include/gs_abi.h): ``mode`` "residual" (r = D - A z) or "expected" (r = D / A - z where
@@ -377,6 +411,49 @@ class GatedTrackLoss(_TrackMaps):
         return self.grad_image, self.grad_depth, self.grad_alpha
 
 
+class GateMask(_MapLoss):
+    """The median gate of ``GatedTrackLoss`` as the mapping inputs of a keyframe (gs_track_gate_mask, include/gs_abi.h): from
+    the frozen map rendered at the frame's pose with its aux maps and the incoming frame, ``range`` -- the range map with the
+    measurements the depth gate rejects written as 0, "no measurement" -- and ``weight`` -- 0 where the map covers the pixel
+    and its colour term does not count (the coupling included), else 1.  The tracker's exact sets, medians and thresholds; a
+    pixel the map does not cover keeps its range and has weight 1.  The call shape of ``GatedTrackLoss`` without ``scale``;
+    ``values`` = (measured pixels, range pixels kept, range pixels removed, sum of weight, its sum over the SSIM interior,
+    m_d, m_c, n_d), on the device.  Owns the workspace, ``range``, ``weight`` and ``values``; a call without a range map
+    leaves ``range`` untouched."""
+
+    def __init__(self, height: int, width: int, alpha_min: float = 0.5, depth_gate_k: float = 0.0, color_gate_k: float = 0.0,
+                 depth_gate_floor: float = 0.0, color_gate_floor: float = 0.0, couple: bool = True, device="cuda"):
+        self.alpha_min = float(alpha_min)
+        self.depth_gate_k, self.color_gate_k = float(depth_gate_k), float(color_gate_k)
+        self.depth_gate_floor, self.color_gate_floor = float(depth_gate_floor), float(color_gate_floor)
+        self.couple = bool(couple)
+        self._setup(height, width, device, _lib.gs_track_gate_mask_workspace_bytes)
+        self.range, self.weight = self._new(self.H, self.W), self._new(self.H, self.W)
+        self.values = torch.zeros(8, dtype=torch.float32, device=self.device)  # stays on the device
+
+    @classmethod
+    def from_track_options(cls, height: int, width: int, opt, device="cuda") -> "GateMask":
+        """The gate a ``gs_track.TrackOptions`` describes (alpha_min, the two k, the two floors, gate_couple)."""
+        return cls(height, width, opt.alpha_min, opt.depth_gate_k, opt.color_gate_k, opt.depth_gate_floor,
+                   opt.color_gate_floor, opt.gate_couple, device)
+
+    def __call__(self, image: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_image: torch.Tensor,
+                 target_range: Optional[torch.Tensor]):
+        """``target_range``: [H,W] range from the camera centre (<= 0, inf, NaN: no measurement) or None (an RGB-only gate).
+        Returns (range or None, weight)."""
+        maps = [("image", image, (3,)), ("depth", depth, ()), ("alpha", alpha, ()), ("target_image", target_image, (3,))]
+        if target_range is not None:
+            maps.append(("target_range", target_range, ()))
+        for name, t, c in maps:
+            check_tensor(name, t, (self.H, self.W) + c)
+        _lib.call("gs_track_gate_mask", image.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_image.data_ptr(),
+                  target_range.data_ptr() if target_range is not None else None, self.H, self.W, self.alpha_min,
+                  self.depth_gate_k, self.color_gate_k, self.depth_gate_floor, self.color_gate_floor, int(self.couple),
+                  self.range.data_ptr() if target_range is not None else None, self.weight.data_ptr(), self.values.data_ptr(),
+                  None, None, self._ws.data_ptr(), self._ws.numel(), stream())
+        return (self.range if target_range is not None else None), self.weight
+
+
 def z_to_range(z: torch.Tensor, camera) -> torch.Tensor:
     """Sensor z-depth [H,W] (distance along the optical axis) -> range from the camera centre, what the aux depth map
     measures (d_i = |p_c|): range = z |ray| / ray_z with the renderer's own per-pixel rays (gs_geometry.RayBasis: pixel
@@ -415,8 +492,20 @@ class Trainer:
                  scale_activation: str = "abs", densify: bool = False, generator: Optional[torch.Generator] = None,
                  per_view_stat: Optional[bool] = None, exchange: str = "all_reduce", n_slices: Optional[int] = None,
                  bwd_rows: Optional[bool] = None, fuse_adam: Optional[bool] = None,
-                 depths: Optional[Sequence[Optional[torch.Tensor]]] = None, depth_kind: str = "range"):
+                 depths: Optional[Sequence[Optional[torch.Tensor]]] = None, depth_kind: str = "range",
+                 weights: Optional[Sequence[Optional[torch.Tensor]]] = None):
         self.opt = opt or TrainOptions()
+        # `weights`: a list parallel to `targets`, each entry a per-pixel weight map [H,W] float32 (finite, >= 0) for the
+        # view's colour loss or None.  A view with a map takes the weighted loss (WeightedImageLoss) where the step calls its
+        # image loss; a view without one issues exactly the calls it issues without `weights`.  Validated once per view,
+        # its two sums taken once, in double (_view_weight).  `test` / `psnr` stay unweighted.
+        self.weights, self._weight_sums = None, None
+        if weights is not None:
+            if len(weights) != len(targets):
+                raise ValueError("weights must be a list parallel to targets (None for a view without a weight map)")
+            views = [self._view_weight(cam_, w_, params[0].device) for cam_, w_ in zip(cameras, weights)]
+            self.weights, self._weight_sums = [v[0] for v in views], [v[1] for v in views]
+        self._weighted_loss = {}
         # `depths`: a list parallel to `targets`, each entry a measured depth map [H,W] float32 or None (a view without one).
         # `depth_kind`: "range" = distance from the camera centre, what the frame's depth map accumulates; "z" = sensor
         # z-depth, converted once here with the renderer's own rays (z_to_range).  Pixels <= 0, inf or NaN carry no
@@ -527,19 +616,43 @@ class Trainer:
         n_valid = int((torch.isfinite(d) & (d > 0)).sum())  # once, here: no count pass in the step
         return d, (1.0 / n_valid if n_valid else 0.0)
 
-    def add_view(self, camera, target: torch.Tensor, depth: Optional[torch.Tensor] = None) -> int:
+    @staticmethod
+    def _view_weight(camera, w: Optional[torch.Tensor], device):
+        """One view's colour weight map as the step uses it -> (the map on the device or None, (its sum, its sum over the SSIM
+        interior) in double): the per-view validation of the constructor and of ``add_view``, stated once.  One host read,
+        here: no count pass in the step."""
+        if w is None:
+            return None, (0.0, 0.0)
+        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or \
+                tuple(w.shape) != (int(camera.height), int(camera.width)):
+            raise ValueError("a weight map must be float32 [H,W] of its camera")
+        w = w.to(device).contiguous()
+        if not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise ValueError("a weight map must be finite and not negative (NaN, inf or a negative weight found)")
+        return w, weight_sums(w)
+
+    def add_view(self, camera, target: torch.Tensor, depth: Optional[torch.Tensor] = None,
+                 weight: Optional[torch.Tensor] = None) -> int:
         """Appends a view to a running fit -> its camera id.  ``depth`` goes through the constructor's own per-view
         validation and conversion (``depth_kind``, the measured-pixel count); a Trainer built without ``depths`` takes
-        ``depth=None`` only.  Nothing else changes -- no rebind, no optimizer reset, no frame abandoned: a step on an earlier
-        view afterwards is the step it would have been."""
+        ``depth=None`` only.  ``weight``: the view's colour weight map (``weights`` of the constructor; a Trainer built
+        without ``weights`` starts its list here, the earlier views without a map).  Nothing else changes -- no rebind, no
+        optimizer reset, no frame abandoned: a step on an earlier view afterwards is the step it would have been."""
         if depth is not None and self.depths is None:
             raise ValueError("this Trainer was built without depths: add_view takes depth=None only")
+        wmap, wsums = self._view_weight(camera, weight, self._depth_device)  # (refused before anything is appended)
         d, inv_n = self._view_depth(camera, depth)
+        if wmap is not None and self.weights is None:
+            self.weights = [None] * len(self.cameras)
+            self._weight_sums = [(0.0, 0.0)] * len(self.cameras)
         self.cameras.append(camera)
         self.targets.append(target)
         if self.depths is not None:
             self.depths.append(d)
             self._depth_inv_n.append(inv_n)
+        if self.weights is not None:
+            self.weights.append(wmap)
+            self._weight_sums.append(wsums)
         return len(self.cameras) - 1
 
     # ------------------------------------------------------------------ free poses (joint refinement of poses and map)
@@ -597,6 +710,12 @@ class Trainer:
         if key not in self._loss:
             self._loss[key] = ImageLoss(h, w, self.opt.ssim_weight, self.flat.flat_param.device)
         return self._loss[key]
+
+    def _weighted_loss_for(self, h: int, w: int) -> WeightedImageLoss:
+        key = (h, w)
+        if key not in self._weighted_loss:
+            self._weighted_loss[key] = WeightedImageLoss(h, w, self.opt.ssim_weight, self.flat.flat_param.device)
+        return self._weighted_loss[key]
 
     def _depth_loss_for(self, h: int, w: int) -> DepthLoss:
         key = (h, w)
@@ -675,8 +794,13 @@ class Trainer:
                           f"the device; several ranks: this rank contributed zero gradients to them); the "
                           f"workspace has been enlarged to {r.max_pairs} pairs")
             self._overflow_warned = r.overflowed_frames
-        loss = self._loss_for(image.shape[0], image.shape[1])
-        grad_image = loss(image, target)
+        wmap = self.weights[camera_id] if self.weights is not None else None
+        if wmap is None:
+            loss = self._loss_for(image.shape[0], image.shape[1])
+            grad_image = loss(image, target)
+        else:  # a weighted view: the same gradient map travels through whichever backward the step takes
+            loss = self._weighted_loss_for(image.shape[0], image.shape[1])
+            grad_image = loss(image, target, wmap, *self._weight_sums[camera_id])
         # depth supervision: + depth_weight / n_valid * sum |r| on the frame's maps; its two gradient maps travel with
         # grad_image through whichever backward the step takes
         aux_grads = {}

@@ -38,6 +38,10 @@ extern "C" {
  *   gs_icp_reset with gs_icp_model_opts / gs_icp_opts / gs_icp_state and the size queries gs_icp_model_bytes,
  *   gs_icp_workspace_bytes and gs_icp_log_bytes (frame-to-model point-to-plane ICP of a range map against the map's vertex and
  *   normal maps: association, normal equations and the 6 x 6 solve on the device, no host read inside the loop).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_track_gate_mask +
+ *   gs_track_gate_mask_workspace_bytes (the median gate of gs_loss_track_gated as a keyframe's mapping inputs: a range map
+ *   without the rejected measurements and a per-pixel colour weight) and gs_loss_l1_ssim_weighted (gs_loss_l1_ssim with a
+ *   per-pixel weight map).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_pyramid_down with
  *   gs_pyramid_opts / GS_PYRAMID_MAX_LEVELS (one level down of an image pyramid -- box-filtered colour and a measurement-aware
  *   range map -- in one launch: the level targets of coarse-to-fine camera tracking).
@@ -797,6 +801,29 @@ int gs_loss_l1_ssim(const float *pred, const float *target, int32_t H, int32_t W
                     float *grad, float *loss_out, void *workspace, size_t workspace_bytes,
                     gs_stream_t stream);
 
+/* gs_loss_l1_ssim with a per-pixel weight map `weight` [H, W] fp32 (finite and >= 0 -- NOT checked here: the caller validates
+ * a map once; the three channels of a pixel share its weight).  With m the weight of a pixel and S the SSIM map on the
+ * interior (rows 5 .. H - 6, columns 5 .. W - 6):
+ *   l1   = sum_p m_p sum_c |x - y|        / (3 weight_sum)
+ *   ssim = sum_{q interior} m_q sum_c S_qc / (3 weight_sum_interior)
+ *   loss = (1 - w) l1 + w (1 - ssim)
+ *   dL/dx = a m sign(x - y) - b [ g*(m D_mu) + 2 x g*(m D_xx) + y g*(m D_xy) ],
+ *   a = (float)((1 - w) / (3 weight_sum)),  b = (float)(w / (3 weight_sum_interior)).
+ * weight_sum and weight_sum_interior -- the sum of the map and its sum over the interior -- are HOST arguments: the caller
+ * takes them once per view; there is no count pass and no host synchronisation.  weight_sum == 0: the L1 term, its value and
+ * its gradient are exactly 0.  weight_sum_interior == 0 or w == 0: the SSIM term (in loss_out[0] too), loss_out[2] and its
+ * gradient are exactly 0, and the weighted L1 kernel runs alone (any image size when w == 0).  A pixel of weight 0 takes no
+ * part in the SSIM term at all: its S is not read, its adjoints are +0.0f, so its gradient is exactly +0.0f where no
+ * interior pixel of non-zero weight lies within 5 rows and 5 columns.  An all-ones map with weight_sum = H W and
+ * weight_sum_interior = (H - 10)(W - 10) gives gs_loss_l1_ssim's gradient and values bit for bit.  loss_out = (loss, l1,
+ * ssim) as there; the workspace is gs_loss_workspace_bytes(H, W).
+ * GS_E_INVALID -- before anything is enqueued, the first that applies --: H or W <= 0; a NULL pred, target, weight or grad;
+ * ssim_weight outside [0, 1] or NaN; ssim_weight > 0 with H <= 10 or W <= 10; a sum that is negative, infinite or NaN; a
+ * workspace that is NULL or too small. */
+int gs_loss_l1_ssim_weighted(const float *pred, const float *target, const float *weight, int32_t H, int32_t W,
+                             float ssim_weight, double weight_sum, double weight_sum_interior, float *grad, float *loss_out,
+                             void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
 /* Depth supervision on the maps of a GS_FRAME_AUX frame: depth D = sum_i w_i d_i and alpha A = sum_i w_i, [H,W] fp32, against
  * a measured RANGE `target` [H,W] (distance from the camera centre, as d_i = |p_c| is; z-depth is converted by the caller:
  * range = z |ray| / ray_z).  A target pixel that is <= 0, infinite or NaN carries no measurement and does not count.
@@ -866,6 +893,34 @@ int gs_loss_track_gated(const float *image, const float *depth, const float *alp
                         float color_gate_floor, int32_t couple, float scale, float *grad_image, float *grad_depth,
                         float *grad_alpha, float *values_out, float *resid_depth, float *resid_color, void *workspace,
                         size_t workspace_bytes, gs_stream_t stream);
+
+/* The gate of gs_loss_track_gated as the MAPPING INPUTS of a keyframe: a GS_FRAME_AUX frame of the frozen map rendered at the
+ * frame's pose (image, depth, alpha) and the incoming frame (target_image, target_range) give a range map without the
+ * measurements the depth gate rejects and a per-pixel colour weight.  covered, measured, the residuals a and c, the sets S_d /
+ * S_c, the lower medians m_d / m_c, the thresholds t_d / t_c and the two decisions "the depth term counts" (dmask) and "the
+ * colour term counts" (cmask, the coupling included) are those of gs_loss_track_gated, unchanged.  Per pixel:
+ *   range_out  = target_range where the pixel is measured and not (covered and measured and not dmask); else exactly +0.0f
+ *                (an unmeasured input -- <= 0, inf, NaN -- is written as +0.0f too);
+ *   weight_out = 0.0f where covered and not cmask, else 1.0f.
+ * A pixel the map does not cover keeps its range and has weight 1: it is new surface, what seeding and mapping are for.  With
+ * both k <= 0 nothing is gated: range_out is the measured input, weight_out all ones.  target_range may be NULL (an RGB-only
+ * gate); range_out must then be NULL too, and only then.  values_out (device, 4-byte aligned, 8 floats, may be NULL) receives
+ * (measured pixels, range pixels kept, range pixels removed, sum of weight_out, sum of weight_out over the SSIM interior --
+ * rows 5 .. H - 6, columns 5 .. W - 6; 0 when H <= 10 or W <= 10 --, m_d, m_c, n_d); the counts are exact integers.
+ * resid_depth / resid_color as in gs_loss_track_gated.  Launches: gs_loss_track_gated's memset, residual pass and two digit
+ * passes as they are, one mask pass in place of the loss pass (reads alpha, the range and the two residual maps), a
+ * one-workgroup sum of the workgroups' integer counts.  No float atomics, no host synchronisation: bitwise repeatable.
+ * GS_E_INVALID -- before anything is enqueued, the first that applies --: H or W <= 0; H W > 2^24; a NULL image, depth, alpha,
+ * target_image or weight_out; target_range and range_out not both NULL or both given; alpha_min <= 0 or NaN; a NaN k; a NaN
+ * or negative floor; a map (inputs, outputs, residual maps) that is not 16-byte aligned; a values_out that is not 4-byte
+ * aligned; an output (range_out, weight_out, values_out, resid_depth, resid_color) that overlaps an input or another
+ * output; a workspace that is null, misaligned or smaller than gs_track_gate_mask_workspace_bytes(H, W). */
+size_t gs_track_gate_mask_workspace_bytes(int32_t H, int32_t W);
+int gs_track_gate_mask(const float *image, const float *depth, const float *alpha, const float *target_image,
+                       const float *target_range, int32_t H, int32_t W, float alpha_min, float depth_gate_k,
+                       float color_gate_k, float depth_gate_floor, float color_gate_floor, int32_t couple, float *range_out,
+                       float *weight_out, float *values_out, float *resid_depth, float *resid_color, void *workspace,
+                       size_t workspace_bytes, gs_stream_t stream);
 
 /* One level down of an image pyramid: the targets of coarse-to-fine camera tracking (csrc/pyramid.hip).  image [H,W,3] and
  * range [H,W] (NULL: RGB only; range_out must then be NULL too) give image_out [H/2,W/2,3] and range_out [H/2,W/2]; H and W

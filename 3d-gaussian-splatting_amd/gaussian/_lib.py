@@ -236,6 +236,13 @@ gs_view_overlap = _sig("gs_view_overlap", ci, vp, C.POINTER(GsSeedCamera), vp, i
 gs_view_overlap_pp = _sig("gs_view_overlap_pp", ci, vp, C.POINTER(GsSeedCameraPP), vp, vp, i32, C.POINTER(GsOverlapOpts), vp,
                           vp, sz, vp)
 
+GS_REDUNDANCY_BINS = 8
+gs_view_redundancy_workspace_bytes = _sig("gs_view_redundancy_workspace_bytes", sz, i32, i32, i32)
+gs_view_redundancy = _sig("gs_view_redundancy", ci, vp, C.POINTER(GsSeedCamera), vp, i32, i32, C.POINTER(GsOverlapOpts), vp, vp,
+                          sz, vp)
+gs_view_redundancy_pp = _sig("gs_view_redundancy_pp", ci, vp, C.POINTER(GsSeedCameraPP), vp, vp, i32, i32,
+                             C.POINTER(GsOverlapOpts), vp, vp, sz, vp)
+
 GS_PRUNE_MAX_ARRAYS = 16
 
 
@@ -341,6 +348,7 @@ EXPORTS = [
     "gs_frame_contrib_workspace_bytes", "gs_frame_contrib", "gs_prune_classify_contrib",
     "gs_pyramid_down",
     "gs_icp_model_bytes", "gs_icp_workspace_bytes", "gs_icp_log_bytes", "gs_icp_model_maps", "gs_icp_reset", "gs_icp_step",
+    "gs_view_redundancy_workspace_bytes", "gs_view_redundancy", "gs_view_redundancy_pp",
 ]
 
 

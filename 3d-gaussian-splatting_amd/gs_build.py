@@ -51,6 +51,8 @@ SOURCES = {
     "track_gate.hip": ["-ffp-contract=off"],
     # the seen / not seen test as written: a float32 restatement decides identically; no SLP packing, as above
     "overlap.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # overlap.hip's decisions (overlap_point.h) under overlap.hip's flags: the same bits, counted per point
+    "redundancy.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     # the keep test (opa > t and ||act(scale)|| < s) as written: densify.hip's delete rule, decided identically
     "map_edit.hip": ["-ffp-contract=off"],
     # the row step of raster_bwd_rows.hip's kernel, built like it (no SLP packing, as above)

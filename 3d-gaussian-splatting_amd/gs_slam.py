@@ -15,8 +15,12 @@ default a keyframe's pose is fixed once set.  With ``SlamOptions.refine_poses`` 
 keyframe also refine the poses of its window (``Trainer.free_pose``: the fused step's pose variant,
 gs_frame_backward_adam_pose, delivers the pose gradient of every step, the Tracker's pose optimizer takes it) -- every view of
 the window except keyframe 0, which fixes the gauge; ``KeyframeSet.set_pose`` carries the result into the view table and the
-tracker's motion history starts from the refined pose.  The keyframe set only grows -- ``KeyframeSet.add`` raises when it is
-full; there is no loop closure and ``adaptive_control`` is never called.
+tracker's motion history starts from the refined pose.  By default the keyframe set only grows -- ``KeyframeSet.add`` raises
+when it is full (256 views).  With ``SlamOptions.max_keyframes`` the set is capped: a keyframe that arrives at the cap first
+evicts the most redundant one -- the keyframe with the largest share of its own measured points seen by at least
+``evict_seen_by`` other keyframes (``gs_view_redundancy``, csrc/redundancy.hip: one call per keyframe, one host read;
+``select_eviction``) -- from the set (``KeyframeSet.remove``) and from the running fit (``Trainer.remove_view``); the Gaussians it
+seeded stay.  There is no loop closure and ``adaptive_control`` is never called.
 
 With ``SlamOptions.gate_map`` (off by default; it needs a gated tracker) a keyframe after the first reaches the trainer
 through the tracker's median gate: the frozen map rendered once at the tracked pose, ``gs_train.GateMask`` on it, the range map
@@ -50,6 +54,7 @@ from gs_track import _SH_REFUSAL, TrackOptions, TrackResult, Tracker
 from gs_train import GateMask, TrainOptions, Trainer
 
 GS_OVERLAP_MAX_VIEWS = _lib.GS_OVERLAP_MAX_VIEWS
+GS_REDUNDANCY_BINS = _lib.GS_REDUNDANCY_BINS
 
 
 def view_overlap(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: int, stride: int = 1, near: float = 0.3,
@@ -83,6 +88,40 @@ def view_overlap(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: 
     return counts
 
 
+def view_redundancy(range_map: torch.Tensor, camera, table: torch.Tensor, n_views: int, self_index: int = -1, stride: int = 1,
+                    near: float = 0.3, border: int = 0, table_pp: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gs_view_redundancy`` (include/gs_abi.h) -> hist [GS_REDUNDANCY_BINS + 1] int64 on the device: of the measured lattice
+    pixels of ``range_map`` -- one view's own range map, ``camera`` its posed camera -- how many are seen by exactly 0, 1, ..., 6
+    and by 7 or more of the rows of ``table`` other than row ``self_index`` (-1: no row is left out), then how many there are.
+    The decisions are ``gs_view_overlap``'s, the checks ``view_overlap``'s: the rows of ``table`` are not validated here and a
+    ``border`` that leaves nothing of a view is not refused.  No host synchronisation.  ``out``: a contiguous int64 tensor of
+    nine elements on the device to write into (a row of a larger tensor: a caller collects many results and reads once);
+    ``ws``: a uint8 workspace of at least ``gs_view_redundancy_workspace_bytes`` to share between stream-ordered calls.
+    ``table_pp`` and ``camera``'s own principal-point offset as in ``view_overlap``."""
+    require_hip(range_map.device, "the redundancy count")
+    cam = gs_seed.seed_camera(camera)
+    check_tensor("range_map", range_map, (cam.height, cam.width))
+    check_tensor("table", table, rows_min=n_views, tail=(16,))
+    opts = _lib.GsOverlapOpts(int(stride), float(near), int(border))
+    if ws is None:
+        ws = workspace(_lib.gs_view_redundancy_workspace_bytes(cam.height, cam.width, max(int(stride), 1)), range_map.device)
+    if out is None:
+        out = torch.empty(GS_REDUNDANCY_BINS + 1, dtype=torch.int64, device=range_map.device)
+    elif not (out.dtype == torch.int64 and out.is_contiguous() and out.numel() == GS_REDUNDANCY_BINS + 1
+              and out.device == range_map.device):
+        raise ValueError(f"out must be a contiguous int64 tensor of {GS_REDUNDANCY_BINS + 1} elements on the range map's device")
+    tail = (int(n_views), int(self_index), C.byref(opts), out.data_ptr(), ws.data_ptr(), ws.numel(), stream())
+    if table_pp is not None or principal_point_offset(camera) != (0.0, 0.0):
+        if table_pp is not None:
+            check_tensor("table_pp", table_pp, rows_min=n_views, tail=(2,), device=table.device)
+        _lib.call("gs_view_redundancy_pp", range_map.data_ptr(), C.byref(gs_seed.seed_camera_pp(camera)), table.data_ptr(),
+                  table_pp.data_ptr() if table_pp is not None else None, *tail)
+    else:
+        _lib.call("gs_view_redundancy", range_map.data_ptr(), C.byref(cam), table.data_ptr(), *tail)
+    return out
+
+
 def view_row(camera) -> np.ndarray:
     """A camera as one 64-byte row of the view table (``struct gs_seed_camera``), validated: ``gs_view_overlap`` cannot
     check rows that live in device memory, so the owner of the table does when it appends one."""
@@ -93,8 +132,10 @@ def view_row(camera) -> np.ndarray:
 
 class KeyframeSet:
     """The keyframes of a mapping run: posed cameras, colour targets, range maps, and the device table of their 64-byte
-    rows that ``gs_view_overlap`` reads.  It only grows: ``add`` raises ``RuntimeError`` once ``capacity`` keyframes are
-    held (at most GS_OVERLAP_MAX_VIEWS = 256; there is no eviction)."""
+    rows that ``gs_view_overlap`` reads.  ``add`` raises ``RuntimeError`` once ``capacity`` keyframes are held (at most
+    GS_OVERLAP_MAX_VIEWS = 256); the set itself never evicts: its owner asks ``redundancy`` which keyframe measured the least
+    that the others do not see, and calls ``remove``.  ``ids``: a list parallel to ``cameras``, the keyframes' stable ids
+    0, 1, 2, ... in order of addition, never reused -- positions shift when a keyframe is removed, ids do not."""
 
     def __init__(self, capacity: int = GS_OVERLAP_MAX_VIEWS, device="cuda"):
         if not 1 <= int(capacity) <= GS_OVERLAP_MAX_VIEWS:
@@ -107,9 +148,16 @@ class KeyframeSet:
         self.table_pp = torch.zeros((self.capacity, 2), dtype=torch.float32, device=device)
         self._offsets = []
         self._min_size = None
+        self.ids: List[int] = []
+        self._next_id = 0
 
     def __len__(self) -> int:
         return len(self.cameras)
+
+    @property
+    def n_added(self) -> int:
+        """Keyframes ever added (the next id): ``len`` without removals."""
+        return self._next_id
 
     def add(self, camera, image: torch.Tensor, range_map: torch.Tensor) -> int:
         """Appends a keyframe -> its index.  The row is validated on the host and written with one 64-byte copy."""
@@ -124,9 +172,27 @@ class KeyframeSet:
         self.cameras.append(copy.copy(camera))
         self.images.append(image)
         self.ranges.append(range_map)
+        self.ids.append(self._next_id)
+        self._next_id += 1
         size = min(int(camera.width), int(camera.height))
         self._min_size = size if self._min_size is None else min(self._min_size, size)
         return n
+
+    def remove(self, index: int):
+        """Deletes the keyframe at position ``index``: the lists drop the entry, rows index + 1 .. n - 1 of ``table`` and
+        ``table_pp`` move up by one (a device copy through a temporary; the freed last row is zeroed), every later keyframe's
+        position falls by one and its id stays.  ``add`` works again on a set that was full."""
+        n = len(self.cameras)
+        index = int(index)
+        if not 0 <= index < n:
+            raise IndexError(f"no keyframe {index}")
+        for t in (self.table, self.table_pp):
+            if index + 1 < n:
+                t[index:n - 1].copy_(t[index + 1:n].clone())
+            t[n - 1].zero_()
+        for lst in (self.cameras, self.images, self.ranges, self.ids, self._offsets):
+            del lst[index]
+        self._min_size = min((min(int(c.width), int(c.height)) for c in self.cameras), default=None)
 
     def set_pose(self, index: int, rot, tran):
         """Replaces the pose of keyframe ``index`` (a mapper refined it): the camera by a copy with (rot, tran) in float32,
@@ -147,6 +213,25 @@ class KeyframeSet:
         table_pp = self.table_pp if any(o != (0.0, 0.0) for o in self._offsets) else None
         return view_overlap(range_map, camera, self.table, len(self.cameras), stride, near, border, table_pp).cpu().numpy()
 
+    def redundancy(self, stride: int = 1, near: float = 0.3, border: int = 0) -> np.ndarray:
+        """hists [len, GS_REDUNDANCY_BINS + 1] int64 on the host: row k is ``view_redundancy`` of keyframe k's own raw range
+        map and camera against the other keyframes (``self_index`` = k).  One call per keyframe into one device tensor
+        through one workspace, stream-ordered; one host read at the end.  ``table_pp`` is honoured as ``overlap`` does."""
+        if not self.cameras:
+            raise RuntimeError("the keyframe set is empty")
+        if 2 * int(border) >= self._min_size:
+            raise RuntimeError(f"border {border} leaves nothing of a {self._min_size}-pixel keyframe")
+        table_pp = self.table_pp if any(o != (0.0, 0.0) for o in self._offsets) else None
+        n = len(self.cameras)
+        hists = torch.empty((n, GS_REDUNDANCY_BINS + 1), dtype=torch.int64, device=self.table.device)
+        nbytes = max(int(_lib.gs_view_redundancy_workspace_bytes(int(c.height), int(c.width), max(int(stride), 1)))
+                     for c in self.cameras)
+        ws = workspace(nbytes, self.table.device)
+        for k in range(n):
+            view_redundancy(self.ranges[k], self.cameras[k], self.table, n, k, stride, near, border, table_pp, out=hists[k],
+                            ws=ws)
+        return hists.cpu().numpy()
+
 
 def select_keyframes(counts: Sequence[int], measured: int, k: int, min_share: float) -> List[int]:
     """The up to ``k`` views with the highest counts among those with count >= min_share x measured, highest first; ties go
@@ -155,6 +240,28 @@ def select_keyframes(counts: Sequence[int], measured: int, k: int, min_share: fl
     ok = [(int(c), i) for i, c in enumerate(counts) if int(c) >= floor]
     ok.sort(key=lambda ci: (-ci[0], -ci[1]))
     return [i for _, i in ok[:max(int(k), 0)]]
+
+
+def select_eviction(hists, seen_by: int, protected: Sequence[int]) -> Optional[int]:
+    """The keyframe to evict -> its position, or None when every position is protected.  ``hists`` [K, 9]: row k the
+    histogram ``KeyframeSet.redundancy`` gives for keyframe k.  The score of row k is the share of its measured points that at
+    least ``seen_by`` other keyframes see, sum(hists[k, seen_by:8]) / hists[k, 8]; a row that measured nothing scores 1.  The
+    unprotected position with the highest score goes; ties go to the lower position (the older keyframe).  Scores are compared
+    as exact fractions, by cross-multiplication of integers: ties are real ties.  No randomness."""
+    seen_by = int(seen_by)
+    if not 1 <= seen_by <= GS_REDUNDANCY_BINS - 1:
+        raise ValueError(f"seen_by must lie in [1, {GS_REDUNDANCY_BINS - 1}]")
+    barred = {int(p) for p in protected}
+    best, best_num, best_den = None, 0, 1
+    for k, row in enumerate(hists):
+        if k in barred:
+            continue
+        num, den = sum(int(v) for v in row[seen_by:GS_REDUNDANCY_BINS]), int(row[GS_REDUNDANCY_BINS])
+        if den == 0:
+            num, den = 1, 1
+        if best is None or num * best_den > best_num * den:  # (strictly higher: a tie keeps the lower position)
+            best, best_num, best_den = k, num, den
+    return best
 
 
 def is_keyframe(count_last: int, measured: int, frames_since: int, overlap_min: float, every: int) -> bool:
@@ -222,6 +329,18 @@ class SlamOptions:
     # the default and nothing more; what the option did on the eight-frame arc is in profiles/contrib_prune.txt.
     prune_unseen_every: int = 0
     prune_unseen_w_min: float = 1.0 / 255.0
+    # Eviction of keyframes (0, the default: none -- no redundancy count is issued, the set grows to GS_OVERLAP_MAX_VIEWS and
+    # the next keyframe raises, the loop issues exactly the calls it issues without the option).  3 .. 256: the most keyframes
+    # held.  When a frame becomes a keyframe and the set holds that many, one keyframe goes first: for every keyframe the share
+    # of its own measured points (lattice ``evict_stride``; None: ``stride``) that at least ``evict_seen_by`` OTHER keyframes see
+    # is counted (KeyframeSet.redundancy: gs_view_redundancy per keyframe, one host read), and the one with the highest share
+    # leaves the set and the trainer (select_eviction) -- never keyframe 0, the founder of the map and the gauge of
+    # ``refine_poses``, never the last one, whose count the overlap rule reads.  The Gaussians it seeded stay.
+    # ``evict_seen_by`` = 3 is ORB-SLAM's culling rule ("seen by at least three other keyframes"); nothing in this tree is
+    # evidence for it.  What the option did on the eight-frame arc: profiles/evict.txt.
+    max_keyframes: int = 0
+    evict_seen_by: int = 3
+    evict_stride: Optional[int] = None
     # The tracker's median gate carried into seeding and mapping (off: no GateMask and no extra renderer exist, the loop issues
     # exactly the calls it issues without the option).  Needs a gated tracker (``track.depth_gate_k`` or ``color_gate_k`` above
     # zero).  Every keyframe after the first renders the frozen map once at its tracked pose, turns the tracker's gate into a
@@ -254,6 +373,10 @@ class SlamFrame:
     refined: Dict[int, Tuple[np.ndarray, np.ndarray]] = field(default_factory=dict)
     pruned: int = 0                  # Gaussians removed behind this keyframe's mapping steps (prune_every)
     pruned_unseen: int = 0           # ... and those removed because no keyframe sees them (prune_unseen_every)
+    # SlamOptions.max_keyframes: the stable id (KeyframeSet.ids) of the keyframe evicted to make room for this one, else None;
+    # `window` holds positions AFTER that removal, `overlap` the counts as computed BEFORE it; seconds["evict"] its wall time
+    evicted: Optional[int] = None
+    window_ids: List[int] = field(default_factory=list)  # the stable ids of `window`
     # SlamOptions.gate_map, a gated keyframe: (range pixels removed, pixels with colour weight 0); None otherwise
     gated: Optional[Tuple[int, int]] = None
     icp: Optional[IcpResult] = None  # SlamOptions.icp: the depth alignment in front of this frame's tracking, accepted or not
@@ -272,6 +395,13 @@ class Slam:
         if self.opt.gate_map and not self.opt.track.gated():  # (before any device work)
             raise ValueError("SlamOptions.gate_map carries the tracker's median gate into seeding and mapping: it needs a gated "
                              "tracker (TrackOptions.depth_gate_k or color_gate_k above zero)")
+        mk = int(self.opt.max_keyframes)
+        if mk != 0 and not 3 <= mk <= GS_OVERLAP_MAX_VIEWS:  # (position 0 and the last one are never evicted)
+            raise ValueError(f"SlamOptions.max_keyframes must be 0 (no eviction) or lie in [3, {GS_OVERLAP_MAX_VIEWS}]")
+        if not 1 <= int(self.opt.evict_seen_by) <= GS_REDUNDANCY_BINS - 1:
+            raise ValueError(f"SlamOptions.evict_seen_by must lie in [1, {GS_REDUNDANCY_BINS - 1}]")
+        if self.opt.evict_stride is not None and int(self.opt.evict_stride) < 1:
+            raise ValueError("SlamOptions.evict_stride must be None (the overlap count's stride) or >= 1")
         # the map is seeded with rgb colours; a `seed` dict that asks for SH rows is refused with the tracker's sentence
         self._seed = {k: v for k, v in self.opt.seed.items() if k != "color_dim"}
         if int(self.opt.seed.get("color_dim", 3)) != 3:
@@ -336,12 +466,13 @@ class Slam:
                 self.tracker.set_last_pose(frame.rot, frame.tran)
         frame.map_losses += [float(v) for v in torch.stack(vals)[:, 0].cpu()] if vals else []
         frame.seconds["map"] = time.perf_counter() - t0
-        if o.prune_every > 0 and len(self.keyframes) % int(o.prune_every) == 0:
+        # (every k-th keyframe ADDED: with eviction the set's length stops growing, the number of keyframes taken does not)
+        if o.prune_every > 0 and self.keyframes.n_added % int(o.prune_every) == 0:
             t0 = time.perf_counter()
             frame.pruned = tr.prune(self.i_iter, opa_min=o.prune_opa_min, scale_max=o.prune_scale_max,
                                     carry_state=bool(o.carry_optimizer))
             frame.seconds["prune"] = time.perf_counter() - t0
-        if o.prune_unseen_every > 0 and len(self.keyframes) % int(o.prune_unseen_every) == 0:
+        if o.prune_unseen_every > 0 and self.keyframes.n_added % int(o.prune_unseen_every) == 0:
             # what reaches w_min in no keyframe is constrained by no training view: seeds that ended up behind a surface,
             # duplicates from several keyframes, whatever lies outside every frustum
             t0 = time.perf_counter()
@@ -377,7 +508,7 @@ class Slam:
         self.trainer = Trainer(params, [cam], [image], o.train, max_pairs=int(o.max_pairs), depths=[range_map])
         frame = SlamFrame(rot=rot, tran=tran, tracked=None, keyframe=True, overlap=None, window=[0],
                           added=int(params[0].shape[0]), pending=int(o.map_iterations_first))
-        self.keyframes.add(cam, image, range_map)
+        frame.window_ids = [self.keyframes.ids[self.keyframes.add(cam, image, range_map)]]
         frame.seconds["seed"] = time.perf_counter() - t0
         return frame
 
@@ -414,12 +545,33 @@ class Slam:
         if icp is not None:
             frame.icp = icp
             frame.seconds["icp"] = ti
-        if frame.keyframe and n >= self.keyframes.capacity:  # before the trainer or the frame count is touched
+        evict = frame.keyframe and n >= int(o.max_keyframes) > 0
+        if frame.keyframe and n >= self.keyframes.capacity and not evict:  # before the trainer or the frame count is touched
             raise RuntimeError(f"the keyframe set is full ({self.keyframes.capacity} views); there is no eviction")
         index = self.n_frames
         self.n_frames += 1
         if not frame.keyframe:
             return frame
+        window_counts = counts[:n]
+        if evict:
+            # the set is at its cap: the keyframe whose measured points the others see best goes first -- never position 0 (the
+            # founder of the map, the gauge of refine_poses) and never the last (the overlap rule reads its count).  One host read.
+            te = time.perf_counter()
+            hists = self.keyframes.redundancy(stride=int(o.evict_stride if o.evict_stride is not None else o.stride),
+                                              near=self.near, border=o.border)
+            gone = select_eviction(hists, o.evict_seen_by, protected=(0, n - 1))
+            if gone is None:
+                raise RuntimeError(f"no keyframe of {n} can be evicted")
+            frame.evicted = self.keyframes.ids[gone]
+            self.keyframes.remove(gone)
+            self.trainer.remove_view(gone)
+            if len(self.trainer.cameras) != len(self.keyframes):
+                raise RuntimeError(f"{len(self.keyframes)} keyframes against {len(self.trainer.cameras)} views of the trainer: "
+                                   "the two lists have diverged")
+            window_counts = np.delete(window_counts, gone)
+            n -= 1
+            frame.seconds["evict"] = time.perf_counter() - te
+            t2 += frame.seconds["evict"]  # (seconds["seed"] below stays the time of adding and seeding)
         map_range, map_weight = range_map, None
         if self.gate_mask is not None:
             # the frozen map once more, at the tracked pose, with its aux maps; the tracker's gate on it gives what the
@@ -438,6 +590,7 @@ class Slam:
         self._last_keyframe_at = index
         frame.added = self.trainer.seed_from_view(new, self.i_iter, carry_state=bool(o.carry_optimizer), **self._seed)
         frame.seconds["seed"] = time.perf_counter() - t2
-        frame.window = [new] + select_keyframes(counts[:n], measured, o.window - 1, o.min_share)
+        frame.window = [new] + select_keyframes(window_counts, measured, o.window - 1, o.min_share)
+        frame.window_ids = [self.keyframes.ids[v] for v in frame.window]
         frame.pending = int(o.map_iterations)
         return frame

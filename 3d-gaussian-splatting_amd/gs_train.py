@@ -655,6 +655,30 @@ class Trainer:
             self._weight_sums.append(wsums)
         return len(self.cameras) - 1
 
+    def remove_view(self, camera_id: int):
+        """The inverse of ``add_view``: view ``camera_id`` leaves the running fit, and every view above it gets the id one
+        lower.  Its entries of ``cameras``, ``targets``, ``depths`` and ``weights`` (where those lists exist) go; the per-view
+        keys above it shift down; a frame projected ahead is abandoned.  Parameters, optimizer state, step count and the flat
+        bucket are not touched: a step on a remaining view afterwards is the step it would have been.  Refused: the last
+        view (``ValueError``) and a view whose pose is free (``RuntimeError``: ``fix_pose`` first)."""
+        camera_id = int(camera_id)
+        if not 0 <= camera_id < len(self.cameras):
+            raise IndexError(f"no view {camera_id}")
+        if len(self.cameras) == 1:
+            raise ValueError("remove_view would leave the Trainer without a view")
+        if camera_id in self._free:
+            raise RuntimeError(f"view {camera_id} has a free pose: fix_pose first")
+        lists = [self.cameras, self.targets]
+        if self.depths is not None:
+            lists += [self.depths, self._depth_inv_n]
+        if self.weights is not None:
+            lists += [self.weights, self._weight_sums]
+        for lst in lists:
+            del lst[camera_id]
+        self._views_checked = {v - (v > camera_id) for v in self._views_checked if v != camera_id}
+        self._free = {v - (v > camera_id): fp for v, fp in self._free.items()}
+        self.renderer.forward_abandon()  # (a frame projected ahead may have been the removed view's)
+
     # ------------------------------------------------------------------ free poses (joint refinement of poses and map)
     def free_pose(self, camera_id: int, lr_rot: float, lr_tran: float, betas: Tuple[float, float] = (0.9, 0.999),
                   eps: float = 1e-8):

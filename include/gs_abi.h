@@ -34,7 +34,10 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_icp_model_maps, gs_icp_step and
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_redundancy,
+ *   gs_view_redundancy_pp and gs_view_redundancy_workspace_bytes with GS_REDUNDANCY_BINS (of the surface points one keyframe
+ *   measured, how many are seen by 0, 1, ..., 7 or more of the OTHER keyframes: the measurement behind keyframe eviction).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_icp_model_maps, gs_icp_step and
  *   gs_icp_reset with gs_icp_model_opts / gs_icp_opts / gs_icp_state and the size queries gs_icp_model_bytes,
  *   gs_icp_workspace_bytes and gs_icp_log_bytes (frame-to-model point-to-plane ICP of a range map against the map's vertex and
  *   normal maps: association, normal equations and the 6 x 6 solve on the device, no host read inside the loop).
@@ -1097,6 +1100,40 @@ int gs_view_overlap(const float *range, const gs_seed_camera *cam,        /* the
 int gs_view_overlap_pp(const float *range, const gs_seed_camera_pp *cam, const gs_seed_camera *views_dev,
                        const float *view_pp_dev, int32_t n_views, const gs_overlap_opts *opts, int64_t *counts_dev,
                        void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- redundancy: of the surface points ONE view measured, how many of the other views see each? ----
+ * gs_view_overlap counts per view; this counts per point, which is what culling a keyframe asks ("nearly all it measured is
+ * seen by at least m others").  range [H,W] and cam: the SOURCE view's own range map and posed camera (by value, on the
+ * host), as gs_view_overlap's frame.  views_dev: the same DEVICE table of 64-byte rows gs_view_overlap reads; self_index: the
+ * row to leave out -- the source's own row in that table -- or -1 to leave none out.
+ * The points are the measured pixels of the `stride` lattice of range, back-projected as gs_view_overlap does
+ * (gs_overlap_point of csrc/overlap_point.h).  For each point, c = the number of rows k != self_index, k < n_views, with
+ * gs_overlap_seen(p, views[k], near, border) true -- the decision of gs_view_overlap, bit for bit.  hist_dev
+ * [GS_REDUNDANCY_BINS + 1] int64 on the device, 8-byte aligned:
+ *   [b], b < 7   measured lattice pixels with c == b
+ *   [7]          measured lattice pixels with c >= 7
+ *   [8]          measured lattice pixels (the sum of the eight bins)
+ * Two launches on `stream`, no atomics and no host synchronisation: a count kernel writes one row of nine uint32 partial
+ * counts per workgroup to the workspace, a finalize kernel adds the rows in int64 in a fixed order.  The result is a pure
+ * function of the inputs, whatever hist_dev and the workspace held.  n_views == 1 with self_index == 0 is valid: every
+ * measured point lands in bin 0.
+ * Refused before anything is enqueued (GS_E_INVALID, gs_last_error): everything gs_view_overlap refuses (a null pointer, a
+ * source of non-positive size or focal length, stride < 1, near <= 0 or NaN, border < 0, n_views < 1 or >
+ * GS_OVERLAP_MAX_VIEWS, a misaligned views_dev, a misaligned or too-small workspace), self_index outside [-1, n_views), a
+ * misaligned hist_dev.  The rows of views_dev are validated by the table's owner (gs_view_overlap_check_view).
+ * gs_view_redundancy_pp: off-centre principal points, as gs_view_overlap_pp -- cam carries the source's offset, view_pp_dev
+ * the views' (two floats a row, 8-byte aligned, or NULL), the *_pp decisions are taken; with no offset anywhere the call IS
+ * gs_view_redundancy.  Also refused: an offset of `cam` that is not finite, a misaligned view_pp_dev. */
+#define GS_REDUNDANCY_BINS 8
+size_t gs_view_redundancy_workspace_bytes(int32_t H, int32_t W, int32_t stride);
+int gs_view_redundancy(const float *range, const gs_seed_camera *cam,      /* the SOURCE view: its range map, its camera (host) */
+                       const gs_seed_camera *views_dev, int32_t n_views,   /* the same DEVICE table gs_view_overlap reads        */
+                       int32_t self_index,                                 /* row to leave out, or -1: none                      */
+                       const gs_overlap_opts *opts, int64_t *hist_dev,     /* [GS_REDUNDANCY_BINS + 1]                           */
+                       void *workspace, size_t workspace_bytes, gs_stream_t stream);
+int gs_view_redundancy_pp(const float *range, const gs_seed_camera_pp *cam, const gs_seed_camera *views_dev,
+                          const float *view_pp_dev, int32_t n_views, int32_t self_index, const gs_overlap_opts *opts,
+                          int64_t *hist_dev, void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 /* ---- editing the map: remove rows by one per-row decision, move everything that shares the row index ----
  * Two calls around one host read, because the caller sizes the destination arrays between them (as gs_densify_* and

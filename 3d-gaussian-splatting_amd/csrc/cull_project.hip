@@ -462,6 +462,33 @@ __global__ void __launch_bounds__(STRIP_THREADS) frame_packed_project_count_pp_k
     project_count_body<DIST, true, true>(nullptr, nullptr, nullptr, nullptr, nullptr, pack_b, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
                                          tile_cost, n_tiles, tile_order, gate);
 }
+// GS_FRAME_DEVICE_POSE: the twins of frame_project_count_kernel / _pp_kernel whose pose is the 12 floats `cam_dev` points to as
+// they stand when the kernel runs (a uniform 48-byte load) instead of the descriptor's: P.cam is replaced, the body is the
+// unchanged one.  Kernels of their own names: the others keep their code.
+template <bool DIST>
+__global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_dp_kernel(
+    const Cam *__restrict__ cam_dev, const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
+    uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
+    uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
+    uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
+    P.cam = *cam_dev;
+    project_count_body<DIST, false, false>(pos, quat, scale, opa, rgb, nullptr, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+                                           tile_cost, n_tiles, tile_order, gate);
+}
+template <bool DIST>
+__global__ void __launch_bounds__(STRIP_THREADS) frame_project_count_pp_dp_kernel(
+    const Cam *__restrict__ cam_dev, const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint32_t *__restrict__ tiles_touched, uint4 *__restrict__ rects, GsDistCull D,
+    uint32_t per_slice, gs_strip_geom SG, uint32_t S, uint32_t slice0, unsigned long long *__restrict__ table,
+    uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis, const uint32_t *__restrict__ tile_cost,
+    uint32_t n_tiles, uint32_t *__restrict__ tile_order, const unsigned long long *__restrict__ gate) {
+    P.cam = *cam_dev;
+    project_count_body<DIST, false, true>(pos, quat, scale, opa, rgb, nullptr, n, P, rec_geom, tiles_touched, rects, D, per_slice, SG, S, slice0, table, slice_pairs, slice_vis,
+                                          tile_cost, n_tiles, tile_order, gate);
+}
 
 // ---------------------------------------------------------------- S1 + L1a of an occlusion-culled frame (first pass)
 // GS_FRAME_OCCLUSION_CULL (gs_frame_layout.h): the previous frame of this workspace left, per tile, the depth behind which
@@ -952,6 +979,25 @@ __global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_pp_kernel
     uint32_t *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis) {
     project_bin_count_body<DIST, true>(pos, quat, scale, opa, rgb, n, P, rec_geom, rects, D, per_block, T, table, slice_pairs, slice_vis);
 }
+// GS_FRAME_DEVICE_POSE: the table variant's twins (see frame_project_count_dp_kernel)
+template <bool DIST>
+__global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_dp_kernel(
+    const Cam *__restrict__ cam_dev, const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, GsDistCull D, uint32_t per_block, uint32_t T,
+    uint32_t *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis) {
+    P.cam = *cam_dev;
+    project_bin_count_body<DIST, false>(pos, quat, scale, opa, rgb, n, P, rec_geom, rects, D, per_block, T, table, slice_pairs, slice_vis);
+}
+template <bool DIST>
+__global__ void __launch_bounds__(BIN_THREADS) frame_project_bin_count_pp_dp_kernel(
+    const Cam *__restrict__ cam_dev, const float *__restrict__ pos, const float4 *__restrict__ quat, const float *__restrict__ scale,
+    const float *__restrict__ opa, const float *__restrict__ rgb, int64_t n, ProjectParams P,
+    float4 *__restrict__ rec_geom, uint4 *__restrict__ rects, GsDistCull D, uint32_t per_block, uint32_t T,
+    uint32_t *__restrict__ table, uint32_t *__restrict__ slice_pairs, uint32_t *__restrict__ slice_vis) {
+    P.cam = *cam_dev;
+    project_bin_count_body<DIST, true>(pos, quat, scale, opa, rgb, n, P, rec_geom, rects, D, per_block, T, table, slice_pairs, slice_vis);
+}
 
 }  // namespace
 
@@ -1057,7 +1103,10 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
                                    (const void *)frame_packed_project_count_pp_kernel<false>,
                                    (const void *)frame_packed_project_count_pp_kernel<true>,
                                    (const void *)frame_project_cull_count_pp_kernel,
-                                   (const void *)frame_packed_project_cull_count_pp_kernel})
+                                   (const void *)frame_packed_project_cull_count_pp_kernel,
+                                   (const void *)frame_project_count_dp_kernel<false>, (const void *)frame_project_count_dp_kernel<true>,
+                                   (const void *)frame_project_count_pp_dp_kernel<false>,
+                                   (const void *)frame_project_count_pp_dp_kernel<true>})
                 // (the kernels also hold ~17 KiB of static LDS -- the tile-order workgroup's bins --: the strip histogram, and the
                 // cut pyramid + survivor queue behind it in a culled frame, get what gs_frame_occlusion_cull's room rule allows)
                 GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_BIN_LDS_BYTES - 8 * 4096));
@@ -1071,6 +1120,8 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         const bool packed = gs_frame_scene_pack(f);
         const float4 *pack_a = packed ? (const float4 *)gs_frame_scene_fields(f)->scene_pack_a : nullptr;
         const float4 *pack_b = packed ? (const float4 *)gs_frame_scene_fields(f)->scene_pack_b : nullptr;
+        // GS_FRAME_DEVICE_POSE (a training frame without a pack or a cull: gs_frame.hip, validate): the *_dp_kernel twins
+        const Cam *cam_dev = (const Cam *)gs_frame_pose_dev(f);
         if (gs_frame_occlusion_cull(f) && !second_pass) {
             // GS_FRAME_OCCLUSION_CULL, first pass: Gaussians behind every cut they can reach are not projected, the level-1
             // entries of the others are trimmed by the cut table the previous frame of this workspace left
@@ -1120,7 +1171,13 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
         ws.slice_vis, ws.tile_cost, (uint32_t)G.n_tiles, ws.tile_order, gate
 #define GS_LAUNCH_PROJECT_COUNT(DIST)                                                                                  \
     do {                                                                                                               \
-        if (packed && P.pp)                                                                                            \
+        if (cam_dev && P.pp)                                                                                           \
+            hipLaunchKernelGGL(frame_project_count_pp_dp_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, stream, \
+                               cam_dev, f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_COUNT_TAIL);     \
+        else if (cam_dev)                                                                                              \
+            hipLaunchKernelGGL(frame_project_count_dp_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, stream, \
+                               cam_dev, f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, GS_COUNT_TAIL);     \
+        else if (packed && P.pp)                                                                                       \
             hipLaunchKernelGGL(frame_packed_project_count_pp_kernel<DIST>, dim3(nsl + extra), dim3(STRIP_THREADS), lds, \
                                stream, pack_b, GS_COUNT_TAIL);                                                         \
         else if (packed)                                                                                               \
@@ -1155,19 +1212,30 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
             std::lock_guard<std::mutex> lock(attr_mu2);
             for (const void *fn : {(const void *)frame_project_bin_count_kernel<false>, (const void *)frame_project_bin_count_kernel<true>,
                                    (const void *)frame_project_bin_count_pp_kernel<false>,
-                                   (const void *)frame_project_bin_count_pp_kernel<true>})
+                                   (const void *)frame_project_bin_count_pp_kernel<true>,
+                                   (const void *)frame_project_bin_count_dp_kernel<false>, (const void *)frame_project_bin_count_dp_kernel<true>,
+                                   (const void *)frame_project_bin_count_pp_dp_kernel<false>,
+                                   (const void *)frame_project_bin_count_pp_dp_kernel<true>})
                 GS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, GS_BIN_MAX_TILES * 4));
             attr_done2.fetch_or(1ull << dev, std::memory_order_release);
         }
         const uint32_t per_block = bin_per_block(f->N), B = (uint32_t)gs_div_up(f->N, per_block);
         const uint32_t T = (uint32_t)G.n_tiles;
+        const Cam *cam_dev = (const Cam *)gs_frame_pose_dev(f);  // GS_FRAME_DEVICE_POSE: the *_dp_kernel twins
+#define GS_BIN_TAIL                                                                                                    \
+    f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, ws.rects, D, per_block, T,        \
+        ws.bin_table, ws.slice_pairs, ws.slice_vis
 #define GS_LAUNCH_PROJECT_BIN_K(KERNEL)                                                                                \
-    hipLaunchKernelGGL(KERNEL, dim3(B), dim3(BIN_THREADS), sizeof(uint32_t) * T, stream,                               \
-                       f->pos, (const float4 *)f->quat, f->scale, f->opa, f->rgb, f->N, P, ws.rec_geom, ws.rects, D,   \
-                       per_block, T, ws.bin_table, ws.slice_pairs, ws.slice_vis)
+    hipLaunchKernelGGL(KERNEL, dim3(B), dim3(BIN_THREADS), sizeof(uint32_t) * T, stream, GS_BIN_TAIL)
+#define GS_LAUNCH_PROJECT_BIN_DP(KERNEL)                                                                               \
+    hipLaunchKernelGGL(KERNEL, dim3(B), dim3(BIN_THREADS), sizeof(uint32_t) * T, stream, cam_dev, GS_BIN_TAIL)
 #define GS_LAUNCH_PROJECT_BIN(DIST)                                                                                    \
     do {                                                                                                               \
-        if (P.pp)                                                                                                      \
+        if (cam_dev && P.pp)                                                                                           \
+            GS_LAUNCH_PROJECT_BIN_DP(frame_project_bin_count_pp_dp_kernel<DIST>);                                      \
+        else if (cam_dev)                                                                                              \
+            GS_LAUNCH_PROJECT_BIN_DP(frame_project_bin_count_dp_kernel<DIST>);                                         \
+        else if (P.pp)                                                                                                 \
             GS_LAUNCH_PROJECT_BIN_K(frame_project_bin_count_pp_kernel<DIST>);                                          \
         else                                                                                                           \
             GS_LAUNCH_PROJECT_BIN_K(frame_project_bin_count_kernel<DIST>);                                             \
@@ -1178,6 +1246,8 @@ int gs_stage_project(const gs_frame *f, const gs_frame_ws &ws, hipStream_t strea
             GS_LAUNCH_PROJECT_BIN(false);
 #undef GS_LAUNCH_PROJECT_BIN
 #undef GS_LAUNCH_PROJECT_BIN_K
+#undef GS_LAUNCH_PROJECT_BIN_DP
+#undef GS_BIN_TAIL
         GS_CHECK_LAUNCH();
         return 0;
     }

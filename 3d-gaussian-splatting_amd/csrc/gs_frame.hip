@@ -66,7 +66,8 @@ static int validate(const gs_frame *f) {
     GS_CHECK_ARG((f->flags & ~(GS_FRAME_EMIT_SORTED_KEYS | GS_FRAME_SLICE_SORT | GS_FRAME_TABLE_BIN |
                                GS_FRAME_SERIAL_LONG_LISTS | GS_FRAME_LONG_LISTS | GS_FRAME_STRIP_BIN |
                                GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR |
-                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD | GS_FRAME_SCENE_PACK | GS_FRAME_PRINCIPAL_POINT)) == 0,
+                               GS_FRAME_AUX | GS_FRAME_POSE_GRAD | GS_FRAME_SCENE_PACK | GS_FRAME_PRINCIPAL_POINT |
+                               GS_FRAME_DEVICE_POSE)) == 0,
                  "unknown flag bits");
     GS_CHECK_ARG(f->sort_mode >= 0 && f->sort_mode <= 2,
                  "sort_mode must be 0 (full LSD radix), 1 (tile-bit radix + per-tile LDS sort) or 2 (LDS counting sort "
@@ -93,6 +94,23 @@ static int validate(const gs_frame *f) {
             gs_set_error("gs_frame: GS_FRAME_POSE_GRAD: pose workspace too small (%zu < %zu bytes)", f->pose_workspace_bytes,
                          pose_need);
             return GS_E_INVALID;
+        }
+    }
+    if (f->flags & GS_FRAME_DEVICE_POSE) {  // (the trailing field behind the principal-point fields, as above)
+        const float *pose_dev = gs_frame_pose_dev(f);
+        GS_CHECK_ARG(pose_dev != nullptr && ((uintptr_t)pose_dev & 15) == 0, "GS_FRAME_DEVICE_POSE: pose_dev null or not 16-byte aligned");
+        // what a flagged frame cannot be: the first rule that applies names itself (nothing is enqueued behind a refusal)
+        const char *why = !f->training                ? "inference frames take the pose by value (training must be 1)"
+                          : f->color_dim != 3         ? "SH colours read rays_o / lefttop / vec_dx / vec_dy, pose-derived host scalars"
+                          : f->sort_mode != 2         ? "sort_mode 0 and 1 have no device-pose project kernel"
+                          : (f->flags & GS_FRAME_OCCLUSION_CULL) ? "GS_FRAME_OCCLUSION_CULL is not supported"
+                          : (f->flags & GS_FRAME_SCENE_PACK)     ? "GS_FRAME_SCENE_PACK is not supported"
+                          : !(gs_frame_uses_strips(f) || gs_frame_fused_table_count(f))
+                              ? "only the strip and table variants of sort_mode 2 have a device-pose project kernel"
+                              : nullptr;
+        if (why) {
+            gs_set_error("gs_frame: GS_FRAME_DEVICE_POSE: %s", why);
+            return GS_E_UNSUPPORTED;
         }
     }
     if (f->flags & GS_FRAME_SCENE_PACK) {  // (trailing fields, as above; checked whether or not this frame's path reads the pack)
@@ -296,6 +314,14 @@ static int raster_backward(const gs_frame *f, const gs_frame_ws &ws, const float
     return gs_stage_raster_backward(f, ws, sids, grad_image, s, prepared);
 }
 
+// GS_FRAME_DEVICE_POSE: an entry point without a device-pose kernel behind it (only gs_frame_forward and
+// gs_frame_backward_pose have one; the queries launch nothing).  Called behind validate(f), before anything is enqueued.
+static int refuse_device_pose(const gs_frame *f, const char *entry) {
+    if (!(f->flags & GS_FRAME_DEVICE_POSE)) return 0;
+    gs_set_error("%s: GS_FRAME_DEVICE_POSE frames are not supported (gs_frame_forward and gs_frame_backward_pose take them)", entry);
+    return GS_E_UNSUPPORTED;
+}
+
 // The forward in two phases: PROJECT (cull + project + activations + level-1 count; in the strip variant it may be
 // issued as several ranges of slices of the Gaussian array, in any order, slice 0's range first) and REST
 // (binning, per-tile sort, compositing).  gs_frame_forward = both; gs_frame_forward_project / _rest expose them to the
@@ -306,6 +332,7 @@ static int frame_forward_impl(const gs_frame *f, hipStream_t s, float *stage_ms,
                               int slice_end = -1) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((phases != 3 || stage_ms) && (rc = refuse_device_pose(f, "gs_frame_forward_project / _rest / _profile"))) return rc;
     GS_CHECK_ARG(!f->training || f->image_padded, "training needs image_padded");
     GS_CHECK_ARG(f->image || f->image_padded, "no output image");
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
@@ -445,6 +472,7 @@ static int frame_backward_impl(const gs_frame *f, const float *grad_image, float
                                float *stage_ms, int64_t g_begin = 0, int64_t g_end = -1) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, "gs_frame_backward / _part / _slice / _profile"))) return rc;
     if (g_end < 0) g_end = f->N;
     GS_CHECK_ARG(g_begin >= 0 && g_begin <= g_end && g_end <= f->N && (g_begin & 255) == 0,
                  "bad Gaussian range (g_begin must be a multiple of 256)");
@@ -526,6 +554,7 @@ extern "C" int gs_frame_contrib(const gs_frame *f, const gs_contrib_opts *opts, 
                                 size_t workspace_bytes, gs_stream_t stream) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, __func__))) return rc;
     GS_CHECK_ARG(f->training && f->image_padded, "gs_frame_contrib needs a training forward (image_padded kept)");
     GS_CHECK_ARG(opts != nullptr, "opts is null");
     GS_CHECK_ARG(opts->w_min > 0.f && opts->w_min <= 1.f, "w_min must lie in (0, 1]");  // (false for NaN)
@@ -609,6 +638,7 @@ extern "C" int gs_frame_backward_adam(const gs_frame *f, const float *grad_image
                                       gs_stream_t stream) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, __func__))) return rc;
     if (f->flags & GS_FRAME_AUX) return refuse_flag(__func__, "GS_FRAME_AUX");
     if (f->flags & GS_FRAME_POSE_GRAD) return refuse_flag(__func__, "GS_FRAME_POSE_GRAD");
     return frame_backward_adam_impl(__func__, f, grad_image, adam, (hipStream_t)stream);
@@ -619,6 +649,7 @@ extern "C" int gs_frame_backward_adam_aux(const gs_frame *f, const float *grad_i
                                           gs_stream_t stream) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, __func__))) return rc;
     GS_CHECK_ARG((f->flags & GS_FRAME_AUX) != 0, "the frame is not flagged GS_FRAME_AUX (gs_frame_backward_adam takes plain frames)");
     if (f->flags & GS_FRAME_POSE_GRAD) return refuse_flag(__func__, "GS_FRAME_POSE_GRAD");
     return frame_backward_adam_impl(__func__, f, grad_image, adam, (hipStream_t)stream);
@@ -630,6 +661,7 @@ extern "C" int gs_frame_backward_adam_pose(const gs_frame *f, const float *grad_
                                            gs_stream_t stream) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, __func__))) return rc;
     GS_CHECK_ARG((f->flags & GS_FRAME_POSE_GRAD) != 0,
                  "the frame is not flagged GS_FRAME_POSE_GRAD (gs_frame_backward_adam / _adam_aux take frames without a pose gradient)");
     if (f->color_dim != 3) return refuse_sh_pose(__func__);
@@ -676,6 +708,7 @@ extern "C" int gs_frame_backward_slice(const gs_frame *f, float *grad_pos, float
     // partial sum is in
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, __func__))) return rc;
     if (f->flags & GS_FRAME_POSE_GRAD) {
         gs_set_error("gs_frame_backward_slice: GS_FRAME_POSE_GRAD frames are not supported (use gs_frame_backward or "
                      "gs_frame_backward_part)");
@@ -825,6 +858,7 @@ extern "C" int gs_frame_debug_views(const gs_frame *f, const uint64_t **sorted_k
                                     const float **rec_color, const uint32_t **tiles_touched) {
     int rc = validate(f);
     if (rc) return rc;
+    if ((rc = refuse_device_pose(f, __func__))) return rc;
     gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
     uint64_t *skeys, *okeys;
     uint32_t *sids;

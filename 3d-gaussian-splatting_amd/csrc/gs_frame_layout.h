@@ -215,6 +215,11 @@ static inline const gs_frame_scene *gs_frame_scene_fields(const gs_frame *f) {
 }
 // GS_FRAME_PRINCIPAL_POINT: the two offsets behind the scene-pack fields of a flagged frame (include/gs_abi.h, gs_frame_pp)
 static inline const gs_frame_pp *gs_frame_pp_fields(const gs_frame *f) { return reinterpret_cast<const gs_frame_pp *>(f); }
+// GS_FRAME_DEVICE_POSE: the pose pointer behind the principal-point fields of a flagged frame (include/gs_abi.h, gs_frame_dp);
+// NULL for an unflagged frame, whose kernels take the pose by value
+static inline const float *gs_frame_pose_dev(const gs_frame *f) {
+    return (f->flags & GS_FRAME_DEVICE_POSE) ? reinterpret_cast<const gs_frame_dp *>(f)->pose_dev : nullptr;
+}
 static inline bool gs_frame_scene_pack(const gs_frame *f) {
     return (f->flags & GS_FRAME_SCENE_PACK) && !f->training && f->N > 0 && gs_frame_uses_strips(f);
 }

@@ -587,6 +587,29 @@ __global__ void __launch_bounds__(256) frame_pose_backward_kernel(
 #include "frame_project_backward_body.inc"
 }
 
+// GS_FRAME_DEVICE_POSE: frame_pose_backward_kernel's twin whose pose is the 12 floats `cam_dev` points to as they stand when the
+// kernel runs (a uniform 48-byte load; the caller's promise: what the frame's forward read) instead of the descriptor's -- P.cam is
+// replaced, the body is the same include.  A kernel of its own name: the others keep their code.
+template <bool AUX>
+__global__ void __launch_bounds__(256) frame_pose_backward_dp_kernel(
+    const float *pos, const float4 *quat, const float *scale,
+    int64_t n, ProjectParams P, const float4 *__restrict__ rec_geom,
+    const float4 *__restrict__ rec_color, const float4 *__restrict__ rows,
+    const unsigned long long *__restrict__ stop_keys, const float *opa_raw,
+    const float *rgb_raw, GsDistCull D,
+    const uint32_t *__restrict__ pair_offsets, const uint4 *__restrict__ rects, uint64_t max_pairs,
+    float *__restrict__ pose_part, float *__restrict__ pose_part_aux, const Cam *__restrict__ cam_dev) {
+    constexpr int CDIM = 3, PART = 1, BLOCK = 256, ADAM = 0;
+    constexpr bool POSE = true, POSE_ONLY = true;
+    const int64_t g_first = 0;
+    [[maybe_unused]] const AdamFusedDev A{};
+    // (no gradient is stored: the names the body's unfused tail mentions)
+    [[maybe_unused]] float *const grad_pos = nullptr, *const grad_scale = nullptr, *const grad_opa = nullptr, *const grad_rgb = nullptr;
+    [[maybe_unused]] float4 *const grad_quat = nullptr;
+    P.cam = *cam_dev;
+#include "frame_project_backward_body.inc"
+}
+
 }  // namespace
 
 // ================================================================= C ABI (section A)
@@ -686,7 +709,15 @@ int gs_stage_project_backward_pose(const gs_frame *f, const gs_frame_ws &ws, flo
 int gs_stage_pose_only_backward(const gs_frame *f, const gs_frame_ws &ws, hipStream_t stream) {
     if (f->N <= 0) return 0;
     const gs_frame_pose_ws pw = gs_frame_pose_carve(f->pose_workspace, f->N);
-    if (f->flags & GS_FRAME_AUX)
+    // GS_FRAME_DEVICE_POSE: the twin, the pose pointer as its tail argument
+    const Cam *cam_dev = (const Cam *)gs_frame_pose_dev(f);
+    if (cam_dev && (f->flags & GS_FRAME_AUX))
+        launch_project_backward(frame_pose_backward_dp_kernel<true>, (unsigned)pw.rows, 256, stream, f, ws, f->N, pw.proj, pw.aux,
+                                cam_dev);
+    else if (cam_dev)
+        launch_project_backward(frame_pose_backward_dp_kernel<false>, (unsigned)pw.rows, 256, stream, f, ws, f->N, pw.proj, pw.aux,
+                                cam_dev);
+    else if (f->flags & GS_FRAME_AUX)
         launch_project_backward(frame_pose_backward_kernel<true>, (unsigned)pw.rows, 256, stream, f, ws, f->N, pw.proj, pw.aux);
     else
         launch_project_backward(frame_pose_backward_kernel<false>, (unsigned)pw.rows, 256, stream, f, ws, f->N, pw.proj, pw.aux);

@@ -63,6 +63,13 @@ class GsFramePP(GsFrameScene):
     _fields_ = [("pp_dx", C.c_double), ("pp_dy", C.c_double)]
 
 
+class GsFrameDP(GsFramePP):
+    """Mirror of ``struct gs_frame_dp``: a ``gs_frame_pp`` followed by the GS_FRAME_DEVICE_POSE field (read by the library only
+    when the flag is set).  An instance is accepted wherever a ``GsFrame`` is."""
+
+    _fields_ = [("pose_dev", vp)]
+
+
 GS_FRAME_EMIT_SORTED_KEYS = 1
 GS_FRAME_SLICE_SORT = 2
 GS_FRAME_TABLE_BIN = 4
@@ -78,6 +85,7 @@ GS_FRAME_AUX = 2048
 GS_FRAME_POSE_GRAD = 4096
 GS_FRAME_SCENE_PACK = 8192
 GS_FRAME_PRINCIPAL_POINT = 16384
+GS_FRAME_DEVICE_POSE = 32768
 
 
 def _sig(name, restype, *argtypes):
@@ -322,6 +330,28 @@ gs_icp_reset = _sig("gs_icp_reset", ci, vp, vp, i32, C.POINTER(C.c_double), C.PO
 gs_icp_step = _sig("gs_icp_step", ci, vp, C.POINTER(GsSeedCameraPP), vp, vp, C.POINTER(GsSeedCameraPP), C.POINTER(GsIcpOpts),
                    vp, vp, i32, i32, vp, sz, vp)
 
+GS_POSE_LOG_HEAD = 24
+
+
+class GsPoseState(C.Structure):
+    """Mirror of ``struct gs_pose_state`` (it lives in device memory)."""
+
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("m", C.c_double * 6), ("v", C.c_double * 6),
+                ("best_R", C.c_double * 9), ("best_t", C.c_double * 3), ("best_loss", C.c_double),
+                ("steps", i32), ("best_row", i32), ("skipped", i32), ("bad", i32)]
+
+
+class GsPoseStepOpts(C.Structure):
+    """Mirror of ``struct gs_pose_step_opts``."""
+
+    _fields_ = [("lr_rot", C.c_double), ("lr_tran", C.c_double), ("lr_scale", C.c_double), ("beta1", C.c_double),
+                ("beta2", C.c_double), ("eps", C.c_double), ("track_best", i32), ("n_values", i32)]
+
+
+gs_pose_log_bytes = _sig("gs_pose_log_bytes", sz, i32, i32)
+gs_pose_reset = _sig("gs_pose_reset", ci, vp, vp, vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp)
+gs_pose_step = _sig("gs_pose_step", ci, vp, vp, vp, vp, C.POINTER(GsPoseStepOpts), vp, vp, vp, i32, i32, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -349,6 +379,7 @@ EXPORTS = [
     "gs_pyramid_down",
     "gs_icp_model_bytes", "gs_icp_workspace_bytes", "gs_icp_log_bytes", "gs_icp_model_maps", "gs_icp_reset", "gs_icp_step",
     "gs_view_redundancy_workspace_bytes", "gs_view_redundancy", "gs_view_redundancy_pp",
+    "gs_pose_log_bytes", "gs_pose_reset", "gs_pose_step",
 ]
 
 

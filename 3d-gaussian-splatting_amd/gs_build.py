@@ -63,6 +63,9 @@ SOURCES = {
     # the vertices, the normals and the keep / drop tests of icp_point.h as written, one rounding per operation: the float32
     # restatement (tests/icp_ref.py) gives the maps bit for bit and the counts exactly; no SLP packing, as above
     "icp.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    # Adam on the pose's six tangent numbers in double, every product rounded before it is added: the Python restatement
+    # (tests/pose_step_ref.py) follows it operation by operation
+    "pose_step.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

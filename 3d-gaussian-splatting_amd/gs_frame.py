@@ -169,9 +169,10 @@ class FrameRenderer:
         self._aux_ws: Optional[torch.Tensor] = None  # GS_FRAME_AUX frames: the library's second workspace (grown with the first)
         self._aux_keep = None  # (depth, alpha, aux_padded) of the last forward, kept for its backward
         self._pose_ws: Optional[torch.Tensor] = None  # GS_FRAME_POSE_GRAD backwards: the per-workgroup partial sums
+        self._pose_dev_keep: Optional[torch.Tensor] = None  # GS_FRAME_DEVICE_POSE: the last forward's pose tensor, kept alive
         self._contrib_ws: Optional[torch.Tensor] = None  # contributions(): the pair rows (regrown with max_pairs)
         self._stats_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
-        self._frame: Optional[_lib.GsFramePP] = None
+        self._frame: Optional[_lib.GsFrameDP] = None
         self._frame_serial = 0  # counts forwards: autograd checks that backward() belongs to the latest one
         self._cam_cache = {}
         self._keep = None
@@ -191,7 +192,7 @@ class FrameRenderer:
                 float(camera.near), np.asarray(camera.rot, np.float32).tobytes(),
                 np.asarray(camera.tran, np.float32).tobytes(), principal_point_offset(camera))
 
-    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFramePP:
+    def _describe(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameDP:
         # A viewer or a benchmark renders the same tensors from the same camera object again and again: the descriptor
         # of the previous call is reused as long as nothing it was built from has changed (tensor identities and
         # storage, camera object, renderer settings) -- the validation below, ~40 ctypes stores and a library call cost
@@ -217,19 +218,19 @@ class FrameRenderer:
                self._ws.data_ptr() if self._ws is not None else 0)
         cached = getattr(self, "_desc_cache", None)
         if cached is not None and cached[0] == key:
-            f = _lib.GsFramePP()
-            C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFramePP))
+            f = _lib.GsFrameDP()
+            C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFrameDP))
             self._grid = cached[3]
             return f
         f = self._describe_uncached(pos, quat, scale, opa, rgb, camera, training, aux)
         # (the key is taken again: building the descriptor may have (re)allocated the workspaces)
         key = key[:-2] + (self._aux_ws.data_ptr() if aux else 0, self._ws.data_ptr())
-        keep = _lib.GsFramePP()
-        C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFramePP))
+        keep = _lib.GsFrameDP()
+        C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFrameDP))
         self._desc_cache = (key, keep, None, self._grid)
         return f
 
-    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFramePP:
+    def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameDP:
         n = int(pos.shape[0])
         color_dim = int(rgb.shape[1]) if rgb.dim() == 2 else 1
         if color_dim not in (3, 27, 48):  # rgb logits, SH degree 2 (the reference's), SH degree 3 (extension)
@@ -258,7 +259,7 @@ class FrameRenderer:
             else:
                 zero3 = np.zeros(3, np.float32)
                 rays = RayBasis(zero3, zero3, zero3, zero3)
-            c = _lib.GsFramePP()
+            c = _lib.GsFrameDP()
             c.rot, c.tran = pose_ctypes(camera)
             c.near_plane, c.half_width, c.half_height = float(camera.near), half_w, half_h
             c.width, c.height = grid.width, grid.height
@@ -274,8 +275,8 @@ class FrameRenderer:
                 self._cam_cache.clear()
             cached = self._cam_cache[ck] = (c, grid)
         proto, grid = cached
-        f = _lib.GsFramePP()
-        C.memmove(C.byref(f), C.byref(proto), C.sizeof(_lib.GsFramePP))
+        f = _lib.GsFrameDP()
+        C.memmove(C.byref(f), C.byref(proto), C.sizeof(_lib.GsFrameDP))
         f.N, f.color_dim, f.scale_activation = n, color_dim, self.scale_activation
         f.pos, f.quat, f.scale, f.opa, f.rgb = (t.data_ptr() for t in (pos, quat, scale, opa, rgb))
         # "dist": the squared distance threshold of splatter.py:577
@@ -426,7 +427,8 @@ class FrameRenderer:
             pass
 
     # ------------------------------------------------------------------ low-level API
-    def forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None, aux: bool = False):
+    def forward(self, pos, quat, scale, opa, rgb, camera, training: Optional[bool] = None, aux: bool = False,
+                pose_dev: Optional[torch.Tensor] = None):
         """Raw parameters -> (image [H,W,3] clamped+cropped, padded raw image or None); with ``aux`` (GS_FRAME_AUX,
         include/gs_abi.h) -> (image, padded, depth [H,W], alpha [H,W]): depth = sum w_i d_i with d_i the distance from the
         camera centre, alpha = sum w_i, over the Gaussians the colour composites, cropped and not clamped.  A training aux
@@ -439,10 +441,18 @@ class FrameRenderer:
         grows the workspace (25 % head room, and already when a frame comes within 25 % of the capacity) -- a training
         frame that overflowed all the same was rendered empty and is counted in ``overflowed_frames`` once its counters
         arrive; ``overflow_flag()`` is the device address of the frame's overflow counter, which gs_train.Trainer hands
-        to the fused Adam so that such a step is skipped on the device.  ``False`` never checks."""
+        to the fused Adam so that such a step is skipped on the device.  ``False`` never checks.
+
+        ``pose_dev`` (GS_FRAME_DEVICE_POSE, include/gs_abi.h): 12 contiguous float32 on the renderer's device, rot [9] row-major
+        then tran [3] -- the frame's kernels read the pose from it as it stands when they execute (a pose an earlier kernel on
+        the stream wrote: gs_pose_step), not ``camera.rot`` / ``camera.tran``, which still fill the descriptor.  Bit for bit
+        the frame of that pose by value.  Training frames with rgb colours and ``sort_mode`` 2 (strip or table variant) only;
+        the tensor must not change before the frame's ``backward_pose``, the only backward such a frame has."""
         training = self.training if training is None else training
+        if pose_dev is not None:
+            self._check_pose_dev(pose_dev, training, rgb)
         with torch.cuda.device(self.device):
-            image, padded = self._forward(pos, quat, scale, opa, rgb, camera, training, aux)
+            image, padded = self._forward(pos, quat, scale, opa, rgb, camera, training, aux, pose_dev)
         if aux:
             return image, padded, self._aux_keep[0], self._aux_keep[1]
         return image, padded
@@ -624,7 +634,22 @@ class FrameRenderer:
         self._poll_async_counters()
         return getattr(self, "_last_overflow_serial", -1) == self._frame_serial
 
-    def _forward(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False):
+    def _check_pose_dev(self, pose_dev, training, rgb):
+        """What the renderer can know of the library's refusals of a GS_FRAME_DEVICE_POSE frame, as Python errors."""
+        check_tensor("pose_dev", pose_dev, device=self.device)
+        if pose_dev.numel() != 12:
+            raise RuntimeError(f"pose_dev must hold 12 floats (rot [9] row-major, tran [3]), got {pose_dev.numel()}")
+        if pose_dev.data_ptr() % 16:
+            raise RuntimeError("pose_dev must be 16-byte aligned")
+        if not training:
+            raise RuntimeError("pose_dev needs a training frame (forward(training=True)): inference frames take the pose by value")
+        if rgb.dim() != 2 or rgb.shape[1] != 3:
+            raise RuntimeError("pose_dev needs rgb colours: with SH colours the frame reads ray vectors the host derives from "
+                               "the pose")
+        if self.sort_mode != 2 or self.slice_sort:
+            raise RuntimeError("pose_dev needs sort_mode 2 in its strip or table variant")
+
+    def _forward(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False, pose_dev=None):
         self._begun = None  # any frame opened by forward_begin lived in the workspace this frame is about to overwrite
         stream = self._stream().cuda_stream
         sync_check = self.auto_grow is True or (self.auto_grow == "async" and (not training or not self._checked_once))
@@ -640,6 +665,10 @@ class FrameRenderer:
             f.image = image.data_ptr()
             f.image_padded = padded.data_ptr() if padded is not None else None
             self._aux_keep = self._aux_outputs(f, training) if aux else None
+            if pose_dev is not None:  # (behind the descriptor cache, which stays that of the by-value frame)
+                f.pose_dev = pose_dev.data_ptr()
+                f.flags |= _lib.GS_FRAME_DEVICE_POSE
+            self._pose_dev_keep = pose_dev
             _lib.check(_lib.gs_frame_forward(C.byref(f), stream), "gs_frame_forward")
             self._frame = f
             self._frame_serial += 1
@@ -882,14 +911,17 @@ class FrameRenderer:
             self._bwd_serial = self._frame_serial  # this frame's bucket counter is final once the stream gets here
         return out
 
-    def backward_pose(self, grad_image, grad_pose, part: int = 0, grad_depth=None, grad_alpha=None):
+    def backward_pose(self, grad_image, grad_pose, part: int = 0, grad_depth=None, grad_alpha=None, pose_dev=None):
         """dL/d(image) -> ``grad_pose`` = (grad_rot [3,3], grad_tran [3]) and nothing else (gs_frame_backward_pose, include/
         gs_abi.h): the pose gradient ``backward(..., grad_pose=...)`` writes, bit for bit, for a caller that holds the map
         fixed -- no per-Gaussian gradient is computed, and no per-Gaussian tensor is allocated or written.  rgb colours only.
         ``part`` 0 = the raster backward and the pose gradient (``grad_depth`` / ``grad_alpha`` / a None ``grad_image`` as in
         ``backward``); ``GS_BWD_GEOMETRY`` = the pose gradient from the rows a preceding ``backward(part=GS_BWD_RASTER)`` of
-        this frame left."""
+        this frame left.  A frame rendered with ``pose_dev`` is differentiated at the pose that tensor holds -- the caller's
+        promise: what its forward read; ``pose_dev`` here must be that tensor (or None: it is kept from the forward)."""
         f = self._training_frame("backward_pose")
+        if pose_dev is not None and pose_dev is not self._pose_dev_keep:
+            raise RuntimeError("backward_pose(pose_dev=...) must be the tensor the frame's forward was given")
         grad_image, grad_depth, grad_alpha = self._raster_inputs(f, part, grad_image, grad_depth, grad_alpha)
         f = self._pose_frame(f, grad_pose, part)
         with torch.cuda.device(self.device):
@@ -934,8 +966,8 @@ class FrameRenderer:
         need = _lib.gs_frame_pose_workspace_bytes(int(f.N))
         if self._pose_ws is None or self._pose_ws.numel() < need + 256:
             self._pose_ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
-        g = _lib.GsFramePP()
-        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFramePP))
+        g = _lib.GsFrameDP()
+        C.memmove(C.byref(g), C.byref(f), C.sizeof(_lib.GsFrameDP))
         base = self._pose_ws.data_ptr()
         g.pose_workspace = (base + 255) // 256 * 256
         g.pose_workspace_bytes = self._pose_ws.numel() - (g.pose_workspace - base)

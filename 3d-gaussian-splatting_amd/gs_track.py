@@ -20,6 +20,12 @@ dL/dtran and the four loss values are views of one 16-float device buffer that a
 The pose step runs on the host in float64: rot = exp([w]x) R re-linearised at w = 0 every iteration, Adam on (w, tran),
 R <- exp([dw]x) R -- rot stays on SO(3) by construction.  The map's parameters are never written.
 
+With ``TrackOptions.device_pose`` the pose itself lives on the device: every frame is a GS_FRAME_DEVICE_POSE frame that reads
+its 12 floats from ``pose_dev``, and one gs_pose_step launch behind ``backward_pose`` takes the Adam step there (PoseAdam,
+so3_exp, rot_tangent_grad and the best-pose bookkeeping below, restated in double in pose_step.hip) and logs the iteration.
+A whole ``track`` call is enqueued without a host wait and read back ONCE; a frame that overflowed its workspace is skipped
+on the device and the call run again in a larger one.  Implies ``pose_only``.  Off by default.
+
 Coarse to fine: ``TrackOptions.pyramid`` = ((level, iterations), ...) walks pyramid levels in order (gs_pyramid: the targets of
 level l are gs_pyramid_down applied l times, its camera the frame's with size, focal lengths and principal point / 2^l), one
 renderer and one loss object per scheduled level, ONE PoseAdam for the whole call.  With the default () nothing of this exists
@@ -27,8 +33,9 @@ and every call is the call described above.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -60,6 +67,9 @@ class TrackOptions:
     # the pose gradient through FrameRenderer.backward_pose: no per-Gaussian gradient is computed or stored (bit for bit the
     # same pose gradient, so the same track)
     pose_only: bool = False
+    # the pose in device memory, stepped there by gs_pose_step: no host wait inside ``track``, one read at its end (implies
+    # pose_only; the renderers do not grow by themselves: an overflowed call is run again, ``TrackResult.attempts``)
+    device_pose: bool = False
     # coarse to fine: stages (pyramid level, iterations) in order, levels strictly decreasing; () (the default): no pyramid,
     # ``iterations`` full-resolution iterations.  With a schedule ``iterations`` is not read: the total is the stages' sum
     pyramid: Tuple[Tuple[int, int], ...] = ()
@@ -107,6 +117,9 @@ class TrackResult:
     medians = None       # (m_d, m_c): the median residuals the thresholds were multiples of
     # With a schedule (TrackOptions.pyramid): [(level, index of its first iteration in ``losses``, count), ...]; else None
     levels = None
+    log = None           # TrackOptions.device_pose: float32 [iterations, 24 + n] -- per row the 12 pose floats the iteration
+    #                      rendered, dL/drot [9], dL/dtran [3] and the loss's n values; else None
+    attempts = 1         # runs of the call (TrackOptions.device_pose: one more per workspace growth; else always 1)
 
 
 def so3_exp(w) -> np.ndarray:
@@ -214,6 +227,8 @@ class Tracker:
 
     def __init__(self, params, camera, options: Optional[TrackOptions] = None, device="cuda"):
         self.opt = options if options is not None else TrackOptions()
+        if self.opt.device_pose and not self.opt.pose_only:  # (the only backward a device-pose frame has)
+            self.opt = replace(self.opt, pose_only=True)
         self._check_map(params)
         self.device = require_hip(device, "Tracker")
         self.camera = camera
@@ -243,6 +258,9 @@ class Tracker:
             self.renderer, self.loss = self._levels[plan[-1][0]][:2]  # the finest scheduled level's
             self._pyramid = Pyramid(self.H, self.W, plan[0][0], self.device)
         self._scratch = None
+        self._dp = None  # TrackOptions.device_pose: the device state + log, pose_dev and their pinned host copy (_device_buffers)
+        if self.opt.device_pose:
+            self._device_buffers(sum(n for _, n in self._stages) if self._stages else int(self.opt.iterations), nfloat - 12)
         self.set_map(params)
         self.reset()
 
@@ -269,8 +287,9 @@ class Tracker:
         return [(level, height >> level, width >> level) for level, _ in stages]
 
     def _new_renderer(self):
+        # (device_pose: reading the pair counters after every frame is one of the two waits the option removes)
         return FrameRenderer(self.device, max_pairs=int(self.opt.max_pairs), training=True, occlusion_cull=False,
-                             auto_grow=True)
+                             auto_grow=not self.opt.device_pose)
 
     @staticmethod
     def _check_map(params):
@@ -343,18 +362,15 @@ class Tracker:
         RGB only): contiguous float32 tensors on the tracker's device.  Returns the pose with the lowest loss seen."""
         o = self.opt
         R, t = self._start_pose(init)
+        if o.device_pose:
+            return self._track_on_device(R, t, image, range_map)
         adam = PoseAdam(R, t, o.lr_rot, o.lr_tran, o.betas, o.eps)  # Adam's moments on (w, tran): kept across iterations, reset per call
         best = (math.inf, R, t, None)
         losses: List[float] = []
         # coarse to fine: the targets once, then the stages in order under ONE PoseAdam (moments and step count carry across
         # stages, the rate decays over the whole call); losses of different levels are not comparable, so the pose returned
         # is the lowest-loss one of the LAST stage.  Without a schedule: one stage at level 0 on the caller's tensors
-        if self._stages is None:
-            stages, images, ranges = ((0, int(o.iterations)),), (image,), (range_map,)
-        else:
-            stages = self._stages
-            images, ranges = self._pyramid.build(image, range_map)
-        total = sum(n for _, n in stages)
+        stages, images, ranges, total = self._stage_list(image, range_map)
         levels, k = [], 0
         for level, n in stages:
             levels.append((level, k, n))
@@ -374,4 +390,106 @@ class Tracker:
             res.inliers = (int(gate[0]), int(gate[4]), int(gate[1]))
             res.medians = (float(gate[2]), float(gate[3]))
         res.levels = levels if self._stages is not None else None
+        return res
+
+    # ------------------------------------------------------------------ TrackOptions.device_pose
+    MAX_ATTEMPTS = 3
+
+    def _device_buffers(self, rows: int, n_values: int):
+        """The device state, ``pose_dev``, the log of ``rows`` rows and ONE pinned host buffer that receives state + log."""
+        if self._dp is None or self._dp["rows"] < rows:
+            state_bytes = C.sizeof(_lib.GsPoseState)
+            state_pad = (state_bytes + 15) // 16 * 16  # (the log behind the state stays 16-byte aligned)
+            log_bytes = int(_lib.gs_pose_log_bytes(rows, n_values))
+            dev = torch.zeros(state_pad + log_bytes, dtype=torch.uint8, device=self.device)
+            self._dp = {"rows": rows, "dev": dev, "state_bytes": state_bytes, "state_pad": state_pad,
+                        "pose": torch.zeros(12, dtype=torch.float32, device=self.device),
+                        "host": torch.zeros(state_pad + log_bytes, dtype=torch.uint8).pin_memory()}
+        return self._dp
+
+    def _stage_list(self, image, range_map):
+        """(stages, targets per level, total iterations) of one call -- what ``track`` walks."""
+        if self._stages is None:
+            stages, images, ranges = ((0, int(self.opt.iterations)),), (image,), (range_map,)
+        else:
+            stages = self._stages
+            images, ranges = self._pyramid.build(image, range_map)
+        return stages, images, ranges, sum(n for _, n in stages)
+
+    def _enqueue_device_track(self, R, t, stages, images, ranges, total, dp, n_values):
+        """One attempt: reset, then per iteration forward (flagged) / loss / backward_pose / gs_pose_step -- nothing waits."""
+        o = self.opt
+        base = dp["dev"].data_ptr()
+        state_ptr, log_ptr, pose = base, base + dp["state_pad"], dp["pose"]
+        rot = (C.c_double * 9)(*np.asarray(R, np.float64).reshape(9))
+        tran = (C.c_double * 3)(*np.asarray(t, np.float64).reshape(3))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.call("gs_pose_reset", state_ptr, pose.data_ptr(), log_ptr, total, n_values, rot, tran, stream)
+            opts = _lib.GsPoseStepOpts(o.lr_rot, o.lr_tran, 1.0, o.betas[0], o.betas[1], o.eps, 0, n_values)
+            k = 0
+            for level, n in stages:
+                if self._levels is None:
+                    r, loss, camera, scale = self.renderer, self.loss, self.camera, 1.0 / (self.H * self.W)
+                else:
+                    r, loss, camera, scale = self._levels[level]
+                opts.track_best = int(level == stages[-1][0])
+                for _ in range(n):
+                    img, _, depth, alpha = r.forward(*self.params, camera, training=True, aux=True, pose_dev=pose)
+                    gi, gd, ga = loss(img, depth, alpha, images[level], ranges[level], scale, values=self._values)
+                    r.backward_pose(gi, self._grad_pose, 0, grad_depth=gd, grad_alpha=ga)
+                    opts.lr_scale = o.lr_final ** (k / total)
+                    _lib.call("gs_pose_step", self._grad_pose[0].data_ptr(), self._grad_pose[1].data_ptr(),
+                              self._values.data_ptr(), r.overflow_flag(), C.byref(opts), state_ptr, pose.data_ptr(), log_ptr,
+                              total, k, stream)
+                    k += 1
+
+    def _read_device_track(self, dp, total, n_values):
+        """THE read of a call: state + log into pinned memory, returned as (GsPoseState, log [total, 24 + n_values])."""
+        dp["host"].copy_(dp["dev"])  # (device -> pinned host: returns when the bytes have landed)
+        raw = dp["host"].numpy()
+        state = _lib.GsPoseState.from_buffer_copy(raw[:dp["state_bytes"]].tobytes())
+        row_len = _lib.GS_POSE_LOG_HEAD + n_values
+        log = raw[dp["state_pad"]:dp["state_pad"] + 4 * row_len * total].view(np.float32).reshape(total, row_len).copy()
+        return state, log
+
+    def _track_on_device(self, R, t, image, range_map) -> TrackResult:
+        stages, images, ranges, total = self._stage_list(image, range_map)
+        n_values = self._values.numel()
+        dp = self._device_buffers(total, n_values)
+        renderers = [self.renderer] if self._levels is None else [lv[0] for lv in self._levels.values()]
+        for attempt in range(1, self.MAX_ATTEMPTS + 1):
+            self._enqueue_device_track(R, t, stages, images, ranges, total, dp, n_values)
+            state, log = self._read_device_track(dp, total, n_values)
+            if state.skipped == 0:
+                break
+            # a frame overflowed its workspace (rendered empty, its step skipped on the device): grow by the renderer's own
+            # rule -- its counters are those of its LAST frame, which is enough to know a larger capacity -- and start over
+            if attempt == self.MAX_ATTEMPTS:
+                raise RuntimeError(f"Tracker.track(device_pose): frames still overflow their workspace after {attempt} attempts "
+                                   f"(max_pairs {[r.max_pairs for r in renderers]})")
+            k = 0
+            for level, n in stages:
+                if np.isnan(log[k:k + n, _lib.GS_POSE_LOG_HEAD]).any():  # (a skipped row's loss is NaN)
+                    r = self.renderer if self._levels is None else self._levels[level][0]
+                    st = r.stats()  # (its last frame's counters: the pairs that frame needed, if it overflowed too)
+                    r.max_pairs = max(int(st.overflow * r.headroom) + 1024, 2 * r.max_pairs)
+                k += n
+        # (an iteration whose loss or gradient was not finite took no step and competes for nothing: its row shows it)
+        levels, k = [], 0
+        for level, n in stages:
+            levels.append((level, k, n))
+            k += n
+        Rb = np.array(state.best_R, np.float64).reshape(3, 3)
+        tb = np.array(state.best_t, np.float64)
+        losses = [float(x) for x in log[:, _lib.GS_POSE_LOG_HEAD]]
+        self._history = (self._history + [(Rb, tb)])[-2:]
+        res = TrackResult(rot=Rb, tran=tb, loss=float(state.best_loss), iterations=total, losses=losses)
+        res.attempts = attempt
+        if n_values == 8 and state.best_row >= 0:  # (depth pixels, colour pixels, m_d, m_c, n_d) of the best row
+            gate = log[state.best_row, _lib.GS_POSE_LOG_HEAD + 3:_lib.GS_POSE_LOG_HEAD + 8]
+            res.inliers = (int(gate[0]), int(gate[4]), int(gate[1]))
+            res.medians = (float(gate[2]), float(gate[3]))
+        res.levels = levels if self._stages is not None else None
+        res.log = log  # [iterations, 24 + n_values]: per row the pose rendered, dL/drot, dL/dtran and the loss's values
         return res

@@ -34,7 +34,13 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_redundancy,
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_DEVICE_POSE with
+ *   gs_frame_dp -- a gs_frame_pp followed by pose_dev, 12 floats in device memory that the frame's kernels read as its pose,
+ *   read only when the flag is set; gs_frame, gs_frame_scene and gs_frame_pp are unchanged --, honoured by gs_frame_forward and
+ *   gs_frame_backward_pose; gs_pose_step, gs_pose_reset and gs_pose_log_bytes with gs_pose_state / gs_pose_step_opts /
+ *   GS_POSE_LOG_HEAD (Adam on the pose's six tangent numbers on the device, one launch per iteration: camera tracking
+ *   without a host read inside the loop).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_view_redundancy,
  *   gs_view_redundancy_pp and gs_view_redundancy_workspace_bytes with GS_REDUNDANCY_BINS (of the surface points one keyframe
  *   measured, how many are seen by 0, 1, ..., 7 or more of the OTHER keyframes: the measurement behind keyframe eviction).
  * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_icp_model_maps, gs_icp_step and
@@ -388,6 +394,26 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        that is not finite (or beyond 1e6 pixels) or a non-positive focal length.  Frames
                                        without the flag run exactly the code paths they ran before it existed. */
 
+#define GS_FRAME_DEVICE_POSE 32768    /* the frame's pose is READ FROM DEVICE MEMORY (the descriptor is a gs_frame_dp, below):
+                                       pose_dev points to 12 floats, rot[9] row-major then tran[3], 16-byte aligned, and the
+                                       frame's kernels take rot / tran from it AS IT STANDS WHEN THEY EXECUTE -- a pose that an
+                                       earlier kernel on the stream wrote (gs_pose_step) needs no host round trip.  f->rot /
+                                       f->tran are still held to the descriptor's rules, but no kernel of a flagged frame reads
+                                       them.  The same expressions run on the same numbers: a flagged frame is the by-value
+                                       frame of that pose bit for bit, forward and backward.
+                                       THE CALLER PROMISES that the 12 floats do not change between a flagged forward and its
+                                       backward (the backward would differentiate another frame than the one rendered).
+                                       Honoured by gs_frame_forward and gs_frame_backward_pose (part 0 and GS_BWD_GEOMETRY);
+                                       the counter, overflow, variant and size queries ignore the pose.  GS_E_INVALID, before
+                                       anything is enqueued, for a null or misaligned pose_dev; else GS_E_UNSUPPORTED, before
+                                       anything is enqueued, for a flagged frame that is not a training frame, has SH colours
+                                       (rays_o / lefttop / vec_dx / vec_dy are pose-derived host scalars), sort_mode 0 or 1
+                                       (as given or as the library would pick for the grid), GS_FRAME_OCCLUSION_CULL or
+                                       GS_FRAME_SCENE_PACK, and from every other entry point that launches: gs_frame_backward,
+                                       _part, _slice, _profile, the fused Adam backwards, gs_frame_forward_project / _rest /
+                                       _profile, gs_frame_contrib and the debug views.  Frames without the flag run exactly
+                                       the kernels they ran before it existed. */
+
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
  * splatter.py does (Tiles, RayInfo, frustum guard band); rot/tran are passed by value. */
 typedef struct gs_frame {
@@ -480,6 +506,14 @@ typedef struct gs_frame_pp {
     gs_frame_scene scene;     /* first member: (const gs_frame_pp *)f == f                                                  */
     double pp_dx, pp_dy;      /* cx - cx0, cy - cy0 in pixels (see the flag)                                               */
 } gs_frame_pp;
+
+/* GS_FRAME_DEVICE_POSE: the descriptor of a flagged frame continues behind gs_frame_pp with one more field, by the rule of
+ * gs_frame_scene and gs_frame_pp: read only when the flag is set; the fields in front of it are read only with their own flags
+ * and may be zero otherwise.  sizeof(gs_frame), sizeof(gs_frame_scene) and sizeof(gs_frame_pp) stay what they were. */
+typedef struct gs_frame_dp {
+    gs_frame_pp pp;           /* first member: (const gs_frame_dp *)f == f                                                  */
+    const float *pose_dev;    /* DEVICE, 16-byte aligned: rot[9] row-major, tran[3] (see the flag)                          */
+} gs_frame_dp;
 
 /* Bytes of workspace needed for N Gaussians, `max_pairs` pairs, a width x height image. */
 size_t gs_frame_workspace_bytes(int64_t N, int64_t max_pairs, int32_t width, int32_t height,
@@ -1294,6 +1328,49 @@ int gs_icp_step(const float *range, const gs_seed_camera_pp *cam,           /* t
                 const float *vertex, const float *normal, const gs_seed_camera_pp *model_cam, /* gs_icp_model_maps' */
                 const gs_icp_opts *opts, gs_icp_state *state_dev, double *log_dev, int32_t log_rows, int32_t log_row,
                 void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- the pose of a tracked frame, stepped on the device (pose_step.hip): what gs_frame_forward / gs_frame_backward_pose of a
+ * GS_FRAME_DEVICE_POSE frame read and write between them, so that a whole tracking call is enqueued without a host wait.
+ * gs_pose_step is gs_track.PoseAdam.step, so3_exp, rot_tangent_grad and the best-pose bookkeeping of Tracker.track in double:
+ * ONE launch of one wave, no atomics, every store a plain store from a vector lane, a pure function of its inputs.
+ * One step, in this order:
+ *   the log row `log_row` = (the 12 floats of pose_dev as the frame just rendered them, grad_rot[9], grad_tran[3], the
+ *     n_values floats of values_dev): GS_POSE_LOG_HEAD + n_values floats;
+ *   *skip_if_nonzero != 0 (8 bytes: gs_frame_overflow_flag's counter; NULL: never) -> skipped += 1, the row's loss
+ *     (value 0) is NaN and nothing else changes;
+ *   else any of the 12 gradients or values[0] not finite -> bad += 1 and nothing else changes;
+ *   else: track_best and values[0] < best_loss -> best_R / best_t = R / t (the pose BEFORE the step), best_loss = values[0],
+ *     best_row = log_row; then g = (dL/dw at w = 0 of exp([w]x) R from G = grad_rot: with M = G R^T, (M21 - M12, M02 - M20,
+ *     M10 - M01), grad_tran); steps += 1; m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g g; d = lr lr_scale (m / (1 - b1^steps))
+ *     / (sqrt(v / (1 - b2^steps)) + eps); R <- exp([-d_w]x) R (Rodrigues; the series I + K + K K / 2 below 1e-8 rad),
+ *     t <- t - d_t; pose_dev <- (float)(R, t), each entry rounded to fp32 once.
+ * gs_pose_reset writes the state (the pose, zero moments and counters, best = the pose with best_loss = +inf and best_row
+ * -1), pose_dev = (float)(rot, tran) and zeroes the log, all on the stream.
+ * GS_E_INVALID, before anything is enqueued: a null pointer (skip_if_nonzero alone may be NULL); a rot / tran of gs_pose_reset
+ * that is not finite; lr_rot, lr_tran, lr_scale or eps not positive and finite; a beta outside [0, 1); n_values other than 4
+ * or 8; log_rows < 1; log_row outside [0, log_rows); state_dev or skip_if_nonzero not 8-byte, pose_dev or log_dev not 16-byte,
+ * a gradient or values_dev not 4-byte aligned. */
+#define GS_POSE_LOG_HEAD 24
+typedef struct gs_pose_state { /* on the DEVICE */
+    double R[9], t[3];        /* the current pose, world -> camera; R on SO(3) by construction                */
+    double m[6], v[6];        /* Adam's moments on (w, tran)                                                  */
+    double best_R[9], best_t[3], best_loss; /* the lowest-loss pose among the rows with track_best set        */
+    int32_t steps;            /* steps taken since gs_pose_reset                                              */
+    int32_t best_row;         /* the log row of `best`; -1: none yet                                          */
+    int32_t skipped;          /* calls that found *skip_if_nonzero set (the frame overflowed its workspace)   */
+    int32_t bad;              /* calls that found a gradient or the loss not finite                           */
+} gs_pose_state;
+typedef struct gs_pose_step_opts {
+    double lr_rot, lr_tran, lr_scale, beta1, beta2, eps;
+    int32_t track_best;       /* does this call's loss compete for `best`? (the last stage of a schedule)     */
+    int32_t n_values;         /* floats of values_dev: 4 (gs_loss_track) or 8 (gs_loss_track_gated)           */
+} gs_pose_step_opts;
+size_t gs_pose_log_bytes(int32_t rows, int32_t n_values); /* 0 on bad arguments */
+int gs_pose_reset(gs_pose_state *state_dev, float *pose_dev, float *log_dev, int32_t log_rows, int32_t n_values,
+                  const double *rot /* [9] host */, const double *tran /* [3] host */, gs_stream_t stream);
+int gs_pose_step(const float *grad_rot_dev, const float *grad_tran_dev, const float *values_dev,
+                 const void *skip_if_nonzero, const gs_pose_step_opts *opts, gs_pose_state *state_dev, float *pose_dev,
+                 float *log_dev, int32_t log_rows, int32_t log_row, gs_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

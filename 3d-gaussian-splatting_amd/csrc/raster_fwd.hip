@@ -447,11 +447,23 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                         al.x = gs_squash_alpha(al.x);
                         al.y = gs_squash_alpha(al.y);
                     }
-                    // w = alpha T with v_mul_legacy_f32 (0 x anything = 0): a finished pixel (T == 0) stays
+                    // LEGACY: w = alpha T with 0 x anything = 0 (v_mul_legacy_f32's rule): a finished pixel (T == 0) stays
                     // untouched whatever alpha is -- NaN, infinite --, like the reference, which `break`s before it
-                    // evaluates the Gaussian (gaussian.cu:906); a live pixel sees the NaN, as there
+                    // evaluates the Gaussian (gaussian.cu:906); a live pixel sees the NaN, as there.
+                    // rgb frames take this variant for SOME chunks (`suspicious`, above) and the plain one for the others,
+                    // and which Gaussians share a chunk depends on the list: an occlusion-culled frame's list lacks the pairs
+                    // behind the tile's cut, so a chunk that holds a suspicious Gaussian in the full list need not hold one
+                    // in the trimmed list.  The two variants must therefore round alike on ordinary values -- the culled
+                    // frame is the unculled one bit for bit -- and the intrinsic does not: behind it T - w is a rounded
+                    // product subtracted, behind the plain product the compiler is free to contract.  So there a finished
+                    // pixel's alpha is replaced by 0 and the statements that follow are the plain variant's.
+                    // (Every other instantiation takes this variant for every chunk and keeps the intrinsic.)
                     f2 w;
-                    if constexpr (LEGACY)
+                    if constexpr (LEGACY && FRAME && CDIM == 3) {
+                        al.x = T[h].x == 0.f ? 0.f : al.x;
+                        al.y = T[h].y == 0.f ? 0.f : al.y;
+                        w = al * T[h];
+                    } else if constexpr (LEGACY)
                         w = f2{mul_legacy(al.x, T[h].x), mul_legacy(al.y, T[h].y)};
                     else
                         w = al * T[h];

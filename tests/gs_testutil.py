@@ -386,6 +386,65 @@ def general_camera(W, H, roll=35.0, pitch=-12.0, yaw=10.0, fy_ratio=0.85, tran=(
     return Camera(W, H, fx, fy, rot, np.asarray(tran, np.float32))
 
 
+def signed_raw_domain(scene, seed):
+    """The raw scales of ``scene`` (make_scene's: all > 0) over the whole domain of the abs activation |s| + 1e-4, in place:
+    every component given a random sign, 2 % of them set to exact zero (half +0.0, half -0.0 -- what the optimiser walks
+    through and seeding writes), and the raw quaternions scaled to norms from 1e-3 to 1e3 (log-uniform).  The activated scales
+    are make_scene's except at the zeros (1e-4); the normalised quaternions are its own up to rounding."""
+    n = scene.n
+    rng = np.random.default_rng(seed + 77)
+    scene.scale *= rng.choice([-1.0, 1.0], size=scene.scale.shape).astype(np.float32)
+    z = rng.choice(n * 3, size=n * 3 // 50, replace=False)
+    flat = scene.scale.reshape(-1)
+    assert np.shares_memory(flat, scene.scale)
+    flat[z[::2]] = 0.0
+    flat[z[1::2]] = -0.0
+    scene.quat *= np.exp(rng.uniform(np.log(1e-3), np.log(1e3), (n, 1))).astype(np.float32)
+    return scene
+
+
+def spread_exp_domain(scene, cam, k):
+    """``scene`` (make_scene's scales, any sign) and ``cam`` for the exp activation, in place: positions and the camera's
+    translation times k, scales log(|s| k + 1e-4) -- the same scene seen k times larger from k times further away, its raw
+    log-scales moved up by log k: with k = 8 they straddle both ends of the exp backward's clamp to [-1, 1]."""
+    k = np.float32(k)
+    scene.pos *= k
+    cam.tran = (cam.tran * k).astype(np.float32)
+    scene.scale = np.log(np.abs(scene.scale) * k + 1e-4).astype(np.float32)
+    return scene, cam
+
+
+RAW_CULL_SHAPE = (6_000, 256, 192, 41)  # n, W, H, seed
+RAW_CULL_SPREAD = 8.0
+
+
+def raw_cull_camera(domain, yaw=0.0):
+    """make_camera yawed by ``yaw`` degrees, its translation (zero) scaled with the "exp" domain's scene."""
+    from gs_scene import make_camera
+
+    cam = make_camera(RAW_CULL_SHAPE[1], RAW_CULL_SHAPE[2], yaw_deg=yaw)
+    if domain == "exp":
+        cam.tran = (cam.tran * np.float32(RAW_CULL_SPREAD)).astype(np.float32)
+    return cam
+
+
+def raw_cull_case(domain):
+    """The opaque, large-footprint scene of test_gpu_cull_exact.py::test_random_edits_with_large_footprints on the raw scale
+    domain ``domain`` ("signed": signed_raw_domain, abs activation; "exp": spread_exp_domain by RAW_CULL_SPREAD), seen from
+    raw_cull_camera.  -> (scene, camera, scale activation)"""
+    from gs_scene import make_scene
+
+    n, W, H, seed = RAW_CULL_SHAPE
+    scene = make_scene(n, W, H, seed, max_px_sigma=64)
+    scene.opa += np.float32(3.0)
+    cam = raw_cull_camera("signed")
+    if domain == "signed":
+        return signed_raw_domain(scene, seed), cam, "abs"
+    assert domain == "exp", domain
+    spread_exp_domain(scene, cam, RAW_CULL_SPREAD)
+    return scene, cam, "exp"
+
+
 def aux_general_case(n, W, H, seed=7, use_sh=False, sh_degree=2, camera=None, **kw):
     """``aux_case``'s scene seen from ``general_camera`` (``camera``: keyword arguments for it)."""
     from gs_scene import make_scene
@@ -399,10 +458,12 @@ def aux_general_case(n, W, H, seed=7, use_sh=False, sh_degree=2, camera=None, **
 # composite, multi-bucket tiles where the GPU test relies on them, few pixels masked for a non-robust stop decision).
 #   n, W, H, seed; sh: 0 = rgb logits, 2 / 3 = SH degree; opa: shift of the opacity logits; exp: log scales for the exp
 #   activation; sigma: make_scene's max_px_sigma; method / dist: tile culling method and its threshold;
-#   deep: the comparison relies on a list beyond one 64-Gaussian bucket; grads: it runs a backward on robust_aux_grads
-def _gc(n, W, H, seed=7, sh=0, opa=0.0, exp=False, sigma=16.0, method="prob2", dist=0.5, deep=False, grads=False):
+#   deep: the comparison relies on a list beyond one 64-Gaussian bucket; grads: it runs a backward on robust_aux_grads;
+#   signed: signed_raw_domain on the scene (abs activation); spread: spread_exp_domain's factor (with exp)
+def _gc(n, W, H, seed=7, sh=0, opa=0.0, exp=False, sigma=16.0, method="prob2", dist=0.5, deep=False, grads=False,
+        signed=False, spread=1.0):
     return dict(n=n, W=W, H=H, seed=seed, sh=sh, opa=opa, exp=exp, sigma=sigma, method=method, dist=dist, deep=deep,
-                grads=grads)
+                grads=grads, signed=signed, spread=spread)
 
 
 GENERAL_CASES = {
@@ -432,6 +493,12 @@ GENERAL_CASES = {
     "adam": _gc(6_000, 160, 112, seed=11),
     "pose": _gc(5_000, 128, 96, deep=True, grads=True),
     "pose_identity": _gc(5_000, 128, 96, seed=41),
+    # the raw scale domain beyond make_scene's positive slice (tests/test_raw_domain_host.py, tests/test_gpu_raw_domain.py)
+    "raw_signed_rgb": _gc(5_000, 128, 96, seed=13, signed=True, deep=True, grads=True),
+    "raw_signed_sh2": _gc(5_000, 128, 96, seed=13, sh=2, signed=True, deep=True, grads=True),
+    "raw_exp_spread": _gc(5_000, 96, 80, seed=13, exp=True, spread=8.0, deep=True, grads=True),
+    "raw_signed_adam": _gc(6_000, 160, 112, seed=11, signed=True),
+    "raw_signed_pose": _gc(5_000, 128, 96, signed=True, deep=True, grads=True),
 }
 _GENERAL_FRAMES = {}
 
@@ -444,7 +511,12 @@ def general_case(key):
     if c["opa"]:
         scene.opa += np.float32(c["opa"])
     of_kw = {}
-    if c["exp"]:
+    if c["signed"]:
+        signed_raw_domain(scene, c["seed"])
+    if c["exp"] and c["spread"] != 1.0:
+        spread_exp_domain(scene, cam, c["spread"])
+        of_kw["scale_activation"] = "exp"
+    elif c["exp"]:
         scene.scale = np.log(np.abs(scene.scale) + 1e-4).astype(np.float32)
         of_kw["scale_activation"] = "exp"
     if c["method"] != "prob2":

@@ -43,12 +43,13 @@ def mode_kwargs(sort_mode):
 
 
 def check_forward(gpu, scene, cam, training=False, sort_mode=2, emit_sorted_keys=False, img_atol=IMG_ATOL,
-                  long_lists=None, of=None):
-    of = OracleFrame(scene, cam) if of is None else of  # (``of``: the caller's frame of this scene and camera, shared)
+                  long_lists=None, of=None, r_kw=None):
+    # (``of``: the caller's frame of this scene and camera, shared; ``r_kw``: further FrameRenderer options, passed through)
+    of = OracleFrame(scene, cam) if of is None else of
     if long_lists is None:  # scenes with lists beyond the LDS window exercise the long-list kernels
         long_lists = bool(np.diff(of.accum).max() > 2048)
     r = FrameRenderer(gpu, max_pairs=max(len(of.ids) + 17, 64), training=training, auto_grow=False,
-                      emit_sorted_keys=emit_sorted_keys, long_lists=long_lists, **mode_kwargs(sort_mode))
+                      emit_sorted_keys=emit_sorted_keys, long_lists=long_lists, **mode_kwargs(sort_mode), **(r_kw or {}))
     params = to_torch(scene, gpu)
     image, padded = r.forward(*params, cam)
     st = r.stats()

@@ -10,7 +10,9 @@
 //   D2 densify_scan_kernel     : exclusive scan of the counts, totals -> device counters;
 //   D3 densify_apply_kernel    : every Gaussian writes itself to its kept rank (split ones with the new
 //                                scale and the first sample), its clone to K + clone rank, its second
-//                                sample to K + C + split rank -- the reference's output order.
+//                                sample to K + C + split rank -- the reference's output order;
+//   D4 densify_apply_state_kernel : (optional, gs_densify_apply_state) the arrays that share the row index -- Adam's
+//                                moments -- follow the same edit: kept and cloned rows to their kept rank, zeros elsewhere.
 // The two standard-normal blocks of the split samples are inputs (the caller draws them once the
 // counts are known, exactly when the reference's MultivariateNormal.sample() would); a sample is
 // pos + chol(R S^2 R^T) eps, which is what torch's MultivariateNormal computes (utils.py:391-402).
@@ -221,6 +223,97 @@ __global__ void __launch_bounds__(256) densify_apply_kernel(DensifyIO IO, int64_
     }
 }
 
+// D4 densify_apply_state_kernel (gs_densify_apply_state): whatever shares the row index with the Gaussians -- the optimizer's
+// moment arrays -- follows the edit of D3.  A kept or cloned row is unchanged by D3, so its state goes to its kept rank; a
+// split row's kept slot holds a new sample at a new scale, and the clones and second samples are new rows: their state is
+// zero.  Pure data movement, written the way map_edit.hip's prune_apply_kernel is: a workgroup's 256 source rows own three
+// contiguous destination spans (kept, clone, second sample) of EVERY array; the ranks come from block_scan3 and the scanned
+// block counts, an LDS table names each kept slot's source row (or STATE_ZERO), and consecutive lanes walk consecutive floats
+// of each span whatever the row width.  No atomics; every row of [0, K + C + S) is written once, by one workgroup.
+struct StateTable {  // the arrays of one call, by value; `magic` = floor(2^32 / width) + 1: e / width for e * width < 2^32
+    int32_t n;
+    uint32_t width[GS_PRUNE_MAX_ARRAYS], magic[GS_PRUNE_MAX_ARRAYS];
+    const float *src[GS_PRUNE_MAX_ARRAYS];
+    float *dst[GS_PRUNE_MAX_ARRAYS];
+};
+constexpr uint32_t STATE_MAGIC_WIDTHS = 4096;  // 256 rows x width^2 < 2^32 below this: the multiply-high quotient is exact
+constexpr uint32_t STATE_ZERO = 0xFFFFFFFFu;   // the table entry of a split row's kept slot
+
+// `cnt` rows of `w` zeros at dst, consecutive lanes on consecutive floats
+__device__ __forceinline__ void state_zero_span(float *__restrict__ dst, uint32_t cnt, uint32_t w) {
+    const uint64_t span = (uint64_t)cnt * w;
+    for (uint64_t e = threadIdx.x; e < span; e += 256) dst[e] = 0.f;
+}
+
+__global__ void __launch_bounds__(256) densify_apply_state_kernel(StateTable T, int64_t n, int64_t capacity,
+                                                                  const uint32_t *__restrict__ cls,
+                                                                  const uint32_t *__restrict__ block_offsets,
+                                                                  const long long *__restrict__ counts) {
+    __shared__ uint32_t s_w[3][4];
+    __shared__ uint32_t s_src[256];  // kept rank within the workgroup -> row within the workgroup, or STATE_ZERO
+    const int64_t row0 = (int64_t)blockIdx.x * 256;
+    const int64_t i = row0 + threadIdx.x;
+    const int c = i < n ? (int)cls[i] : CLS_DELETE;
+    uint32_t r[3], tot[3];
+    block_scan3(c != CLS_DELETE, c == CLS_CLONE, c == CLS_SPLIT, r, tot, s_w);
+    const int64_t K = counts[0], Cn = counts[1], S = counts[2];
+    // (the whole grid alike; the host reads the same counts.  counts[3] is densify_apply_kernel's test, the sum keeps a
+    // mismatched pair of counts and workspace in bounds)
+    if (K < 0 || Cn < 0 || S < 0 || counts[3] > capacity || K + Cn + S > capacity) return;
+    if (c != CLS_DELETE) s_src[r[0]] = c == CLS_SPLIT ? STATE_ZERO : threadIdx.x;
+    __syncthreads();
+    // (base + cnt <= the class's total always holds for the workspace and counts of ONE classify call)
+    const int64_t base[3] = {block_offsets[(size_t)blockIdx.x * 3 + 0], block_offsets[(size_t)blockIdx.x * 3 + 1],
+                             block_offsets[(size_t)blockIdx.x * 3 + 2]};
+    const int64_t have[3] = {K, Cn, S};
+    uint32_t cnt[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int64_t room = have[k] - base[k];
+        cnt[k] = room <= 0 ? 0u : (uint32_t)(room < (int64_t)tot[k] ? room : (int64_t)tot[k]);
+    }
+    for (int k = 0; k < T.n; ++k) {
+        const uint32_t w = T.width[k], magic = T.magic[k];
+        const float *__restrict__ src = T.src[k] + row0 * w;
+        float *__restrict__ dst = T.dst[k] + base[0] * w;
+        if (w < STATE_MAGIC_WIDTHS) {
+            // ONE walk over the floats of the three spans laid end to end (at most 3 x 256 rows: below 2^32 floats): three
+            // walks would spend, for the narrow arrays, three part-filled store instructions where this spends one or two.
+            // Four loads in flight per lane before the first store, as in prune_apply_kernel.
+            const uint32_t n0 = cnt[0] * w, n01 = n0 + cnt[1] * w, span = n01 + cnt[2] * w;
+            float *__restrict__ dst1 = T.dst[k] + (K + base[1]) * w;        // e in [n0, n01): the clones' rows
+            float *__restrict__ dst2 = T.dst[k] + (K + Cn + base[2]) * w;   // e in [n01, span): the second samples' rows
+            for (uint32_t e0 = threadIdx.x; e0 < span; e0 += 4 * 256) {
+                float v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t e = e0 + j * 256;
+                    v[j] = 0.f;
+                    if (e < n0) {
+                        const uint32_t q = w == 1 ? e : __umulhi(e, magic);
+                        const uint32_t sr = s_src[q];
+                        if (sr != STATE_ZERO) v[j] = src[(size_t)sr * w + (e - q * w)];
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t e = e0 + j * 256;
+                    if (e < span) *(e < n0 ? dst + e : e < n01 ? dst1 + (e - n0) : dst2 + (e - n01)) = v[j];
+                }
+            }
+        } else {  // rows of 16 KiB and more: span by span, with 64-bit indices and a division
+            const uint64_t span = (uint64_t)cnt[0] * w;
+            for (uint64_t e = threadIdx.x; e < span; e += 256) {
+                const uint64_t q = e / w;
+                const uint32_t sr = s_src[q];
+                dst[e] = sr == STATE_ZERO ? 0.f : src[(size_t)sr * w + (e - q * w)];
+            }
+            state_zero_span(T.dst[k] + (K + base[1]) * w, cnt[1], w);
+            state_zero_span(T.dst[k] + (K + Cn + base[2]) * w, cnt[2], w);
+        }
+    }
+}
+
 int fill_params(const gs_densify_opts *o, DensifyParams &P) {
     GS_CHECK_ARG(o != nullptr, "opts is null");
     GS_CHECK_ARG(o->scale_activation == 0 || o->scale_activation == 1, "scale_activation must be 0 (abs) or 1 (exp)");
@@ -301,6 +394,45 @@ extern "C" int gs_densify_apply(const float *pos, const float *quat, const float
     DensifyIO IO = {pos, quat, scale, opa, rgb, grad, eps1, eps2, out_pos, out_quat, out_scale, out_opa, out_rgb};
     hipLaunchKernelGGL(densify_apply_kernel, dim3((unsigned)gs_div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, IO, N,
                        P, w.cls, w.block_counts, (const long long *)counts_dev, capacity, n_eps);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gs_densify_apply_state(const gs_prune_arrays *arrays, int64_t N, int64_t capacity,
+                                      const int64_t *counts_dev, const void *workspace, size_t workspace_bytes,
+                                      gs_stream_t stream) {
+    GS_CHECK_ARG(arrays != nullptr, "arrays is null");
+    GS_CHECK_ARG(arrays->n >= 1 && arrays->n <= GS_PRUNE_MAX_ARRAYS, "the number of arrays must lie in 1 .. 16");
+    GS_CHECK_ARG(N >= 0 && N < (1ll << 31), "N out of range");
+    GS_CHECK_ARG(capacity >= 0, "capacity must not be negative");
+    StateTable T;
+    T.n = arrays->n;
+    for (int k = 0; k < GS_PRUNE_MAX_ARRAYS; ++k) {
+        T.width[k] = T.magic[k] = 0;
+        T.src[k] = nullptr;
+        T.dst[k] = nullptr;
+    }
+    for (int k = 0; k < arrays->n; ++k) {
+        GS_CHECK_ARG(arrays->width[k] >= 1, "a row width must be >= 1");
+        // (an array of no rows has no address: src may be null with N = 0, dst with capacity = 0)
+        GS_CHECK_ARG((N == 0 || arrays->src[k] != nullptr) && (capacity == 0 || arrays->dst[k] != nullptr),
+                     "a src or dst pointer is null");
+        T.width[k] = (uint32_t)arrays->width[k];
+        T.magic[k] = T.width[k] > 1 ? (uint32_t)((1ull << 32) / T.width[k] + 1ull) : 0u;
+        T.src[k] = arrays->src[k];
+        T.dst[k] = arrays->dst[k];
+    }
+    for (int k = 0; k < arrays->n; ++k)
+        for (int j = 0; j < arrays->n; ++j)
+            GS_CHECK_ARG(arrays->dst[k] == nullptr || (const float *)arrays->dst[k] != arrays->src[j],
+                         "a dst array is a src array (the move is not in place)");
+    GS_CHECK_ARG(counts_dev != nullptr, "counts_dev is null");
+    GS_CHECK_ARG(workspace && ((uintptr_t)workspace & 3) == 0 && workspace_bytes >= gs_densify_workspace_bytes(N),
+                 "workspace null, misaligned or too small");
+    if (N == 0 || capacity == 0) return 0;  // no row can be written
+    DensifyWs w = carve(const_cast<void *>(workspace), N);
+    hipLaunchKernelGGL(densify_apply_state_kernel, dim3((unsigned)gs_div_up(N, 256)), dim3(256), 0, (hipStream_t)stream, T,
+                       N, capacity, w.cls, w.block_counts, (const long long *)counts_dev);
     GS_CHECK_LAUNCH();
     return 0;
 }

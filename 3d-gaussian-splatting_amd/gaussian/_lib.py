@@ -270,6 +270,8 @@ class GsPruneArrays(C.Structure):
 gs_prune_workspace_bytes = _sig("gs_prune_workspace_bytes", sz, i64)
 gs_prune_classify = _sig("gs_prune_classify", ci, vp, vp, i64, C.POINTER(GsPruneOpts), vp, vp, sz, vp)
 gs_prune_apply = _sig("gs_prune_apply", ci, C.POINTER(GsPruneArrays), i64, i64, i64, vp, vp, sz, vp)
+# (beside gs_prune_apply, as in the header: it takes gs_prune_arrays)
+gs_densify_apply_state = _sig("gs_densify_apply_state", ci, C.POINTER(GsPruneArrays), i64, i64, vp, vp, sz, vp)
 
 
 class GsContribOpts(C.Structure):
@@ -366,7 +368,7 @@ EXPORTS = [
     "gs_frame_backward_profile", "gs_adam_step", "gs_adam_step_range", "gs_adam_step_sharded", "gs_frame_overflow_flag", "gs_grad_stat_update", "gs_loss_workspace_bytes", "gs_loss_l1_ssim",
     "gs_loss_depth_workspace_bytes", "gs_loss_depth", "gs_frame_backward_adam_aux", "gs_frame_backward_adam_pose",
     "gs_frame_backward_pose",
-    "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply",
+    "gs_densify_workspace_bytes", "gs_densify_classify", "gs_densify_apply", "gs_densify_apply_state",
     "gs_seed_workspace_bytes", "gs_seed_classify", "gs_seed_apply",
     "gs_loss_track_workspace_bytes", "gs_loss_track",
     "gs_loss_track_gated_workspace_bytes", "gs_loss_track_gated",

@@ -493,7 +493,7 @@ class Trainer:
                  per_view_stat: Optional[bool] = None, exchange: str = "all_reduce", n_slices: Optional[int] = None,
                  bwd_rows: Optional[bool] = None, fuse_adam: Optional[bool] = None,
                  depths: Optional[Sequence[Optional[torch.Tensor]]] = None, depth_kind: str = "range",
-                 weights: Optional[Sequence[Optional[torch.Tensor]]] = None):
+                 weights: Optional[Sequence[Optional[torch.Tensor]]] = None, densify_carry: bool = False):
         self.opt = opt or TrainOptions()
         # `weights`: a list parallel to `targets`, each entry a per-pixel weight map [H,W] float32 (finite, >= 0) for the
         # view's colour loss or None.  A view with a map takes the weighted loss (WeightedImageLoss) where the step calls its
@@ -550,6 +550,13 @@ class Trainer:
         # gradient exchange under view parallelism (gs_dp.py): "all_reduce" + replicated Adam, or "reduce_scatter" +
         # sharded Adam + all-gather of the parameters
         self.exchange = exchange
+        # `densify_carry`: every adaptive_control of the schedule EDITS the running fit instead of restarting it -- the rows that
+        # survive keep their Adam moments, new rows (and split ones) start from zero, the step count goes on -- and an opacity
+        # reset zeroes the opacity moments (what the original 3DGS optimizer does; the reference restarts Adam, and so does the
+        # default).  One rank with a replicated optimizer only: refused here, not at the first control iteration.
+        self.densify_carry = bool(densify_carry)
+        if self.densify_carry:
+            self._refuse_carry("Trainer(densify_carry=True)", stat=False)
         # densification statistic: fused into the Adam launch on one GPU; with several ranks it must be taken from
         # each rank's own gradient before the all-reduce (gs_dp.ViewParallelGradStat).  `per_view_stat=True` forces
         # that path on a single rank too (it then gives bit-identical results; used by the tests).
@@ -927,6 +934,9 @@ class Trainer:
             self.flat.finish_gather()
             self.renderer.forward_abandon()
             reset_opa(self.flat.params[3])
+            if self.densify_carry:  # the moments belong to the opacities that were: the original 3DGS optimizer zeroes them too
+                for m in self.optimizer.moment_rows("opa"):
+                    m.zero_()
         return loss.values
 
     def tune_slices(self, i_iter: int, camera_id: int, candidates: Sequence[int] = (1, 2, 4), iters: int = 6,
@@ -1008,10 +1018,19 @@ class Trainer:
                                          expect_per_slice=per)
         return ok
 
-    def adaptive_control(self, i_iter: int, densify: bool = True):
-        """train.py:156-180: prune (+ clone / split when ``densify``), then a fresh optimizer."""
+    def adaptive_control(self, i_iter: int, densify: bool = True, carry_state: Optional[bool] = None):
+        """train.py:156-180: prune (+ clone / split when ``densify``), then a fresh optimizer.
+        ``carry_state`` (None: the constructor's ``densify_carry``): the set is edited the way ``prune`` edits it.  Classify,
+        the one host read, the draws, then ``gs_densify_apply`` writes the new set straight into the new flat buffer and ONE
+        ``gs_densify_apply_state`` moves the ten moment arrays into the new optimizer: a kept or cloned row keeps its moments,
+        a split row, the clones and the second samples start from zero, the step count stays.  The statistic is not carried
+        (it has just been consumed and restarts at zero, as without carrying); the parameters are the ones the call
+        without carrying produces, bit for bit (the draws are taken at the same point, in the same order)."""
         from gs_densify import adaptive_control
 
+        carry = self.densify_carry if carry_state is None else bool(carry_state)
+        if carry:
+            self._refuse_carry("adaptive_control(carry_state=True)", stat=False)
         o = self.opt
         self.flat.finish_gather()
         if self.view_stat is not None:  # combine the ranks' per-view statistics: one collective per boundary
@@ -1021,6 +1040,9 @@ class Trainer:
             accum = self.optimizer.accum_grad
             counter = 1.0 if o.grad_accum_method == "max" or self.grad_counter is None else self.grad_counter
         stat = accum / (counter + 1e-3 if isinstance(counter, float) else (counter + 1e-3).unsqueeze(-1))  # train.py:160
+        if carry:
+            with torch.no_grad():
+                return self._adaptive_control_carry(i_iter, stat.contiguous(), densify)
         new, counts = adaptive_control(self.flat.params, stat.contiguous(), taus=o.split_thresh,
                                        delete_thresh=o.delete_thresh, scale_activation=self.scale_activation,
                                        grad_thresh=o.grad_thresh, grad_aggregation=o.grad_aggregation,
@@ -1031,6 +1053,35 @@ class Trainer:
         # split are not unless every rank seeds `generator` alike: rank 0's new set is the one that counts
         self.flat.broadcast_params(0)
         return counts
+
+    def _adaptive_control_carry(self, i_iter: int, stat: torch.Tensor, densify: bool):
+        """``adaptive_control`` as an edit of the running fit (``carry_state``): no temporary set, the moments travel."""
+        from gs_densify import densify_apply, densify_apply_state, densify_classify, densify_draws
+
+        o = self.opt
+        old_flat, old_opt = self.flat, self.optimizer
+        params, n = [t.detach() for t in old_flat.params], old_flat.n
+        counts, ws, opts = densify_classify(params, stat, taus=o.split_thresh, delete_thresh=o.delete_thresh,
+                                            scale_activation=self.scale_activation, grad_thresh=o.grad_thresh,
+                                            grad_aggregation=o.grad_aggregation, use_clone=bool(o.use_clone) and densify,
+                                            use_split=bool(o.use_split) and densify, clone_dt=o.clone_dt)
+        kept, cloned, split, total = (int(v) for v in counts.cpu())  # the one host synchronisation
+        draws = densify_draws(split, stat.device, self.generator)  # (where gs_densify.adaptive_control draws them)
+
+        def fill(flat, optimizer):
+            densify_apply(params, stat, flat.params, counts, ws, opts, draws, split, total)
+            torch.autograd.graph.increment_version(flat.flat_param)  # (written through raw pointers, as FusedAdam.step)
+            src, dst = [], []
+            for name in ("pos", "quat", "scale", "opa", "rgb"):
+                src += old_opt.moment_rows(name)
+                dst += optimizer.moment_rows(name)
+            densify_apply_state(src, dst, n, counts, ws, capacity=total)
+
+        # placeholders give the new flat buffer its shapes; the rows arrive with `fill`, not through a temporary set
+        shapes = [torch.empty((total,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device) for t in params]
+        self._bind(shapes, i_iter, carry=_Carry(old_opt.step_count, fill))
+        self.flat.broadcast_params(0)
+        return kept, cloned, split
 
     def _eval_renderer_for_set(self) -> FrameRenderer:
         """The inference renderer ``test`` and ``seed_from_view`` share (created on first use)."""
@@ -1073,9 +1124,12 @@ class Trainer:
         return out
 
     @torch.no_grad()
-    def _refuse_carry(self, what: str):
-        """The optimizer state can travel with the rows only where one rank holds all of it, addressed by row."""
-        if self.optimizer.sharded or self.world_size > 1 or self.view_stat is not None or self.grad_counter is not None:
+    def _refuse_carry(self, what: str, stat: bool = True):
+        """The optimizer state can travel with the rows only where one rank holds all of it, addressed by row.  ``stat=False``
+        (``adaptive_control``, which has just consumed the statistic and carries none): the moments alone decide."""
+        optimizer = getattr(self, "optimizer", None)  # (the constructor asks before there is one: FusedAdam.sharded's rule)
+        sharded = optimizer.sharded if optimizer is not None else self.exchange == "reduce_scatter"
+        if sharded or self.world_size > 1 or (stat and (self.view_stat is not None or self.grad_counter is not None)):
             raise RuntimeError(f"{what} cannot carry the optimizer state of a sharded optimizer (exchange='reduce_scatter'), "
                                "of several ranks (world_size > 1) or of a per-view statistic (per_view_stat, a 'mean' view "
                                "counter): their moments are not row-addressable from one rank; pass carry_state=False")

@@ -34,7 +34,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_DEVICE_POSE with
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_densify_apply_state (the arrays
+ *   that share the row index with the Gaussians -- the optimizer's moments -- follow a densification: kept and cloned rows keep
+ *   theirs, split rows, clones and second samples start from zero; gs_prune_arrays is reused, gs_densify_classify and
+ *   gs_densify_apply are unchanged).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_DEVICE_POSE with
  *   gs_frame_dp -- a gs_frame_pp followed by pose_dev, 12 floats in device memory that the frame's kernels read as its pose,
  *   read only when the flag is set; gs_frame, gs_frame_scene and gs_frame_pp are unchanged --, honoured by gs_frame_forward and
  *   gs_frame_backward_pose; gs_pose_step, gs_pose_reset and gs_pose_log_bytes with gs_pose_state / gs_pose_step_opts /
@@ -1209,6 +1213,28 @@ int gs_prune_classify(const float *scale, const float *opa, int64_t N, const gs_
                       void *workspace, size_t workspace_bytes, gs_stream_t stream);
 int gs_prune_apply(const gs_prune_arrays *arrays, int64_t N, int64_t dst_offset, int64_t capacity,
                    const int64_t *counts_dev, const void *workspace, size_t workspace_bytes, gs_stream_t stream);
+
+/* ---- densification, continued: whatever shares the row index follows the edit of gs_densify_apply ----
+ * (declared here because it takes gs_prune_arrays as it stands: n arrays of fp32 rows that share the row index.)
+ * Takes the workspace and counts_dev that gs_densify_classify wrote for these N rows and follows that call as
+ * gs_densify_apply does; neither disturbs the other and the order between the two is free.  With (K, C, S) = counts_dev[0..2]
+ * and kept_rank(i) the number of non-deleted rows before row i, for every array k:
+ *   row i kept, or kept and cloned (gs_densify_apply leaves the row itself unchanged): dst[k][kept_rank(i)] = src[k][i]
+ *   row i split (its kept slot holds a new sample at a new scale)                    : dst[k][kept_rank(i)] = 0
+ *   row i deleted                                                                    : nothing
+ *   destination rows [K, K + C + S) (the clones, the second split samples)           : 0
+ * Every row of [0, K + C + S) of every dst[k] is written exactly once; rows at and beyond K + C + S are not touched; nothing
+ * at all is written when the total exceeds `capacity` (gs_densify_apply's rule).  The result is a pure function of the
+ * inputs, whatever dst held: one launch for all arrays, no atomics, bitwise repeatable.  A workgroup's 256 source rows own
+ * three contiguous destination spans (kept, clone, second sample) and consecutive lanes walk consecutive floats of each,
+ * whatever the width (1, 3, 4, 27 and 48 occur) -- gs_prune_apply's way.  Meant for Adam's moment arrays: a zero-moment row
+ * takes a first step of a fresh Adam's magnitude.
+ * Refused before anything is enqueued (GS_E_INVALID, gs_last_error), as gs_prune_apply: a null pointer (a src may be null only
+ * with N = 0, a dst only with capacity = 0), N < 0 or >= 2^31, n outside 1 .. GS_PRUNE_MAX_ARRAYS, a width < 1, a dst[k] equal
+ * to a src[j], a missing, misaligned (4 bytes) or too-small workspace (gs_densify_workspace_bytes(N)), a negative capacity.
+ * N = 0 is valid and moves nothing. */
+int gs_densify_apply_state(const gs_prune_arrays *arrays, int64_t N, int64_t capacity, const int64_t *counts_dev,
+                           const void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 /* ---- per-Gaussian contributions: each Gaussian's share of a rendered frame ----
  * For a TRAINING frame that gs_frame_forward has rendered (any colour model, with or without GS_FRAME_AUX,

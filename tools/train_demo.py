@@ -11,10 +11,15 @@ import time
 
 import numpy as np
 
-# python tools/train_demo.py [n_iters] [--seed S] [--tree PATH]
+# python tools/train_demo.py [n_iters] [--seed S] [--tree PATH] [--densify] [--densify-carry]
 #   --seed S    : seed of the start perturbation AND of the random view order (default: 11 / 2023, the historical run)
 #   --tree PATH : run another checkout of this repository (its own libgs_amd.so), e.g. build/r03 = round 3's final tree
+#   --densify   : Trainer(densify=True): the reference's densification schedule (adaptive_control every 100 iterations from 700
+#                 on, a fresh Adam behind each), its split draws from a generator seeded like the start perturbation
+#   --densify-carry : the same with Trainer(densify_carry=True): the surviving rows keep their Adam moments (tools/densify_carry_fit.py)
 _args = sys.argv[1:]
+_carry = "--densify-carry" in _args
+_densify = _carry or "--densify" in _args
 _seed = int(_args[_args.index("--seed") + 1]) if "--seed" in _args else None
 _tree = os.path.abspath(_args[_args.index("--tree") + 1]) if "--tree" in _args else \
     os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,7 +46,11 @@ start[4] += 0.5 * torch.randn(start[4].shape, device=dev, generator=g)    # colo
 start[3] += 0.3 * torch.randn(start[3].shape, device=dev, generator=g)    # opacity logits
 start[0] += 0.002 * torch.randn(start[0].shape, device=dev, generator=g)  # positions
 start[2] *= 1.0 + 0.1 * torch.randn(start[2].shape, device=dev, generator=g)
-tr = Trainer(start, cams, targets, TrainOptions(n_iters=n_iters), max_pairs=1 << 21)
+if _densify:
+    tr = Trainer(start, cams, targets, TrainOptions(n_iters=n_iters), max_pairs=1 << 21, densify=True,
+                 generator=torch.Generator(device=dev).manual_seed(11 if _seed is None else _seed), densify_carry=_carry)
+else:
+    tr = Trainer(start, cams, targets, TrainOptions(n_iters=n_iters), max_pairs=1 << 21)
 test_split = np.arange(0, len(cams), 8)                                    # train.py:68-69
 train_split = np.array(sorted(set(range(len(cams))) - set(test_split)))
 
@@ -63,7 +72,10 @@ dt = time.perf_counter() - t0
 psnr1, ssim1, fps = evaluate()
 print(json.dumps({"tree": os.path.relpath(_tree, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) or ".",
                   "seed": _seed, "workload": f"cfg3 scene ({n} Gaussians), 1080p, {len(train_split)} training + {len(test_split)} "
-                              f"held-out synthetic views, {n_iters} iterations of train.py's step (no densification)",
+                              f"held-out synthetic views, {n_iters} iterations of train.py's step " +
+                              ("(densification, Adam carried)" if _carry else "(densification)" if _densify else
+                               "(no densification)"),
+                  "densify": _densify, "densify_carry": _carry, "n_gaussians_start": n, "n_gaussians_end": tr.n_gaussians,
                   "iters_per_s": round(n_iters / dt, 1), "wall_s": round(dt, 2),
                   "test_psnr_before_dB": round(psnr0, 2), "test_psnr_after_dB": round(psnr1, 2),
                   "test_ssim_before": round(ssim0, 4), "test_ssim_after": round(ssim1, 4),

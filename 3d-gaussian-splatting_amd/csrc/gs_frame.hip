@@ -42,6 +42,18 @@ static int tile_bits(int n_tiles) {
     return b < 1 ? 1 : b;
 }
 
+// GS_FRAME_CULL_REPEAT promises a frame that repeats the previous one; GS_FRAME_CULL_DILATE says the camera moved since the
+// cut table was recorded.  A descriptor that carries both contradicts itself: refused by every entry point (validate) and by
+// the launch-free query, before anything is enqueued.
+static int refuse_cull_repeat(const gs_frame *f) {
+    if ((f->flags & GS_FRAME_CULL_REPEAT) && (f->flags & GS_FRAME_CULL_DILATE)) {
+        gs_set_error("gs_frame: GS_FRAME_CULL_REPEAT with GS_FRAME_CULL_DILATE: dilated cuts belong to a camera that moved, a "
+                     "repeated frame has the pose the cut table was recorded under");
+        return GS_E_INVALID;
+    }
+    return 0;
+}
+
 static int validate(const gs_frame *f) {
     GS_CHECK_ARG(f != nullptr, "frame is null");
     GS_CHECK_ARG(f->N >= 0 && f->N < (1ll << 31), "N out of range");
@@ -67,8 +79,9 @@ static int validate(const gs_frame *f) {
                                GS_FRAME_SERIAL_LONG_LISTS | GS_FRAME_LONG_LISTS | GS_FRAME_STRIP_BIN |
                                GS_FRAME_BWD_ROWS | GS_FRAME_LONG_SORT | GS_FRAME_OCCLUSION_CULL | GS_FRAME_CULL_DILATE | GS_FRAME_CULL_DILATE_NEAR |
                                GS_FRAME_AUX | GS_FRAME_POSE_GRAD | GS_FRAME_SCENE_PACK | GS_FRAME_PRINCIPAL_POINT |
-                               GS_FRAME_DEVICE_POSE)) == 0,
+                               GS_FRAME_DEVICE_POSE | GS_FRAME_CULL_REPEAT)) == 0,
                  "unknown flag bits");
+    if (int rc = refuse_cull_repeat(f)) return rc;
     GS_CHECK_ARG(f->sort_mode >= 0 && f->sort_mode <= 2,
                  "sort_mode must be 0 (full LSD radix), 1 (tile-bit radix + per-tile LDS sort) or 2 (LDS counting sort "
                  "by tile + per-tile LDS sort)");
@@ -322,6 +335,12 @@ static int refuse_device_pose(const gs_frame *f, const char *entry) {
     return GS_E_UNSUPPORTED;
 }
 
+// Does a forward of this descriptor enqueue the gated second pass of an occlusion-culled frame?  (GS_FRAME_CULL_REPEAT is
+// ignored wherever GS_FRAME_OCCLUSION_CULL is: no second pass exists there.)
+static bool cull_second_pass(const gs_frame *f) {
+    return effective_sort_mode(f) == 2 && gs_frame_occlusion_cull(f) && !(f->flags & GS_FRAME_CULL_REPEAT);
+}
+
 // The forward in two phases: PROJECT (cull + project + activations + level-1 count; in the strip variant it may be
 // issued as several ranges of slices of the Gaussian array, in any order, slice 0's range first) and REST
 // (binning, per-tile sort, compositing).  gs_frame_forward = both; gs_frame_forward_project / _rest expose them to the
@@ -398,12 +417,13 @@ static int frame_forward_impl(const gs_frame *f, hipStream_t s, float *stage_ms,
     tm.mark();  // stage "ranges" = tile ranges (+ the per-tile depth sort in mode 1)
     if ((rc = gs_stage_raster_forward(f, ws, sids, s))) return rc;
     tm.mark();
-    if (mode == 2 && gs_frame_occlusion_cull(f)) {
+    if (cull_second_pass(f)) {
         // The lists of this frame were trimmed by the occlusion cuts of the previous one (gs_frame_layout.h).  If a tile ran
         // past its cut, counters[GS_CNT_RANPAST] is set and the launches below render the frame again from the full
         // lists; otherwise each of them returns at its first instruction (five gated launches: project + count -- the
         // first pass did not project the Gaussians behind every cut they could reach --, column scan, scatter, per-tile
-        // sort, compositing).
+        // sort, compositing).  A GS_FRAME_CULL_REPEAT frame is one the caller knows cannot run past (include/gs_abi.h):
+        // the five launches are not enqueued, the counter is raised and reported as in any culled frame.
         if ((rc = gs_stage_project(f, ws, s, 0, -1, true))) return rc;
         if ((rc = gs_stage_strip_bin(f, ws, s, true))) return rc;
         uint64_t *keys_out = nullptr;  // (frames that export their sorted keys are never culled)
@@ -790,6 +810,13 @@ extern "C" int gs_frame_is_occlusion_culled(const gs_frame *f, int32_t *culled) 
     return 0;
 }
 
+extern "C" int gs_frame_cull_second_pass(const gs_frame *f, int32_t *enqueued) {
+    GS_CHECK_ARG(f && enqueued, "null argument");
+    if (int rc = refuse_cull_repeat(f)) return rc;
+    *enqueued = cull_second_pass(f) ? 1 : 0;
+    return 0;
+}
+
 extern "C" int gs_frame_reads_scene_pack(const gs_frame *f) {
     if (!f || f->training || f->N <= 0 || effective_sort_mode(f) != 2) return 0;
     return gs_frame_uses_strips(f) ? 1 : 0;
@@ -850,6 +877,17 @@ extern "C" int gs_frame_debug_cull_stage(const gs_frame *f, const uint64_t **ent
     *slice_entries = ws.slice_entries;
     *slices = (int32_t)plan.slices;
     *cap = gs_cull_stage_cap(f->max_pairs, plan.slices);
+    return 0;
+}
+
+extern "C" int gs_frame_debug_cut_table(const gs_frame *f, const uint32_t **cut, int32_t *n_tiles) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG(cut && n_tiles, "null pointer");
+    GS_CHECK_ARG(!f->training, "the cut table is written by inference forwards only");
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
+    *cut = ws.cut;
+    *n_tiles = gs_frame_geometry(f).n_tiles;
     return 0;
 }
 

@@ -19,6 +19,7 @@ import copy
 import ctypes as C
 import os
 import sys
+import warnings
 import weakref
 from dataclasses import dataclass
 from typing import Optional
@@ -43,6 +44,7 @@ class FrameStats:
     longest_list: int = 0  # longest tile list of the frame (lists of up to 1024 pairs are reported as 0)
     saturated_buckets: int = 0  # ... of them in tiles whose compositing stopped before the end of their list
     cull_fallback: bool = False  # an occlusion-culled frame whose lists proved too short: rendered again from the full ones
+    cull_unrepaired: bool = False  # a GS_FRAME_CULL_REPEAT frame that ran past a cut: NOT rendered again, its image is not guaranteed
 
 
 _LOG_FLAGS = os.environ.get("GS_LOG_FLAGS", "") == "1"
@@ -92,8 +94,10 @@ class FrameRenderer:
                  emit_sorted_keys: bool = False, slice_sort: bool = False, table_bin: bool = False,
                  serial_long_lists: bool = False, long_lists: Optional[bool] = None, bwd_rows: Optional[bool] = None,
                  force_strips: Optional[bool] = None, occlusion_cull: Optional[bool] = None,
-                 scene_pack: Optional[bool] = None):
+                 scene_pack: Optional[bool] = None, cull_second_pass: str = "auto"):
         self.device = require_hip(device, "FrameRenderer")
+        if cull_second_pass not in ("auto", "always"):
+            raise ValueError('cull_second_pass must be "auto" or "always"')
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if tile_culling_method not in TILE_CULLING:
@@ -138,7 +142,22 @@ class FrameRenderer:
         self._cull_backoff = 256      # frames it is switched off for when it did not pay; doubles up to 4,096
         self._cull_full_pairs = None  # pairs of the last UNCULLED inference frame whose counters have arrived
         self._cull_settled = False    # a culled frame's counters have confirmed that the cull pays (until it is disturbed)
-        self._cull_probe = None       # (event, pinned host buffer, serial, frame was culled)
+        self._cull_probe = None       # (event, pinned host buffer, serial, frame was culled, repeat key, repeat epoch, flagged)
+        # GS_FRAME_CULL_REPEAT (include/gs_abi.h): a culled frame that repeats the previous forward -- a viewer at rest -- is
+        # issued without the five gated launches of its second pass, which provably cannot run there (_repeat_step).  "auto":
+        # the renderer makes the promise from what it tracks; "always": the second pass is always enqueued -- for callers who
+        # edit parameters through raw pointers without advancing the tensors' `_version`, and for A/B runs.
+        self.cull_second_pass = cull_second_pass
+        self._pack_builds = 0          # serial number of the latest scene-pack build
+        self._capturing = False        # _scene_pack_step: the stream of the frame being described is captured into a graph
+        self._repeat_prev = None       # repeat key of the previous forward (None: that forward licenses nothing)
+        self._repeat_licence = None    # the key under which a repeated culled frame was SEEN to finish without running past
+        self._repeat_epoch = 0         # advances whenever a forward is not a repeat of the one before: evidence from before is void
+        self._repeat_is_repeat = False  # the last forward had a key and it was the key of the forward before it
+        self._repeat_flagged = False   # the last forward carried GS_FRAME_CULL_REPEAT
+        self._repeat_unchecked = 0     # flagged frames since the last health probe
+        self.cull_repeat_frames = 0    # frames issued with GS_FRAME_CULL_REPEAT
+        self.broken_promises = 0       # flagged frames found to have run past (a bookkeeping error: warned about, backed off)
         self.long_lists = long_lists
         self._long_lists_seen = False
         self._long_sort_seen = False  # GS_FRAME_LONG_SORT: a list beyond the per-tile sort's LDS window was seen (see _note_lists)
@@ -221,13 +240,19 @@ class FrameRenderer:
             f = _lib.GsFrameDP()
             C.memmove(C.byref(f), C.byref(cached[1]), C.sizeof(_lib.GsFrameDP))
             self._grid = cached[3]
+            self._desc_sig = cached[2]
             return f
         f = self._describe_uncached(pos, quat, scale, opa, rgb, camera, training, aux)
         # (the key is taken again: building the descriptor may have (re)allocated the workspaces)
         key = key[:-2] + (self._aux_ws.data_ptr() if aux else 0, self._ws.data_ptr())
         keep = _lib.GsFrameDP()
         C.memmove(C.byref(keep), C.byref(f), C.sizeof(_lib.GsFrameDP))
-        self._desc_cache = (key, keep, None, self._grid)
+        # the descriptor's bytes without the pose fields (no output pointer is set yet): what _repeat_step compares with the
+        # previous forward's -- taken here, once per descriptor, so that a cache hit hands out the same objects again
+        b = C.string_at(C.addressof(f), C.sizeof(f))
+        (p0, p1), (r0, r1) = self._REPEAT_POSE, self._REPEAT_RAYS
+        self._desc_sig = (b[:p0], b[p1:r0], b[r1:])
+        self._desc_cache = (key, keep, self._desc_sig, self._grid)
         return f
 
     def _describe_uncached(self, pos, quat, scale, opa, rgb, camera, training, aux: bool = False) -> _lib.GsFrameDP:
@@ -366,7 +391,7 @@ class FrameRenderer:
         color_dim = int(rgb.shape[1]) if rgb.dim() == 2 else 1
         state = self._scene_pack_state(tensors)
         cur = self._stream()
-        capturing = torch.cuda.is_current_stream_capturing()
+        capturing = self._capturing = torch.cuda.is_current_stream_capturing()  # (_repeat_step asks the same of this frame)
         pk = self._pack
         if pk is not None and self._scene_pack_key_matches(pk["key"], tensors, state, color_dim):
             if cur.cuda_stream not in pk["streams"]:
@@ -394,7 +419,9 @@ class FrameRenderer:
                                                 cur.cuda_stream), "gs_scene_pack_build")
             ev = torch.cuda.Event()
             ev.record(cur)
+            self._pack_builds += 1  # (a build's serial number: what a repeated frame's licence names, never an address)
             self._pack = self._pack_cur = {
+                "serial": self._pack_builds,
                 "key": (tuple(weakref.ref(t) for t in tensors), state, (self.scale_activation, color_dim)),
                 "a": a, "b": b, "planes": (pa, pb, a_bytes.value, b_bytes.value), "event": ev, "streams": {cur.cuda_stream}}
             self._pack_seen = None
@@ -416,6 +443,7 @@ class FrameRenderer:
             _lib.check(_lib.gs_frame_async_wait(self._async, self._stream().cuda_stream), "gs_frame_async_wait")
             self._frame = None
         self._cut_key = None
+        self._repeat_drop()  # (another workspace: whatever was seen in the old one licenses nothing)
 
     def __del__(self):
         try:
@@ -531,6 +559,77 @@ class FrameRenderer:
     # back, else switches it off for `_cull_backoff` frames (256, doubling up to 4,096 while it keeps failing).
     CULL_MIN_GAIN = float(os.environ.get("GS_FRAME_CULL_MIN_GAIN", "0.65"))
 
+    def _cull_back_off(self):
+        self._cull_off_until = self._frame_serial + self._cull_backoff
+        self._cull_backoff = min(2 * self._cull_backoff, 4096)
+        self._cull_settled = False
+
+    # A culled frame that REPEATS the previous forward cannot run past its cuts (at an unchanged pose and
+    # scene a tile stops at the Gaussian that set its cut; a slice overflows its staging region if and only if it did in the
+    # frame before), so its five gated launches -- which return at their first instruction -- need not be enqueued:
+    # GS_FRAME_CULL_REPEAT.  The renderer makes that promise for a frame whose REPEAT KEY equals the previous forward's and
+    # the key its licence was given under:
+    #   the key: the descriptor byte for byte -- workspace, max_pairs, N, size, intrinsics, thresholds, listing method,
+    #     activation, colour dimension, every flag, the pack planes -- without the output pointers (not yet set where the
+    #     key is taken) and without the pose fields, plus the serial number of the scene-pack BUILD the frame reads (tensor
+    #     identity, `_version`, address and shape stand behind a build: _scene_pack_key_matches; an address alone can come
+    #     back in another tensor).  Only inference frames that carry a pack and take the tiles' OWN cuts have a key: own
+    #     cuts are taken at a pose byte-identical to the recorded one only (_camera_shift_px == 0.0), which is how the
+    #     pose enters;
+    #   the licence: the tagged asynchronous counters of a culled frame that was itself such a repeat have landed with
+    #     ran_past == 0 and overflow == 0, and every forward since had the same key (the epoch).
+    # Whatever else happens to the workspace -- another pose or pack build, a training or aux forward, forward_begin,
+    # profile_forward with other flags, a reallocation, another max_pairs, the cull's own back-off, a frame captured into a
+    # graph -- is a forward with another key or none: the licence is gone until new evidence arrives.
+    # The check after the fact is complete (a culled frame whose run-past counter stayed 0 is the unculled frame bit for bit), so
+    # a flagged run probes its counters every CULL_HEALTH_EVERY-th frame, the same tagged copy, no synchronisation.
+    CULL_HEALTH_EVERY = 64
+    _REPEAT_POSE = (_lib.GsFrame.rot.offset, _lib.GsFrame.tran.offset + _lib.GsFrame.tran.size)
+    _REPEAT_RAYS = (_lib.GsFrame.rays_o.offset, _lib.GsFrame.vec_dy.offset + _lib.GsFrame.vec_dy.size)
+
+    def _repeat_step(self, f, training, aux=False) -> bool:
+        """In front of a forward of ``f`` (as ``_describe`` returned it: no output pointer set yet): flag it with
+        GS_FRAME_CULL_REPEAT if the renderer can make the promise, and note what this forward does to the licence."""
+        key = None
+        own_cuts = (f.flags & (_lib.GS_FRAME_OCCLUSION_CULL | _lib.GS_FRAME_CULL_DILATE | _lib.GS_FRAME_SCENE_PACK)) == \
+            (_lib.GS_FRAME_OCCLUSION_CULL | _lib.GS_FRAME_SCENE_PACK)
+        # (a frame that carries a pack has been through _scene_pack_step, which asked whether the stream is being captured: a
+        # captured flag would be replayed after the evidence has gone stale)
+        if self.cull_second_pass == "auto" and own_cuts and not training and not aux and self._pack_cur is not None \
+                and not self._capturing:
+            key = (self._pack_cur["serial"],) + self._desc_sig
+        repeat = key is not None and key == self._repeat_prev
+        if not repeat:
+            self._repeat_epoch += 1
+            self._repeat_licence = None
+        self._repeat_prev = key
+        self._repeat_is_repeat = repeat
+        self._repeat_flagged = repeat and self._repeat_licence == key
+        if self._repeat_flagged:
+            f.flags |= _lib.GS_FRAME_CULL_REPEAT
+            self.cull_repeat_frames += 1
+            self._repeat_unchecked += 1
+        return self._repeat_flagged
+
+    def _repeat_drop(self):
+        """Something other than a forward of this renderer's own bookkeeping touched the workspace (or is about to)."""
+        self._repeat_prev = self._repeat_licence = None
+        self._repeat_is_repeat = False
+        self._repeat_epoch += 1
+
+    def _broken_promise(self, serial: int, epoch: int):
+        """A frame issued with GS_FRAME_CULL_REPEAT ran past a cut: it was not rendered again."""
+        if getattr(self, "_repeat_broken_epoch", None) == epoch:
+            return  # (already acted upon: the frames of one flagged run share the broken licence and are counted once)
+        self._repeat_broken_epoch = epoch
+        self._repeat_drop()
+        self._cull_back_off()
+        self.broken_promises += 1
+        warnings.warn(f"FrameRenderer: frame {serial} was issued as a repeat of the frame before it (GS_FRAME_CULL_REPEAT) and "
+                      f"ran past an occlusion cut: it was not rendered again and its image is not guaranteed.  The licence "
+                      f"is withdrawn and the occlusion cull backs off; FrameRenderer(cull_second_pass=\"always\") if the "
+                      f"scene is edited behind the tensors' version counters.")
+
     def _cull_probe_step(self, f, stream):
         if torch.cuda.is_current_stream_capturing():
             return  # (a frame being captured into a graph: no event queries, no copies to the host)
@@ -540,17 +639,22 @@ class FrameRenderer:
             self._cull_probe = None
             if (int(h[11]) & 0xffffffff) == (p[2] & 0xffffffff):
                 pairs, ran_past = int(h[1]), int(h[10])
-                if int(h[2]) or pairs <= 0:
+                if p[6] and ran_past:
+                    self._broken_promise(p[2], p[5])
+                elif int(h[2]) or pairs <= 0:
                     pass  # an overflowed (empty) frame says nothing about the scene
                 elif not p[3]:
                     self._cull_full_pairs, self._cull_full_serial = pairs, p[2]
-                elif self._cull_full_pairs:
-                    if ran_past or pairs > self.CULL_MIN_GAIN * self._cull_full_pairs:
-                        self._cull_off_until = self._frame_serial + self._cull_backoff
-                        self._cull_backoff = min(2 * self._cull_backoff, 4096)
-                        self._cull_settled = False
-                    else:
-                        self._cull_settled, self._cull_backoff = True, 256
+                else:
+                    if self._cull_full_pairs:
+                        if ran_past or pairs > self.CULL_MIN_GAIN * self._cull_full_pairs:
+                            self._cull_back_off()
+                        else:
+                            self._cull_settled, self._cull_backoff = True, 256
+                    if not ran_past and p[4] is not None and p[5] == self._repeat_epoch and \
+                            self._frame_serial >= self._cull_off_until:
+                        self._repeat_licence = p[4]  # the evidence: a repeated culled frame of this key did not run past
+                        self._repeat_unchecked = 0
         culled = bool(f.flags & _lib.GS_FRAME_OCCLUSION_CULL)
         # (judged from the SECOND culled frame of a run on: the first one may have been trimmed by a cut table that another
         # scene or another set of parameters left in the workspace -- all GS_NO_CUT, or cuts that make it fall back)
@@ -561,9 +665,16 @@ class FrameRenderer:
         # count is unknown or older than 64 frames (a moving camera renders unculled frame after unculled frame)
         fresh = self._cull_full_pairs is not None and self._frame_serial - getattr(self, "_cull_full_serial", -10**9) <= 64
         want = (not self._cull_settled and self._cull_full_pairs is not None and self._cull_run >= 2) if culled else not fresh
+        # GS_FRAME_CULL_REPEAT: a repeated culled frame without a licence is the evidence for one; a flagged run is looked
+        # at every CULL_HEALTH_EVERY-th frame
+        flagged, repeat = self._repeat_flagged, self._repeat_is_repeat
+        if culled and repeat:
+            want = want or (self._repeat_unchecked >= self.CULL_HEALTH_EVERY if flagged else self._repeat_licence is None)
         if culled and self._cull_full_pairs is None and self._cull_probe is None:
             self._cull_off_until = self._frame_serial + 1  # nothing to compare with yet: one unculled frame, which is probed
         if self._cull_probe is None and want:
+            if flagged:
+                self._repeat_unchecked = 0
             host = getattr(self, "_cull_host", None)
             if host is None:
                 host = self._cull_host = torch.zeros(_lib.GS_STATS_TAGGED_N, dtype=torch.int64).pin_memory()
@@ -571,7 +682,8 @@ class FrameRenderer:
                        "gs_frame_stats_tagged_async")
             ev = torch.cuda.Event()
             ev.record(self._stream())
-            self._cull_probe = (ev, host, self._frame_serial, culled)
+            self._cull_probe = (ev, host, self._frame_serial, culled, self._repeat_prev if (culled and repeat) else None,
+                                self._repeat_epoch, flagged)
 
     def _note_cut_table(self, f):
         """Every inference frame's compositing launch leaves the per-tile occlusion cuts of ITS frame in the workspace: the
@@ -658,6 +770,7 @@ class FrameRenderer:
         self._scene_pack_step(pos, quat, scale, opa, rgb, training)
         while True:
             f = self._describe(pos, quat, scale, opa, rgb, camera, training, aux)
+            self._repeat_step(f, training, aux)  # (GS_FRAME_CULL_REPEAT: in front of the output pointers)
             g = self._grid
             image = torch.empty(g.height, g.width, 3, device=self.device, dtype=torch.float32)
             padded = torch.empty(g.padded_height, g.padded_width, 3, device=self.device,
@@ -731,6 +844,7 @@ class FrameRenderer:
                         or cur.max_pairs != self.max_pairs or cur.N != pos.shape[0]):
                     return False
                 self._pack_cur = None  # (a training frame)
+                self._repeat_drop()    # ... whose project stage is about to write the workspace
                 f = self._describe(pos, quat, scale, opa, rgb, camera, True)
                 if f.workspace != cur.workspace:
                     return False
@@ -790,6 +904,7 @@ class FrameRenderer:
             rows = self.bwd_rows or (self.bwd_rows is None and self._bwd_rows_seen)
             f.flags = (f.flags & ~_lib.GS_FRAME_BWD_ROWS) | (_lib.GS_FRAME_BWD_ROWS if rows else 0)
             _lib.check(_lib.gs_frame_forward_rest(C.byref(f), stream), "gs_frame_forward_rest")
+            self._repeat_drop()
             self._frame = f
             self._frame_serial += 1
             self._keep = (*b["keep"], b["image"], b["padded"])
@@ -983,6 +1098,8 @@ class FrameRenderer:
         with torch.cuda.device(self.device):
             self._scene_pack_step(pos, quat, scale, opa, rgb, training)
         f = self._describe(pos, quat, scale, opa, rgb, camera, training, aux)
+        with torch.cuda.device(self.device):
+            self._repeat_step(f, training, aux)  # (a profiled frame is a forward like any other: flagged where the promise holds)
         g = self._grid
         image = torch.empty(g.height, g.width, 3, device=self.device, dtype=torch.float32)
         padded = torch.empty(g.padded_height, g.padded_width, 3, device=self.device,
@@ -1035,8 +1152,12 @@ class FrameRenderer:
         if bwd_done:
             self._note_buckets(b)
         culled = bool(self._frame.flags & _lib.GS_FRAME_OCCLUSION_CULL)
+        # a GS_FRAME_CULL_REPEAT frame has no second pass: one that ran past was NOT rendered again (a broken promise)
+        flagged = culled and bool(self._frame.flags & _lib.GS_FRAME_CULL_REPEAT)
+        if flagged and ran_past:
+            self._broken_promise(self._frame_serial, self._repeat_epoch)
         return FrameStats(v, m, o, (b & 0xffffffff) if bwd_done else 0, longest, (b >> 32) if bwd_done else 0,
-                          bool(ran_past) and culled)
+                          bool(ran_past) and culled and not flagged, bool(ran_past) and flagged)
 
     def binning_variant(self) -> str:
         """Which binning / sort path the last frame took: "radix64", "radix_tile_bits", "table", "slice", "strip"."""
@@ -1055,6 +1176,17 @@ class FrameRenderer:
         ptr = C.c_void_p()
         _lib.call("gs_frame_overflow_flag", C.byref(self._frame), C.byref(ptr))
         return ptr.value
+
+    def cut_table(self) -> torch.Tensor:
+        """[T] int32 view of the workspace: the per-tile occlusion cuts the last inference forward left behind (depth bits; -1
+        = no cut), what the next GS_FRAME_OCCLUSION_CULL frame trims by.  A test aid; no host synchronisation."""
+        f = self._frame
+        if f is None:
+            raise RuntimeError("no frame rendered yet")
+        ptr, n = C.c_void_p(), C.c_int32()
+        _lib.call("gs_frame_debug_cut_table", C.byref(f), C.byref(ptr), C.byref(n))
+        off = ptr.value - self._ws.data_ptr()
+        return self._ws[off:off + 4 * n.value].view(torch.int32)
 
     def _rects(self, allow_culled: bool = False) -> torch.Tensor:
         """[N,4] int32 view of the workspace: (y0 | y1 << 16, x0 | x1 << 16, depth bits, tiles touched) per Gaussian.

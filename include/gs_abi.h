@@ -34,7 +34,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_densify_apply_state (the arrays
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_CULL_REPEAT (an
+ *   occlusion-culled frame that repeats the previous one is issued without the five gated launches of its second pass) and
+ *   gs_frame_cull_second_pass (does a forward of this descriptor enqueue them: host-side, no launch);
+ *   gs_frame_debug_cut_table (a read-only view of the per-tile cuts, for tests).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_densify_apply_state (the arrays
  *   that share the row index with the Gaussians -- the optimizer's moments -- follow a densification: kept and cloned rows keep
  *   theirs, split rows, clones and second samples start from zero; gs_prune_arrays is reused, gs_densify_classify and
  *   gs_densify_apply are unchanged).
@@ -279,7 +283,8 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        only), and a tile that composites anything behind its cut -- or reaches the end of
                                        its trimmed list with a live pixel -- makes the library render the frame
                                        again from the full lists, on the device, inside the same call (five gated launches:
-                                       ~13 us when nothing ran past its cut; 0.6 of a frame when something did, which with thousands
+                                       8.6 us of a 215-us frame when nothing ran past its cut -- GS_FRAME_CULL_REPEAT leaves them
+                                       out where they cannot run --; 0.6 of a frame when something did, which with thousands
                                        of tiles is nearly every frame of a MOVING camera: set the flag for a camera at rest).  The CALLER's promise: the previous
                                        forward of this workspace was an inference frame (training = 0: training forwards do
                                        not write the table) of the same width and height (the cut table is per tile).
@@ -417,6 +422,43 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
                                        _part, _slice, _profile, the fused Adam backwards, gs_frame_forward_project / _rest /
                                        _profile, gs_frame_contrib and the debug views.  Frames without the flag run exactly
                                        the kernels they ran before it existed. */
+
+#define GS_FRAME_CULL_REPEAT 65536    /* with GS_FRAME_OCCLUSION_CULL: this frame REPEATS the previous forward of its workspace, and
+                                       the library does not enqueue the five gated launches of the second pass behind it.
+                                       Nothing else changes: the first pass trims by the recorded cuts, the compositing
+                                       epilogue compares against them and raises the run-past counter, the cut table, the
+                                       tile costs and every counter are written as in any culled frame.
+                                       THE CALLER PROMISES that (1) the previous forward of this workspace used this
+                                       descriptor field for field, the output pointers (image, image_padded, depth, alpha)
+                                       aside; (2) the scene bytes the two frames read -- the raw arrays or the scene pack --
+                                       are the same; (3) a culled frame (GS_FRAME_OCCLUSION_CULL without
+                                       GS_FRAME_CULL_DILATE) with exactly these inputs has been seen to finish with the
+                                       run-past counter at 0 (gs_frame_cull_fallback_async, or [10] and, for the capacity,
+                                       [2] of gs_frame_stats_tagged_async).
+                                       Why that is enough: at an unchanged pose and scene a tile stops
+                                       at the Gaussian that set its cut, so the depth test of the epilogue never fires and the
+                                       frame writes the cut table it read; the one other source of a run-past, a slice
+                                       that overflows its staging region, depends on entry counts alone, which identical
+                                       inputs reproduce whatever the order of the LDS adds.  A frame with identical inputs
+                                       therefore runs past if and only if the one before it did.
+                                       What a client tracks to make the promise: the pose and intrinsics by value, every
+                                       other descriptor field, the workspace (address, size, max_pairs), and the CONTENTS of
+                                       the scene -- not its address alone: an in-place edit, or a freed array whose address
+                                       comes back, breaks (2) -- and it drops the promise until it holds fresh evidence (3)
+                                       whenever one of them changes or another forward used the workspace in between.
+                                       The check after the fact is complete: for ANY cut table, a culled frame that ends with
+                                       the run-past counter at 0 is the unculled frame bit for bit.  A flagged frame has the
+                                       counter at 0 and is exact, or at 1 and the caller can know it for certain
+                                       (gs_frame_cull_fallback_async): no silent third case.  A non-zero counter on a
+                                       flagged frame means the promise was broken, the frame was NOT rendered again and the
+                                       image delivered is not guaranteed; the next forward without this flag is repaired
+                                       as usual.
+                                       Ignored wherever GS_FRAME_OCCLUSION_CULL is ignored (no second pass exists there).
+                                       GS_E_INVALID, before anything is enqueued, together with GS_FRAME_CULL_DILATE: dilated
+                                       cuts belong to a camera that moved, which contradicts (1).  gs_frame_cull_second_pass
+                                       tells, without a launch, whether a forward enqueues the gated launches.
+                                       gs_frame_forward_profile honours the flag: the "total" of a flagged frame closes behind
+                                       the compositing launch. */
 
 /* Frame descriptor.  All scalars are per-camera constants computed on the host exactly as
  * splatter.py does (Tiles, RayInfo, frustum guard band); rot/tran are passed by value. */
@@ -605,8 +647,16 @@ int gs_frame_longest_list_async(const gs_frame *f, int64_t *longest_host, gs_str
 int gs_frame_stats_tagged_async(const gs_frame *f, uint32_t tag, int64_t *stats_host, gs_stream_t stream);
 
 /* Non-zero in *ran_past_host (after `stream` has reached this copy) iff the frame's lists had been trimmed
- * (GS_FRAME_OCCLUSION_CULL) and a tile ran past its cut, i.e. the frame was rendered a second time from the full lists. */
+ * (GS_FRAME_OCCLUSION_CULL) and a tile ran past its cut, i.e. the frame was rendered a second time from the full lists.
+ * On a GS_FRAME_CULL_REPEAT frame, which has no second pass, a non-zero value means: the caller's promise was broken, the
+ * frame was NOT rendered again, and the image it delivered is not guaranteed to be the unculled frame.  (Zero means, as for
+ * every culled frame, that the image is exact.)  The next forward of the workspace without that flag is repaired as usual. */
 int gs_frame_cull_fallback_async(const gs_frame *f, int64_t *ran_past_host, gs_stream_t stream);
+
+/* *enqueued = 1 iff a forward of this frame description enqueues the five gated launches of an occlusion-culled frame's second
+ * pass: the frame is culled (gs_frame_is_occlusion_culled) and does not carry GS_FRAME_CULL_REPEAT.  Host-side, no launch, no
+ * device.  GS_E_INVALID with the reason of the forward's refusal for GS_FRAME_CULL_REPEAT with GS_FRAME_CULL_DILATE. */
+int gs_frame_cull_second_pass(const gs_frame *f, int32_t *enqueued);
 
 /* *culled = 1 iff the library renders this frame description with the occlusion cull (the flag is set AND none of the
  * conditions under which it is ignored holds); host-side, no launch.  Such a frame's first pass tests every Gaussian
@@ -639,6 +689,12 @@ int gs_frame_binning_variant(const gs_frame *f);
  * `depth bits != 0`); the 64-byte record (rec_geom / rec_cov / rec_color above) of a culled Gaussian is NOT written and
  * holds whatever an earlier frame left there. */
 int gs_frame_debug_rects(const gs_frame *f, const uint32_t **rects);
+
+/* The per-tile occlusion cuts the last INFERENCE forward of this workspace left behind (uint32 [*n_tiles], row-major over the
+ * tile grid): the float bits of the depth behind which the next GS_FRAME_OCCLUSION_CULL frame trims the tile's list, 0xffffffff
+ * for a tile without a cut.  A read-only view, for tests: a GS_FRAME_CULL_REPEAT frame that kept its promise leaves the
+ * table it read.  GS_E_INVALID for a training frame (training forwards do not write the table). */
+int gs_frame_debug_cut_table(const gs_frame *f, const uint32_t **cut, int32_t *n_tiles);
 
 /* Where the FIRST PASS of an occlusion-culled frame (gs_frame_is_occlusion_culled) stages its level-1 entries, for tests of
  * that path: slice s of the Gaussian array owns slots [s x *cap, (s + 1) x *cap) of *entries (8 bytes each) and *tags

@@ -891,6 +891,29 @@ extern "C" int gs_frame_debug_cut_table(const gs_frame *f, const uint32_t **cut,
     return 0;
 }
 
+extern "C" int gs_frame_debug_tile_compact(const gs_frame *f, const uint32_t **at, int32_t *n_tiles) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG(at && n_tiles, "null pointer");
+    GS_CHECK_ARG(!f->training && f->color_dim == 3 && !(f->flags & GS_FRAME_AUX),
+                 "the compact phase belongs to rgb inference frames without the depth / alpha maps");
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
+    *at = ws.tile_compact;
+    *n_tiles = gs_frame_geometry(f).n_tiles;
+    return 0;
+}
+
+extern "C" int gs_frame_debug_tile_cost(const gs_frame *f, const uint32_t **cost, int32_t *n_tiles) {
+    int rc = validate(f);
+    if (rc) return rc;
+    GS_CHECK_ARG(cost && n_tiles, "null pointer");
+    GS_CHECK_ARG(effective_sort_mode(f) == 2 && gs_frame_uses_strips(f), "the tile costs are recorded by frames of the strip variant");
+    gs_frame_ws ws = gs_frame_carve(f->workspace, f->N, f->max_pairs, f->width, f->height, f->color_dim, f->training);
+    *cost = ws.tile_cost;
+    *n_tiles = gs_frame_geometry(f).n_tiles;
+    return 0;
+}
+
 extern "C" int gs_frame_debug_views(const gs_frame *f, const uint64_t **sorted_keys, const uint32_t **sorted_ids,
                                     const int32_t **tile_ranges, const float **rec_geom, const float **rec_cov,
                                     const float **rec_color, const uint32_t **tiles_touched) {

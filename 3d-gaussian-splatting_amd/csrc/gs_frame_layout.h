@@ -351,6 +351,8 @@ struct gs_frame_ws {
     uint32_t *big_tiles;           // [T] queue of the tiles whose list exceeds strip_sort_kernel's LDS window
     uint32_t *tile_cost;           // [T] Gaussian steps every tile composited in the LAST forward of this workspace
     uint32_t *tile_order;          // [T] tiles in descending order of that cost: the dispatch order of this forward
+    uint32_t *tile_compact;        // [T] rgb inference frames: the step at which a tile's wave compacted its live pixels in the
+                                   // LAST forward (raster_fwd.hip), 0xffffffff if it never did.  Diagnostic.
     uint4 *group_queue;            // dense frames: (tile, first slot, keys, -) of the groups big_list_sort_kernel cut
     // dense frames only (else NULL): segmented compositing of long tile lists (raster_fwd.hip)
     float4 *cont_state;            // [T][256] (T, C) of a tile's pixels after its first GS_LONG_MIN Gaussians
@@ -483,6 +485,8 @@ static inline gs_frame_ws gs_frame_carve(void *base, int64_t N, int64_t max_pair
         ws.mfma_n_items = nullptr;
         ws.stop_keys = nullptr;
     }
+    // (behind everything else: the layout in front of it is what it was)
+    ws.tile_compact = (uint32_t *)take(sizeof(uint32_t) * G.n_tiles);
     ws.total_bytes = off;
     return ws;
 }

@@ -94,6 +94,11 @@ __device__ __forceinline__ f2 live_mask(f2 t, f2 scale, f2 bias) {
                          // (checkpoint stores) 130 VGPRs = three waves; with the hint it fits 128 without scratch: training
                          // forward at 2.4 M Gaussians 136 -> 129 us, inference 126 VGPRs, +-1 % (same-box A/B, round 3)
 #endif
+#ifndef GS_FWD_COMPACT_MIN
+#define GS_FWD_COMPACT_MIN 16  // rgb inference frames: the Gaussians a list must have left for a tile to compact (the compact
+                               // phase, below).  Measured with 8 / 16 / 32: 4,807 / 4,758 - 4,800 / 4,789 FPS on the
+                               // headline scene, all within one build's own spread (profiles/raster_compact_ab.txt): 16 stays
+#endif
 #ifndef GS_FWD_SH27_WPE
 #define GS_FWD_SH27_WPE 3  // waves per SIMD the register allocation of the SH kernels aims at (A/B switches; degree 2 at
                            // 3: 168 VGPRs and 22 spilled outside the loop, 0.535 -> 0.510 ms at 2.4 M Gaussians)
@@ -113,7 +118,7 @@ struct AuxFwdOut {
 // with d = rec_geom.z staged in LDS as one more field, and A = sum w accumulated exactly like a colour channel of value
 // 1.0 -- with their checkpoints and maps; everything else (stop, cut table, order, statistics) as in the plain kernel.
 // AUX = false compiles to the plain kernel unchanged.
-template <int CDIM, bool FRAME, bool CKPT, bool SIG, bool WN, bool EXACT, bool AUX>
+template <int CDIM, bool FRAME, bool CKPT, bool SIG, bool WN, bool EXACT, bool AUX, bool COMPACT = false>
 __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                                                     const int32_t *__restrict__ ranges,
                                                     float *__restrict__ out_padded,
@@ -128,7 +133,10 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                                                     const uint32_t *cut_in, uint32_t *cut_out,
                                                     unsigned long long *__restrict__ ranpast,
                                                     const unsigned long long *__restrict__ gate,
-                                                    const AuxFwdOut &X) {
+                                                    const AuxFwdOut &X, uint32_t compact_min = 0,
+                                                    uint32_t *__restrict__ tile_compact = nullptr) {
+    static_assert(!COMPACT || (CDIM == 3 && FRAME && !CKPT && !SIG && !WN && !EXACT && !AUX),
+                  "the compact phase belongs to the rgb inference frame");
     static_assert(!AUX || (FRAME && !SIG && !WN && !EXACT), "depth / alpha maps belong to the frame path");
     static_assert(!(EXACT && FRAME), "the exact-exp flavour belongs to the reference API (gs_draw, fast = 0)");
     // frame path, temporal occlusion cull (gs_frame_layout.h): `cut_out` [T] receives, per tile, the depth behind which this
@@ -152,6 +160,11 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
     constexpr uint32_t LIVE_EVERY = CDIM == 3 ? GS_FWD_LIVE_EVERY : 4;
     __shared__ SM sm;
     __shared__ float s_dep[AUX ? SM::NBUF : 1][AUX ? CH : 1] __attribute__((aligned(16)));  // AUX: d of the chunk's Gaussians
+    // COMPACT: the hand-over area of the compact phase (below), one entry per live pixel: T, three colour sums, the pixel's x
+    // and y coordinate and its index in the tile; 3.5 KiB beside FwdSmem<3>: 16 one-wave workgroups per CU still fit
+    enum { KT, KR, KG, KB, KX, KY, KI, KFIELD };
+    constexpr int KCAP = 128;
+    __shared__ float s_cmp[COMPACT ? KFIELD : 1][COMPACT ? KCAP : 1] __attribute__((aligned(16)));
     const int lane = threadIdx.x;
 
     auto range_of = [&](uint32_t t, uint32_t &s0, uint32_t &cnt) {
@@ -240,6 +253,73 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
     asm volatile("" : "+v"(live_scale), "+v"(live_bias));
     uint32_t nproc = 0, steps = 0;  // steps: Gaussians composited before the wave stopped (the tile's cost)
 
+    // One finished pixel: weight normalisation, padded image, clamp + centred crop.  The epilogue's statement; the compact
+    // phase writes a pixel that has stopped when it hands the live ones over, and its own two per lane at the end.
+    auto write_pixel = [&](uint32_t id_xp, uint32_t id_y, float c0, float c1, float c2, float aw) {
+        if (!WN || aw < 0.01f) aw = 1.0f;  // gaussian.cu:964-969
+        const float o0 = c0 / aw, o1 = c1 / aw, o2 = c2 / aw;
+        if (out_padded) {
+            float *o = out_padded + ((size_t)id_y * G.padW + id_xp) * 3;
+            o[0] = o0;
+            o[1] = o1;
+            o[2] = o2;
+        }
+        if (out_image) {  // clamp + centred crop (splatter.py:652-653, 267-272)
+            const int ox = (int)id_xp - G.crop_left, oy = (int)id_y - G.crop_top;
+            if (ox >= 0 && ox < G.width && oy >= 0 && oy < G.height) {
+                float *o = out_image + ((size_t)oy * G.width + ox) * 3;
+                // torch.clamp semantics: NaN stays NaN (fminf / fmaxf would turn it into 0)
+                o[0] = o0 > 1.f ? 1.f : (o0 < 0.f ? 0.f : o0);
+                o[1] = o1 > 1.f ? 1.f : (o1 < 0.f ? 0.f : o1);
+                o[2] = o2 > 1.f ? 1.f : (o2 < 0.f ? 0.f : o2);
+            }
+        }
+    };
+
+    // COMPACT (rgb inference frames).  A wave composites all 256 pixels of its tile until the last of them stops, and the last
+    // one is typically a ray through a gap: a quarter of a frame's steps run with at most half of the pixel slots alive.  At the
+    // first liveness test that finds at most KCAP = 128 pixels alive, with at least `compact_min` Gaussians of the list left,
+    // the wave COMPACTS: a pixel that has stopped is final -- the masked T is 0, so nothing is ever added to it again -- and is
+    // written to the image there and then; the live ones go to s_cmp, ranked in the fixed order of their tile index (ballot
+    // masks + mbcnt), and lane L takes entries L and L + 64.  From there on a step is ONE pixel pair per lane instead of two:
+    // the same expressions in the same order on the same operands, only dx, B dx and A dx^2 + nlop are per pixel now (three
+    // more packed instructions per pair).  T[0], cr[0], cg[0], cb[0] are the pair's state; px2 / py2c its coordinates -- the
+    // floats the full phase held, not recomputed; cidx the two tile indices (0xffff: no pixel, T = 0).
+    // `vote`: the full phase stops on a LANE's sum of four T, so a pixel whose T is NaN (suspicious chunks only) silences the
+    // three other pixels of its lane in the vote.  The compact phase votes per pixel and keeps that rule: vote is 0 for every
+    // pixel whose lane of the full layout holds a NaN, refreshed where a NaN can appear (suspicious chunks, `seen_legacy`).
+    bool compacted = false, seen_legacy = false;  // (wave-uniform)
+    uint32_t compact_at = 0xffffffffu;
+    // the kernel sits at its 128 VGPRs: the compact phase's per-lane values live in the registers of the pair it gave up
+    f2 &vote = T[1], &px2 = cg[1], &py2c = cb[1];
+    auto cidx = [&]() { return __float_as_uint(cr[1].x); };
+    auto refresh_vote = [&]() {
+        if constexpr (COMPACT) {
+            // flags[l] = 1: lane l of the full layout holds a pixel whose T is NaN (the hand-over area is free by now)
+            uint32_t l = lane;
+            asm volatile("" : "+v"(l));  // (not to be moved: see hand_over)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            s_cmp[KT][l] = 0.f;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (T[0].x != T[0].x) s_cmp[KT][cidx() & 63u] = 1.f;
+            if (T[0].y != T[0].y) s_cmp[KT][(cidx() >> 16) & 63u] = 1.f;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            vote.x = 1.0f - s_cmp[KT][cidx() & 63u];
+            vote.y = 1.0f - s_cmp[KT][(cidx() >> 16) & 63u];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    };
+    // a pixel votes if T x vote > 0; v_max ignores a NaN operand (a NaN pixel's own vote is 0, and NaN x 0 = NaN)
+    auto compact_live = [&](bool refresh) {
+        if (refresh) refresh_vote();
+        const f2 s = T[0] * vote;
+        return __ballot(__builtin_fmaxf(s.x, s.y) > 0.0f) != 0ull;
+    };
+
     auto write_ckpt = [&](uint32_t idx_in_tile) {
         float4 *c = ckpt + raster_ckpt_slot(start, tile, idx_in_tile / GS_BUCKET) * 256;
 #pragma unroll
@@ -262,6 +342,51 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
         for (int h = 1; h < NPP; ++h) sum += T[h];
         return __ballot(sum.x + sum.y > 0.0f) != 0ull;
     };
+    // the hand-over: m[2 h + e] = the lanes whose pixel (h, e) is alive (T != 0: a NaN is carried along), live <= KCAP
+    auto hand_over = [&](const unsigned long long (&m)[4]) {
+        if constexpr (COMPACT) {
+            uint32_t first = 0;
+            // opaque, and not to be moved: the four pixels' addresses are per-tile values, and hoisted out of the chunk loop
+            // they would sit in registers (or scratch) through the hot loops for a use that comes once per tile
+            uint32_t x_here = id_x, y_here = id_y0, l = lane;
+            asm volatile("" : "+v"(x_here), "+v"(y_here), "+v"(l));
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int h = q >> 1;
+                const bool e = q & 1;
+                const float t = e ? T[h].y : T[h].x, c0 = e ? cr[h].y : cr[h].x, c1 = e ? cg[h].y : cg[h].x,
+                            c2 = e ? cb[h].y : cb[h].x;
+                const uint32_t slot = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(m[q] >> 32),
+                                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)m[q], 0u));
+                if (t != 0.f) {  // (the lane's bit of m[q]) slot < live <= KCAP
+                    s_cmp[KT][slot] = t;
+                    s_cmp[KR][slot] = c0;
+                    s_cmp[KG][slot] = c1;
+                    s_cmp[KB][slot] = c2;
+                    s_cmp[KX][slot] = px;
+                    s_cmp[KY][slot] = e ? py2[h].y : py2[h].x;
+                    s_cmp[KI][slot] = __uint_as_float(64u * q + l);
+                } else {
+                    write_pixel(x_here, y_here + 4 * q, c0, c1, c2, 1.0f);  // stopped: final
+                }
+                first += (uint32_t)__popcll(m[q]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t live = first;
+            const bool a = l < live, b = l + 64u < live;
+            T[0] = f2{a ? s_cmp[KT][l] : 0.f, b ? s_cmp[KT][l + 64] : 0.f};
+            cr[0] = f2{a ? s_cmp[KR][l] : 0.f, b ? s_cmp[KR][l + 64] : 0.f};
+            cg[0] = f2{a ? s_cmp[KG][l] : 0.f, b ? s_cmp[KG][l + 64] : 0.f};
+            cb[0] = f2{a ? s_cmp[KB][l] : 0.f, b ? s_cmp[KB][l + 64] : 0.f};
+            px2 = f2{a ? s_cmp[KX][l] : 0.f, b ? s_cmp[KX][l + 64] : 0.f};
+            py2c = f2{a ? s_cmp[KY][l] : 0.f, b ? s_cmp[KY][l + 64] : 0.f};
+            cr[1] = f2{__uint_as_float((a ? __float_as_uint(s_cmp[KI][l]) : 0xffffu) |
+                                       ((b ? __float_as_uint(s_cmp[KI][l + 64]) : 0xffffu) << 16)), 0.f};
+            vote = f2{1.f, 1.f};
+            if (seen_legacy) refresh_vote();
+        }
+    };
 
     bool done = false, staged_next = false;  // staged_next: the register stage holds chunk 0 of the NEXT tile
     bool continues = false;  // dense frames: the rest of a long list goes to the segment kernels (below)
@@ -272,10 +397,13 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                 // ONE wave busy for milliseconds): the pixels' state is saved and the rest of the list is composited in
                 // segments by many waves (raster_segment_kernel); lists that saturate earlier never get here
                 float4 *c = cont_state + (size_t)tile * 256;
+                uint32_t l = lane;
+                // (COMPACT: the kernel has no register to spare for a lane's address that is used once in a dense frame's tile)
+                if constexpr (COMPACT) asm volatile("" : "+v"(l));
 #pragma unroll
                 for (int h = 0; h < NPP; ++h) {
-                    c[128 * h + lane] = make_float4(T[h].x, cr[h].x, cg[h].x, cb[h].x);
-                    c[128 * h + 64 + lane] = make_float4(T[h].y, cr[h].y, cg[h].y, cb[h].y);
+                    c[128 * h + l] = make_float4(T[h].x, cr[h].x, cg[h].x, cb[h].x);
+                    c[128 * h + 64 + l] = make_float4(T[h].y, cr[h].y, cg[h].y, cb[h].y);
                 }
                 continues = true;
             }
@@ -371,12 +499,29 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
         auto composite_chunk = [&](auto legacy_tag) {
         constexpr bool LEGACY = decltype(legacy_tag)::value;
         uint32_t stop = cnt;  // Gaussians of this chunk composited before the wave stopped
+        uint32_t i = 0;
+        bool hand = false;  // (uniform) the full loop has just asked for the hand-over
+        if (!COMPACT || !compacted) {
 #pragma unroll 1
-        for (uint32_t i = 0; i < cnt; i += GROUP) {
-            if ((i & (LIVE_EVERY - 1)) == 0 && !any_live()) {
-                done = true;
-                stop = i;
-                break;
+        for (; i < cnt; i += GROUP) {
+            if ((i & (LIVE_EVERY - 1)) == 0) {
+                if (!any_live()) {
+                    done = true;
+                    stop = i;
+                    break;
+                }
+                if constexpr (COMPACT) {
+                    // (compact_min = 0: switched off, or a dense frame -- its hand-over at GS_LONG_MIN stores the fixed layout)
+                    // only the COUNT of live pixels (T != 0: a NaN is carried along) is taken inside the loop: four v_cmp into
+                    // SGPR masks and s_bcnt1.  The hand-over itself stands behind the loop, so that nothing of it is live here.
+                    if (compact_min && n - (base + i) >= compact_min &&
+                        __popcll(__ballot(T[0].x != 0.f)) + __popcll(__ballot(T[0].y != 0.f)) + __popcll(__ballot(T[1].x != 0.f)) +
+                                __popcll(__ballot(T[1].y != 0.f)) <= KCAP) {
+                        compacted = hand = true;
+                        compact_at = base + i;
+                        break;
+                    }
+                }
             }
             {
             constexpr uint32_t i4 = 0;
@@ -412,6 +557,9 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                 G4 = ld4(SM::G);
                 L4 = ld4(SM::BL);
             }
+            f2 fp[NPP], fm[NPP];  // COMPACT: the step before, unmasked, and its liveness mask
+#pragma unroll
+            for (int h = 0; h < NPP; ++h) fp[h] = fm[h] = T[h];
 #pragma unroll
             for (int u = 0; u < (int)GROUP; ++u) {
                 const float gx = X.v[u], gy = Y.v[u], cA = A4.v[u], cB = B4.v[u], cC = C4.v[u], nlop = O4.v[u];
@@ -459,7 +607,19 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                     // pixel's alpha is replaced by 0 and the statements that follow are the plain variant's.
                     // (Every other instantiation takes this variant for every chunk and keeps the intrinsic.)
                     f2 w;
-                    if constexpr (LEGACY && FRAME && CDIM == 3) {
+                    if constexpr (COMPACT) {
+                        // The kernel with a compact phase: both phases must round T (1 - alpha) alike, so the step is stated
+                        // with builtins here and there -- the forms the compiler's contraction gave this loop when the
+                        // statements below were left to it (raster_compact_codegen.txt), so that the frame is what it was.
+                        // T of the group's first Gaussian is materialised; behind it T = t' m is the product of the step before
+                        // (fp[h], fm[h]; m = 0 or 1: exact).
+                        const f2 Tn = u == 0 ? T[h] : fp[h] * fm[h];
+                        if constexpr (LEGACY) {
+                            al.x = Tn.x == 0.f ? 0.f : al.x;
+                            al.y = Tn.y == 0.f ? 0.f : al.y;
+                        }
+                        w = Tn * al;
+                    } else if constexpr (LEGACY && FRAME && CDIM == 3) {
                         al.x = T[h].x == 0.f ? 0.f : al.x;
                         al.y = T[h].y == 0.f ? 0.f : al.y;
                         w = al * T[h];
@@ -495,14 +655,88 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                         asm("" : "+v"(wr));
                         ca[h] += wr;
                     }
-                    const f2 t = T[h] - w;  // T * (1 - alpha)
-                    T[h] = t * live_mask(t, live_scale, live_bias);
+                    if constexpr (COMPACT) {
+                        const f2 Tn = u == 0 ? T[h] : fp[h] * fm[h];
+                        const f2 t = u == 0 ? pk_fma(-Tn, al, Tn) : u == 1 ? pk_fma(fp[h], fm[h], -w) : pk_fma(fm[h], fp[h], -w);
+                        fp[h] = t;
+                        fm[h] = live_mask(t, live_scale, live_bias);
+                        if (u == (int)GROUP - 1) T[h] = fp[h] * fm[h];
+                    } else {
+                        const f2 t = T[h] - w;  // T * (1 - alpha)
+                        T[h] = t * live_mask(t, live_scale, live_bias);
+                    }
                 }
             }
             }
         }
+        }
+        if constexpr (COMPACT) {
+            if (hand) {
+                asm volatile("" : "+v"(T[0]), "+v"(T[1]));  // (the masks are taken again here, not carried out of the loop)
+                const unsigned long long m[4] = {__ballot(T[0].x != 0.f), __ballot(T[0].y != 0.f), __ballot(T[1].x != 0.f),
+                                                 __ballot(T[1].y != 0.f)};
+                hand_over(m);
+            }
+            if (compacted && !done) {
+                // the compact loop: eight Gaussians per trip, one liveness test; i is a multiple of LIVE_EVERY here
+                static_assert(GROUP == 4 && LIVE_EVERY == 8, "the compact loop walks two groups of four per liveness test");
+                // (a NaN that appeared behind the last test of a suspicious chunk: the plain loop's tests do not look again)
+                if (!LEGACY && seen_legacy && i == 0) refresh_vote();
+#pragma unroll 1
+                for (; i < cnt; i += 2 * GROUP) {
+                    if (!compact_live(LEGACY)) {
+                        done = true;
+                        stop = i;
+                        break;
+                    }
+#pragma unroll
+                    for (uint32_t i4 = 0; i4 < 2 * GROUP; i4 += GROUP) {
+                        if (i4 && i + i4 >= cnt) break;  // (uniform) the list ends inside the trip
+                        // (the second group's nine operand reads stay behind the first group's math: 36 registers)
+                        __builtin_amdgcn_sched_barrier(0);
+                        auto ld4 = [&](int q) { return *(const float4 *)__builtin_assume_aligned(&sm.f[buf][q][i + i4], 16); };
+                        const float4 X = ld4(SM::X), Y = ld4(SM::Y), A4 = ld4(SM::A), B4 = ld4(SM::B), C4 = ld4(SM::C);
+                        const float4 O4 = ld4(SM::NLOP), R4 = ld4(SM::R), G4 = ld4(SM::G), L4 = ld4(SM::BL);
+                        auto at = [](const float4 &v, int u) { return u == 0 ? v.x : u == 1 ? v.y : u == 2 ? v.z : v.w; };
+                        f2 tp = T[0], mk = T[0];  // the step before: T (1 - alpha) unmasked, and its liveness mask
+#pragma unroll
+                        for (int u = 0; u < (int)GROUP; ++u) {
+                            const float gx = at(X, u), gy = at(Y, u), cA = at(A4, u), cB = at(B4, u), cC = at(C4, u),
+                                        nlop = at(O4, u);
+                            // the full loop's expressions, per pixel: every product and sum rounds as it does there
+                            const f2 dx = px2 - splat(gx);
+                            const f2 bdx = splat(cB) * dx;
+                            const f2 f = pk_fma(splat(cA) * dx, dx, splat(nlop));
+                            const f2 dy = py2c - splat(gy);
+                            const f2 q = pk_fma(pk_fma(splat(cC), dy, -bdx), dy, f);
+                            f2 al = {gs_exp2(-q.x), gs_exp2(-q.y)};
+                            // T (1 - alpha) as the full loop's code computes it.  That code is compiled with contraction, and
+                            // what the compiler makes of `T - al * T` there is pinned here by builtins, instruction for
+                            // instruction -- operand roles included, which decide the sign of a NaN: the first Gaussian of a
+                            // group of four takes fma(-T, al, T); for the three others T is the product t' m of the step
+                            // before (m = 0 or 1: exact) and the step is fma(t', m, -w) with the ROUNDED w = T al.
+                            const f2 Tn = u == 0 ? T[0] : tp * mk;
+                            if constexpr (LEGACY) {
+                                al.x = Tn.x == 0.f ? 0.f : al.x;
+                                al.y = Tn.y == 0.f ? 0.f : al.y;
+                            }
+                            const f2 w = Tn * al;
+                            // (the factors' places are the full loop's too: t' m for the second Gaussian, m t' for the last two)
+                            const f2 t = u == 0 ? pk_fma(-Tn, al, Tn) : u == 1 ? pk_fma(tp, mk, -w) : pk_fma(mk, tp, -w);
+                            cr[0] = pk_fma(splat(at(R4, u)), w, cr[0]);
+                            cg[0] = pk_fma(splat(at(G4, u)), w, cg[0]);
+                            cb[0] = pk_fma(splat(at(L4, u)), w, cb[0]);
+                            tp = t;
+                            mk = live_mask(t, live_scale, live_bias);
+                        }
+                        T[0] = tp * mk;
+                    }
+                }
+            }
+        }
         return stop;
         };
+        if constexpr (COMPACT) seen_legacy = seen_legacy || chunk_legacy;
         steps = base + (chunk_legacy ? composite_chunk(std::true_type{}) : composite_chunk(std::false_type{}));
         // a chunk whose checkpoint was written counts as processed even if the wave stopped inside it:
         // the backward pass masks finished pixels by their transmittance
@@ -511,7 +745,7 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
     if (!staged_next) fetch(nstart, nn, 0);  // empty tile, or the wave stopped before its last chunk
     if (FRAME && !CKPT && cut_out) {  // (uniform; inference frames only: the training variant sits at its 128-VGPR budget)
         // all pixels stopped inside the list (or exactly at its end): nothing behind the last composited Gaussian matters
-        const bool sat = !continues && steps > 0 && (done || !any_live());
+        const bool sat = !continues && steps > 0 && (done || !((COMPACT && compacted) ? compact_live(seen_legacy) : any_live()));
         if (lane == 0) {
             uint32_t c = GS_NO_CUT, dlast = GS_NO_CUT;
             if (sat) {
@@ -525,7 +759,9 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
             // The list ascends in depth, so the last composited pair decides.  (cut_in may be cut_out: read before the store)
             if (cut_in) {
                 const uint32_t ci = cut_in[tile];
-                if (ci != GS_NO_CUT && dlast > ci) *ranpast = 1ull;  // (!sat: dlast = GS_NO_CUT, the largest value there is)
+                unsigned long long one = 1ull;
+                if constexpr (COMPACT) asm volatile("" : "+v"(one));  // (as above: not a constant kept in two registers)
+                if (ci != GS_NO_CUT && dlast > ci) *ranpast = one;  // (!sat: dlast = GS_NO_CUT, the largest value there is)
             }
             cut_out[tile] = c;
         }
@@ -540,16 +776,24 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
         if (steps > (uint32_t)GS_LONGEST_MIN) atomicMax(ranpast + (GS_CNT_MAXWALK - GS_CNT_RANPAST), (unsigned long long)steps);
     }
     if (FRAME && cont_flag && lane == 0) cont_flag[tile] = continues ? 1u : 0u;
+    if constexpr (COMPACT) {  // the step at which the tile compacted (gs_frame_debug_tile_compact)
+        if (lane == 0) tile_compact[tile] = compact_at;  // (never null for this instantiation: gs_stage_raster_forward)
+    }
 
+    if (COMPACT && compacted) {  // (uniform) each lane's up to two pixels, by their index in the tile
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const uint32_t p = (cidx() >> (16 * e)) & 0xffffu;
+            if (p != 0xffffu)
+                write_pixel(tx * 16 + (p & 15u), ty * 16 + ((p >> 4) & 3u) + 4 * (p >> 6), e ? cr[0].y : cr[0].x,
+                            e ? cg[0].y : cg[0].x, e ? cb[0].y : cb[0].x, 1.0f);
+        }
+    } else {
 #pragma unroll
     for (int h = 0; h < NPP; ++h)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const uint32_t id_y = id_y0 + 8 * h + 4 * e;
-            float aw = e ? accw[h].y : accw[h].x;
-            if (!WN || aw < 0.01f) aw = 1.0f;  // gaussian.cu:964-969
-            const float o0 = (e ? cr[h].y : cr[h].x) / aw, o1 = (e ? cg[h].y : cg[h].x) / aw,
-                        o2 = (e ? cb[h].y : cb[h].x) / aw;
             if constexpr (AUX) {
                 const float dv = e ? cd[h].y : cd[h].x, av = e ? ca[h].y : ca[h].x;
                 if (X.padded) X.padded[(size_t)id_y * G.padW + id_x] = make_float2(dv, av);
@@ -559,23 +803,10 @@ __device__ __forceinline__ void raster_forward_body(RasterSrc S, RasterGeom G,
                     if (X.alpha) X.alpha[(size_t)oy * G.width + ox] = av;
                 }
             }
-            if (out_padded) {
-                float *o = out_padded + ((size_t)id_y * G.padW + id_x) * 3;
-                o[0] = o0;
-                o[1] = o1;
-                o[2] = o2;
-            }
-            if (out_image) {  // clamp + centred crop (splatter.py:652-653, 267-272)
-                const int ox = (int)id_x - G.crop_left, oy = (int)id_y - G.crop_top;
-                if (ox >= 0 && ox < G.width && oy >= 0 && oy < G.height) {
-                    float *o = out_image + ((size_t)oy * G.width + ox) * 3;
-                    // torch.clamp semantics: NaN stays NaN (fminf / fmaxf would turn it into 0)
-                    o[0] = o0 > 1.f ? 1.f : (o0 < 0.f ? 0.f : o0);
-                    o[1] = o1 > 1.f ? 1.f : (o1 < 0.f ? 0.f : o1);
-                    o[2] = o2 > 1.f ? 1.f : (o2 < 0.f ? 0.f : o2);
-                }
-            }
+            write_pixel(id_x, id_y, e ? cr[h].y : cr[h].x, e ? cg[h].y : cg[h].x, e ? cb[h].y : cb[h].x,
+                        e ? accw[h].y : accw[h].x);
         }
+    }
     }  // tile loop
 }
 
@@ -588,10 +819,14 @@ raster_forward_kernel(RasterSrc S, RasterGeom G, const int32_t *__restrict__ ran
                       uint32_t n_tiles, float4 *__restrict__ cont_state, uint32_t *__restrict__ cont_flag,
                       const uint32_t *__restrict__ tile_order, uint32_t *__restrict__ tile_cost, const uint32_t *cut_in,
                       uint32_t *cut_out, unsigned long long *__restrict__ ranpast,
-                      const unsigned long long *__restrict__ gate) {
-    raster_forward_body<CDIM, FRAME, CKPT, SIG, WN, EXACT, false>(S, G, ranges, out_padded, out_image, ckpt, tile_nproc,
-                                                                  n_tiles, cont_state, cont_flag, tile_order, tile_cost,
-                                                                  cut_in, cut_out, ranpast, gate, AuxFwdOut{});
+                      const unsigned long long *__restrict__ gate, uint32_t compact_min,
+                      uint32_t *__restrict__ tile_compact) {
+    // the compact phase: the rgb inference frame only (compact_min = 0 switches it off: GS_FWD_COMPACT=0)
+    constexpr bool COMPACT = CDIM == 3 && FRAME && !CKPT && !SIG && !WN && !EXACT;
+    raster_forward_body<CDIM, FRAME, CKPT, SIG, WN, EXACT, false, COMPACT>(S, G, ranges, out_padded, out_image, ckpt,
+                                                                           tile_nproc, n_tiles, cont_state, cont_flag,
+                                                                           tile_order, tile_cost, cut_in, cut_out, ranpast,
+                                                                           gate, AuxFwdOut{}, compact_min, tile_compact);
 }
 
 // GS_FRAME_AUX frames (frame path only): the compositing with the depth and alpha maps.  No segmented compositing of long
@@ -951,7 +1186,7 @@ void launch_fwd(const RasterSrc &S, const RasterGeom &G, const int32_t *ranges, 
                 float4 *ckpt, uint32_t *tile_nproc, int wn, hipStream_t stream, float4 *cont_state = nullptr,
                 uint32_t *cont_flag = nullptr, const uint32_t *tile_order = nullptr, uint32_t *tile_cost = nullptr,
                 const uint32_t *cut_in = nullptr, uint32_t *cut_out = nullptr, unsigned long long *ranpast = nullptr,
-                const unsigned long long *gate = nullptr) {
+                const unsigned long long *gate = nullptr, uint32_t compact_min = 0, uint32_t *tile_compact = nullptr) {
     if (!fwd_plan().order) tile_order = nullptr;
     const uint32_t T = (uint32_t)(G.ntx * G.nty);
     // the gated second pass of a culled frame almost never runs: a small persistent grid (every wave walks several tiles)
@@ -960,11 +1195,11 @@ void launch_fwd(const RasterSrc &S, const RasterGeom &G, const int32_t *ranges, 
     if (wn)
         hipLaunchKernelGGL((raster_forward_kernel<CDIM, FRAME, CKPT, SIG, true, EXACT>), dim3(grid), dim3(FWD_THREADS),
                            0, stream, S, G, ranges, out_padded, out_image, ckpt, tile_nproc, T, cont_state, cont_flag,
-                           tile_order, tile_cost, cut_in, cut_out, ranpast, gate);
+                           tile_order, tile_cost, cut_in, cut_out, ranpast, gate, compact_min, tile_compact);
     else
         hipLaunchKernelGGL((raster_forward_kernel<CDIM, FRAME, CKPT, SIG, false, EXACT>), dim3(grid), dim3(FWD_THREADS),
                            0, stream, S, G, ranges, out_padded, out_image, ckpt, tile_nproc, T, cont_state, cont_flag,
-                           tile_order, tile_cost, cut_in, cut_out, ranpast, gate);
+                           tile_order, tile_cost, cut_in, cut_out, ranpast, gate, compact_min, tile_compact);
 }
 
 }  // namespace
@@ -1083,6 +1318,12 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
     const uint32_t *cut_in = culled && !second_pass ? gs_frame_cut_table(f, ws) : nullptr;
     unsigned long long *ranpast = ws.counters + GS_CNT_RANPAST;
     const unsigned long long *gate = second_pass ? ranpast : nullptr;
+    // GS_FWD_COMPACT, read per frame: 0 keeps every tile in the full layout to its end (the compact phase of the rgb
+    // inference kernel switched off); both settings render the same bits
+    uint32_t compact_min = GS_FWD_COMPACT_MIN;
+    if (const char *e = getenv("GS_FWD_COMPACT")) {
+        if (e[0] == '0' && e[1] == 0) compact_min = 0;
+    }
     if (aux) {
         if (!fwd_plan().order) order = nullptr;
         const uint32_t T = (uint32_t)FG.n_tiles;
@@ -1108,7 +1349,8 @@ int gs_stage_raster_forward(const gs_frame *f, const gs_frame_ws &ws, const uint
                                                   stream, cs, cf, order, cost, nullptr, nullptr, ranpast, nullptr);
             else
                 launch_fwd<CD, true, false, false>(S, G, ws.tile_ranges, f->image_padded, f->image, nullptr, nullptr, 0, stream,
-                                                   cs, cf, order, cost, cut_in, ws.cut, ranpast, gate);
+                                                   cs, cf, order, cost, cut_in, ws.cut, ranpast, gate, dense ? 0u : compact_min,
+                                                   ws.tile_compact);
         });
     }
     GS_CHECK_LAUNCH();

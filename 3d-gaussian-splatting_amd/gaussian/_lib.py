@@ -139,6 +139,8 @@ gs_frame_cull_fallback_async = _sig("gs_frame_cull_fallback_async", ci, C.POINTE
 gs_frame_is_occlusion_culled = _sig("gs_frame_is_occlusion_culled", ci, C.POINTER(GsFrame), C.POINTER(C.c_int32))
 gs_frame_cull_second_pass = _sig("gs_frame_cull_second_pass", ci, C.POINTER(GsFrame), C.POINTER(C.c_int32))
 gs_frame_debug_cut_table = _sig("gs_frame_debug_cut_table", ci, C.POINTER(GsFrame), C.POINTER(vp), C.POINTER(C.c_int32))
+gs_frame_debug_tile_compact = _sig("gs_frame_debug_tile_compact", ci, C.POINTER(GsFrame), C.POINTER(vp), C.POINTER(C.c_int32))
+gs_frame_debug_tile_cost = _sig("gs_frame_debug_tile_cost", ci, C.POINTER(GsFrame), C.POINTER(vp), C.POINTER(C.c_int32))
 GS_STATS_TAGGED_N = 15
 gs_frame_debug_views = _sig("gs_frame_debug_views", ci, C.POINTER(GsFrame), C.POINTER(vp), C.POINTER(vp),
                             C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp))
@@ -364,7 +366,7 @@ EXPORTS = [
     "gs_gather_gaussians", "gs_draw", "gs_draw_backward_workspace_bytes", "gs_draw_backward",
     "gs_sort_pairs_tmp_bytes", "gs_sort_pairs", "gs_sort_pairs_bits", "gs_frame_workspace_bytes",
     "gs_frame_aux_workspace_bytes", "gs_frame_pose_workspace_bytes", "gs_frame_forward",
-    "gs_frame_stats_async", "gs_frame_longest_list_async", "gs_frame_stats_tagged_async", "gs_frame_cull_fallback_async", "gs_frame_is_occlusion_culled", "gs_frame_cull_second_pass", "gs_frame_debug_cut_table", "gs_frame_debug_views", "gs_frame_debug_rects", "gs_frame_debug_cull_stage", "gs_frame_binning_variant", "gs_frame_debug_tile_nproc", "gs_frame_debug_bwd_exec_rows", "gs_frame_backward", "gs_frame_backward_adam", "gs_frame_forward_profile",
+    "gs_frame_stats_async", "gs_frame_longest_list_async", "gs_frame_stats_tagged_async", "gs_frame_cull_fallback_async", "gs_frame_is_occlusion_culled", "gs_frame_cull_second_pass", "gs_frame_debug_cut_table", "gs_frame_debug_tile_compact", "gs_frame_debug_tile_cost", "gs_frame_debug_views", "gs_frame_debug_rects", "gs_frame_debug_cull_stage", "gs_frame_binning_variant", "gs_frame_debug_tile_nproc", "gs_frame_debug_bwd_exec_rows", "gs_frame_backward", "gs_frame_backward_adam", "gs_frame_forward_profile",
     "gs_frame_backward_part", "gs_frame_async_create", "gs_frame_async_wait", "gs_frame_async_destroy",
     "gs_frame_backward_slice", "gs_frame_project_slices", "gs_frame_forward_project", "gs_frame_forward_rest",
     "gs_adam_step_multi",

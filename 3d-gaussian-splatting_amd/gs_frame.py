@@ -1180,13 +1180,28 @@ class FrameRenderer:
     def cut_table(self) -> torch.Tensor:
         """[T] int32 view of the workspace: the per-tile occlusion cuts the last inference forward left behind (depth bits; -1
         = no cut), what the next GS_FRAME_OCCLUSION_CULL frame trims by.  A test aid; no host synchronisation."""
+        return self._tile_words("gs_frame_debug_cut_table")
+
+    def _tile_words(self, entry: str) -> torch.Tensor:
+        """[T] int32 view of one per-tile word of the workspace, as the library's debug entry point `entry` locates it."""
         f = self._frame
         if f is None:
             raise RuntimeError("no frame rendered yet")
         ptr, n = C.c_void_p(), C.c_int32()
-        _lib.call("gs_frame_debug_cut_table", C.byref(f), C.byref(ptr), C.byref(n))
+        _lib.call(entry, C.byref(f), C.byref(ptr), C.byref(n))
         off = ptr.value - self._ws.data_ptr()
         return self._ws[off:off + 4 * n.value].view(torch.int32)
+
+    def tile_compact_steps(self) -> torch.Tensor:
+        """[T] int32 view of the workspace: per tile of the last rgb inference forward, the number of Gaussians it had
+        composited when its wave compacted the live pixels (raster_fwd.hip), -1 for a tile that never did.  A test and
+        measurement aid; no host synchronisation."""
+        return self._tile_words("gs_frame_debug_tile_compact")
+
+    def tile_cost(self) -> torch.Tensor:
+        """[T] int32 view of the workspace: the Gaussians every tile composited before its wave stopped in the last forward
+        (frames of the strip variant only).  A test and measurement aid; no host synchronisation."""
+        return self._tile_words("gs_frame_debug_tile_cost")
 
     def _rects(self, allow_culled: bool = False) -> torch.Tensor:
         """[N,4] int32 view of the workspace: (y0 | y1 << 16, x0 | x1 << 16, depth bits, tiles touched) per Gaussian.

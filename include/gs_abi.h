@@ -34,7 +34,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_CULL_REPEAT (an
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_debug_tile_compact and
+ *   gs_frame_debug_tile_cost (read-only views of two per-tile words of the last forward, for tests and measurements: the step
+ *   at which a tile's compositing wave compacted its live pixels, and the steps it composited); the workspace of a frame grows
+ *   by one word per tile (gs_frame_workspace_bytes).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): GS_FRAME_CULL_REPEAT (an
  *   occlusion-culled frame that repeats the previous one is issued without the five gated launches of its second pass) and
  *   gs_frame_cull_second_pass (does a forward of this descriptor enqueue them: host-side, no launch);
  *   gs_frame_debug_cut_table (a read-only view of the per-tile cuts, for tests).
@@ -695,6 +699,18 @@ int gs_frame_debug_rects(const gs_frame *f, const uint32_t **rects);
  * for a tile without a cut.  A read-only view, for tests: a GS_FRAME_CULL_REPEAT frame that kept its promise leaves the
  * table it read.  GS_E_INVALID for a training frame (training forwards do not write the table). */
 int gs_frame_debug_cut_table(const gs_frame *f, const uint32_t **cut, int32_t *n_tiles);
+
+/* The compact phase of the rgb inference compositing kernel (raster_fwd.hip), per tile of the last forward of this workspace
+ * (uint32 [*n_tiles], row-major over the tile grid): the number of Gaussians of its list the tile had composited when its wave
+ * handed the live pixels over to the two-pixels-per-lane layout, 0xffffffff for a tile that never did (always, with
+ * GS_FWD_COMPACT=0 in the environment, and in a GS_FRAME_LONG_LISTS frame).  A read-only view, for tests and measurements.
+ * GS_E_INVALID unless the frame is an rgb inference frame without GS_FRAME_AUX (no other kernel writes the word). */
+int gs_frame_debug_tile_compact(const gs_frame *f, const uint32_t **at, int32_t *n_tiles);
+
+/* The Gaussians every tile composited before its wave stopped in the last forward of this workspace (uint32 [*n_tiles]): the
+ * cost that orders the next forward's tiles.  Recorded by frames of the strip variant only (gs_frame_binning_variant == 4):
+ * GS_E_INVALID for the others.  A read-only view, for tests and measurements. */
+int gs_frame_debug_tile_cost(const gs_frame *f, const uint32_t **cost, int32_t *n_tiles);
 
 /* Where the FIRST PASS of an occlusion-culled frame (gs_frame_is_occlusion_culled) stages its level-1 entries, for tests of
  * that path: slice s of the Gaussian array owns slots [s x *cap, (s + 1) x *cap) of *entries (8 bytes each) and *tags

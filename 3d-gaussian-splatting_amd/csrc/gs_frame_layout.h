@@ -52,7 +52,7 @@ static inline gs_bin_plan gs_bin_plan_for(int64_t N, int64_t max_pairs, int n_ti
 #define GS_STRIP_ID_BITS 26   // an entry keeps the Gaussian index in 26 bits: scenes beyond 2^26 take the table variant
 #define GS_STRIP_MAX 8192     // strips per frame the LDS histograms are sized for
 // Frames with long tile lists launch the extra kernels for them: the big-list sort (tile_sort.hip) and the segmented
-// compositing of tiles that are still alive after GS_LONG_MIN Gaussians (raster_fwd.hip); other frames save those
+// compositing of tiles that are still alive after GS_LONG_MIN Gaussians (raster_fwd_segment.hip); other frames save those
 // launches (~25 us of idle grids at 1080p).  The caller asks for them with GS_FRAME_LONG_LISTS, normally once the
 // longest-list statistic of an earlier frame (gs_frame_longest_list_async) exceeded the LDS window; a frame WITHOUT the
 // flag is still correct whatever its lists are (strip_sort_kernel sorts a long list itself, the tile's own wave
@@ -352,9 +352,9 @@ struct gs_frame_ws {
     uint32_t *tile_cost;           // [T] Gaussian steps every tile composited in the LAST forward of this workspace
     uint32_t *tile_order;          // [T] tiles in descending order of that cost: the dispatch order of this forward
     uint32_t *tile_compact;        // [T] rgb inference frames: the step at which a tile's wave compacted its live pixels in the
-                                   // LAST forward (raster_fwd.hip), 0xffffffff if it never did.  Diagnostic.
+                                   // LAST forward (raster_fwd_body.h), 0xffffffff if it never did.  Diagnostic.
     uint4 *group_queue;            // dense frames: (tile, first slot, keys, -) of the groups big_list_sort_kernel cut
-    // dense frames only (else NULL): segmented compositing of long tile lists (raster_fwd.hip)
+    // dense frames only (else NULL): segmented compositing of long tile lists (raster_fwd_segment.hip)
     float4 *cont_state;            // [T][256] (T, C) of a tile's pixels after its first GS_LONG_MIN Gaussians
     uint32_t *cont_flag;           // [T] 1: the tile was still alive there and continues in segments
     uint32_t *seg_item_base;       // [T + 1] first segment item of every tile

@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(64 * BwdCfg<CDIM>::WPB) raster_backward_kernel
     if (gvalid) raster_conic(g, cA, cB, cC);
     float opa = gvalid ? g.opa : 0.f;  // opacity 0 => alpha 0 => state passes through unchanged
     const float p0 = 1.5707963268f * rsqrtf(raster_det(g.a, g.b, g.c, g.d) + 1e-7f);
-    opa *= p0;  // the same folding as the forward kernel (raster_fwd.hip)
+    opa *= p0;  // the same folding as the forward kernel (raster_fwd_body.h)
     write_segment(0, 0);
 
     // gradient accumulators

@@ -63,12 +63,12 @@ static inline void gs_frame_raster_args(const gs_frame *f, const gs_frame_ws &ws
         G.vdy[i] = f->vec_dy[i];
     }
 }
-// The (S, G) of a reference-API call (gs_draw / gs_draw_backward, raster_fwd.hip): attributes in sorted order, whole tiles,
+// The (S, G) of a reference-API call (gs_draw / gs_draw_backward, raster_fwd_ref.hip): attributes in sorted order, whole tiles,
 // and with SH colours the ray basis.  Nonzero: refused (SH without the basis), the error set under the name `entry`.
 int gs_ref_raster_args(const char *entry, const float *pos, const float *rgb, const float *opa, const float *cov, int32_t h,
                        int32_t w, float focal_x, float focal_y, int use_sh_coeff, const float *rays_o,
                        const float *lefttop_pos, const float *vec_dx, const float *vec_dy, RasterSrc &S, RasterGeom &G);
-// The reference API's forward (raster_fwd.hip); gs_draw_backward replays it for the checkpoints (`ckpt` != NULL).  `exact`:
+// The reference API's forward (raster_fwd_ref.hip); gs_draw_backward replays it for the checkpoints (`ckpt` != NULL).  `exact`:
 // the reference's `fast = 0` flavour of the exponential (double division + double exp per pixel, gaussian.cu:922-923).
 int gs_raster_forward_ref(const RasterSrc &S, const RasterGeom &G, const int32_t *accum, float *res, int use_sh,
                           int sigmoid, int weight_normalize, float4 *ckpt, uint32_t *tile_nproc,

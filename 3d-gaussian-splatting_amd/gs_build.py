@@ -33,6 +33,8 @@ SOURCES = {
     "strip_bin.hip": [],
     # no SLP packing: v_pk_*_f32 has no rate advantage on gfx950 and costs extra v_mov shuffles
     "raster_fwd.hip": ["-fno-slp-vectorize"],
+    "raster_fwd_ref.hip": ["-fno-slp-vectorize"],  # the same kernel (raster_fwd_body.h), built the same way
+    "raster_fwd_segment.hip": ["-fno-slp-vectorize"],  # its steps restated for the segments of a long list, as above
     "raster_bwd.hip": ["-fno-slp-vectorize"],
     "raster_bwd_systolic.hip": ["-fno-slp-vectorize"],
     "raster_bwd_pixel.hip": ["-fno-slp-vectorize"],
@@ -71,6 +73,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=h
           "-Wno-unused-function", "-munsafe-fp-atomics",
           *os.environ.get("GS_EXTRA_HIPCC_FLAGS", "").split()]  # experiments only (-D switches)
 HEADERS = ["gs_common.h", "gs_frame_layout.h", "project_common.h", "raster_common.h", "raster_bwd_common.h", "strip_common.h", "tile_bin_common.h",
+           "raster_fwd_common.h", "raster_fwd_body.h",
            "frame_project_backward_body.inc", "aux_depth_backward_body.inc", "aux_depth_term.inc", "overlap_point.h",
            "seed_apply_body.inc", "overlap_count_body.inc", "map_terms.h", "icp_point.h", "loss_fused_body.inc",
            os.path.join("..", "..", "include", "gs_abi.h")]

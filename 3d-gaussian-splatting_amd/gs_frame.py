@@ -1194,7 +1194,7 @@ class FrameRenderer:
 
     def tile_compact_steps(self) -> torch.Tensor:
         """[T] int32 view of the workspace: per tile of the last rgb inference forward, the number of Gaussians it had
-        composited when its wave compacted the live pixels (raster_fwd.hip), -1 for a tile that never did.  A test and
+        composited when its wave compacted the live pixels (raster_fwd_body.h), -1 for a tile that never did.  A test and
         measurement aid; no host synchronisation."""
         return self._tile_words("gs_frame_debug_tile_compact")
 

@@ -252,7 +252,7 @@ int gs_sort_pairs_bits(uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32
 
 #define GS_FRAME_SERIAL_LONG_LISTS 8 /* dense frames (capacity above 1024 pairs per tile on average) cut the rest of a tile's
                                        list into segments composited by many waves when its pixels are still alive after
-                                       4096 Gaussians (raster_fwd.hip); this flag keeps the one-wave-per-tile walk for
+                                       4096 Gaussians (raster_fwd_segment.hip); this flag keeps the one-wave-per-tile walk for
                                        such tiles (A/B and equivalence tests).  Same result up to the rounding of the
                                        transmittance entering a segment. */
 
@@ -700,7 +700,7 @@ int gs_frame_debug_rects(const gs_frame *f, const uint32_t **rects);
  * table it read.  GS_E_INVALID for a training frame (training forwards do not write the table). */
 int gs_frame_debug_cut_table(const gs_frame *f, const uint32_t **cut, int32_t *n_tiles);
 
-/* The compact phase of the rgb inference compositing kernel (raster_fwd.hip), per tile of the last forward of this workspace
+/* The compact phase of the rgb inference compositing kernel (raster_fwd_body.h), per tile of the last forward of this workspace
  * (uint32 [*n_tiles], row-major over the tile grid): the number of Gaussians of its list the tile had composited when its wave
  * handed the live pixels over to the two-pixels-per-lane layout, 0xffffffff for a tile that never did (always, with
  * GS_FWD_COMPACT=0 in the environment, and in a GS_FRAME_LONG_LISTS frame).  A read-only view, for tests and measurements.

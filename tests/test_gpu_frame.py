@@ -566,7 +566,7 @@ def test_long_lists_composited_in_segments(gpu, use_sh):
     """Dense frame with low-opacity pile-ups: every tile's pixels are still alive after 4096 Gaussians, so the rest
     of each list (up to ~12,000 here; beyond the first GS_LONG_MIN = 512 since round 5) is composited in segments of
     GS_SEG_LEN = 512 by separate waves (transmittance products ->
-    incoming transmittance -> per-segment colours -> combine; raster_fwd.hip).  Against the one-wave-per-tile walk of
+    incoming transmittance -> per-segment colours -> combine; raster_fwd_segment.hip).  Against the one-wave-per-tile walk of
     the same build (GS_FRAME_SERIAL_LONG_LISTS): image, processed counts and all five parameter gradients must agree to
     the rounding of the transmittance that enters a segment; against the oracle: the list exactly, the image to 1e-3
     (a chain of 10,000 layers is conditioned like that in fp32 whoever walks it)."""

@@ -1,4 +1,4 @@
-"""GPU tier of the compact phase of the rgb inference compositing kernel (raster_fwd.hip, raster_forward_kernel<3, true,
+"""GPU tier of the compact phase of the rgb inference compositing kernel (raster_fwd_body.h, raster_forward_kernel<3, true,
 false, ...>): once at most 128 of a tile's 256 pixels are alive, the wave writes the stopped ones out, hands the live ones
 over through LDS and composites two pixels per lane instead of four.
 

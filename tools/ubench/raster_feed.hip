@@ -2,7 +2,7 @@
 // (4 pixels per lane, packed over pixel pairs); the per-Gaussian operands (x, y, A, B, C, opacity,
 // r, g, b -- identical for every lane of the wave) come from
 //   MODE 0: registers (no memory at all; lower bound),
-//   MODE 1: LDS, nine broadcast ds_read_b128 per group of four Gaussians (what raster_fwd.hip does),
+//   MODE 1: LDS, nine broadcast ds_read_b128 per group of four Gaussians (what raster_fwd_body.h does),
 //   MODE 2: SGPRs, one s_load_dwordx16 per Gaussian through the scalar cache, gathered by a sorted id
 //           list (scalar loads, prefetched one group ahead),
 //   MODE 3: as 2 but reading records sequentially (no id indirection).

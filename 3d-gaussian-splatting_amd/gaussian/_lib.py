@@ -359,6 +359,24 @@ gs_pose_log_bytes = _sig("gs_pose_log_bytes", sz, i32, i32)
 gs_pose_reset = _sig("gs_pose_reset", ci, vp, vp, vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp)
 gs_pose_step = _sig("gs_pose_step", ci, vp, vp, vp, vp, C.POINTER(GsPoseStepOpts), vp, vp, vp, i32, i32, vp)
 
+
+class GsExposureState(C.Structure):
+    """Mirror of ``struct gs_exposure_state`` (it lives in device memory)."""
+
+    _fields_ = [("m", C.c_double * 6), ("v", C.c_double * 6), ("steps", C.c_double)]
+
+
+class GsExposureAdam(C.Structure):
+    """Mirror of ``struct gs_exposure_adam``."""
+
+    _fields_ = [("state", vp), ("lr_gain", C.c_double), ("lr_bias", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("lr_scale", C.c_double), ("skip_if_nonzero", vp)]
+
+
+gs_exposure_workspace_bytes = _sig("gs_exposure_workspace_bytes", sz, i32, i32)
+gs_exposure_apply = _sig("gs_exposure_apply", ci, vp, vp, i32, i32, vp, vp)
+gs_exposure_backward = _sig("gs_exposure_backward", ci, vp, vp, vp, i32, i32, vp, C.POINTER(GsExposureAdam), vp, sz, vp)
+
 # Every symbol include/gs_abi.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTS = [
     "gs_last_error", "gs_abi_version", "gs_culling", "gs_world2camera", "gs_world2camera_backward",
@@ -387,6 +405,7 @@ EXPORTS = [
     "gs_icp_model_bytes", "gs_icp_workspace_bytes", "gs_icp_log_bytes", "gs_icp_model_maps", "gs_icp_reset", "gs_icp_step",
     "gs_view_redundancy_workspace_bytes", "gs_view_redundancy", "gs_view_redundancy_pp",
     "gs_pose_log_bytes", "gs_pose_reset", "gs_pose_step",
+    "gs_exposure_workspace_bytes", "gs_exposure_apply", "gs_exposure_backward",
 ]
 
 

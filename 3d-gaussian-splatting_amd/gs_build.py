@@ -68,6 +68,10 @@ SOURCES = {
     # Adam on the pose's six tangent numbers in double, every product rounded before it is added: the Python restatement
     # (tests/pose_step_ref.py) follows it operation by operation
     "pose_step.hip": ["-ffp-contract=off"],
+    # I' = fl(fl(gain I) + bias) and g = fl(gain g') as written, the Adam step in double with every product rounded before
+    # it is added: the restatement (tests/exposure_ref.py) gives the maps bit for bit and follows the step operation by
+    # operation
+    "exposure.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall",
           "-Wno-unused-function", "-munsafe-fp-atomics",

@@ -329,6 +329,15 @@ class SlamOptions:
     # the default and nothing more; what the option did on the eight-frame arc is in profiles/contrib_prune.txt.
     prune_unseen_every: int = 0
     prune_unseen_w_min: float = 1.0 / 255.0
+    # Per-view exposure.  Tracking it arrives through ``track.fit_exposure``: a keyframe is then added to the trainer with its
+    # tracked exposure, held fixed; keyframe 0 is the gauge -- the identity, no exposure object, never freed.  With
+    # ``refine_exposure`` (off: the loop issues exactly the calls it issues without the option) the mapping steps of a keyframe
+    # also step the exposures of its window (Trainer.free_exposure, on the device), every view but keyframe 0 -- the mirror
+    # of ``refine_poses``.  The rates are TrackOptions' 3e-2 x 0.1, held constant, by the reasoning of ``pose_lr_rot``; no
+    # evidence beyond the two-frame arc of tests/test_gpu_track_exposure.py (profiles/exposure.txt).
+    refine_exposure: bool = False
+    exposure_lr_gain: float = 3e-3
+    exposure_lr_bias: float = 3e-3
     # Eviction of keyframes (0, the default: none -- no redundancy count is issued, the set grows to GS_OVERLAP_MAX_VIEWS and
     # the next keyframe raises, the loop issues exactly the calls it issues without the option).  3 .. 256: the most keyframes
     # held.  When a frame becomes a keyframe and the set holds that many, one keyframe goes first: for every keyframe the share
@@ -377,6 +386,9 @@ class SlamFrame:
     # `window` holds positions AFTER that removal, `overlap` the counts as computed BEFORE it; seconds["evict"] its wall time
     evicted: Optional[int] = None
     window_ids: List[int] = field(default_factory=list)  # the stable ids of `window`
+    # track.fit_exposure / refine_exposure: the frame's (gain [3], bias [3]) float64 -- as tracked, then as its mapping steps
+    # left it; None with both off and for the first frame (the gauge: the identity)
+    exposure: Optional[Tuple[np.ndarray, np.ndarray]] = None
     # SlamOptions.gate_map, a gated keyframe: (range pixels removed, pixels with colour weight 0); None otherwise
     gated: Optional[Tuple[int, int]] = None
     icp: Optional[IcpResult] = None  # SlamOptions.icp: the depth alignment in front of this frame's tracking, accepted or not
@@ -392,6 +404,7 @@ class Slam:
 
     def __init__(self, camera, options: Optional[SlamOptions] = None, device="cuda"):
         self.opt = options if options is not None else SlamOptions()
+        self.opt.track.fits_exposure()  # (refuses fit_exposure with device_pose before any device work)
         if self.opt.gate_map and not self.opt.track.gated():  # (before any device work)
             raise ValueError("SlamOptions.gate_map carries the tracker's median gate into seeding and mapping: it needs a gated "
                              "tracker (TrackOptions.depth_gate_k or color_gate_k above zero)")
@@ -414,6 +427,7 @@ class Slam:
         self.tracker: Optional[Tracker] = None
         self.aligner: Optional[IcpAligner] = None
         self.gate_mask: Optional[GateMask] = None
+        self._gate_exposure = None  # gate_map with track.fit_exposure: compensates the render the gate is taken on
         self._icp_renderer = None
         if self.opt.icp is not None or self.opt.gate_map:
             # an inference renderer of their own, shared: the tracker's workspace and counters stay untouched
@@ -436,6 +450,16 @@ class Slam:
     def _posed(self, rot, tran):
         return posed(self.camera, rot, tran)
 
+    def free_exposures(self, views: Sequence[int]):
+        """Frees the exposures of the keyframes at positions ``views`` for the mapping steps that follow
+        (``Trainer.free_exposure`` at ``exposure_lr_gain`` / ``exposure_lr_bias``).  Keyframe 0 is refused: it is the gauge --
+        the map's radiometry is its radiometry -- and with it free a common gain could drift between map and exposures."""
+        views = [int(v) for v in views]
+        if 0 in views:
+            raise ValueError("keyframe 0 fixes the radiometric gauge (the identity exposure): its exposure is never freed")
+        for v in views:
+            self.trainer.free_exposure(v, self.opt.exposure_lr_gain, self.opt.exposure_lr_bias)
+
     def map(self, frame: SlamFrame) -> SlamFrame:
         """The mapping steps of a keyframe that ``begin`` returned, round-robin over its window starting with the new view,
         then the tracker's (re)bind to the trainer's parameters.  A frame that is no keyframe has none: nothing happens."""
@@ -448,11 +472,20 @@ class Slam:
         before = {v: (tr.cameras[v].rot, tr.cameras[v].tran) for v in freed}
         for v in freed:
             tr.free_pose(v, o.pose_lr_rot, o.pose_lr_tran)
+        # refine_exposure: likewise, on the device
+        freed_ex = [v for v in frame.window if v != 0] if (o.refine_exposure and frame.pending > 0) else []
+        self.free_exposures(freed_ex)
         vals = []
         for s in range(frame.pending):
             vals.append(self.trainer.train_step(self.i_iter, frame.window[s % len(frame.window)]).clone())
             self.i_iter += 1
         frame.pending = 0
+        for v in freed_ex:
+            tr.fix_exposure(v)
+        if freed_ex and frame.window[0] in freed_ex:
+            frame.exposure = tr.exposure(frame.window[0])  # (one host read)
+            if frame.tracked is not None and self.tracker is not None and self.opt.track.fit_exposure:
+                self.tracker.set_last_exposure(*frame.exposure)  # the next frame's exposure fit starts from the refined one
         for v in freed:
             rot, tran = tr.pose(v)  # (float64; settles the last step's update)
             tr.fix_pose(v)
@@ -542,6 +575,7 @@ class Slam:
         frame = SlamFrame(rot=res.rot, tran=res.tran, tracked=res, overlap=counts,
                           keyframe=is_keyframe(int(counts[n - 1]), measured, frames_since, o.overlap_min, o.keyframe_every))
         frame.seconds.update(track=t1 - t0, overlap=t2 - t1)
+        frame.exposure = res.exposure  # (None without track.fit_exposure)
         if icp is not None:
             frame.icp = icp
             frame.seconds["icp"] = ti
@@ -578,13 +612,21 @@ class Slam:
             # trainer sees of this keyframe (clones: the GateMask's maps are rewritten by the next keyframe).  One host read.
             tg = time.perf_counter()
             rimg, _, rdepth, ralpha = self._icp_renderer.forward(*self.tracker.params, cam, training=False, aux=True)
-            g_range, g_weight = self.gate_mask(rimg.contiguous(), rdepth.contiguous(), ralpha.contiguous(), image, range_map)
+            rimg = rimg.contiguous()
+            if res.exposure is not None:  # the tracker's gate was taken on the compensated render: so is this one
+                if self._gate_exposure is None:
+                    from gs_exposure import Exposure
+
+                    self._gate_exposure = Exposure(self.gate_mask.H, self.gate_mask.W, self.device)
+                self._gate_exposure.set(*res.exposure)
+                rimg = self._gate_exposure.apply(rimg)
+            g_range, g_weight = self.gate_mask(rimg, rdepth.contiguous(), ralpha.contiguous(), image, range_map)
             map_range, map_weight = g_range.clone(), g_weight.clone()
             v = self.gate_mask.values.tolist()
             frame.gated = (int(v[2]), int(self.gate_mask.H * self.gate_mask.W - v[3]))
             frame.seconds["gate"] = time.perf_counter() - tg
         new = self.keyframes.add(cam, image, range_map)  # (the raw range: the overlap count reads what was measured)
-        added_as = self.trainer.add_view(cam, image, map_range, weight=map_weight)
+        added_as = self.trainer.add_view(cam, image, map_range, weight=map_weight, exposure=res.exposure)
         if added_as != new:
             raise RuntimeError(f"keyframe {new} became view {added_as} of the trainer: the two lists have diverged")
         self._last_keyframe_at = index

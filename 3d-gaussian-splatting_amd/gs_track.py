@@ -30,6 +30,13 @@ Coarse to fine: ``TrackOptions.pyramid`` = ((level, iterations), ...) walks pyra
 level l are gs_pyramid_down applied l times, its camera the frame's with size, focal lengths and principal point / 2^l), one
 renderer and one loss object per scheduled level, ONE PoseAdam for the whole call.  With the default () nothing of this exists
 and every call is the call described above.
+
+With ``TrackOptions.fit_exposure`` the frame's affine exposure (gs_exposure.Exposure: gain[3] and bias[3] in device memory) is
+fitted with the pose: forward -> gs_exposure_apply -> the loss on the compensated render, TrackLoss or GatedTrackLoss unchanged
+-> gs_exposure_backward (the colour gradient map scaled in place, the six gradients, one Adam step on the six numbers on the
+device at the iteration's decay) -> the pose backward as before.  One exposure fit per call, shared by the levels; the read
+grows by 24 bytes; ``TrackResult.exposure`` is the exposure the returned pose's iteration rendered with.  Refused with
+``device_pose``.  Off by default: the Tracker then issues the calls it always issued.
 """
 from __future__ import annotations
 
@@ -70,6 +77,13 @@ class TrackOptions:
     # the pose in device memory, stepped there by gs_pose_step: no host wait inside ``track``, one read at its end (implies
     # pose_only; the renderers do not grow by themselves: an overflowed call is run again, ``TrackResult.attempts``)
     device_pose: bool = False
+    # the frame's affine exposure (gs_exposure.Exposure: gain[3], bias[3]) fitted with the pose: the colour loss is taken on the
+    # compensated render and every iteration takes one Adam step on the six numbers on the device, at the iteration's decay
+    # and with ``betas`` / ``eps`` above; the iteration's read grows by 24 bytes.  Not with ``device_pose``.  The rates are
+    # those of the exposure-only fit of tests/test_gpu_track_exposure.py, the only evidence there is
+    fit_exposure: bool = False
+    lr_gain: float = 3e-2
+    lr_bias: float = 3e-2
     # coarse to fine: stages (pyramid level, iterations) in order, levels strictly decreasing; () (the default): no pyramid,
     # ``iterations`` full-resolution iterations.  With a schedule ``iterations`` is not read: the total is the stages' sum
     pyramid: Tuple[Tuple[int, int], ...] = ()
@@ -79,6 +93,13 @@ class TrackOptions:
     depth_gate_floor: float = 0.0
     color_gate_floor: float = 0.0
     gate_couple: bool = True        # a pixel that fails the depth gate loses its colour term too
+
+    def fits_exposure(self) -> bool:
+        """Whether the exposure is fitted; refuses the option together with ``device_pose``."""
+        if self.fit_exposure and self.device_pose:
+            raise ValueError("fit_exposure is not available with device_pose: gs_pose_step's log row has no room for the six "
+                             "numbers and the best-pose bookkeeping lives there; track with the pose on the host")
+        return bool(self.fit_exposure)
 
     def gated(self) -> bool:
         """Whether the median gate is on (-> GatedTrackLoss and the 20-float buffer); refuses the two depth gates together."""
@@ -120,6 +141,7 @@ class TrackResult:
     log = None           # TrackOptions.device_pose: float32 [iterations, 24 + n] -- per row the 12 pose floats the iteration
     #                      rendered, dL/drot [9], dL/dtran [3] and the loss's n values; else None
     attempts = 1         # runs of the call (TrackOptions.device_pose: one more per workspace growth; else always 1)
+    exposure = None      # TrackOptions.fit_exposure: (gain [3], bias [3]) float64 that (rot, tran)'s iteration rendered with
 
 
 def so3_exp(w) -> np.ndarray:
@@ -229,6 +251,7 @@ class Tracker:
         self.opt = options if options is not None else TrackOptions()
         if self.opt.device_pose and not self.opt.pose_only:  # (the only backward a device-pose frame has)
             self.opt = replace(self.opt, pose_only=True)
+        fit_exposure = self.opt.fits_exposure()  # (refused with device_pose before any device work)
         self._check_map(params)
         self.device = require_hip(device, "Tracker")
         self.camera = camera
@@ -238,11 +261,24 @@ class Tracker:
         self.device = self.renderer.device
         cls, args, nfloat = self.loss_plan(self.opt, self.H, self.W)
         # grad_rot [0:9], grad_tran [9:12], (loss, colour term, depth term, depth pixels) [12:16] and, with the median gate,
-        # (colour pixels, m_d, m_c, n_d) [16:20]: one read per iteration
-        self._dev = torch.zeros(nfloat, dtype=torch.float32, device=self.device)
+        # (colour pixels, m_d, m_c, n_d) [16:20]: one read per iteration.  fit_exposure: six floats more behind them, the
+        # exposure's own numbers (gs_exposure.Exposure adopts them: the read brings what the iteration's step left, which is
+        # what the next iteration renders with -- the first one's are known to the host)
+        self._nfloat = nfloat
+        self._dev = torch.zeros(nfloat + (6 if fit_exposure else 0), dtype=torch.float32, device=self.device)
         self._grad_pose = (self._dev[0:9].view(3, 3), self._dev[9:12])
         self._values = self._dev[12:nfloat]
-        self._host = torch.zeros(nfloat, dtype=torch.float32).pin_memory()
+        self._host = torch.zeros(self._dev.numel(), dtype=torch.float32).pin_memory()
+        # per level an Exposure with buffers of its own, all on the same six numbers and the same Adam state; None: option off
+        self._exposures = None
+        if fit_exposure:
+            from gs_exposure import Exposure
+
+            sizes = [(0, self.H, self.W)] if plan is None else plan
+            first = Exposure(sizes[0][1], sizes[0][2], self.device, numbers=self._dev[nfloat:nfloat + 6])
+            self._exposures = {sizes[0][0]: first}
+            for level, h, w in sizes[1:]:
+                self._exposures[level] = first.sibling(h, w)
         if plan is None:  # no schedule: one renderer, one loss, no Pyramid
             self.loss = cls(*args, self.device)
             self._stages = self._levels = self._pyramid = None
@@ -314,6 +350,7 @@ class Tracker:
     def reset(self):
         """Forget the motion history: the next ``track`` without ``init`` starts from the constructor camera's pose."""
         self._history: List[Tuple[np.ndarray, np.ndarray]] = []
+        self._last_exposure = None  # fit_exposure: the six float32 numbers of the last tracked frame
 
     def set_last_pose(self, rot, tran):
         """Replace the last tracked pose of the motion history (a mapper refined the pose of the frame just tracked): the
@@ -321,6 +358,15 @@ class Tracker:
         if not self._history:
             raise RuntimeError("set_last_pose() needs a tracked frame")
         self._history[-1] = pose64(rot, tran)
+
+    def set_last_exposure(self, gain, bias):
+        """Replace the last tracked frame's exposure (a mapper refined it): the exposure fit of the next ``track`` starts from
+        it.  ``TrackOptions.fit_exposure`` only."""
+        if self._exposures is None:
+            raise RuntimeError("set_last_exposure() needs TrackOptions.fit_exposure")
+        from gs_exposure import numbers32
+
+        self._last_exposure = numbers32(gain, bias)
 
     def _start_pose(self, init):
         if init is not None:
@@ -331,12 +377,14 @@ class Tracker:
             return pose64(*self._history[-1])
         return pose64(self.camera.rot, self.camera.tran)
 
-    def iteration(self, rot, tran, image, range_map=None, level=0):
+    def iteration(self, rot, tran, image, range_map=None, level=0, lr_scale=1.0):
         """One forward / loss / pose backward at the pose (rot, tran); the 16 floats land in ``self._host`` (pinned):
         dL/drot [0:9], dL/dtran [9:12], (loss, colour term, depth term, depth pixels) [12:16]; with the median gate 20 floats,
         [16:20] = (colour pixels, m_d, m_c, n_d).  Returns that buffer.  ``level``: a scheduled level of ``TrackOptions.pyramid``
         -- ``image`` / ``range_map`` are then that level's targets (gs_pyramid.Pyramid.build), rendered through the level camera;
-        without a schedule only level 0 exists."""
+        without a schedule only level 0 exists.  ``TrackOptions.fit_exposure``: the loss is taken on the compensated render,
+        the exposure's backward scales the colour gradient map and -- inside ``track``, where the exposure is free -- steps the
+        six numbers at ``lr_scale`` x their rates; the buffer ends with six floats more, the numbers AFTER that step."""
         if self._levels is None:
             if level != 0:
                 raise ValueError(f"level {level}: this Tracker has no schedule (TrackOptions.pyramid), only level 0")
@@ -348,7 +396,12 @@ class Tracker:
         cam = posed(camera, rot, tran)
         img, _, depth, alpha = r.forward(*self.params, cam, training=True, aux=True)
         with torch.cuda.device(self.device):
-            gi, gd, ga = loss(img, depth, alpha, image, range_map, scale, values=self._values)
+            if self._exposures is None:
+                gi, gd, ga = loss(img, depth, alpha, image, range_map, scale, values=self._values)
+            else:
+                ex = self._exposures[level]
+                gi, gd, ga = loss(ex.apply(img), depth, alpha, image, range_map, scale, values=self._values)
+                ex.backward(img, gi, lr_scale)
         if self.opt.pose_only:
             r.backward_pose(gi, self._grad_pose, 0, grad_depth=gd, grad_alpha=ga)
         else:
@@ -357,15 +410,29 @@ class Tracker:
         self._host.copy_(self._dev)  # (device -> pinned host: returns when the 64 -- gated: 80 -- bytes have landed)
         return self._host
 
-    def track(self, image, range_map=None, init=None) -> TrackResult:
+    def track(self, image, range_map=None, init=None, init_exposure=None) -> TrackResult:
         """``image`` [H,W,3] and ``range_map`` [H,W] (range from the camera centre; <= 0, inf, NaN: no measurement; None:
-        RGB only): contiguous float32 tensors on the tracker's device.  Returns the pose with the lowest loss seen."""
+        RGB only): contiguous float32 tensors on the tracker's device.  Returns the pose with the lowest loss seen.
+        ``init_exposure`` = (gain, bias) (``TrackOptions.fit_exposure`` only): where the exposure fit starts; without it from
+        the last tracked frame's exposure, else from the identity."""
         o = self.opt
+        if init_exposure is not None and self._exposures is None:
+            raise ValueError("init_exposure needs TrackOptions.fit_exposure")
         R, t = self._start_pose(init)
         if o.device_pose:
             return self._track_on_device(R, t, image, range_map)
         adam = PoseAdam(R, t, o.lr_rot, o.lr_tran, o.betas, o.eps)  # Adam's moments on (w, tran): kept across iterations, reset per call
-        best = (math.inf, R, t, None)
+        nf, ex32 = self._nfloat, None
+        if self._exposures is not None:
+            # ONE exposure fit for the call: the numbers start over, Adam's state on the device from zero (shared by the levels)
+            from gs_exposure import numbers32
+
+            ex32 = numbers32(*init_exposure) if init_exposure is not None else \
+                self._last_exposure if self._last_exposure is not None else numbers32()
+            ex = next(iter(self._exposures.values()))
+            ex.set(ex32[0:3], ex32[3:6])
+            ex.free(o.lr_gain, o.lr_bias, o.betas, o.eps)
+        best = (math.inf, R, t, None, ex32)
         losses: List[float] = []
         # coarse to fine: the targets once, then the stages in order under ONE PoseAdam (moments and step count carry across
         # stages, the rate decays over the whole call); losses of different levels are not comparable, so the pose returned
@@ -376,16 +443,24 @@ class Tracker:
             levels.append((level, k, n))
             last = level == stages[-1][0]
             for _ in range(n):
-                h = self.iteration(R, t, images[level], ranges[level], level).numpy().astype(np.float64)
+                decay = o.lr_final ** (k / total)
+                h32 = self.iteration(R, t, images[level], ranges[level], level, decay).numpy()
+                h = h32.astype(np.float64)
                 loss = float(h[12])
                 losses.append(loss)
                 if last and loss < best[0]:
-                    best = (loss, R, t, h[15:20] if len(h) == 20 else None)
-                R, t = adam.step(h[0:9], h[9:12], o.lr_final ** (k / total))
+                    best = (loss, R, t, h[15:20] if nf == 20 else None, ex32)
+                if ex32 is not None:
+                    ex32 = h32[nf:nf + 6].copy()  # what the step left: the next iteration's exposure
+                R, t = adam.step(h[0:9], h[9:12], decay)
                 k += 1
-        loss, R, t, gate = best
+        loss, R, t, gate, ex32 = best
         self._history = (self._history + [(R, t)])[-2:]
         res = TrackResult(rot=R, tran=t, loss=loss, iterations=len(losses), losses=losses)
+        if ex32 is not None:
+            next(iter(self._exposures.values())).fix()
+            self._last_exposure = ex32
+            res.exposure = (ex32[0:3].astype(np.float64), ex32[3:6].astype(np.float64))
         if gate is not None:  # (depth pixels, colour pixels, m_d, m_c, n_d) of the returned pose's iteration
             res.inliers = (int(gate[0]), int(gate[4]), int(gate[1]))
             res.medians = (float(gate[2]), float(gate[3]))

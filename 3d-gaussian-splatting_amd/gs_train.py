@@ -493,7 +493,8 @@ class Trainer:
                  per_view_stat: Optional[bool] = None, exchange: str = "all_reduce", n_slices: Optional[int] = None,
                  bwd_rows: Optional[bool] = None, fuse_adam: Optional[bool] = None,
                  depths: Optional[Sequence[Optional[torch.Tensor]]] = None, depth_kind: str = "range",
-                 weights: Optional[Sequence[Optional[torch.Tensor]]] = None, densify_carry: bool = False):
+                 weights: Optional[Sequence[Optional[torch.Tensor]]] = None, densify_carry: bool = False,
+                 exposures: Optional[dict] = None):
         self.opt = opt or TrainOptions()
         # `weights`: a list parallel to `targets`, each entry a per-pixel weight map [H,W] float32 (finite, >= 0) for the
         # view's colour loss or None.  A view with a map takes the weighted loss (WeightedImageLoss) where the step calls its
@@ -583,6 +584,16 @@ class Trainer:
         self._lambdas, self._base = lr_lambdas(self.opt), base_lrs(self.opt)
         self._loss = {}
         self._free = {}  # camera id -> _FreePose: gs_track.FreePose: the views whose pose is refined with the map (free_pose)
+        # `exposures`: {camera id: (gain [3], bias [3])}, the affine exposure of the views that have one (gs_exposure.Exposure:
+        # six numbers in device memory).  Such a view's colour loss -- plain or weighted -- is taken on the compensated render,
+        # and the exposure's backward scales the gradient map before it travels through whichever backward the step takes;
+        # fixed unless `free_exposure` frees it.  A view without one issues exactly the calls it issues without `exposures`,
+        # and no Exposure object exists for it.  `test` and every evaluation render stay uncompensated.
+        self._exposure = {}
+        for cid, (gain, bias) in (exposures or {}).items():
+            if not 0 <= int(cid) < len(self.cameras):
+                raise IndexError(f"exposures names view {cid}: no such view")
+            self._exposure[int(cid)] = self._view_exposure(self.cameras[int(cid)], (gain, bias), dev)
         self._bind(params, 0)
 
     def _bind(self, params: Sequence[torch.Tensor], i_iter: int, carry: Optional[_Carry] = None):
@@ -638,17 +649,28 @@ class Trainer:
             raise ValueError("a weight map must be finite and not negative (NaN, inf or a negative weight found)")
         return w, weight_sums(w)
 
+    @staticmethod
+    def _view_exposure(camera, exposure, device):
+        """One view's exposure (gain, bias) as the step uses it: a fixed ``gs_exposure.Exposure`` of the camera's size."""
+        from gs_exposure import Exposure
+
+        gain, bias = exposure
+        return Exposure(int(camera.height), int(camera.width), device, gain, bias)
+
     def add_view(self, camera, target: torch.Tensor, depth: Optional[torch.Tensor] = None,
-                 weight: Optional[torch.Tensor] = None) -> int:
+                 weight: Optional[torch.Tensor] = None, exposure=None) -> int:
         """Appends a view to a running fit -> its camera id.  ``depth`` goes through the constructor's own per-view
         validation and conversion (``depth_kind``, the measured-pixel count); a Trainer built without ``depths`` takes
         ``depth=None`` only.  ``weight``: the view's colour weight map (``weights`` of the constructor; a Trainer built
         without ``weights`` starts its list here, the earlier views without a map).  Nothing else changes -- no rebind, no
-        optimizer reset, no frame abandoned: a step on an earlier view afterwards is the step it would have been."""
+        optimizer reset, no frame abandoned: a step on an earlier view afterwards is the step it would have been.  ``exposure`` =
+        (gain, bias): the view's affine exposure (``exposures`` of the constructor), held fixed until ``free_exposure``."""
         if depth is not None and self.depths is None:
             raise ValueError("this Trainer was built without depths: add_view takes depth=None only")
         wmap, wsums = self._view_weight(camera, weight, self._depth_device)  # (refused before anything is appended)
         d, inv_n = self._view_depth(camera, depth)
+        if exposure is not None:
+            self._exposure[len(self.cameras)] = self._view_exposure(camera, exposure, self._depth_device)
         if wmap is not None and self.weights is None:
             self.weights = [None] * len(self.cameras)
             self._weight_sums = [(0.0, 0.0)] * len(self.cameras)
@@ -684,6 +706,8 @@ class Trainer:
             del lst[camera_id]
         self._views_checked = {v - (v > camera_id) for v in self._views_checked if v != camera_id}
         self._free = {v - (v > camera_id): fp for v, fp in self._free.items()}
+        # (getattr: a Trainer from before `exposures` -- the host tests build one attribute by attribute -- has none)
+        self._exposure = {v - (v > camera_id): e for v, e in getattr(self, "_exposure", {}).items() if v != camera_id}
         self.renderer.forward_abandon()  # (a frame projected ahead may have been the removed view's)
 
     # ------------------------------------------------------------------ free poses (joint refinement of poses and map)
@@ -731,6 +755,34 @@ class Trainer:
         if fp is None or not fp.settle():
             return
         self.cameras[camera_id] = posed(self.cameras[camera_id], fp.adam.rot, fp.adam.tran)
+
+    # ------------------------------------------------------------------ per-view exposure (gs_exposure.Exposure)
+    def free_exposure(self, camera_id: int, lr_gain: float, lr_bias: float, betas: Tuple[float, float] = (0.9, 0.999),
+                      eps: float = 1e-8):
+        """From now on every ``train_step`` on view ``camera_id`` also takes one Adam step on that view's six exposure numbers,
+        on the device behind the exposure's backward (no host wait; skipped with the optimizer's step where the frame
+        overflowed).  A view without an exposure gets the identity first.  Moments and step count start at zero.  Refused
+        under several ranks: each rank would step its own copy."""
+        if self.world_size > 1:
+            raise RuntimeError("free_exposure is not available under view parallelism (world_size > 1): each rank would step "
+                               "its own copy of the exposure")
+        camera_id = int(camera_id)
+        if not 0 <= camera_id < len(self.cameras):
+            raise IndexError(f"no view {camera_id}")
+        if camera_id not in self._exposure:
+            self._exposure[camera_id] = self._view_exposure(self.cameras[camera_id], (None, None), self.flat.flat_param.device)
+        self._exposure[camera_id].free(lr_gain, lr_bias, betas, eps)
+
+    def fix_exposure(self, camera_id: int):
+        """Ends ``free_exposure``: the view keeps the exposure it has, its optimizer state is dropped."""
+        ex = self._exposure.get(int(camera_id))
+        if ex is not None:
+            ex.fix()
+
+    def exposure(self, camera_id: int):
+        """(gain [3], bias [3]) of view ``camera_id`` in float64 -- one host read --, None for a view without an exposure."""
+        ex = self._exposure.get(int(camera_id))
+        return ex.values() if ex is not None else None
 
     @property
     def n_gaussians(self) -> int:
@@ -826,12 +878,19 @@ class Trainer:
                           f"workspace has been enlarged to {r.max_pairs} pairs")
             self._overflow_warned = r.overflowed_frames
         wmap = self.weights[camera_id] if self.weights is not None else None
+        # a view with an exposure: the colour loss sees the compensated render (the depth loss below never does)
+        exposure = self._exposure.get(camera_id) if self._exposure else None
+        pred = image if exposure is None else exposure.apply(image)
         if wmap is None:
             loss = self._loss_for(image.shape[0], image.shape[1])
-            grad_image = loss(image, target)
+            grad_image = loss(pred, target)
         else:  # a weighted view: the same gradient map travels through whichever backward the step takes
             loss = self._weighted_loss_for(image.shape[0], image.shape[1])
-            grad_image = loss(image, target, wmap, *self._weight_sums[camera_id])
+            grad_image = loss(pred, target, wmap, *self._weight_sums[camera_id])
+        if exposure is not None:
+            # dL/dI' -> dL/dI in place, the six gradients, and a free exposure's Adam step on the device -- skipped, like the
+            # optimizer's, where the frame overflowed
+            exposure.backward(image, grad_image, skip_flag=self.optimizer.skip_flag)
         # depth supervision: + depth_weight / n_valid * sum |r| on the frame's maps; its two gradient maps travel with
         # grad_image through whichever backward the step takes
         aux_grads = {}

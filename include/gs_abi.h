@@ -34,7 +34,11 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_debug_tile_compact and
+/* 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_exposure_apply,
+ *   gs_exposure_backward and gs_exposure_workspace_bytes with gs_exposure_state / gs_exposure_adam (a view's affine exposure,
+ *   gain[3] and bias[3] in device memory, around any colour loss: the compensated image in front of it, the scaled gradient
+ *   map, the six gradients and an optional Adam step on the device behind it; csrc/exposure.hip).
+ * 8, purely additive (clients built against the earlier version 8 header are unaffected): gs_frame_debug_tile_compact and
  *   gs_frame_debug_tile_cost (read-only views of two per-tile words of the last forward, for tests and measurements: the step
  *   at which a tile's compositing wave compacted its live pixels, and the steps it composited); the workspace of a frame grows
  *   by one word per tile (gs_frame_workspace_bytes).
@@ -1469,6 +1473,43 @@ int gs_pose_reset(gs_pose_state *state_dev, float *pose_dev, float *log_dev, int
 int gs_pose_step(const float *grad_rot_dev, const float *grad_tran_dev, const float *values_dev,
                  const void *skip_if_nonzero, const gs_pose_step_opts *opts, gs_pose_state *state_dev, float *pose_dev,
                  float *log_dev, int32_t log_rows, int32_t log_row, gs_stream_t stream);
+
+/* ---- a view's affine exposure (exposure.hip): six numbers per view in device memory, exposure_dev = gain[3] then bias[3],
+ * contiguous fp32, read by the kernels as they stand when the kernels run (as a GS_FRAME_DEVICE_POSE frame reads its pose).
+ * Every colour loss of this section is taken on the compensated image I' in place of the rendered I; depth and alpha terms
+ * are untouched.  All arithmetic on the maps is fp32 with one rounding per operation, no contraction:
+ *   gs_exposure_apply   : out_pc = fl(fl(gain_c image_pc) + bias_c); image, out [H,W,3].  One streaming pass, one launch.  The
+ *     identity (1,1,1,0,0,0) gives out = image bit for bit (a -0 element alone becomes +0).  out may not overlap image: the
+ *     backward needs I.
+ *   gs_exposure_backward: on entry grad [H,W,3] holds g' = dL/dI' (what a loss kernel wrote), on exit g_pc = fl(gain_c g'_pc)
+ *     (what the frame backward takes; the identity leaves it bit for bit).  grad_exposure_out (6 floats on the device; may be
+ *     NULL) = (dL/dgain_c = sum_p g'_pc image_pc, dL/dbias_c = sum_p g'_pc): each product in double from its two fp32 operands,
+ *     summed in double per thread in pixel order, per wave, per workgroup and by one last workgroup over the workgroups' rows
+ *     in a fixed order, each total rounded to fp32 once.  No atomics: bitwise repeatable.
+ *     adam (may be NULL): the same last workgroup then takes ONE Adam step on the six numbers in double, on the six fp32
+ *     gradients just formed g: steps += 1; m = b1 m + (1 - b1) g; v = b2 v + ((1 - b2) g) g; d = (lr lr_scale (m / (1 -
+ *     b1^steps))) / (sqrt(v / (1 - b2^steps)) + eps), lr = lr_gain for the gains and lr_bias for the biases; exposure_dev[k] =
+ *     (float)((double)exposure_dev[k] - d).  It is a second launch: every read of the gain precedes the write.  No step --
+ *     state and numbers untouched bit for bit -- where *skip_if_nonzero != 0 (8 bytes on the device, the meaning of
+ *     gs_adam_fused.skip_if_nonzero; NULL: never) or one of the six gradients is not finite.  With adam NULL exposure_dev is
+ *     not written.  With grad_exposure_out and adam both NULL no sum is formed: one launch.
+ * GS_E_INVALID, before anything is enqueued: a null image, grad, out or exposure_dev; a map not 16-byte, exposure_dev or
+ * grad_exposure_out not 4-byte, state or skip_if_nonzero not 8-byte aligned; H or W <= 0; out or grad overlapping image; a
+ * null state; lr_gain, lr_bias, lr_scale or eps negative, NaN or infinite; a beta outside [0, 1); a workspace that is null,
+ * not 8-byte aligned or smaller than gs_exposure_workspace_bytes(H, W) (48 bytes per 1,024 pixels). */
+typedef struct gs_exposure_state { /* on the DEVICE, 104 bytes; all zero = a fresh optimizer */
+    double m[6], v[6];        /* Adam's moments on (gain[3], bias[3])                                         */
+    double steps;             /* steps taken                                                                  */
+} gs_exposure_state;
+typedef struct gs_exposure_adam {
+    gs_exposure_state *state; /* device                                                                       */
+    double lr_gain, lr_bias, beta1, beta2, eps, lr_scale;
+    const void *skip_if_nonzero; /* device, 8 bytes; may be NULL                                              */
+} gs_exposure_adam;
+size_t gs_exposure_workspace_bytes(int32_t H, int32_t W); /* 0 on bad arguments */
+int gs_exposure_apply(const float *image, const float *exposure_dev, int32_t H, int32_t W, float *out, gs_stream_t stream);
+int gs_exposure_backward(const float *image, float *grad, float *exposure_dev, int32_t H, int32_t W, float *grad_exposure_out,
+                         const gs_exposure_adam *adam, void *workspace, size_t workspace_bytes, gs_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

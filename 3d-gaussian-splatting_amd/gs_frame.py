@@ -116,7 +116,7 @@ class FrameRenderer:
         self.force_strips = FrameRenderer.default_force_strips if force_strips is None else bool(force_strips)
         self.serial_long_lists = bool(serial_long_lists)  # frames with long lists: no segmented compositing
         # GS_FRAME_LONG_LISTS (big-list sort + segmented compositing of long tile lists): True / False, or None = as soon
-        # as an earlier frame of this renderer reported a tile list beyond LONG_LIST_FLAG_AT = 6,144 pairs (the counters that auto_grow reads
+        # as an earlier frame of this renderer reported a tile list beyond LONG_LIST_FLAG_AT = 2,048 pairs (the counters that auto_grow reads
         # back anyway carry the longest list).  The workspace capacity plays no part in it.
         # GS_FRAME_OCCLUSION_CULL (include/gs_abi.h): inference frames drop, at emission, the pairs behind the depth at which
         # the PREVIOUS forward of this workspace saw all pixels of their tile stop -- exact (a frame whose trimmed lists
@@ -326,6 +326,11 @@ class FrameRenderer:
         f.sort_mode = self.sort_mode
         f.tile_culling_method = self.tile_culling_method
         need = _lib.gs_frame_workspace_bytes(n, self.max_pairs, grid.width, grid.height, color_dim, int(training))
+        # (`< need`, not `< need + 256` as for the aux workspace below: the 256 bytes allocated on top are slack for aligning
+        # the base, and torch's caching allocator hands out blocks aligned to 512 bytes, so the slack is never used and a
+        # workspace of `need` bytes or more holds the frame.  That alignment is how torch's allocator behaves, not a promise
+        # of its API: were a base ever unaligned, workspace_bytes below would come out short of `need` and the library, which
+        # checks it against its own need, would refuse the frame -- an error, never a write past the buffer)
         if self._ws is None or self._ws.numel() < need:
             self._release_workspace()  # side-stream work of an earlier training frame may still touch the old one
             self._ws = torch.empty(int(need) + 256, dtype=torch.uint8, device=self.device)
